@@ -4,12 +4,19 @@
 One "step" = the hot path of one smoke time step over the synthetic S-smoke input:
     restore velocity (device copy) -> advectSemiLagrange(density, order=2) -> advectSemiLagrange(vel, order=2)
     -> setWallBcs -> solvePressure(MIC-preconditioned CG, cgAccuracy 1e-3)
-All inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line (contract in the task prompt)
-with two extra objects: `roofline` (ApplyMatrix, the kernel BASELINE.json's north_star names: 28 B/cell algorithmic
-bytes / HIP-event launch time, vs 8 TB/s) and `cpu_baseline` (the reference C++/OpenMP path -- oracle/_ref, or the
+All inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line (metric, value, unit,
+higher_is_better, dtype, ms_per_step of the timed steps, and the step's configuration).  A plain run does nothing else.
+
+--full adds the measurements that take runs of their own: `roofline` (ApplyMatrix, the kernel BASELINE.json's
+north_star names: 28 B/cell algorithmic bytes / HIP-event launch time, vs 8 TB/s), `roofline_mic`, `roofline_step`,
+`other_configs` (BASELINE configs 3, 4 and 5) and `cpu_baseline` (the reference C++/OpenMP path -- oracle/_ref, or the
 oracle port when the compiled reference is absent -- timed on the host cores on a bounded sample of the workload).
 
-Launch: python bench.py --gpus 1 [--steps K --warmup W]  |  torchrun --nproc-per-node N bench.py --gpus N ...
+--dump-outputs DIR writes what the last timed step computed (density, velocity, pressure at a fixed sample of cells,
+and its CG iteration count) as DIR/<name>.npy, so that two builds can be compared output for output.
+
+Launch: python bench.py --gpus 1 [--steps K --warmup W] [--full] [--dump-outputs DIR]
+        torchrun --nproc-per-node N bench.py --gpus N ...
 """
 import argparse
 import ctypes
@@ -409,16 +416,41 @@ def other_configs(torch, core, plugins):
     return out
 
 
+DUMP_CELLS = 1 << 21    # cells sampled by --dump-outputs: 2 Mi cells x (density + 3 velocity + pressure) x 4 B = 40 MiB
+
+
+def dump_outputs(out_dir, n, dens, vel, pres, cg_iterations):
+    """What a caller of the timed step receives after its last step -- density, velocity ([cell][c]) and pressure -- at a fixed,
+    seeded sample of DUMP_CELLS cells (every cell when the grid has fewer), plus the step's CG iteration count."""
+    import torch
+    cells = n ** 3
+    if cells <= DUMP_CELLS:
+        idx = np.arange(cells, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(20240).choice(cells, DUMP_CELLS, replace=False))
+    ti = torch.from_numpy(idx).to(dens.data.device)
+    os.makedirs(out_dir, exist_ok=True)
+    outs = {"density": dens.data[ti], "velocity": vel.data.view(3, cells)[:, ti].t(), "pressure": pres.data[ti]}
+    for name, t in outs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(t.cpu().numpy(), dtype=np.float32))
+    np.save(os.path.join(out_dir, "cg_iterations.npy"), np.array([cg_iterations], np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--grid", type=int, default=GRID)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short single-GPU runs of BASELINE configs 3, 4 and 5")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the rooflines, BASELINE configs 3, 4 and 5 and the CPU baseline (runs of their own after the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (single-GPU path)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short single-GPU runs of BASELINE configs 3, 4 and 5")
     ap.add_argument("--slab", action="store_true", help="N=1 only: run the z-slab code path with one rank (overhead check)")
     a = ap.parse_args()
+    if a.dump_outputs and (a.gpus > 1 or a.slab):
+        ap.error("--dump-outputs is implemented for the single-GPU path only")
 
     import torch
     import torch.distributed as dist
@@ -444,7 +476,7 @@ def main():
             os.environ.setdefault("MASTER_PORT", "29533")
             dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", local))
         result = slab.bench_slab_step(n, dt, a.steps, a.warmup, rank, world)
-        if rank == 0:
+        if rank == 0 and a.full:
             # the roofline object of the line, for the kernel north_star names, on what one rank computes per PCG iteration: its owned
             # planes + one ghost plane per interior face (HIP events on the launch stream, after the timed region)
             nz = n // world + (1 if world > 1 else 0) + (1 if world > 2 else 0)
@@ -496,96 +528,99 @@ def main():
         el = time.perf_counter() - t0
         result = {"elapsed": el, "cells": n ** 3, "cg_iterations": iters[-a.steps:] if a.steps else []}
 
-        # ---- roofline of the ApplyMatrix stencil (HIP events on the launch stream, inside the library) ----
-        A0, Ai, Aj, Ak, src, dst = (core.Grid(s) for _ in range(6))
-        lib.call("mf_make_laplace_matrix", n, n, n, flags.ptr, A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr, None, s.stream)
-        src.from_numpy(np.random.default_rng(1234).uniform(-1, 1, (n, n, n)).astype(np.float32))
-        us = ctypes.c_double()
-        lib.call("mf_time_apply_matrix", n, n, n, flags.ptr, dst.ptr, src.ptr, A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr, 200, ctypes.byref(us), s.stream)
-        gbs = APPLY_MATRIX_BYTES_PER_CELL * n ** 3 / (us.value * 1e-6) / 1e9
-        # the variant the PCG loop runs for this matrix: flags + Ai + Aj + Ak packed into one byte per cell by mf_mic_init
-        # (13 B per cell: src, dst, A0, packed byte); reported next to the general kernel, never instead of it
-        apk = core.Grid(s)
-        lib.call("mf_mic_init", n, n, n, flags.ptr, apk.ptr, A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr, s.stream)
-        us_pk = ctypes.c_double()
-        lib.call("mf_time_apply_matrix_packed", n, n, n, flags.ptr, dst.ptr, src.ptr, A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr, 200, ctypes.byref(us_pk), s.stream)
-        del apk
-        # HBM traffic needs the PMC counters (rocprofv3 --pmc, separate passes): not measurable from inside this process, so
-        # the number is read from the committed counter summary and labelled with its source
-        traffic, traffic_src = None, None
-        tp = os.path.join(ROOT, "profiles", "apply_matrix_traffic.json")
-        if os.path.exists(tp) and n == GRID:
-            try:
-                traffic = json.load(open(tp)).get("hbm_bytes_per_launch")
-                traffic_src = "profiles/apply_matrix_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, not measured in this run)"
-            except Exception:
-                traffic = None
-        result["roofline"] = {"kernel": "k_apply_matrix_v5 (ApplyMatrix, conjugategrad.h:118-133)", "bound": "hbm",
-                              "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
-                              "traffic": traffic, "traffic_source": traffic_src, "avg_launch_us": round(us.value, 2),
-                              "algorithmic_bytes_per_launch": APPLY_MATRIX_BYTES_PER_CELL * n ** 3,
-                              "pcg_variant": {"kernel": "k_apply_matrix_v5<PACKED> (flags + Ai + Aj + Ak + the integer diagonal A0 as one byte per cell, exact for a MakeLaplaceMatrix system)",
-                                              "avg_launch_us": round(us_pk.value, 2), "bytes_per_cell": 9,
-                                              "achieved": round(9 * n ** 3 / (us_pk.value * 1e-6) / 1e9, 1),
-                                              "frac": round(9 * n ** 3 / (us_pk.value * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}}
-        # ---- the kernel that takes most of the step: the two MIC(0) substitution sweeps (conjugategrad.cpp:135-159).
-        # forward reads flags, rhs, Ai, Aj, Ak, Aprecond, dst and writes dst (32 B/cell), backward does not read rhs (28 B/cell)
-        ap = core.Grid(s)
-        lib.call("mf_mic_init", n, n, n, flags.ptr, ap.ptr, A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr, s.stream)
-        for _ in range(3):
-            lib.call("mf_mic_apply", n, n, n, flags.ptr, dst.ptr, src.ptr, ap.ptr, Ai.ptr, Aj.ptr, Ak.ptr, s.stream)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(torch.cuda.current_stream())
-        for _ in range(50):
-            lib.call("mf_mic_apply", n, n, n, flags.ptr, dst.ptr, src.ptr, ap.ptr, Ai.ptr, Aj.ptr, Ak.ptr, s.stream)
-        e1.record(torch.cuda.current_stream())
-        torch.cuda.synchronize()
-        mic_us = e0.elapsed_time(e1) * 1e3 / 50
-        mic_bytes = MIC_BYTES_PER_CELL * n ** 3
-        mic_traffic, mic_traffic_src = None, None
-        tp = os.path.join(ROOT, "profiles", "mic_traffic.json")
-        if os.path.exists(tp) and n == GRID:
-            try:
-                mic_traffic = json.load(open(tp)).get("hbm_bytes_per_apply")     # PMC counters, see profiles/README.md
-                mic_traffic_src = "profiles/mic_traffic.json (rocprofv3 --pmc passes, not measured in this run)"
-            except Exception:
-                mic_traffic = None
-        result["roofline_mic"] = {"kernel": "k_mic_rows<1> + k_mic_rows<2> (ApplyPreconditionModifiedIncompCholesky2, conjugategrad.cpp:135-159)",
-                                  "bound": "dependency chain (serial sweep in the reference), hbm if it were free",
-                                  "achieved": round(mic_bytes / (mic_us * 1e-6) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                  "frac": round(mic_bytes / (mic_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4), "avg_apply_us": round(mic_us, 1),
-                                  "algorithmic_bytes_per_apply": mic_bytes, "traffic": mic_traffic, "traffic_source": mic_traffic_src,
-                                  "achieved_on_measured_traffic": None if not mic_traffic else round(mic_traffic / (mic_us * 1e-6) / 1e9, 1),
-                                  "frac_on_measured_traffic": None if not mic_traffic else round(mic_traffic / (mic_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                                  "note": "achieved / frac price the reference's unfused structure (SURVEY 8d: 56 B per cell and apply) at the measured "
-                                          "time -- a speed against the reference-structure roofline; the packed sweeps move fewer bytes (traffic), "
-                                          "and *_on_measured_traffic is the bandwidth they really draw"}
-        # ---- the whole step against the HBM roofline: SURVEY 8d's algorithmic bytes of every operator of the step / ms_per_step
-        its = float(np.mean(result["cg_iterations"])) if result["cg_iterations"] else 0.0
-        step_bytes = (STEP_FIXED_BYTES_PER_CELL + its * CG_ITERATION_BYTES_PER_CELL) * n ** 3
-        step_gbs = step_bytes / (el / max(a.steps, 1)) / 1e9
-        result["roofline_step"] = {"bound": "hbm", "achieved": round(step_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                   "frac": round(step_gbs / HBM_PEAK_GBS, 4), "algorithmic_bytes_per_step": int(step_bytes),
-                                   "bytes_per_cell": {"fixed (MacCormack Real 92 + MAC 188 + outflow sweeps 20 + velocity restore 24 + setWallBcs 28 "
-                                                      "+ MakeRhs 20 + MakeLaplaceMatrix 20 + MIC init 28 + correctVelocity 32)": STEP_FIXED_BYTES_PER_CELL,
-                                                      "per CG iteration (ApplyMatrix 28 + 2 dot 16 + 2 axpy 24 + max-norm 8 + search update 12 + MIC apply 56)": CG_ITERATION_BYTES_PER_CELL,
-                                                      "mean CG iterations": round(its, 1)},
-                                   "moved_bytes_per_step": int((MOVED_FIXED_BYTES_PER_CELL + its * MOVED_ITERATION_BYTES_PER_CELL) * n ** 3),
-                                   "moved_bytes_per_cell": {"per CG iteration as built (ApplyMatrix on packed bytes 9 + residual update and max-norm 12 + forward sweep 13 "
-                                                            "+ backward sweep with dot 17 + search / pressure update 20)": MOVED_ITERATION_BYTES_PER_CELL,
-                                                            "fixed as built (MacCormack Real 76 + MAC 160 + restore 24 + setWallBcs 28 + MakeRhs 20 + MakeLaplaceMatrix 20 "
-                                                            "+ pack 21 + MIC init 28 + doInit copies 36 + correctVelocity 32)": MOVED_FIXED_BYTES_PER_CELL},
-                                   "frac_on_moved_bytes": round((MOVED_FIXED_BYTES_PER_CELL + its * MOVED_ITERATION_BYTES_PER_CELL) * n ** 3
-                                                                / (el / max(a.steps, 1)) / 1e9 / HBM_PEAK_GBS, 4),
-                                   "note": "achieved / frac price the reference's structure (SURVEY 8d) at the measured step time; frac_on_moved_bytes uses the "
-                                           "bytes the fused / packed kernels stream (own model, DESIGN.md section 3)"}
-        del A0, Ai, Aj, Ak, src, dst, ap
-        if not a.no_other_configs and n == GRID:
-            del flags, vel, vel0, dens, pres, s
-            torch.cuda.empty_cache()
-            result["other_configs"] = other_configs(torch, core, plugins)
-        if not a.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline((n, n, n), v_np, d_np, dt, result["cg_iterations"][-1] if result["cg_iterations"] else None)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, n, dens, vel, pres, iters[-1] if iters else 0)
+        if a.full:
+            # ---- roofline of the ApplyMatrix stencil (HIP events on the launch stream, inside the library) ----
+            A0, Ai, Aj, Ak, src, dst = (core.Grid(s) for _ in range(6))
+            lib.call("mf_make_laplace_matrix", n, n, n, flags.ptr, A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr, None, s.stream)
+            src.from_numpy(np.random.default_rng(1234).uniform(-1, 1, (n, n, n)).astype(np.float32))
+            us = ctypes.c_double()
+            lib.call("mf_time_apply_matrix", n, n, n, flags.ptr, dst.ptr, src.ptr, A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr, 200, ctypes.byref(us), s.stream)
+            gbs = APPLY_MATRIX_BYTES_PER_CELL * n ** 3 / (us.value * 1e-6) / 1e9
+            # the variant the PCG loop runs for this matrix: flags + Ai + Aj + Ak packed into one byte per cell by mf_mic_init
+            # (13 B per cell: src, dst, A0, packed byte); reported next to the general kernel, never instead of it
+            apk = core.Grid(s)
+            lib.call("mf_mic_init", n, n, n, flags.ptr, apk.ptr, A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr, s.stream)
+            us_pk = ctypes.c_double()
+            lib.call("mf_time_apply_matrix_packed", n, n, n, flags.ptr, dst.ptr, src.ptr, A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr, 200, ctypes.byref(us_pk), s.stream)
+            del apk
+            # HBM traffic needs the PMC counters (rocprofv3 --pmc, separate passes): not measurable from inside this process, so
+            # the number is read from the committed counter summary and labelled with its source
+            traffic, traffic_src = None, None
+            tp = os.path.join(ROOT, "profiles", "apply_matrix_traffic.json")
+            if os.path.exists(tp) and n == GRID:
+                try:
+                    traffic = json.load(open(tp)).get("hbm_bytes_per_launch")
+                    traffic_src = "profiles/apply_matrix_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, not measured in this run)"
+                except Exception:
+                    traffic = None
+            result["roofline"] = {"kernel": "k_apply_matrix_v5 (ApplyMatrix, conjugategrad.h:118-133)", "bound": "hbm",
+                                  "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4),
+                                  "traffic": traffic, "traffic_source": traffic_src, "avg_launch_us": round(us.value, 2),
+                                  "algorithmic_bytes_per_launch": APPLY_MATRIX_BYTES_PER_CELL * n ** 3,
+                                  "pcg_variant": {"kernel": "k_apply_matrix_v5<PACKED> (flags + Ai + Aj + Ak + the integer diagonal A0 as one byte per cell, exact for a MakeLaplaceMatrix system)",
+                                                  "avg_launch_us": round(us_pk.value, 2), "bytes_per_cell": 9,
+                                                  "achieved": round(9 * n ** 3 / (us_pk.value * 1e-6) / 1e9, 1),
+                                                  "frac": round(9 * n ** 3 / (us_pk.value * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}}
+            # ---- the kernel that takes most of the step: the two MIC(0) substitution sweeps (conjugategrad.cpp:135-159).
+            # forward reads flags, rhs, Ai, Aj, Ak, Aprecond, dst and writes dst (32 B/cell), backward does not read rhs (28 B/cell)
+            ap = core.Grid(s)
+            lib.call("mf_mic_init", n, n, n, flags.ptr, ap.ptr, A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr, s.stream)
+            for _ in range(3):
+                lib.call("mf_mic_apply", n, n, n, flags.ptr, dst.ptr, src.ptr, ap.ptr, Ai.ptr, Aj.ptr, Ak.ptr, s.stream)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(torch.cuda.current_stream())
+            for _ in range(50):
+                lib.call("mf_mic_apply", n, n, n, flags.ptr, dst.ptr, src.ptr, ap.ptr, Ai.ptr, Aj.ptr, Ak.ptr, s.stream)
+            e1.record(torch.cuda.current_stream())
+            torch.cuda.synchronize()
+            mic_us = e0.elapsed_time(e1) * 1e3 / 50
+            mic_bytes = MIC_BYTES_PER_CELL * n ** 3
+            mic_traffic, mic_traffic_src = None, None
+            tp = os.path.join(ROOT, "profiles", "mic_traffic.json")
+            if os.path.exists(tp) and n == GRID:
+                try:
+                    mic_traffic = json.load(open(tp)).get("hbm_bytes_per_apply")     # PMC counters, see profiles/README.md
+                    mic_traffic_src = "profiles/mic_traffic.json (rocprofv3 --pmc passes, not measured in this run)"
+                except Exception:
+                    mic_traffic = None
+            result["roofline_mic"] = {"kernel": "k_mic_rows<1> + k_mic_rows<2> (ApplyPreconditionModifiedIncompCholesky2, conjugategrad.cpp:135-159)",
+                                      "bound": "dependency chain (serial sweep in the reference), hbm if it were free",
+                                      "achieved": round(mic_bytes / (mic_us * 1e-6) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                      "frac": round(mic_bytes / (mic_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4), "avg_apply_us": round(mic_us, 1),
+                                      "algorithmic_bytes_per_apply": mic_bytes, "traffic": mic_traffic, "traffic_source": mic_traffic_src,
+                                      "achieved_on_measured_traffic": None if not mic_traffic else round(mic_traffic / (mic_us * 1e-6) / 1e9, 1),
+                                      "frac_on_measured_traffic": None if not mic_traffic else round(mic_traffic / (mic_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+                                      "note": "achieved / frac price the reference's unfused structure (SURVEY 8d: 56 B per cell and apply) at the measured "
+                                              "time -- a speed against the reference-structure roofline; the packed sweeps move fewer bytes (traffic), "
+                                              "and *_on_measured_traffic is the bandwidth they really draw"}
+            # ---- the whole step against the HBM roofline: SURVEY 8d's algorithmic bytes of every operator of the step / ms_per_step
+            its = float(np.mean(result["cg_iterations"])) if result["cg_iterations"] else 0.0
+            step_bytes = (STEP_FIXED_BYTES_PER_CELL + its * CG_ITERATION_BYTES_PER_CELL) * n ** 3
+            step_gbs = step_bytes / (el / max(a.steps, 1)) / 1e9
+            result["roofline_step"] = {"bound": "hbm", "achieved": round(step_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                       "frac": round(step_gbs / HBM_PEAK_GBS, 4), "algorithmic_bytes_per_step": int(step_bytes),
+                                       "bytes_per_cell": {"fixed (MacCormack Real 92 + MAC 188 + outflow sweeps 20 + velocity restore 24 + setWallBcs 28 "
+                                                          "+ MakeRhs 20 + MakeLaplaceMatrix 20 + MIC init 28 + correctVelocity 32)": STEP_FIXED_BYTES_PER_CELL,
+                                                          "per CG iteration (ApplyMatrix 28 + 2 dot 16 + 2 axpy 24 + max-norm 8 + search update 12 + MIC apply 56)": CG_ITERATION_BYTES_PER_CELL,
+                                                          "mean CG iterations": round(its, 1)},
+                                       "moved_bytes_per_step": int((MOVED_FIXED_BYTES_PER_CELL + its * MOVED_ITERATION_BYTES_PER_CELL) * n ** 3),
+                                       "moved_bytes_per_cell": {"per CG iteration as built (ApplyMatrix on packed bytes 9 + residual update and max-norm 12 + forward sweep 13 "
+                                                                "+ backward sweep with dot 17 + search / pressure update 20)": MOVED_ITERATION_BYTES_PER_CELL,
+                                                                "fixed as built (MacCormack Real 76 + MAC 160 + restore 24 + setWallBcs 28 + MakeRhs 20 + MakeLaplaceMatrix 20 "
+                                                                "+ pack 21 + MIC init 28 + doInit copies 36 + correctVelocity 32)": MOVED_FIXED_BYTES_PER_CELL},
+                                       "frac_on_moved_bytes": round((MOVED_FIXED_BYTES_PER_CELL + its * MOVED_ITERATION_BYTES_PER_CELL) * n ** 3
+                                                                    / (el / max(a.steps, 1)) / 1e9 / HBM_PEAK_GBS, 4),
+                                       "note": "achieved / frac price the reference's structure (SURVEY 8d) at the measured step time; frac_on_moved_bytes uses the "
+                                               "bytes the fused / packed kernels stream (own model, DESIGN.md section 3)"}
+            del A0, Ai, Aj, Ak, src, dst, ap
+            if not a.no_other_configs and n == GRID:
+                del flags, vel, vel0, dens, pres, s
+                torch.cuda.empty_cache()
+                result["other_configs"] = other_configs(torch, core, plugins)
+            if not a.no_cpu_baseline:
+                result["cpu_baseline"] = cpu_baseline((n, n, n), v_np, d_np, dt, result["cg_iterations"][-1] if result["cg_iterations"] else None)
 
     if world > 1:
         t = torch.tensor([result["elapsed"]], dtype=torch.float64, device="cuda")
