@@ -69,7 +69,7 @@ int mf_set_slab_window_source(int zoff, int gsz);
 /* How the MIC(0) sweeps are parallelised on the GPU (no reference counterpart; every mode gives the same bits as the serial sweeps of
  * conjugategrad.cpp:66-97, 135-159): "rows" (default for 3D: row-streaming dataflow sweeps, one 8 x 8 bundle of x-rows per workgroup,
  * one launch per sweep) or "levels" (one launch per hyperplane of 8^3 tiles: no waiting between workgroups); NULL or "" = back to the
- * default / MF_MIC_MODE.  The mode is taken by the next mf_mic_init* and stays with the system it registers.  Returns 0, or -1 for an
+ * default ("rows").  The mode is taken by the next mf_mic_init* and stays with the system it registers.  Returns 0, or -1 for an
  * unknown name.  The oracle accepts and ignores it. */
 int mf_set_mic_mode(const char* name);
 /* Synchronises the stream and reports whether any MIC sweep since the last check gave up waiting for a neighbouring

@@ -1223,32 +1223,41 @@ k_mic_empty_dot(Dim d, int nbj, int nbk, int X8, const int* __restrict__ bempty,
 // The system handle of the sweeps (per device; built by mf_mic_init_blocked / mf_pack_matrix, used by the apply sweeps of the
 // grids it was built for): sweep mode, preconditioner blocks, bundle order, hand-off buffers, packed operands, empty-bundle map.
 struct FlowState {
-	int mode = 2;                // sweep mode this system was initialised under: 2 "rows", 0 "levels" (mf_set_mic_mode / MF_MIC_MODE)
+	// the four grids a system is known by: flags, Aprecond (registered system) or Ai (packed bytes), Aj, Ak
+	struct Grids {
+		const void *flags = nullptr, *A = nullptr, *Aj = nullptr, *Ak = nullptr;
+		bool of(const void* fl, const void* a, const void* aj, const void* ak) const { return flags == fl && A == a && Aj == aj && Ak == ak; }
+	};
+	int mode = 2;                // sweep mode this system was initialised under: 2 "rows", 0 "levels" (mf_set_mic_mode)
 	int nbj = 0, nbk = 0, nblocks = 0, nchunks = 0;
 	int* border = nullptr;       // ticket order of the forward sweep, then of the backward sweep (nblocks entries each)
+	size_t border_cap = 0;
 	int jb = 0;                  // bundles per j-block the order was built for
 	int nxb = 0;                 // x-blocks per row (1 = whole rows)
 	int* rows_xt = nullptr;      // [2]: ticket counter of the forward / backward sweep
 	// bundles without a fluid cell (and without coupling into them) need no sweep at all: built by mf_mic_init for the grids
 	// it was given, used by the apply sweeps only when they are given the same grids
 	int* bempty = nullptr;
-	int bempty_cap = 0;
+	size_t bempty_cap = 0;
 	int nempty_host = -1;        // number of empty bundles of the registered system as the host knows it (-1: not read back yet)
-	const void *be_flags = nullptr, *be_Ap = nullptr, *be_Aj = nullptr, *be_Ak = nullptr;
+	Grids reg;                   // the registered system (flags, Aprecond, Aj, Ak)
 	// preconditioner blocks of the system mf_mic_init_blocked was given (0 = uncut): the apply sweeps use them only when they
-	// are called with the same flags / Aprecond / Aj / Ak (be_*), any other system is swept as the uncut reference algorithm
+	// are called with the same flags / Aprecond / Aj / Ak (reg), any other system is swept as the uncut reference algorithm
 	int blk_rows = 0, blk_cells = 0;
-	// packed operands of the apply sweeps (k_mic_pack), valid for the grids mf_mic_init was given
+	// packed operands of the apply sweeps (k_mic_pack), valid for the grids mf_mic_init was given; pk_A0: the diagonal it was given
 	unsigned char* pack = nullptr;
 	int* pack_ok = nullptr;
 	size_t pack_cap = 0;
-	const void *pk_flags = nullptr, *pk_Ai = nullptr, *pk_Aj = nullptr, *pk_Ak = nullptr, *pk_A0 = nullptr;
-	// a second set of packed bytes, built on request (mf_pack_matrix) for the plain mf_apply_matrix entry point
+	Grids pk;
+	const void* pk_A0 = nullptr;
+	// a second set of packed bytes, built on request (mf_pack_matrix) for the plain mf_apply_matrix entry point; up_A0: the diagonal
+	// these bytes carry in bits 4-7, if any
 	unsigned char* upack = nullptr;
 	int* upack_ok = nullptr;
 	size_t upack_cap = 0;
 	int upack_ok_host = 0;
-	const void *up_flags = nullptr, *up_Ai = nullptr, *up_Aj = nullptr, *up_Ak = nullptr, *up_A0 = nullptr;
+	Grids up;
+	const void* up_A0 = nullptr;
 	unsigned long long *sxj = nullptr, *sxk = nullptr;
 	unsigned long long *sxj1 = nullptr, *sxk1 = nullptr;      // second hand-off value of the init sweep (k_mic_rows_init)
 	size_t sx_cap = 0;
@@ -1256,11 +1265,40 @@ struct FlowState {
 	FlowCtl* ctl = nullptr;
 };
 static FlowState g_flow[16];
+static FlowState& flow_state() {
+	int dev = 0;
+	(void)hipGetDevice(&dev);
+	return g_flow[dev & 15];
+}
+
+// compute units of the current device: the sweeps launch one workgroup per CU at most (round 1: 834 us per apply with 256 workgroups,
+// 1040 us with 512; round 2, with a packed-only <= 128-VGPR variant and a 32- / 48-step ring for two workgroups per CU: 445 vs 412 us,
+// 217 vs 204 us per sweep -- mid-sweep the 256 bundles already stream ~4 TB/s, the rest of the sweep is the dependency chain)
+static int cu_count() {
+	static thread_local int ncu[16] = {};
+	int dev = 0;
+	(void)hipGetDevice(&dev);
+	int& n = ncu[dev & 15];
+	if (!n) {
+		n = 256;
+		(void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+		if (n < 1) n = 1;
+	}
+	return n;
+}
+// f.nempty_host: how many bundles of the registered system sit out the sweeps, read back once per system (smoke scenes: none)
+static int count_empty_bundles(FlowState& f, hipStream_t st) {
+	if (f.nempty_host >= 0) return 0;
+	std::vector<int> hb((size_t)f.nbj * f.nbk);
+	MF_HIP(hipMemcpyAsync(hb.data(), f.bempty, sizeof(int) * hb.size(), hipMemcpyDeviceToHost, st));
+	MF_HIP(hipStreamSynchronize(st));
+	f.nempty_host = 0;
+	for (int v : hb) f.nempty_host += v != 0;
+	return 0;
+}
 
 static int rows_prepare(const Dim& d, FlowState** out, hipStream_t st, int jblock_rows, int xblock_cells) {
-	int dev = 0;
-	MF_HIP(hipGetDevice(&dev));
-	FlowState& f = g_flow[dev];
+	FlowState& f = flow_state();
 	const int nbj = (d.sy + 7) / 8, nbk = (d.sz + 7) / 8;
 	// x-blocks of xblock_cells cells (independent systems, the caller has cut Ai) -- or the whole row
 	const int xcells = (xblock_cells > 0 && xblock_cells < d.sx) ? xblock_cells : ((d.sx + 7) / 8) * 8;
@@ -1275,7 +1313,7 @@ static int rows_prepare(const Dim& d, FlowState** out, hipStream_t st, int jbloc
 	if (f.nbj != nbj || f.nbk != nbk || f.nchunks != nchunks || f.jb != jb || f.nxb != nxb) {
 		MF_HIP(hipStreamSynchronize(st));
 		const int nb = nbj * nbk * nxb;
-		int* h = (int*)malloc(sizeof(int) * 2 * nb);
+		std::vector<int> h((size_t)2 * nb);
 		// tickets in topological order of each sweep: key = position of the bundle inside its j-block along the sweep
 		// direction + tkl (anti-diagonals of the block-local dependency graph); ONE queue per sweep (see k_mic_rows)
 		for (int rev = 0; rev < 2; rev++) {
@@ -1292,22 +1330,19 @@ static int rows_prepare(const Dim& d, FlowState** out, hipStream_t st, int jbloc
 		}
 		if (!f.rows_xt) MF_HIP(hipMalloc((void**)&f.rows_xt, 2 * sizeof(int)));
 		MF_HIP(hipMemset(f.rows_xt, 0, 2 * sizeof(int)));
-		if (f.border) MF_HIP(hipFree(f.border));
-		MF_HIP(hipMalloc((void**)&f.border, sizeof(int) * 2 * nb));
-		MF_HIP(hipMemcpy(f.border, h, sizeof(int) * 2 * nb, hipMemcpyHostToDevice));
-		free(h);
+		MF_TRY(grow_buffer(&f.border, &f.border_cap, sizeof(int) * h.size(), st));
+		MF_HIP(hipMemcpy(f.border, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice));
 		// one granule per (bundle, x', face lane) and face
+		// (fine-grained memory, hipExtMallocWithFlags, was tried for these: 0.45 instead of 0.71 us per idle hand-off in
+		// tools/micro/pingpong_scalar.hip, but no change of the sweep time -- 575.0 vs 576.4 us per apply at 256^3; so were four
+		// scalar-path poller waves (s_load_dwordx16 glc, 0.45 us per hand-off in the micro-benchmark): bit-exact, 700+ us)
 		const size_t need = (size_t)nb * 8 * (8 * (size_t)nchunks + 2 * ROWS_PAD) * sizeof(unsigned long long);
-		if (need > f.sx_cap) {
-			// (fine-grained memory, hipExtMallocWithFlags, was tried for these: 0.45 instead of 0.71 us per idle hand-off in
-			// tools/micro/pingpong_scalar.hip, but no change of the sweep time -- 575.0 vs 576.4 us per apply at 256^3; so were four
-			// scalar-path poller waves (s_load_dwordx16 glc, 0.45 us per hand-off in the micro-benchmark): bit-exact, 700+ us)
-			for (unsigned long long** q : {&f.sxj, &f.sxk, &f.sxj1, &f.sxk1}) {
-				if (*q) MF_HIP(hipFree(*q));
-				MF_HIP(hipMalloc((void**)q, need));
-			}
-			f.sx_cap = need;
+		size_t cap = f.sx_cap;
+		for (unsigned long long** q : {&f.sxj, &f.sxk, &f.sxj1, &f.sxk1}) {
+			cap = f.sx_cap;
+			MF_TRY(grow_buffer(q, &cap, need, st));
 		}
+		f.sx_cap = cap;
 		for (unsigned long long* q : {f.sxj, f.sxk, f.sxj1, f.sxk1}) MF_HIP(hipMemset(q, 0, f.sx_cap));
 		MF_HIP(hipMemset(f.ctl, 0, sizeof(FlowCtl)));
 		f.sgen = 0;
@@ -1330,44 +1365,43 @@ static int rows_next_gen(FlowState* f, hipStream_t st) {
 	}
 	return 0;
 }
+// the MIC factor in one dataflow sweep (k_mic_rows_init) of the system rows_prepare set f up for: from flags / A0 / Ai / Aj / Ak, or
+// from the packed bytes of the matrix-free set-up (pack; the five arrays are then null)
+static int launch_rows_init(const Dim& d, FlowState* f, const int32_t* flags, float* Aprecond, const float* A0, const float* Ai,
+                            const float* Aj, const float* Ak, const unsigned char* pack, hipStream_t st) {
+	MF_TRY(rows_next_gen(f, st));
+	const int ncu = cu_count(), grid = f->nblocks < ncu ? f->nblocks : ncu;
+	const bool vec = (d.sx % 4 == 0) && al16(flags) && al16(Aprecond) && al16(A0) && al16(Ai) && al16(Aj) && al16(Ak);
+	auto kern = vec ? k_mic_rows_init<true> : k_mic_rows_init<false>;
+	hipLaunchKernelGGL(kern, dim3(grid), dim3(ROWS_THREADS), 0, st, d, f->nbj, f->nbk, f->jb, f->nblocks, f->nchunks, f->border, f->ctl, f->rows_xt,
+	                   f->sxj, f->sxk, f->sxj1, f->sxk1, f->sgen, flags, Aprecond, A0, Ai, Aj, Ak, pack);
+	MF_LAUNCH_CHECK();
+	return 0;
+}
 
 // How the sweeps are parallelised (both give the bits of the serial sweep):
 // 2 "rows"  : one launch per sweep, a 7-wave workgroup per 8x8 bundle of x-rows streaming along x (default for 3D grids)
 // 0 "levels": one launch per tile hyperplane (no inter-workgroup waiting at all; the conservative fallback, 2.2 ms per 256^3 apply)
-// mf_set_mic_mode / MF_MIC_MODE choose the mode the NEXT mf_mic_init registers its system under; the apply sweeps of that system
-// follow the handle, a system the handle does not know is swept in the requested mode.
+// mf_set_mic_mode chooses the mode the NEXT mf_mic_init registers its system under; the apply sweeps of that system follow the
+// handle, a system the handle does not know is swept in the requested mode.
 // (Round 2 also carried "tiles", single-wave 8^3 tiles in one launch -- 1.32 ms -- and "rows-sb", 2 x 2 bundles per workgroup --
 // 1.05 ms; both bit-exact, both slower than "rows", deleted in round 3.)
-static int g_mic_mode = -1;     // requested mode: 0 levels, 2 rows
+static int g_mic_mode = 2;     // requested mode: 0 levels, 2 rows
 extern "C" int mf_set_mic_mode(const char* name) {
-	if (!name || !*name) g_mic_mode = -1;
+	if (!name || !*name || !strcmp(name, "rows")) g_mic_mode = 2;
 	else if (!strcmp(name, "levels")) g_mic_mode = 0;
-	else if (!strcmp(name, "rows")) g_mic_mode = 2;
 	else return fail("mf_set_mic_mode: unknown mode (rows | levels)");
 	return 0;
 }
-static int mic_mode_() {
-	if (g_mic_mode < 0) {
-		const char* e = getenv("MF_MIC_MODE");
-		g_mic_mode = (e && !strcmp(e, "levels")) ? 0 : 2;
-	}
-	return g_mic_mode;
-}
+int mf::mic_mode() { return g_mic_mode; }
 extern "C" int mf_pack_matrix(int sx, int sy, int sz, const int32_t* flags, const float* A0, const float* Ai, const float* Aj, const float* Ak, void* stream) {
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
-	int dev = 0;
-	MF_HIP(hipGetDevice(&dev));
-	FlowState& f = g_flow[dev];
+	FlowState& f = flow_state();
 	hipStream_t st = (hipStream_t)stream;
 	f.upack_ok_host = 0;
 	if (!d.is3d || (d.sx % 4) != 0) return 0;
-	if ((size_t)d.n > f.upack_cap) {
-		MF_HIP(hipStreamSynchronize(st));
-		if (f.upack) MF_HIP(hipFree(f.upack));
-		MF_HIP(hipMalloc((void**)&f.upack, (size_t)d.n + 64));
-		f.upack_cap = (size_t)d.n;
-	}
+	MF_TRY(grow_buffer(&f.upack, &f.upack_cap, (size_t)d.n + 64, st));
 	if (!f.upack_ok) MF_HIP(hipMalloc((void**)&f.upack_ok, 2 * sizeof(int)));
 	MF_HIP(hipMemsetAsync(f.upack_ok, 1, 2 * sizeof(int), st));
 	hipLaunchKernelGGL(k_mic_pack, dim3((unsigned)((d.n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, d.n, flags, A0, Ai, Aj, Ak, f.upack, f.upack_ok);
@@ -1376,99 +1410,67 @@ extern "C" int mf_pack_matrix(int sx, int sy, int sz, const int32_t* flags, cons
 	MF_HIP(hipMemcpyAsync(ok, f.upack_ok, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
 	MF_HIP(hipStreamSynchronize(st));
 	f.upack_ok_host = ok[0] != 0;
-	f.up_A0 = (ok[0] && ok[1] && A0) ? A0 : nullptr;      // the diagonal this set of bytes carries in bits 4-7, if any
-	f.up_flags = flags;
-	f.up_Ai = Ai;
-	f.up_Aj = Aj;
-	f.up_Ak = Ak;
+	f.up_A0 = (ok[0] && ok[1] && A0) ? A0 : nullptr;
+	f.up = FlowState::Grids{flags, Ai, Aj, Ak};
 	return 0;
 }
 
-// set by mic_launch_dot for the duration of one backward-sweep launch
-static thread_local double* g_dot_request = nullptr;
-static thread_local int g_dot_count = 0;
-static thread_local bool g_dot_empty_ext = false;
-static thread_local BetaTail g_dot_tail = BetaTail{nullptr, 0, nullptr, nullptr, 0};
-static thread_local bool g_dot_tail_done = false;
-// x-range the caller asks the sweeps of the registered system to keep to (mf::mic_set_trim): first cell, chunks of 8 cells; 0 = whole rows
-static thread_local int g_trim_xoff = 0, g_trim_chunks = 0;
 template <int MODE>
 static int launch_mic(const Dim& d, const int32_t* flags, float* dst, const float* var1, const float* Ap, const float* Ai,
-                      const float* Aj, const float* Ak, const CgScalars* sc, hipStream_t st) {
+                      const float* Aj, const float* Ak, const CgScalars* sc, hipStream_t st, MicSweep& o) {
+	o.ndot = 0;
+	o.tail_done = false;
 	const int nti = (d.sx + 7) / 8, ntj = (d.sy + 7) / 8, ntk = (d.sz + 7) / 8;
 	const int levels = nti + ntj + ntk - 2;
 	const bool vec = (d.sx % 4 == 0) && al16(flags) && al16(dst) && al16(var1) && al16(Ai) && al16(Aj) && al16(Ak) && (MODE == 0 || al16(Ap));
 	if constexpr (MODE != 0) {
-		int dev_ = 0;
-		MF_HIP(hipGetDevice(&dev_));
-		const FlowState& f0 = g_flow[dev_];
 		// the system mf_mic_init registered: its mode and its preconditioner blocks; any other system: requested mode, uncut
-		const bool same_system = f0.be_flags == flags && f0.be_Ap == Ap && f0.be_Aj == Aj && f0.be_Ak == Ak;
-		const int mode = same_system ? f0.mode : mic_mode_();
+		const FlowState& f0 = flow_state();
+		const bool same_system = f0.reg.of(flags, Ap, Aj, Ak);
+		const int mode = same_system ? f0.mode : mic_mode();
 		if (mode == 2 && d.is3d) {
 			FlowState* f;
 			MF_TRY(rows_prepare(d, &f, st, same_system ? f0.blk_rows : 0, same_system ? f0.blk_cells : 0));
 			MF_TRY(rows_next_gen(f, st));
-			static int ncu = 0;
-			if (!ncu) {
-				// one bundle per CU measured best (round 1: 834 us per apply with 256 workgroups, 1040 us with 512; round 2, with a
-				// packed-only <= 128-VGPR variant and a 32- / 48-step ring for two workgroups per CU: 445 vs 412 us, 217 vs 204 us per
-				// sweep -- mid-sweep the 256 bundles already stream ~4 TB/s, the rest of the sweep is the dependency chain)
-				int dev = 0;
-				ncu = 256;
-				(void)hipGetDevice(&dev);
-				(void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-				if (ncu < 1) ncu = 1;
-			}
-			const int grid = f->nblocks < ncu ? f->nblocks : ncu;
+			const int ncu = cu_count(), grid = f->nblocks < ncu ? f->nblocks : ncu;
 			const int* be = (f->bempty && same_system) ? f->bempty : nullptr;
-			static const bool nopack = getenv("MF_MIC_NOPACK") != nullptr;       // debugging: sweeps on the four coefficient arrays
-			const bool use_pack = !nopack && f->pack && (d.sx % 8 == 0) && f->pk_flags == flags && f->pk_Ai == Ai && f->pk_Aj == Aj && f->pk_Ak == Ak;
+			const bool use_pack = (d.sx % 8 == 0) && f->pack && f->pk.of(flags, Ai, Aj, Ak);
 			const unsigned char* pk = use_pack ? f->pack : nullptr;
-			double* dotp = (MODE == 2 && al16(var1) && f->nblocks <= MAX_BLOCKS) ? g_dot_request : nullptr;
-			g_dot_count = dotp ? f->nblocks : 0;
-			const int empty_ext = (MODE == 2 && dotp && be && g_dot_empty_ext) ? 1 : 0;
+			double* dotp = (MODE == 2 && al16(var1) && f->nblocks <= MAX_BLOCKS) ? o.dotpart : nullptr;
+			o.ndot = dotp ? f->nblocks : 0;
+			const int empty_ext = (MODE == 2 && dotp && be && o.empty_ext) ? 1 : 0;
+			// a separate launch sums the dot shares of the empty bundles (the sweep's workgroups draw several bundles each)
+			bool empty_dot = false;
 			if (MODE == 2 && dotp && be && f->nblocks > grid && !empty_ext) {
-				if (f->nempty_host < 0) {
-					// once per system: does any bundle sit out the sweeps?  (smoke scenes: none -- no extra launch per iteration)
-					static thread_local std::vector<int> hb;
-					hb.resize((size_t)f->nbj * f->nbk);
-					MF_HIP(hipMemcpyAsync(hb.data(), f->bempty, sizeof(int) * hb.size(), hipMemcpyDeviceToHost, st));
-					MF_HIP(hipStreamSynchronize(st));
-					int cnt = 0;
-					for (int v : hb) cnt += v != 0;
-					f->nempty_host = cnt;
-				}
-				if (f->nempty_host > 0 && f->nblocks > grid)
+				MF_TRY(count_empty_bundles(*f, st));
+				empty_dot = f->nempty_host > 0;
+				if (empty_dot)
 					hipLaunchKernelGGL(k_mic_empty_dot, dim3(f->nblocks), dim3(BLOCK), 0, st, d, f->nbj, f->nbk, f->nchunks * 8, be, dst, var1, sc, dotp);
 			}
-			// rows trimmed to the x-range of the fluid (mic_set_trim; only for the registered system on its packed bytes)
+			// rows trimmed to the x-range of the fluid (only for the registered system on its packed bytes)
 			int nch = f->nchunks, xoff0 = 0;
-			if (same_system && use_pack && g_trim_chunks > 0 && g_trim_chunks < f->nchunks && f->nxb == 1) {
-				nch = g_trim_chunks;
-				xoff0 = g_trim_xoff;
+			if (same_system && use_pack && o.trim_chunks > 0 && o.trim_chunks < f->nchunks && f->nxb == 1) {
+				nch = o.trim_chunks;
+				xoff0 = o.trim_xoff;
 			}
 			BetaTail ktail = BetaTail{nullptr, 0, nullptr, nullptr, 0};
-			if (MODE == 2 && dotp && (g_dot_tail.sc || g_dot_tail.sum_out) && !(be && f->nblocks > grid && !empty_ext && f->nempty_host > 0)) {
+			if (MODE == 2 && dotp && (o.tail.sc || o.tail.sum_out) && !empty_dot) {
 				// (not with the separate empty-share kernel: its partials are plain stores of another launch -- fine -- but keep it simple)
-				ktail = g_dot_tail;
+				ktail = o.tail;
 				ktail.nsig += f->nblocks;      // the sweep's own partials come first
-				g_dot_tail_done = true;
+				o.tail_done = true;
 			}
-			if (vec)
-				hipLaunchKernelGGL((k_mic_rows<MODE, true>), dim3(grid), dim3(ROWS_THREADS), 0, st, d, f->nbj, f->nbk, f->jb, f->nblocks, nch, xoff0, f->border + (MODE == 2 ? f->nblocks : 0), f->ctl, f->rows_xt + (MODE == 2 ? 1 : 0), f->sxj, f->sxk, f->sgen, flags, dst, var1, Ap, Ai, Aj, Ak, sc, dotp, be, pk, f->pack_ok, empty_ext, ktail);
-			else
-				hipLaunchKernelGGL((k_mic_rows<MODE, false>), dim3(grid), dim3(ROWS_THREADS), 0, st, d, f->nbj, f->nbk, f->jb, f->nblocks, nch, xoff0, f->border + (MODE == 2 ? f->nblocks : 0), f->ctl, f->rows_xt + (MODE == 2 ? 1 : 0), f->sxj, f->sxk, f->sgen, flags, dst, var1, Ap, Ai, Aj, Ak, sc, dotp, be, pk, f->pack_ok, empty_ext, ktail);
+			auto kern = vec ? k_mic_rows<MODE, true> : k_mic_rows<MODE, false>;
+			hipLaunchKernelGGL(kern, dim3(grid), dim3(ROWS_THREADS), 0, st, d, f->nbj, f->nbk, f->jb, f->nblocks, nch, xoff0, f->border + (MODE == 2 ? f->nblocks : 0),
+			                   f->ctl, f->rows_xt + (MODE == 2 ? 1 : 0), f->sxj, f->sxk, f->sgen, flags, dst, var1, Ap, Ai, Aj, Ak, sc, dotp, be, pk, f->pack_ok,
+			                   empty_ext, ktail);
 			MF_LAUNCH_CHECK();
 			return 0;
 		}
 	}
-	for (int L = 0; L < levels; L++) {
-		if (vec)
-			hipLaunchKernelGGL((k_mic_tiles<MODE, true>), dim3(ntj, ntk), dim3(64), 0, st, d, L, nti, ntj, ntk, flags, dst, var1, Ap, Ai, Aj, Ak, sc);
-		else
-			hipLaunchKernelGGL((k_mic_tiles<MODE, false>), dim3(ntj, ntk), dim3(64), 0, st, d, L, nti, ntj, ntk, flags, dst, var1, Ap, Ai, Aj, Ak, sc);
-	}
+	auto kern = vec ? k_mic_tiles<MODE, true> : k_mic_tiles<MODE, false>;
+	for (int L = 0; L < levels; L++)
+		hipLaunchKernelGGL(kern, dim3(ntj, ntk), dim3(64), 0, st, d, L, nti, ntj, ntk, flags, dst, var1, Ap, Ai, Aj, Ak, sc);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -1501,33 +1503,13 @@ static __global__ void __launch_bounds__(BLOCK) k_mic_fin_maxabs_live(int nb, co
 }
 
 namespace mf {
-void mic_set_trim(int xoff_cells, int nchunks) {
-	g_trim_xoff = xoff_cells;
-	g_trim_chunks = nchunks;
-}
-int mic_launch(int mode, const Dim& d, const int32_t* flags, float* dst, const float* var1, const float* Ap, const float* Ai,
-               const float* Aj, const float* Ak, const CgScalars* sc, hipStream_t st) {
-	if (mode == 0) return launch_mic<0>(d, flags, dst, var1, Ap, Ai, Aj, Ak, sc, st);
-	if (mode == 1) return launch_mic<1>(d, flags, dst, var1, Ap, Ai, Aj, Ak, sc, st);
-	return launch_mic<2>(d, flags, dst, var1, Ap, Ai, Aj, Ak, sc, st);
-}
-// backward sweep with GridDotProduct(dst, var1) fused: *ndot = number of partials written to dotpart (0: not fused in
-// this mode -- the caller runs its own dot kernel)
-int mic_launch_dot(const Dim& d, const int32_t* flags, float* dst, const float* var1, const float* Ap, const float* Ai,
-                   const float* Aj, const float* Ak, const CgScalars* sc, double* dotpart, int* ndot, hipStream_t st, bool empty_ext,
-                   BetaTail tail, bool* tail_done) {
-	g_dot_request = dotpart;
-	g_dot_empty_ext = empty_ext;
-	g_dot_tail = tail;
-	g_dot_tail_done = false;
-	g_dot_count = 0;
-	const int rc = launch_mic<2>(d, flags, dst, var1, Ap, Ai, Aj, Ak, sc, st);
-	g_dot_request = nullptr;
-	g_dot_empty_ext = false;
-	g_dot_tail = BetaTail{nullptr, 0, nullptr, nullptr, 0};
-	if (tail_done) *tail_done = g_dot_tail_done;
-	*ndot = g_dot_count;
-	return rc;
+int mic_sweep(int mode, const Dim& d, const int32_t* flags, float* dst, const float* var1, const float* Ap, const float* Ai,
+              const float* Aj, const float* Ak, const CgScalars* sc, hipStream_t st, MicSweep* opt) {
+	MicSweep plain;
+	MicSweep& o = opt ? *opt : plain;
+	if (mode == 0) return launch_mic<0>(d, flags, dst, var1, Ap, Ai, Aj, Ak, sc, st, o);
+	if (mode == 1) return launch_mic<1>(d, flags, dst, var1, Ap, Ai, Aj, Ak, sc, st, o);
+	return launch_mic<2>(d, flags, dst, var1, Ap, Ai, Aj, Ak, sc, st, o);
 }
 int mic_apply_dot_fold(const Dim& d, const int32_t* flags, float* dst, const float* var1, const float* Ap, const float* Ai,
                        const float* Aj, const float* Ak, double* dot_dev, int nbr, const float* fpart, double* maxabs_dev,
@@ -1537,12 +1519,13 @@ int mic_apply_dot_fold(const Dim& d, const int32_t* flags, float* dst, const flo
 	double* part = ws->partials + 2 * MAX_BLOCKS;
 	// live->done (the z-slab solver's iterations queued past the stop): both sweeps return at once, *dot_dev / *maxabs_dev keep the
 	// values of the stopping iteration (dst and var1 have not changed since)
-	MF_TRY(mic_launch(1, d, flags, dst, var1, Ap, Ai, Aj, Ak, live, st));
-	int nsig = 0;
-	bool folded = false;
-	BetaTail tail = BetaTail{nullptr, nbr, fpart, nullptr, 0, dot_dev, maxabs_dev, live};
-	MF_TRY(mic_launch_dot(d, flags, dst, var1, Ap, Ai, Aj, Ak, live, part, &nsig, st, false, tail, &folded));
-	if (folded) return 0;
+	MF_TRY(mic_sweep(1, d, flags, dst, var1, Ap, Ai, Aj, Ak, live, st));
+	MicSweep bwd;
+	bwd.dotpart = part;
+	bwd.tail = BetaTail{nullptr, nbr, fpart, nullptr, 0, dot_dev, maxabs_dev, live};
+	MF_TRY(mic_sweep(2, d, flags, dst, var1, Ap, Ai, Aj, Ak, live, st, &bwd));
+	if (bwd.tail_done) return 0;
+	int nsig = bwd.ndot;
 	if (nsig == 0) {
 		nsig = blocks_for(d.n, BLOCK * 4, 2048);
 		hipLaunchKernelGGL(k_mic_plain_dot, dim3(nsig), dim3(BLOCK), 0, st, d.n, dst, var1, part);
@@ -1558,12 +1541,8 @@ int mic_pack_query(const Dim& d, const int32_t* flags, const float* A0, const fl
                    const unsigned char** pack, bool* a0_packed, hipStream_t st) {
 	*pack = nullptr;
 	*a0_packed = false;
-	static const bool nopack = getenv("MF_MIC_NOPACK") != nullptr;
-	if (nopack || !d.is3d) return 0;
-	int dev = 0;
-	MF_HIP(hipGetDevice(&dev));
-	FlowState& f = g_flow[dev];
-	if (f.mode != 2 || !f.pack || !f.pack_ok || f.pk_flags != flags || f.pk_Ai != Ai || f.pk_Aj != Aj || f.pk_Ak != Ak) return 0;
+	const FlowState& f = flow_state();
+	if (!d.is3d || f.mode != 2 || !f.pack || !f.pack_ok || !f.pk.of(flags, Ai, Aj, Ak)) return 0;
 	int ok[2] = {0, 0};
 	MF_HIP(hipMemcpyAsync(ok, f.pack_ok, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
 	MF_HIP(hipStreamSynchronize(st));
@@ -1571,81 +1550,53 @@ int mic_pack_query(const Dim& d, const int32_t* flags, const float* A0, const fl
 	*a0_packed = ok[0] && ok[1] && f.pk_A0 == A0 && A0 != nullptr;
 	return 0;
 }
-// the empty-bundle map of the system registered for (flags, Ap, Aj, Ak) in "rows" mode, if that system has empty bundles and its sweeps
-// draw several tickets per workgroup (then the shares of those bundles in the fused dot are worth summing elsewhere): one small read-back
-// per system.  *bempty = nullptr otherwise.
-int mic_empty_map(const Dim& d, const int32_t* flags, const float* Ap, const float* Aj, const float* Ak, const int** bempty, int* nbj, hipStream_t st,
-                  bool any_size) {
+int mic_empty_map(const Dim& d, const int32_t* flags, const float* Ap, const float* Aj, const float* Ak, const int** bempty, int* nbj, bool* several,
+                  hipStream_t st) {
 	*bempty = nullptr;
 	*nbj = 0;
-	int dev = 0;
-	MF_HIP(hipGetDevice(&dev));
-	FlowState& f = g_flow[dev];
-	if (!d.is3d || f.mode != 2 || !f.bempty || f.be_flags != flags || f.be_Ap != Ap || f.be_Aj != Aj || f.be_Ak != Ak) return 0;
+	*several = false;
+	FlowState& f = flow_state();
+	if (!d.is3d || f.mode != 2 || !f.bempty || !f.reg.of(flags, Ap, Aj, Ak)) return 0;
 	if (f.nbj != (d.sy + 7) / 8 || f.nbk != (d.sz + 7) / 8 || f.nxb != 1) return 0;
-	int ncu = 256;
-	(void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-	if (f.nblocks <= ncu && !any_size) return 0;
-	if (f.nempty_host < 0) {
-		static thread_local std::vector<int> hb;
-		hb.resize((size_t)f.nbj * f.nbk);
-		MF_HIP(hipMemcpyAsync(hb.data(), f.bempty, sizeof(int) * hb.size(), hipMemcpyDeviceToHost, st));
-		MF_HIP(hipStreamSynchronize(st));
-		int cnt = 0;
-		for (int v : hb) cnt += v != 0;
-		f.nempty_host = cnt;
-	}
+	MF_TRY(count_empty_bundles(f, st));
 	if (f.nempty_host > 0) {
 		*bempty = f.bempty;
 		*nbj = f.nbj;
+		*several = f.nblocks > cu_count();
 	}
 	return 0;
 }
 // packed bytes built by mf_pack_matrix for exactly these grids (no synchronisation: the verdict was read when they were built)
 const unsigned char* mic_pack_user(const int32_t* flags, const float* A0, const float* Ai, const float* Aj, const float* Ak, bool* a0_packed) {
+	const FlowState& f = flow_state();
 	*a0_packed = false;
-	int dev = 0;
-	if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-	FlowState& f = g_flow[dev];
-	if (!f.upack || !f.upack_ok_host || f.up_flags != flags || f.up_Ai != Ai || f.up_Aj != Aj || f.up_Ak != Ak) return nullptr;
+	if (!f.upack || !f.upack_ok_host || !f.up.of(flags, Ai, Aj, Ak)) return nullptr;
 	*a0_packed = f.up_A0 != nullptr && f.up_A0 == A0;
 	return f.upack;
 }
 int mic_flow_error() {
-	int dev = 0;
-	MF_HIP(hipGetDevice(&dev));
-	if (!g_flow[dev].ctl) return 0;
+	FlowState& f = flow_state();
+	if (!f.ctl) return 0;
 	FlowCtl fc;
-	MF_HIP(hipMemcpy(&fc, g_flow[dev].ctl, sizeof fc, hipMemcpyDeviceToHost));
+	MF_HIP(hipMemcpy(&fc, f.ctl, sizeof fc, hipMemcpyDeviceToHost));
 	if (fc.err) {
-		MF_HIP(hipMemset(g_flow[dev].ctl, 0, sizeof(FlowCtl)));
+		MF_HIP(hipMemset(f.ctl, 0, sizeof(FlowCtl)));
 		return fail("MIC dataflow sweep: a workgroup timed out waiting for its predecessor faces");
 	}
 	return 0;
 }
-int mic_mode() { return mic_mode_(); }      // the requested mode (0 levels, 2 rows)
 // matrix-free set-up (mf_solve_pressure_fused): the handle's packed-byte and empty-bundle buffers for a d-sized system, the map
 // preset to "empty" (the set-up kernel clears the entry of every bundle it finds a fluid cell in)
 int mic_fused_begin(const Dim& d, hipStream_t st, unsigned char** pack, int** bempty, int* nbj) {
 	if (!d.is3d || (d.sx % 8) != 0) return fail("mic_fused_begin: needs a 3D grid with sx % 8 == 0");
 	FlowState* f;
 	MF_TRY(rows_prepare(d, &f, st, 0, 0));
-	if (f->nblocks + 1 > f->bempty_cap) {
-		MF_HIP(hipStreamSynchronize(st));
-		if (f->bempty) MF_HIP(hipFree(f->bempty));
-		MF_HIP(hipMalloc((void**)&f->bempty, sizeof(int) * (f->nblocks + 1)));
-		f->bempty_cap = f->nblocks + 1;
-	}
-	if ((size_t)d.n > f->pack_cap) {
-		MF_HIP(hipStreamSynchronize(st));
-		if (f->pack) MF_HIP(hipFree(f->pack));
-		MF_HIP(hipMalloc((void**)&f->pack, (size_t)d.n + 64));
-		f->pack_cap = (size_t)d.n;
-	}
+	f->reg = f->pk = FlowState::Grids{};      // map and bytes are rebuilt: no registered system, no packed grids until mic_fused_finish
+	MF_TRY(grow_buffer(&f->bempty, &f->bempty_cap, sizeof(int) * (f->nblocks + 1), st));
+	MF_TRY(grow_buffer(&f->pack, &f->pack_cap, (size_t)d.n + 64, st));
 	if (!f->pack_ok) MF_HIP(hipMalloc((void**)&f->pack_ok, 2 * sizeof(int)));
 	MF_HIP(hipMemsetD32Async((hipDeviceptr_t)f->bempty, 1, f->nblocks + 1, st));
 	MF_HIP(hipMemsetAsync(f->pack_ok, 1, 2 * sizeof(int), st));      // both verdicts hold by construction
-	f->be_flags = nullptr;
 	*pack = f->pack;
 	*bempty = f->bempty;
 	*nbj = f->nbj;
@@ -1653,26 +1604,16 @@ int mic_fused_begin(const Dim& d, hipStream_t st, unsigned char** pack, int** be
 }
 // ... and the MIC factor from those bytes (k_mic_rows_init), registered as the system of (flags, Aprecond) with no coefficient arrays
 int mic_fused_finish(const Dim& d, const int32_t* flags, float* Aprecond, hipStream_t st) {
-	int dev = 0;
-	MF_HIP(hipGetDevice(&dev));
-	FlowState* f;
-	MF_TRY(rows_prepare(d, &f, st, 0, 0));
+	FlowState* f = &flow_state();      // (mic_fused_begin prepared it for d)
 	MF_HIP(hipMemsetAsync(Aprecond, 0, sizeof(float) * d.n, st));
-	MF_TRY(rows_next_gen(f, st));
-	int ncu = 256;
-	(void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-	const int grid = f->nblocks < ncu ? f->nblocks : ncu;
 	if (!al16(Aprecond)) return fail("mic_fused_finish: Aprecond must be 16-byte aligned");
-	hipLaunchKernelGGL((k_mic_rows_init<true>), dim3(grid), dim3(ROWS_THREADS), 0, st, d, f->nbj, f->nbk, f->jb, f->nblocks, f->nchunks, f->border, f->ctl, f->rows_xt, f->sxj, f->sxk, f->sxj1, f->sxk1, f->sgen, flags, Aprecond, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const unsigned char*)f->pack);
-	MF_LAUNCH_CHECK();
+	MF_TRY(launch_rows_init(d, f, flags, Aprecond, nullptr, nullptr, nullptr, nullptr, f->pack, st));
 	f->mode = 2;
 	f->blk_rows = f->blk_cells = 0;
-	f->be_flags = flags;
-	f->be_Ap = Aprecond;
-	f->be_Aj = f->be_Ak = nullptr;
+	f->reg = FlowState::Grids{flags, Aprecond, nullptr, nullptr};
 	f->nempty_host = -1;
-	f->pk_flags = flags;
-	f->pk_A0 = f->pk_Ai = f->pk_Aj = f->pk_Ak = nullptr;
+	f->pk = FlowState::Grids{flags, nullptr, nullptr, nullptr};
+	f->pk_A0 = nullptr;
 	return 0;
 }
 }  // namespace mf
@@ -1692,58 +1633,32 @@ int mf_mic_init_blocked(int sx, int sy, int sz, const int32_t* flags, float* Apr
 	if (!d.is3d) return fail("mICP only supports 3D grids so far");
 	hipStream_t st = (hipStream_t)stream;
 	MF_HIP(hipMemsetAsync(Aprecond, 0, sizeof(float) * d.n, st));
-	const int mode = mic_mode_();
-	int dev = 0;
-	MF_HIP(hipGetDevice(&dev));
-	g_flow[dev].mode = mode;
-	g_flow[dev].be_flags = nullptr;        // no registered system until this call has built one
-	if (mode != 2) return mic_launch(0, d, flags, Aprecond, A0, nullptr, Ai, Aj, Ak, nullptr, st);   // one launch per tile hyperplane
+	FlowState& f0 = flow_state();
+	f0.mode = mic_mode();
+	f0.reg = FlowState::Grids{};        // no registered system until this call has built one
+	if (f0.mode != 2) return mic_sweep(0, d, flags, Aprecond, A0, nullptr, Ai, Aj, Ak, nullptr, st);   // one launch per tile hyperplane
 	// "rows": one dataflow sweep (k_mic_rows_init)
 	FlowState* f;
 	MF_TRY(rows_prepare(d, &f, st, rows_j, cells_x));
-	MF_TRY(rows_next_gen(f, st));
-	int ncu = 256;
-	(void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-	const int grid = f->nblocks < ncu ? f->nblocks : ncu;
-	const bool vec = (d.sx % 4 == 0) && al16(flags) && al16(Aprecond) && al16(A0) && al16(Ai) && al16(Aj) && al16(Ak);
-	if (vec)
-		hipLaunchKernelGGL((k_mic_rows_init<true>), dim3(grid), dim3(ROWS_THREADS), 0, st, d, f->nbj, f->nbk, f->jb, f->nblocks, f->nchunks, f->border, f->ctl, f->rows_xt, f->sxj, f->sxk, f->sxj1, f->sxk1, f->sgen, flags, Aprecond, A0, Ai, Aj, Ak, (const unsigned char*)nullptr);
-	else
-		hipLaunchKernelGGL((k_mic_rows_init<false>), dim3(grid), dim3(ROWS_THREADS), 0, st, d, f->nbj, f->nbk, f->jb, f->nblocks, f->nchunks, f->border, f->ctl, f->rows_xt, f->sxj, f->sxk, f->sxj1, f->sxk1, f->sgen, flags, Aprecond, A0, Ai, Aj, Ak, (const unsigned char*)nullptr);
-	MF_LAUNCH_CHECK();
+	MF_TRY(launch_rows_init(d, f, flags, Aprecond, A0, Ai, Aj, Ak, nullptr, st));
 	// which row bundles the apply sweeps of THIS system may leave out (valid for the grids given here)
 	f->blk_rows = rows_j;
 	f->blk_cells = cells_x;
-	if (f->nblocks + 1 > f->bempty_cap) {
-		MF_HIP(hipStreamSynchronize(st));
-		if (f->bempty) MF_HIP(hipFree(f->bempty));
-		MF_HIP(hipMalloc((void**)&f->bempty, sizeof(int) * (f->nblocks + 1)));
-		f->bempty_cap = f->nblocks + 1;
-	}
+	MF_TRY(grow_buffer(&f->bempty, &f->bempty_cap, sizeof(int) * (f->nblocks + 1), st));
 	MF_HIP(hipMemsetAsync(f->bempty + f->nbj * f->nbk, 0, sizeof(int), st));
 	hipLaunchKernelGGL(k_bundle_empty, dim3(f->nbj * f->nbk), dim3(BLOCK), 0, st, d, f->nbj, flags, Aj, Ak, f->bempty);
 	MF_LAUNCH_CHECK();
-	f->be_flags = flags;
-	f->be_Ap = Aprecond;
-	f->be_Aj = Aj;
-	f->be_Ak = Ak;
+	f->reg = FlowState::Grids{flags, Aprecond, Aj, Ak};
 	f->nempty_host = -1;
 	// packed operands for the apply sweeps
-	if ((size_t)d.n > f->pack_cap) {
-		MF_HIP(hipStreamSynchronize(st));
-		if (f->pack) MF_HIP(hipFree(f->pack));
-		MF_HIP(hipMalloc((void**)&f->pack, (size_t)d.n + 64));
-		f->pack_cap = (size_t)d.n;
-	}
+	f->pk = FlowState::Grids{};
+	MF_TRY(grow_buffer(&f->pack, &f->pack_cap, (size_t)d.n + 64, st));
 	if (!f->pack_ok) MF_HIP(hipMalloc((void**)&f->pack_ok, 2 * sizeof(int)));
 	MF_HIP(hipMemsetAsync(f->pack_ok, 1, 2 * sizeof(int), st));     // non-zero = valid until k_mic_pack clears it
 	hipLaunchKernelGGL(k_mic_pack, dim3((unsigned)((d.n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, d.n, flags, A0, Ai, Aj, Ak, f->pack, f->pack_ok);
 	MF_LAUNCH_CHECK();
 	f->pk_A0 = A0;
-	f->pk_flags = flags;
-	f->pk_Ai = Ai;
-	f->pk_Aj = Aj;
-	f->pk_Ak = Ak;
+	f->pk = FlowState::Grids{flags, Ai, Aj, Ak};
 	return 0;
 }
 int mf_mic_apply(int sx, int sy, int sz, const int32_t* flags, float* dst, const float* var1, const float* Aprecond,
@@ -1751,8 +1666,8 @@ int mf_mic_apply(int sx, int sy, int sz, const int32_t* flags, float* dst, const
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
 	if (!d.is3d) return fail("mICP only supports 3D grids so far");
-	MF_TRY(mic_launch(1, d, flags, dst, var1, Aprecond, Ai, Aj, Ak, nullptr, (hipStream_t)stream));
-	return mic_launch(2, d, flags, dst, var1, Aprecond, Ai, Aj, Ak, nullptr, (hipStream_t)stream);
+	MF_TRY(mic_sweep(1, d, flags, dst, var1, Aprecond, Ai, Aj, Ak, nullptr, (hipStream_t)stream));
+	return mic_sweep(2, d, flags, dst, var1, Aprecond, Ai, Aj, Ak, nullptr, (hipStream_t)stream);
 }
 
 int mf_mic_apply_dot_dev(int sx, int sy, int sz, const int32_t* flags, float* dst, const float* var1, const float* Aprecond,

@@ -27,38 +27,63 @@ struct BetaTail {
 	double* maxabs_out;
 	const CgScalars* live;
 };
+// options of one MIC sweep (mic_sweep), filled by the caller; the outputs are written by the call
+struct MicSweep {
+	// backward sweep in "rows" mode: GridDotProduct(dst, var1) fused into the write-back, one partial per bundle into dotpart (summed
+	// in index order by the caller)
+	double* dotpart = nullptr;
+	// the caller sums the dot shares of the bundles the sweep leaves out itself (mic_empty_map tells which), their entries come out 0
+	bool empty_ext = false;
+	// the beta step (or the z-slab solver's fold) as the tail of the sweep's last workgroup, where the sweep can take it
+	BetaTail tail = BetaTail{nullptr, 0, nullptr, nullptr, 0};
+	// the sweeps of the registered system (on its packed bytes) cover the cells [trim_xoff, trim_xoff + 8 trim_chunks) of every row
+	// only (0 chunks: whole rows).  The caller guarantees that every cell outside has a zero packed byte (non-fluid, no couplings) and
+	// the value +0 in the swept grid, and accounts for nothing of them in the fused dot (their products are +0).
+	int trim_xoff = 0, trim_chunks = 0;
+	int ndot = 0;             // out: partials written to dotpart (0: the active mode cannot fuse the dot -- the caller runs its own)
+	bool tail_done = false;   // out: the tail was folded into the sweep
+};
 namespace mf {
 // mode 0: InitPreconditionModifiedIncompCholesky2 (dst := Aprecond, var1 := A0); 1 / 2: forward / backward substitution
-// of ApplyPreconditionModifiedIncompCholesky2.  sc (nullable): skip when sc->done.
-int mic_launch(int mode, const Dim& d, const int32_t* flags, float* dst, const float* var1, const float* Ap, const float* Ai,
-               const float* Aj, const float* Ak, const CgScalars* sc, hipStream_t st);
-// backward substitution with GridDotProduct(dst, var1) fused into the sweep ("rows" mode): *ndot partials in dotpart, summed in
-// index order by the caller; *ndot == 0 when the active mode cannot fuse it (the caller then runs its own dot kernel)
-int mic_launch_dot(const Dim& d, const int32_t* flags, float* dst, const float* var1, const float* Ap, const float* Ai,
-                   const float* Aj, const float* Ak, const CgScalars* sc, double* dotpart, int* ndot, hipStream_t st, bool empty_ext = false,
-                   BetaTail tail = BetaTail{nullptr, 0, nullptr, nullptr, 0}, bool* tail_done = nullptr);
+// of ApplyPreconditionModifiedIncompCholesky2.  sc (nullable): skip when sc->done.  opt (nullable): see MicSweep
+int mic_sweep(int mode, const Dim& d, const int32_t* flags, float* dst, const float* var1, const float* Ap, const float* Ai,
+              const float* Aj, const float* Ak, const CgScalars* sc, hipStream_t st, MicSweep* opt = nullptr);
 // forward + backward substitution with dot(dst, var1) -> *dot_dev and (nbr > 0) the max |.| of the nbr min / max pairs in fpart ->
 // *maxabs_dev (skipped once live->done): folded by the backward sweep's last workgroup where the active mode allows, by one-block
 // kernels behind it otherwise
 int mic_apply_dot_fold(const Dim& d, const int32_t* flags, float* dst, const float* var1, const float* Ap, const float* Ai,
                        const float* Aj, const float* Ak, double* dot_dev, int nbr, const float* fpart, double* maxabs_dev,
                        const CgScalars* live, hipStream_t st);
-// empty_ext: the caller sums the shares of the bundles the sweep leaves out itself (mic_empty_map tells which), their entries come out 0
-// (any_size: also where every workgroup draws one bundle only and the sweep sums the shares of the empty ones itself -- the map is then only
-// what the vector kernels of the PCG skip by)
-int mic_empty_map(const Dim& d, const int32_t* flags, const float* Ap, const float* Aj, const float* Ak, const int** bempty, int* nbj, hipStream_t st,
-                  bool any_size = false);
+// the empty-bundle map of the system registered for (flags, Ap, Aj, Ak) in "rows" mode, if that system has empty bundles (one small
+// read-back per system); *bempty = nullptr otherwise.  *several: the sweeps draw several bundles per workgroup -- then the shares of the
+// empty bundles in the fused dot are worth summing elsewhere (MicSweep::empty_ext); otherwise the map is only what the vector kernels of
+// the PCG skip by
+int mic_empty_map(const Dim& d, const int32_t* flags, const float* Ap, const float* Aj, const float* Ak, const int** bempty, int* nbj, bool* several,
+                  hipStream_t st);
 // packed {fluid, Ai, Aj, Ak} bytes built by the last mf_mic_init for exactly these grids (nullptr when unavailable / not exact);
 // synchronises the stream once.  *a0_packed: bits 4-7 of every byte hold the (small integer) diagonal A0 of these grids as well
 int mic_pack_query(const Dim& d, const int32_t* flags, const float* A0, const float* Ai, const float* Aj, const float* Ak,
                    const unsigned char** pack, bool* a0_packed, hipStream_t st);
 // packed bytes built by mf_pack_matrix for exactly these grids, or nullptr (no synchronisation); *a0_packed: they carry this A0
 const unsigned char* mic_pack_user(const int32_t* flags, const float* A0, const float* Ai, const float* Aj, const float* Ak, bool* a0_packed);
-int mic_mode();          // the requested sweep mode: 0 levels, 2 rows
-// until reset with (0, 0): the apply sweeps of the registered system (on its packed bytes) cover the cells [xoff, xoff + 8 nchunks) of
-// every row only.  The caller guarantees that every cell outside has a zero packed byte (non-fluid, no couplings) and the value +0 in
-// the swept grid, and accounts for nothing of them in the fused dot (their products are +0).
-void mic_set_trim(int xoff_cells, int nchunks);
+int mic_mode();          // the requested sweep mode (mf_set_mic_mode): 0 levels, 2 rows
+// device buffer growth: when *cap < bytes, allocates `bytes` bytes into a temporary and only then synchronises st (queued work may still
+// read the old buffer), frees the old buffer and sets *buf and *cap.  On failure *buf and *cap keep their old, consistent values
+template <class T>
+int grow_buffer(T** buf, size_t* cap, size_t bytes, hipStream_t st) {
+	if (bytes <= *cap) return 0;
+	T* nb = nullptr;
+	MF_HIP(hipMalloc((void**)&nb, bytes));
+	hipError_t e = *buf ? hipStreamSynchronize(st) : hipSuccess;
+	if (e == hipSuccess) e = hipFree(*buf);
+	if (e != hipSuccess) {
+		(void)hipFree(nb);
+		return fail("grow_buffer: %s", hipGetErrorString(e));
+	}
+	*buf = nb;
+	*cap = bytes;
+	return 0;
+}
 // matrix-free set-up of mf_solve_pressure_fused: buffers of the system handle (empty-bundle map preset to 1 = empty), then the MIC
 // factor from the packed bytes and the registration of (flags, Aprecond) as a system without coefficient arrays
 int mic_fused_begin(const Dim& d, hipStream_t st, unsigned char** pack, int** bempty, int* nbj);

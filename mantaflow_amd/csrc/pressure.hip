@@ -20,89 +20,10 @@ static thread_local int g_last_shortcut[3] = {0, 0, 0};      // what mf_cg_last_
 //   Optional fusion: per-block fp64 partial sums of dst*src (GridDotProduct(tmp, search)).
 // =========================================================================================================
 
-template <bool DOT, bool IS3D>
-__global__ void __launch_bounds__(BLOCK)
-k_apply_matrix_v4(Dim d, const int32_t* __restrict__ flags, float* __restrict__ dst, const float* __restrict__ src,
-                  const float* __restrict__ A0, const float* __restrict__ Ai, const float* __restrict__ Aj,
-                  const float* __restrict__ Ak, double* __restrict__ partials, const CgScalars* __restrict__ sc, int qpt) {
-	if (DOT && sc->done) return;
-	const int64_t nq = d.n >> 2;
-	const int qx = d.sx >> 2;  // quads per row (sx % 4 == 0)
-	double acc = 0.0;
-	// each block owns a contiguous run of qpt*BLOCK quads; with the XCD remap every XCD sweeps one contiguous
-	// z-slab front to back, so the +-Z neighbour planes are still in that XCD's L2 when they are re-read
-	const int vb = xcd_swizzle(blockIdx.x, gridDim.x);
-	const int64_t base = (int64_t)vb * BLOCK * qpt + threadIdx.x;
-	for (int t = 0; t < qpt; t++) {
-		const int64_t q = base + (int64_t)t * BLOCK;
-		if (q >= nq) break;
-		const int64_t idx = q << 2;
-		const int4 f = ((const int4*)flags)[q];
-		const float4 s = ((const float4*)src)[q];
-		float4 r = s;
-		if ((f.x | f.y | f.z | f.w) & MF_FLUID) {
-			const int64_t row = q / qx;
-			const int i0 = (int)(q - row * qx) << 2;
-			const int j = (int)(row % d.sy);
-			const int k = (int)(row / d.sy);
-			const float4 a0 = ((const float4*)A0)[q];
-			const float4 ai = ((const float4*)Ai)[q];
-			const float4 aj = ((const float4*)Aj)[q];
-			const float sl = (idx > 0) ? src[idx - 1] : 0.f;
-			const float al = (idx > 0) ? Ai[idx - 1] : 0.f;
-			const float sr = (idx + 4 < d.n) ? src[idx + 4] : 0.f;
-			const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-			const float4 sym = (j > 0) ? *(const float4*)(src + idx - d.Y) : z4;
-			const float4 ajm = (j > 0) ? *(const float4*)(Aj + idx - d.Y) : z4;
-			const float4 syp = (j < d.sy - 1) ? *(const float4*)(src + idx + d.Y) : z4;
-			float4 szm = z4, akm = z4, szp = z4, ak = z4;
-			if (IS3D) {
-				ak = ((const float4*)Ak)[q];
-				if (k > 0) {
-					szm = *(const float4*)(src + idx - d.Z);
-					akm = *(const float4*)(Ak + idx - d.Z);
-				}
-				if (k < d.sz - 1) szp = *(const float4*)(src + idx + d.Z);
-			}
-			(void)i0;
-#define CELL(c, SL, AL, SR)                                                                       \
-	if (f.c & MF_FLUID) {                                                                         \
-		float v = s.c * a0.c;                                                                     \
-		v = v + (SL) * (AL);                                                                      \
-		v = v + (SR) * ai.c;                                                                      \
-		v = v + sym.c * ajm.c;                                                                    \
-		v = v + syp.c * aj.c;                                                                     \
-		if (IS3D) {                                                                               \
-			v = v + szm.c * akm.c;                                                                \
-			v = v + szp.c * ak.c;                                                                 \
-		}                                                                                         \
-		r.c = v;                                                                                  \
-	}
-			CELL(x, sl, al, s.y)
-			CELL(y, s.x, ai.x, s.z)
-			CELL(z, s.y, ai.y, s.w)
-			CELL(w, s.z, ai.z, sr)
-#undef CELL
-		}
-		((float4*)dst)[q] = r;
-		if (DOT) {
-			const float p0 = r.x * s.x, p1 = r.y * s.y, p2 = r.z * s.z, p3 = r.w * s.w;
-			acc += (double)p0;
-			acc += (double)p1;
-			acc += (double)p2;
-			acc += (double)p3;
-		}
-	}
-	if (DOT) {
-		acc = block_sum(acc);
-		if (threadIdx.x == 0) partials[blockIdx.x] = acc;
-	}
-}
-
 // v5: every load is issued before anything depends on it (no flags -> operand round trip), each thread owns R
 // consecutive y-rows of one x-quad so src[j+-1] / Aj[j-1] are reused from registers, and the +-X neighbours come
-// from the adjacent lanes (DPP wave shift) instead of three extra 4-byte-per-lane loads.  Same arithmetic, same
-// order per cell as v4.
+// from the adjacent lanes (DPP wave shift) instead of three extra 4-byte-per-lane loads.  Per cell: the 7 products of the
+// reference in its order.
 __device__ __forceinline__ float wave_shr1(float v) {  // lane l gets lane l-1 (lane 0: unchanged)
 	return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x138, 0xf, 0xf, false));
 }
@@ -334,46 +255,38 @@ k_apply_matrix_scalar(Dim d, const int32_t* __restrict__ flags, float* __restric
 
 static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-// returns the number of blocks launched (== number of partials written when DOT)
+// what ApplyMatrix may use beyond the four coefficient grids (every field optional)
+struct AmOpts {
+	const unsigned char* pack = nullptr;     // packed bytes of these grids (k_mic_pack) instead of flags / Ai / Aj / Ak
+	bool a0p = false;                        // ... that carry A0 in bits 4-7 as well
+	int dk0 = 0, dk1 = 0x7fffffff;           // DOT: the planes [dk0, dk1) only (a z-slab's own)
+	// liquid scenes (mf_cg_solve): the 8 x 8 bundles of rows to skip (nbj per row of bundles), honoured while *outside_bad == 0
+	// (k_cg_outside_zero), and the x-range of the packed system (k_pack_xrange) whose outside is skipped as well
+	const int* bempty = nullptr;
+	int nbj = 0;
+	const int* outside_bad = nullptr;
+	const int* xr = nullptr;
+	int nt = -1;                             // DOT: non-temporal vector streams -- 1 on, 0 off, -1 by size (PCG_NT_CELLS)
+};
+// *nblocks: the number of blocks launched (== number of partials written when DOT); *ranged: DOT honoured dk0 / dk1
 template <bool DOT>
 static int launch_apply_matrix(const Dim& d, const int32_t* flags, float* dst, const float* src, const float* A0,
                                const float* Ai, const float* Aj, const float* Ak, double* partials,
-                               const CgScalars* sc, hipStream_t st, int* nblocks, const unsigned char* pack = nullptr,
-                               int dk0 = 0, int dk1 = 0x7fffffff, bool* ranged = nullptr, bool a0p = false, const int* bempty = nullptr,
-                               int nbj = 0, const int* outside_bad = nullptr, const int* xr = nullptr, int nt = -1) {
+                               const CgScalars* sc, hipStream_t st, const AmOpts& o = AmOpts{}, int* nblocks = nullptr, bool* ranged = nullptr) {
 	if (ranged) *ranged = false;
-	const int a0pn = (a0p ? 1 : 0) | ((DOT && (nt < 0 ? d.n > PCG_NT_CELLS : nt != 0)) ? 2 : 0);
+	const int a0pn = (o.a0p ? 1 : 0) | ((DOT && (o.nt < 0 ? d.n > PCG_NT_CELLS : o.nt != 0)) ? 2 : 0);
 	const bool vec = (d.sx % 4 == 0) && al16(flags) && al16(dst) && al16(src) && al16(A0) && al16(Ai) && al16(Aj) && al16(Ak);
 	int nb;
-	static const int am_rows = [] {
-		const char* e = getenv("MF_AM_ROWS");
-		return e ? atoi(e) : 2;
-	}();
-	if (vec && am_rows > 0) {
-		const int R = am_rows >= 4 ? 4 : (am_rows >= 2 ? 2 : 1);
+	if (vec) {
+		constexpr int R = 2;     // y-rows per thread
 		const int jgroups = (d.sy + R - 1) / R;
 		const int64_t vblocks = ((int64_t)(d.sx >> 2) * jgroups * d.sz + BLOCK - 1) / BLOCK;
 		const int tpb = (int)((vblocks + MAX_BLOCKS - 1) / MAX_BLOCKS);
 		nb = (int)((vblocks + tpb - 1) / tpb);
-#define AM5(RR)                                                                                                                                   \
-	if (d.is3d && pack)                                                                                                                           \
-		hipLaunchKernelGGL((k_apply_matrix_v5<DOT, true, RR, true>), dim3(nb), dim3(BLOCK), 0, st, d, flags, dst, src, A0, Ai, Aj, Ak, partials, sc, jgroups, tpb, pack, dk0, dk1, a0pn, bempty, nbj, outside_bad, xr); \
-	else if (d.is3d)                                                                                                                              \
-		hipLaunchKernelGGL((k_apply_matrix_v5<DOT, true, RR, false>), dim3(nb), dim3(BLOCK), 0, st, d, flags, dst, src, A0, Ai, Aj, Ak, partials, sc, jgroups, tpb, pack, dk0, dk1, a0pn, bempty, nbj, outside_bad, xr); \
-	else                                                                                                                                          \
-		hipLaunchKernelGGL((k_apply_matrix_v5<DOT, false, RR, false>), dim3(nb), dim3(BLOCK), 0, st, d, flags, dst, src, A0, Ai, Aj, Ak, partials, sc, jgroups, tpb, pack, dk0, dk1, a0pn, bempty, nbj, outside_bad, xr);
-		if (R == 4) { AM5(4) } else if (R == 2) { AM5(2) } else { AM5(1) }
-#undef AM5
+		auto kern = !d.is3d ? k_apply_matrix_v5<DOT, false, R, false> : o.pack ? k_apply_matrix_v5<DOT, true, R, true> : k_apply_matrix_v5<DOT, true, R, false>;
+		hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, st, d, flags, dst, src, A0, Ai, Aj, Ak, partials, sc, jgroups, tpb, o.pack, o.dk0, o.dk1, a0pn,
+		                   o.bempty, o.nbj, o.outside_bad, o.xr);
 		if (ranged) *ranged = true;
-	} else if (vec) {
-		const int64_t nq = d.n >> 2;
-		const int qpt = (int)((nq + (int64_t)BLOCK * MAX_BLOCKS - 1) / ((int64_t)BLOCK * MAX_BLOCKS));
-		nb = (int)((nq + (int64_t)BLOCK * qpt - 1) / ((int64_t)BLOCK * qpt));
-		if (nb < 1) nb = 1;
-		if (d.is3d)
-			hipLaunchKernelGGL((k_apply_matrix_v4<DOT, true>), dim3(nb), dim3(BLOCK), 0, st, d, flags, dst, src, A0, Ai, Aj, Ak, partials, sc, qpt);
-		else
-			hipLaunchKernelGGL((k_apply_matrix_v4<DOT, false>), dim3(nb), dim3(BLOCK), 0, st, d, flags, dst, src, A0, Ai, Aj, Ak, partials, sc, qpt);
 	} else {
 		nb = blocks_for(d.n, BLOCK, 2048);
 		hipLaunchKernelGGL((k_apply_matrix_scalar<DOT>), dim3(nb), dim3(BLOCK), 0, st, d, flags, dst, src, A0, Ai, Aj, Ak, partials, sc);
@@ -888,24 +801,6 @@ k_cg_beta(CgScalars* sc, int nbr, const float* __restrict__ fpart, const double*
 		}
 	}
 }
-// search = tmp + beta*search, conjugategrad.cpp:193-196, 283
-__global__ void __launch_bounds__(BLOCK)
-k_cg_update_search(int64_t n, CgScalars* __restrict__ sc, float* __restrict__ search, const float* __restrict__ tmp) {
-	if (sc->done) return;
-	const float beta = sc->beta;
-	const int64_t n4 = n >> 2;
-	for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < n4; q += (int64_t)gridDim.x * BLOCK) {
-		float4 s = ((float4*)search)[q];
-		const float4 t = ((const float4*)tmp)[q];
-		s.x = t.x + beta * s.x; s.y = t.y + beta * s.y; s.z = t.z + beta * s.z; s.w = t.w + beta * s.w;
-		((float4*)search)[q] = s;
-	}
-	if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-		const int64_t i = (n4 << 2) + threadIdx.x;
-		search[i] = tmp[i] + beta * search[i];
-	}
-}
-
 // dst += alpha*search (conjugategrad.cpp:254, left over from this iteration: xpending) and, unless the iteration has converged,
 // search = tmp + beta*search (:283) -- `search` is read once for both
 // SKIP (liquid scenes, see k_cg_outside_zero): dst, search and tmp are zero in the bundles without fluid and stay zero
@@ -1167,6 +1062,11 @@ k_unpad(int sx, int px, int64_t n, const float* __restrict__ padded, float* __re
 	}
 }
 
+// the padded copy of mf_cg_solve's system, per device (solves on one device are ordered on one stream): 11 arrays -- flags, dst, rhs,
+// residual, search, tmp, A0, Ai, Aj, Ak, Aprecond -- of g_pad_bytes / (11 * 4) floats each, every one 256-byte aligned
+static float* g_pad_buf[16];
+static size_t g_pad_bytes[16];
+
 extern "C" {
 
 int mf_apply_matrix(int sx, int sy, int sz, const int32_t* flags, float* dst, const float* src, const float* A0,
@@ -1175,7 +1075,7 @@ int mf_apply_matrix(int sx, int sy, int sz, const int32_t* flags, float* dst, co
 	const Dim d = mkdim(sx, sy, sz);
 	bool a0p = false;
 	const unsigned char* pk = mic_pack_user(flags, A0, Ai, Aj, Ak, &a0p);
-	return launch_apply_matrix<false>(d, flags, dst, src, A0, Ai, Aj, Ak, nullptr, nullptr, (hipStream_t)stream, nullptr, pk, 0, 0x7fffffff, nullptr, a0p);
+	return launch_apply_matrix<false>(d, flags, dst, src, A0, Ai, Aj, Ak, nullptr, nullptr, (hipStream_t)stream, AmOpts{pk, a0p});
 }
 
 static int time_apply_matrix(int sx, int sy, int sz, const int32_t* flags, float* dst, const float* src, const float* A0,
@@ -1183,18 +1083,17 @@ static int time_apply_matrix(int sx, int sy, int sz, const int32_t* flags, float
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
 	hipStream_t st = (hipStream_t)stream;
-	const unsigned char* pack = nullptr;
-	bool a0p = false;
+	AmOpts am;
 	if (packed) {
-		MF_TRY(mic_pack_query(d, flags, A0, Ai, Aj, Ak, &pack, &a0p, st));
-		if (!pack) return fail("mf_time_apply_matrix_packed: no packed coefficients for these grids (call mf_mic_init on them; the off-diagonals must all be +0 or -1)");
+		MF_TRY(mic_pack_query(d, flags, A0, Ai, Aj, Ak, &am.pack, &am.a0p, st));
+		if (!am.pack) return fail("mf_time_apply_matrix_packed: no packed coefficients for these grids (call mf_mic_init on them; the off-diagonals must all be +0 or -1)");
 	}
 	hipEvent_t e0, e1;
 	MF_HIP(hipEventCreate(&e0));
 	MF_HIP(hipEventCreate(&e1));
-	for (int i = 0; i < 3; i++) MF_TRY(launch_apply_matrix<false>(d, flags, dst, src, A0, Ai, Aj, Ak, nullptr, nullptr, st, nullptr, pack, 0, 0x7fffffff, nullptr, a0p));
+	for (int i = 0; i < 3; i++) MF_TRY(launch_apply_matrix<false>(d, flags, dst, src, A0, Ai, Aj, Ak, nullptr, nullptr, st, am));
 	MF_HIP(hipEventRecord(e0, st));
-	for (int i = 0; i < reps; i++) MF_TRY(launch_apply_matrix<false>(d, flags, dst, src, A0, Ai, Aj, Ak, nullptr, nullptr, st, nullptr, pack, 0, 0x7fffffff, nullptr, a0p));
+	for (int i = 0; i < reps; i++) MF_TRY(launch_apply_matrix<false>(d, flags, dst, src, A0, Ai, Aj, Ak, nullptr, nullptr, st, am));
 	MF_HIP(hipEventRecord(e1, st));
 	MF_HIP(hipEventSynchronize(e1));
 	float ms = 0.f;
@@ -1297,9 +1196,11 @@ int mf_apply_matrix_dot_dev(int sx, int sy, int sz, const int32_t* flags, float*
 	const CgScalars* sc = (const CgScalars*)scalars;
 	int nb = 0;
 	bool ranged = false;
-	bool a0p = false;
-	const unsigned char* pk = mic_pack_user(flags, A0, Ai, Aj, Ak, &a0p);
-	MF_TRY(launch_apply_matrix<true>(d, flags, dst, src, A0, Ai, Aj, Ak, ws->partials, sc, st, &nb, pk, k0, k1, &ranged, a0p));
+	AmOpts am;
+	am.pack = mic_pack_user(flags, A0, Ai, Aj, Ak, &am.a0p);
+	am.dk0 = k0;
+	am.dk1 = k1;
+	MF_TRY(launch_apply_matrix<true>(d, flags, dst, src, A0, Ai, Aj, Ak, ws->partials, sc, st, am, &nb, &ranged));
 	if (!ranged) {
 		// the fallback kernels sum over the whole grid: redo the dot over the requested planes
 		const int64_t XY = (int64_t)sx * sy, n = (int64_t)(k1 - k0) * XY;
@@ -1368,38 +1269,35 @@ int mf_cg_solve(int sx, int sy, int sz, const int32_t* flags, float* dst, const 
 	// coefficients and zero rhs, so they pass zeros through ApplyMatrix and the sweeps and add zeros to every reduction -- the
 	// iterates of the fluid cells are those of the unpadded system.  (A fluid cell in the last column, which MakeLaplaceMatrix
 	// never writes, would read the pad cell instead of the next row's first cell, both times a zero coefficient: the same value.)
-	static const bool nopad = getenv("MF_CG_NOPAD") != nullptr;
-	if (pc == MF_PC_MICP && (sx % 8) != 0 && sx >= 16 && !nopad) {
+	// If the padded copy cannot be allocated, the solve runs unpadded on the caller's grids (the path of every sx % 8 == 0 system).
+	if (pc == MF_PC_MICP && (sx % 8) != 0 && sx >= 16) {
 		const int px = (sx + 7) & ~7;
 		const int64_t rows = (int64_t)sy * sz, np_ = (int64_t)px * rows;
 		if (np_ < ((int64_t)1 << 31)) {
 			int dev = 0;
 			MF_HIP(hipGetDevice(&dev));
-			static float* pad_buf[16] = {};
-			static int64_t pad_cap[16] = {};
-			if (np_ > pad_cap[dev & 15]) {
-				MF_HIP(hipStreamSynchronize(st));
-				if (pad_buf[dev & 15]) MF_HIP(hipFree(pad_buf[dev & 15]));
-				pad_cap[dev & 15] = ((np_ + np_ / 8 + 63) / 64) * 64;       // every array of the block 256-byte aligned
-				MF_HIP(hipMalloc((void**)&pad_buf[dev & 15], sizeof(float) * 11 * pad_cap[dev & 15]));
+			float*& b = g_pad_buf[dev & 15];
+			size_t& bytes = g_pad_bytes[dev & 15];
+			const size_t cell = 11 * sizeof(float);
+			if ((size_t)np_ * cell <= bytes || grow_buffer(&b, &bytes, cell * (size_t)(((np_ + np_ / 8 + 63) / 64) * 64), st) == 0) {   // (1/8 to spare)
+				const int64_t cap = (int64_t)(bytes / cell);
+				float *p_flags = b, *p_dst = b + cap, *p_rhs = b + 2 * cap, *p_res = b + 3 * cap, *p_search = b + 4 * cap, *p_tmp = b + 5 * cap,
+				      *p_A0 = b + 6 * cap, *p_Ai = b + 7 * cap, *p_Aj = b + 8 * cap, *p_Ak = b + 9 * cap, *p_Ap = b + 10 * cap;
+				// the work grids are fresh (zeroed) temp grids in solvePressureSystem, and the algorithm relies on it: the sweeps never
+				// write a non-fluid cell of tmp, ApplyMatrix copies search there, and the dots run over all cells
+				MF_HIP(hipMemsetAsync(p_dst, 0, sizeof(float) * np_, st));
+				MF_HIP(hipMemsetAsync(p_res, 0, sizeof(float) * (2 * cap + np_), st));      // residual, search, tmp
+				MF_HIP(hipMemsetAsync(p_Ap, 0, sizeof(float) * np_, st));
+				hipLaunchKernelGGL(k_pad_system, dim3(blocks_for(np_, BLOCK, 4096)), dim3(BLOCK), 0, st, sx, px, np_, flags, rhs, A0, Ai, Aj, Ak, (int32_t*)p_flags,
+				                   p_rhs, p_A0, p_Ai, p_Aj, p_Ak);
+				MF_LAUNCH_CHECK();
+				MF_TRY(mf_cg_solve(px, sy, sz, (const int32_t*)p_flags, p_dst, p_rhs, p_res, p_search, p_tmp, p_A0, p_Ai, p_Aj, p_Ak, p_Ap, pc, accuracy,
+				                   maxIter, useL2Norm, out_host, stream));
+				hipLaunchKernelGGL(k_unpad, dim3(blocks_for(d.n, BLOCK, 4096)), dim3(BLOCK), 0, st, sx, px, d.n, p_dst, dst);
+				MF_LAUNCH_CHECK();
+				return 0;
 			}
-			float* b = pad_buf[dev & 15];
-			const int64_t cap = pad_cap[dev & 15];
-			float *p_flags = b, *p_dst = b + cap, *p_rhs = b + 2 * cap, *p_res = b + 3 * cap, *p_search = b + 4 * cap, *p_tmp = b + 5 * cap,
-			      *p_A0 = b + 6 * cap, *p_Ai = b + 7 * cap, *p_Aj = b + 8 * cap, *p_Ak = b + 9 * cap, *p_Ap = b + 10 * cap;
-			// the work grids are fresh (zeroed) temp grids in solvePressureSystem, and the algorithm relies on it: the sweeps never
-			// write a non-fluid cell of tmp, ApplyMatrix copies search there, and the dots run over all cells
-			MF_HIP(hipMemsetAsync(p_dst, 0, sizeof(float) * np_, st));
-			MF_HIP(hipMemsetAsync(p_res, 0, sizeof(float) * (2 * cap + np_), st));      // residual, search, tmp
-			MF_HIP(hipMemsetAsync(p_Ap, 0, sizeof(float) * np_, st));
-			hipLaunchKernelGGL(k_pad_system, dim3(blocks_for(np_, BLOCK, 4096)), dim3(BLOCK), 0, st, sx, px, np_, flags, rhs, A0, Ai, Aj, Ak, (int32_t*)p_flags, p_rhs,
-			                   p_A0, p_Ai, p_Aj, p_Ak);
-			MF_LAUNCH_CHECK();
-			MF_TRY(mf_cg_solve(px, sy, sz, (const int32_t*)p_flags, p_dst, p_rhs, p_res, p_search, p_tmp, p_A0, p_Ai, p_Aj, p_Ak, p_Ap, pc, accuracy,
-			                   maxIter, useL2Norm, out_host, stream));
-			hipLaunchKernelGGL(k_unpad, dim3(blocks_for(d.n, BLOCK, 4096)), dim3(BLOCK), 0, st, sx, px, d.n, p_dst, dst);
-			MF_LAUNCH_CHECK();
-			return 0;
+			(void)hipGetLastError();      // the allocation failed: clear its error, solve unpadded
 		}
 	}
 	return cg_solve_core(d, flags, dst, rhs, residual, search, tmp, A0, Ai, Aj, Ak, Aprecond, pc, accuracy, maxIter, useL2Norm, out_host, stream, nullptr);
@@ -1453,6 +1351,67 @@ k_cg_outside_zero(int64_t n, int sx, int sy, const int* __restrict__ bempty, int
 	}
 	if (__any(found) && (threadIdx.x & 63) == 0) atomicAdd(bad, 1);
 }
+// What the iterations of one PCG solve run, decided once before the first of them (pcg_setup); the iteration loop reads nothing else.
+// Liquid scenes: am.bempty is the map of the 8 x 8 bundles of rows the vector kernels skip (every vector is +0 there, k_cg_outside_zero
+// checks it on the device, verdict in *am.outside_bad); where the sweep's workgroups draw several bundles each, be_map is the same map
+// for the sweep: the dot shares of its empty bundles then ride on the residual update (k_cg_axpy_r<.., EDOT>), behind its partials.
+struct PcgPlan {
+	AmOpts am;                    // ApplyMatrix: packed bytes, skip map, x-range, non-temporal policy (also that of the vector kernels)
+	const int* be_map = nullptr;
+	MicSweep sweep;               // the x-range trim of the MIC sweeps
+};
+// The set-up after doInit: packed bytes, empty-bundle maps, x-range verdict (one read-back), non-temporal policy -> *p and
+// g_last_shortcut.  free_pack (mf_solve_pressure_fused): the system exists as packed bytes only.
+static int pcg_setup(const Dim& d, const int32_t* flags, const float* rhs, const float* search, const float* tmp, const float* A0, const float* Ai,
+                     const float* Aj, const float* Ak, const float* Aprecond, int pc, const unsigned char* free_pack, Workspace* ws, hipStream_t st,
+                     PcgPlan* p) {
+	const int sx = d.sx, sy = d.sy;
+	const int64_t n = d.n;
+	const int nbs = blocks_for(n >> 2, BLOCK, 2048);
+	// ApplyMatrix reads the same packed coefficient bytes as the MIC sweeps when mf_mic_init found the matrix packable
+	if (free_pack) {
+		p->am.pack = free_pack;
+		p->am.a0p = true;
+	} else if (pc == MF_PC_MICP) {
+		MF_TRY(mic_pack_query(d, flags, A0, Ai, Aj, Ak, &p->am.pack, &p->am.a0p, st));
+	}
+	bool several = false;
+	if (pc == MF_PC_MICP && (sx % 4) == 0) MF_TRY(mic_empty_map(d, flags, Aprecond, Aj, Ak, &p->am.bempty, &p->am.nbj, &several, st));
+	if (several) p->be_map = p->am.bempty;
+	g_last_shortcut[0] = g_last_shortcut[1] = g_last_shortcut[2] = 0;
+	p->am.nt = (!p->am.bempty && n > PCG_NT_CELLS) ? 1 : 0;
+	if (p->am.bempty) {
+		// (n % 4 == 0 here: sx % 4 == 0.)  residual = rhs and dst = 0 were set by doInit; tmp and search are the caller's
+		int* p_bad = (int*)((char*)ws->scalars + WS_PCG_FLAGS);
+		int* p_xr = p_bad + 1;
+		const bool ranged = p->am.pack != nullptr && (sx % 8) == 0;
+		p->am.outside_bad = p_bad;
+		if (ranged) p->am.xr = p_xr;
+		const int init3[3] = {0, 0x7fffffff, 0};
+		MF_HIP(hipMemcpyAsync(p_bad, init3, sizeof init3, hipMemcpyHostToDevice, st));
+		if (ranged) hipLaunchKernelGGL(k_pack_xrange, dim3(blocks_for(n >> 3, BLOCK, 2048)), dim3(BLOCK), 0, st, n, sx, p->am.pack, p_xr);
+		hipLaunchKernelGGL(k_cg_outside_zero, dim3(nbs), dim3(BLOCK), 0, st, n, sx, sy, p->am.bempty, p->am.nbj, rhs, tmp, search, p_bad, p->am.xr);
+		MF_LAUNCH_CHECK();
+		if (ranged) {
+			// the sweeps keep to the x-range of the fluid, if the host may know that everything outside is +0
+			int h3[3] = {1, 0, 0};
+			MF_HIP(hipMemcpyAsync(h3, p_bad, sizeof h3, hipMemcpyDeviceToHost, st));
+			MF_HIP(hipStreamSynchronize(st));
+			int c0 = h3[1] >> 3, c1 = (h3[2] + 7) >> 3;
+			if (c1 > sx / 8) c1 = sx / 8;
+			if (h3[0] == 0 && h3[2] > 0 && c1 > c0) {
+				p->sweep.trim_xoff = 8 * c0;
+				p->sweep.trim_chunks = c1 - c0;
+				g_last_shortcut[0] = 1;
+				if (c1 - c0 < sx / 8) {
+					g_last_shortcut[1] = 8 * c0;
+					g_last_shortcut[2] = 8 * (c1 - c0);
+				}
+			}
+		}
+	}
+	return 0;
+}
 // doInit + iterate loop of GridCg (conjugategrad.cpp:210-307).  free_pack (mf_solve_pressure_fused): the system exists as packed bytes
 // only -- A0 / Ai / Aj / Ak are null, the MIC factor is already in Aprecond and the system is registered with the sweeps
 static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const float* rhs, float* residual, float* search, float* tmp,
@@ -1484,64 +1443,12 @@ static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const f
 	hipLaunchKernelGGL(k_cg_dot, dim3(nbs), dim3(BLOCK), 0, st, n, sc, tmp, residual, p_sig);
 	hipLaunchKernelGGL(k_cg_begin, dim3(1), dim3(BLOCK), 0, st, sc, nbs, p_sig, accuracy, useL2Norm);
 	MF_LAUNCH_CHECK();
-	// ApplyMatrix reads the same packed coefficient bytes as the MIC sweeps when mf_mic_init found the matrix packable
-	const unsigned char* am_pack = nullptr;
-	bool am_a0p = false;
-	if (free_pack) {
-		am_pack = free_pack;
-		am_a0p = true;
-	} else if (pc == MF_PC_MICP) {
-		MF_TRY(mic_pack_query(d, flags, A0, Ai, Aj, Ak, &am_pack, &am_a0p, st));
-	}
+	PcgPlan p;
+	MF_TRY(pcg_setup(d, flags, rhs, search, tmp, A0, Ai, Aj, Ak, Aprecond, pc, free_pack, ws, st, &p));
 
 	// ---- iterate, conjugategrad.cpp:238-299; the host only polls `done`, one batch behind the batch it has just queued
 	// (every kernel of an iteration returns at once when `done` is already set, so running ahead costs a few empty
 	// launches after convergence and keeps the GPU from idling between iterations) ----
-	// liquid scenes whose sweeps leave bundles out: their dot shares ride on the residual update (k_cg_axpy_r<.., EDOT>)
-	const int* be_map = nullptr;
-	int be_nbj = 0;
-	if (pc == MF_PC_MICP && (sx % 4) == 0) MF_TRY(mic_empty_map(d, flags, Aprecond, Aj, Ak, &be_map, &be_nbj, st));
-	const int be_nb = ((sy + 7) / 8) * ((sz + 7) / 8);      // the sweep's partials (one per bundle) come first, the nbs of the residual update behind them
-	int* p_bad = (int*)((char*)ws->scalars + WS_PCG_FLAGS);
-	// the map the vector kernels skip by: the same one, also where the sweep sums the shares of the empty bundles itself (<= one bundle per CU)
-	const int* sk_map = be_map;
-	int sk_nbj = be_nbj;
-	if (!sk_map && pc == MF_PC_MICP && (sx % 4) == 0) MF_TRY(mic_empty_map(d, flags, Aprecond, Aj, Ak, &sk_map, &sk_nbj, st, true));
-	// ... and the sweeps keep to the x-range of the fluid (the packed bytes tell it), if the host may know that everything outside is +0
-	struct TrimGuard {
-		~TrimGuard() { mic_set_trim(0, 0); }
-	} trim_guard;
-	g_last_shortcut[0] = g_last_shortcut[1] = g_last_shortcut[2] = 0;
-	const int* xr_dev = nullptr;      // device x-range of the packed system, for the kernels that skip by it
-	const int pcg_nt = (!sk_map && n > PCG_NT_CELLS) ? 1 : 0;      // the vector streams around the sweeps non-temporal (see PCG_NT_CELLS)
-	if (sk_map) {
-		// (n % 4 == 0 here: sx % 4 == 0.)  residual = rhs and dst = 0 were set above; tmp and search are the caller's
-		int* p_xr = p_bad + 1;
-		const bool ranged = am_pack != nullptr && (sx % 8) == 0;
-		if (ranged) xr_dev = p_xr;
-		const int init3[3] = {0, 0x7fffffff, 0};
-		MF_HIP(hipMemcpyAsync(p_bad, init3, sizeof init3, hipMemcpyHostToDevice, st));
-		if (ranged) hipLaunchKernelGGL(k_pack_xrange, dim3(blocks_for(n >> 3, BLOCK, 2048)), dim3(BLOCK), 0, st, n, sx, am_pack, p_xr);
-		hipLaunchKernelGGL(k_cg_outside_zero, dim3(nbs), dim3(BLOCK), 0, st, n, sx, sy, sk_map, sk_nbj, rhs, tmp, search, p_bad, ranged ? p_xr : nullptr);
-		MF_LAUNCH_CHECK();
-		static const bool notrim = getenv("MF_MIC_NOTRIM") != nullptr;
-		if (ranged && !notrim) {
-			int h3[3] = {1, 0, 0};
-			MF_HIP(hipMemcpyAsync(h3, p_bad, sizeof h3, hipMemcpyDeviceToHost, st));
-			MF_HIP(hipStreamSynchronize(st));
-			int c0 = h3[1] >> 3, c1 = (h3[2] + 7) >> 3;
-			if (c1 > sx / 8) c1 = sx / 8;
-			if (h3[0] == 0 && h3[2] > 0 && c1 > c0) {
-				mic_set_trim(8 * c0, c1 - c0);
-				g_last_shortcut[0] = 1;
-				if (c1 - c0 < sx / 8) {
-					g_last_shortcut[1] = 8 * c0;
-					g_last_shortcut[2] = 8 * (c1 - c0);
-				}
-			}
-		}
-	}
-	const int batch = (pc == MF_PC_MICP && mic_mode() == 0) ? 1 : 4;
 	CgScalars h;
 	memset(&h, 0, sizeof h);
 	h.resNorm = 1e20f;
@@ -1555,28 +1462,34 @@ static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const f
 		MF_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
 	}
 	CgScalars* hslot = (CgScalars*)ws->host;   // two pinned slots
+	const int batch = (pc == MF_PC_MICP && mic_mode() == 0) ? 1 : 4;
+	const int be_nb = ((sy + 7) / 8) * ((sz + 7) / 8);      // the sweep's partials (one per bundle) come first, the nbs of the residual update behind them
 	int issued = 0, slot = 0, pending = -1;
 	while (issued < maxIter) {
 		const int todo = (maxIter - issued < batch) ? (maxIter - issued) : batch;
 		for (int it = 0; it < todo; it++) {
 			int nba = 0, nsig = 0;
 			bool beta_done = false;
-			MF_TRY(launch_apply_matrix<true>(d, flags, tmp, search, A0, Ai, Aj, Ak, p_dot, sc, st, &nba, am_pack, 0, 0x7fffffff, nullptr, am_a0p, sk_map,
-			                                 sk_nbj, sk_map ? p_bad : nullptr, xr_dev, pcg_nt));
+			MF_TRY(launch_apply_matrix<true>(d, flags, tmp, search, A0, Ai, Aj, Ak, p_dot, sc, st, p.am, &nba));
 			hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(BLOCK), 0, st, sc, nba, p_dot);
 			if (pc == MF_PC_MICP) {
-				if (sk_map)      // (without be_map the shares it writes behind the sweep's partials are not summed: the sweep has them)
-					hipLaunchKernelGGL((k_cg_axpy_r<false, true>), dim3(nbs), dim3(BLOCK), 0, st, n, sc, residual, tmp, p_mm, p_res, sk_map, sk_nbj, sx, sy, p_sig + be_nb, p_bad, xr_dev, pcg_nt);
-				else
-					hipLaunchKernelGGL((k_cg_axpy_r<false>), dim3(nbs), dim3(BLOCK), 0, st, n, sc, residual, tmp, p_mm, p_res, (const int*)nullptr, 0, 0, 0,
-					                   (double*)nullptr, (const int*)nullptr, (const int*)nullptr, pcg_nt);
-				MF_TRY(mic_launch(1, d, flags, tmp, residual, Aprecond, Ai, Aj, Ak, sc, st));
+				// (with the skip map but without be_map, the shares it writes behind the sweep's partials are not summed: the sweep has them)
+				auto axpy = p.am.bempty ? k_cg_axpy_r<false, true> : k_cg_axpy_r<false, false>;
+				hipLaunchKernelGGL(axpy, dim3(nbs), dim3(BLOCK), 0, st, n, sc, residual, tmp, p_mm, p_res, p.am.bempty, p.am.nbj, sx, sy, p_sig + be_nb,
+				                   p.am.outside_bad, p.am.xr, p.am.nt);
+				MicSweep fwd = p.sweep;
+				MF_TRY(mic_sweep(1, d, flags, tmp, residual, Aprecond, Ai, Aj, Ak, sc, st, &fwd));
 				// sigma_new = dot(tmp, residual) comes out of the backward sweep's write-back (one partial per row bundle); the shares of
 				// the bundles the sweeps leave out: from the residual update above, behind the sweep's partials
 				// ... and the beta step is the tail of the sweep's last workgroup (one launch less per iteration)
-				MF_TRY(mic_launch_dot(d, flags, tmp, residual, Aprecond, Ai, Aj, Ak, sc, p_sig, &nsig, st, be_map != nullptr,
-				                      BetaTail{sc, nbs, p_mm, p_res, be_map ? nbs : 0}, &beta_done));
-				if (be_map) {
+				MicSweep bwd = p.sweep;
+				bwd.dotpart = p_sig;
+				bwd.empty_ext = p.be_map != nullptr;
+				bwd.tail = BetaTail{sc, nbs, p_mm, p_res, p.be_map ? nbs : 0};
+				MF_TRY(mic_sweep(2, d, flags, tmp, residual, Aprecond, Ai, Aj, Ak, sc, st, &bwd));
+				nsig = bwd.ndot;
+				beta_done = bwd.tail_done;
+				if (p.be_map) {
 					if (nsig != be_nb) return fail("mf_cg_solve: the backward sweep wrote %d dot partials, %d expected", nsig, be_nb);
 					nsig += nbs;
 				}
@@ -1588,11 +1501,8 @@ static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const f
 				nsig = nbs;
 			}
 			if (!beta_done) hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, st, sc, nbs, p_mm, p_res, nsig, p_sig);
-			if (sk_map)
-				hipLaunchKernelGGL((k_cg_update_search_x<true>), dim3(nbs), dim3(BLOCK), 0, st, n, sc, dst, search, tmp, sk_map, sk_nbj, sx, sy, p_bad, xr_dev, pcg_nt);
-			else
-				hipLaunchKernelGGL((k_cg_update_search_x<false>), dim3(nbs), dim3(BLOCK), 0, st, n, sc, dst, search, tmp, (const int*)nullptr, 0, 0, 0, (const int*)nullptr,
-				                   (const int*)nullptr, pcg_nt);
+			auto update = p.am.bempty ? k_cg_update_search_x<true> : k_cg_update_search_x<false>;
+			hipLaunchKernelGGL(update, dim3(nbs), dim3(BLOCK), 0, st, n, sc, dst, search, tmp, p.am.bempty, p.am.nbj, sx, sy, p.am.outside_bad, p.am.xr, p.am.nt);
 		}
 		MF_LAUNCH_CHECK();
 		issued += todo;
