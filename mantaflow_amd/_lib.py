@@ -5,7 +5,9 @@ library is missing or cannot be loaded the import of any hot-path function raise
 the test-suite can drive the *same* host code with another implementation of the same ABI (the plain-C oracle
 restatement, host pointers) -- nothing in this package ever loads anything from ``oracle/`` by itself.
 
-Prototypes are parsed from the header itself, so the binding cannot drift from ``include/manta_hip.h``.
+Prototypes are parsed from the header itself, so the binding cannot drift from ``include/manta_hip.h``.  The optional
+extension ``include/manta_hip_obstacles.h`` (fill-fraction obstacle boundaries) is parsed the same way: its entries are bound
+when the loaded library exports them (``Library.obstacles``), and a library without them still loads.
 """
 import ctypes
 import os
@@ -13,6 +15,7 @@ import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip.h")
+OBSTACLES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_obstacles.h")
 DEFAULT_LIB = os.path.join(_HERE, "csrc", "libmanta_hip.so")
 
 _CTYPES = {
@@ -78,10 +81,32 @@ class Library:
         if got != want:
             raise RuntimeError("mantaflow_amd: %s implements ABI revision %d, include/manta_hip.h declares %d -- rebuild the library"
                                % (path, got, want))
+        self.obstacles = self._bind_extension(path, OBSTACLES_HEADER, "mf_obstacles_abi_version", "MF_OBSTACLES_ABI_VERSION")
         # the z-slab window is thread-local state of the shared object (which stays loaded across Library instances): start
         # from "the grid is the whole domain"; solvers carry their own window and set it per call (core.SolverLib)
         self.cdll.mf_set_slab_window(0, 0)
         self.cdll.mf_set_slab_window_source(0, 0)
+
+    def _bind_extension(self, path, header, version_fn, version_macro):
+        """bind the entries of an optional extension header; False when the library has none of it"""
+        protos = parse_header(header)
+        have = [n for n in protos if hasattr(self.cdll, n)]
+        if not have:
+            return False
+        missing = [n for n in protos if n not in have]
+        if missing:
+            raise RuntimeError("mantaflow_amd: %s implements part of %s, lacks: %s" % (path, os.path.basename(header), ", ".join(missing)))
+        for name in have:
+            restype, argtypes, _ = protos[name]
+            fn = getattr(self.cdll, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
+        want = int(re.search(r"#define\s+%s\s+(\d+)" % version_macro, open(header).read()).group(1))
+        got = int(getattr(self.cdll, version_fn)())
+        if got != want:
+            raise RuntimeError("mantaflow_amd: %s implements %s revision %d, the header declares %d -- rebuild the library"
+                               % (path, os.path.basename(header), got, want))
+        return True
 
     def call(self, name, *args):
         fn = getattr(self.cdll, name)

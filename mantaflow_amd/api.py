@@ -10,7 +10,8 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       solvePressureSystem, pushOutofObs, gridParticleIndex, unionParticleLevelset, extrapolateLsSimple,
                       setPartType, markIsolatedFluidCell, addForcePvel, updateVelocityFromDeltaPos, eulerStep,
                       interpolateGrid, interpolateGridVec3, interpolateMACGrid, computeEnergy, computeWaveletCoeffs,
-                      vorticityConfinement, applyNoiseVec3, setOpenBound)
+                      vorticityConfinement, applyNoiseVec3, setOpenBound,
+                      updateFractions, setObstacleFlags, setInflowBcs, addNoise)
 
 from .scene import (Box, Cylinder, Gui, NoiseField, Shape, Sphere, densityInflow, sampleFlagsWithParticles,
                     sampleLevelsetWithParticles, sampleShapeWithParticles)

@@ -159,6 +159,7 @@ class SolverLib(object):
     def __init__(self, lib, solver):
         self._lib, self._solver = lib, solver
         self.backend, self.device, self.cdll, self.path = lib.backend, lib.device, lib.cdll, lib.path
+        self.obstacles = lib.obstacles
 
     def call(self, name, *args):
         # set on every call: the window is thread-local state of the shared object, so a cache per Library object would go

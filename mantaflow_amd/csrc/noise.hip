@@ -3,6 +3,7 @@
 // process: MT19937 + Box-Muller in double precision, fp32 filter passes), uploaded, and evaluated on the device by
 // densityInflow (KnApplyNoiseInfl, plugin/initplugins.cpp:27-43).
 #include "common.h"
+#include "../../include/manta_hip_obstacles.h"
 #include <math.h>
 #include <stdlib.h>
 #include <vector>
@@ -184,6 +185,34 @@ k_density_inflow(Dim d, const int32_t* __restrict__ flags, float* __restrict__ d
 	if (density[idx] < target) density[idx] = target;
 }
 
+// KnAddNoise, plugin/initplugins.cpp:45-48: density += noise.evaluate(Vec3(i,j,k)) * scale on fluid cells outside the sdf
+__global__ void __launch_bounds__(BLOCK)
+k_add_noise(Dim d, const int32_t* __restrict__ flags, float* __restrict__ density, const float* __restrict__ sdf,
+            const float* __restrict__ tile, NoiseParams P, float scale) {
+	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+	if (idx >= d.n) return;
+	if (!(flags[idx] & MF_FLUID) || (sdf && sdf[idx] > 0.f)) return;
+	const int i = (int)(idx % d.sx), j = (int)((idx / d.sx) % d.sy), k = (int)(idx / ((int64_t)d.sx * d.sy));
+	density[idx] += noise_evaluate(P, tile, (float)i, (float)j, (float)k) * scale;
+}
+
+static NoiseParams noise_params(const float* params) {
+	NoiseParams P;
+	for (int c = 0; c < 3; c++) {
+		P.gsInv[c] = params[c];
+		P.seedOff[c] = params[3 + c];
+		P.posScale[c] = params[7 + c];
+		P.posOffset[c] = params[10 + c];
+	}
+	P.time = params[6];
+	P.valOffset = params[13];
+	P.valScale = params[14];
+	P.clamp = params[15];
+	P.clampNeg = params[16];
+	P.clampPos = params[17];
+	return P;
+}
+
 }  // namespace
 
 extern "C" {
@@ -224,20 +253,18 @@ int mf_density_inflow(int sx, int sy, int sz, const int32_t* flags, float* densi
                       const float* params, float scale, float sigma, void* stream) {
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
-	NoiseParams P;
-	for (int c = 0; c < 3; c++) {
-		P.gsInv[c] = params[c];
-		P.seedOff[c] = params[3 + c];
-		P.posScale[c] = params[7 + c];
-		P.posOffset[c] = params[10 + c];
-	}
-	P.time = params[6];
-	P.valOffset = params[13];
-	P.valScale = params[14];
-	P.clamp = params[15];
-	P.clampNeg = params[16];
-	P.clampPos = params[17];
+	const NoiseParams P = noise_params(params);
 	hipLaunchKernelGGL(k_density_inflow, dim3((unsigned)((d.n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, density, sdf, tile, P, scale, sigma);
+	MF_LAUNCH_CHECK();
+	return 0;
+}
+
+int mf_add_noise(int sx, int sy, int sz, const int32_t* flags, float* density, const float* sdf, const float* tile,
+                 const float* params, float scale, void* stream) {
+	MF_TRY(check_dim(sx, sy, sz));
+	const Dim d = mkdim(sx, sy, sz);
+	hipLaunchKernelGGL(k_add_noise, dim3((unsigned)((d.n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, density, sdf,
+	                   tile, noise_params(params), scale);
 	MF_LAUNCH_CHECK();
 	return 0;
 }

@@ -6,6 +6,9 @@ PYTHON() declarations; orchestration mirrors the reference function by function,
   mapPartsToMAC / mapMACToParts / flipVelocityUpdate / mapPartsToGrid(+Vec3) / mapGridToParts(+Vec3)
                                              source/plugin/flip.cpp:637-742
   setWallBcs / addBuoyancy / addGravity      source/plugin/extforces.cpp (SURVEY 8f-1 glue)
+  updateFractions / setObstacleFlags / addNoise   source/plugin/initplugins.cpp:45-51, 351-474
+  setWallBcs(fractions=, phiObs=) / setInflowBcs  source/plugin/extforces.cpp:163-182, 240-335
+                                             (include/manta_hip_obstacles.h; not on z-slab solvers)
 """
 import ctypes
 import functools
@@ -770,10 +773,95 @@ def setOpenBound(flags, bWidth, openBound="", type=16 | 4):
 @plugin
 def setWallBcs(flags, vel, obvel=None, fractions=None, phiObs=None, boundaryWidth=0):
     obvel = _opt(obvel, MACGrid, "MACGrid")
-    if phiObs is not None and fractions is not None:
-        raise RuntimeError("setWallBcs: the fill-fraction variant (KnSetWallBcsFrac, extforces.cpp:240-324) is outside the hot path")
     s = flags.parent
+    fractions, phiObs = _opt(fractions, MACGrid, "MACGrid"), _opt(phiObs, Grid, "Grid<Real>")
+    if fractions is not None and phiObs is not None:
+        # KnSetWallBcsFrac + vel.swap(tmpvel), extforces.cpp:240-335 (obvel and boundaryWidth unused there as well); in place
+        lib = _obstacles_lib(s, "setWallBcs")
+        scratch = _wall_frac_scratch(s)
+        lib.call("mf_set_wall_bcs_frac", flags.sx, flags.sy, flags.sz, flags.ptr, vel.ptr, phiObs.ptr, _ptr(scratch), scratch.numel(),
+                 s.stream)
+        return
     s.lib.call("mf_set_wall_bcs", flags.sx, flags.sy, flags.sz, flags.ptr, vel.ptr, None if obvel is None else obvel.ptr, s.stream)
+
+
+# =========================================================================================================
+# fill-fraction obstacle boundaries (include/manta_hip_obstacles.h)
+# =========================================================================================================
+def _obstacles_lib(s, name):
+    """the solver's library, if it implements the obstacle extension (the CPU test backend does not)"""
+    lib = s.lib
+    if not lib.obstacles:
+        raise RuntimeError("%s: the '%s' backend does not implement the fill-fraction obstacle plugins (manta_hip_obstacles.h)"
+                           % (name, lib.backend))
+    if tuple(s._slab_window) != (0, 0):
+        raise RuntimeError("%s: the fill-fraction obstacle plugins do not run on a z-slab solver" % name)
+    return lib
+
+
+def _wall_frac_scratch(s):
+    """per-solver scratch of mf_set_wall_bcs_frac (new face values + one bit per face), allocated once; never initialised"""
+    sc = getattr(s, "_wall_frac_scratch", None)
+    if sc is None:
+        words = ctypes.c_int64(0)
+        s.lib.call("mf_set_wall_bcs_frac_scratch_words", s.mGridSize[0], s.mGridSize[1], s.mGridSize[2], ctypes.byref(words))
+        sc = torch.empty(int(words.value), dtype=torch.int32, device=s.device)
+        s._wall_frac_scratch = sc
+    return sc
+
+
+@plugin
+def updateFractions(flags, phiObs, fractions, boundaryWidth=0, fracThreshold=0.01):
+    """initplugins.cpp:436-440: fractions.setConst(0) + KnUpdateFractions (the serial-sweep result)"""
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(phiObs, Grid, "Grid<Real>"); _chk(fractions, MACGrid, "MACGrid")
+    s = flags.parent
+    lib = _obstacles_lib(s, "updateFractions")
+    lib.call("mf_update_fractions", flags.sx, flags.sy, flags.sz, flags.ptr, phiObs.ptr, fractions.ptr, int(boundaryWidth),
+             float(np.float32(fracThreshold)), s.stream)
+
+
+@plugin
+def setObstacleFlags(flags, phiObs, fractions=None, phiOut=None, phiIn=None, boundaryWidth=1):
+    """initplugins.cpp:470-474 -> KnUpdateFlagsObs"""
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(phiObs, Grid, "Grid<Real>")
+    fractions = _opt(fractions, MACGrid, "MACGrid")
+    phiOut, phiIn = _opt(phiOut, Grid, "Grid<Real>"), _opt(phiIn, Grid, "Grid<Real>")
+    s = flags.parent
+    lib = _obstacles_lib(s, "setObstacleFlags")
+    lib.call("mf_set_obstacle_flags", flags.sx, flags.sy, flags.sz, flags.ptr, phiObs.ptr, None if fractions is None else fractions.ptr,
+             None if phiOut is None else phiOut.ptr, None if phiIn is None else phiIn.ptr, int(boundaryWidth), s.stream)
+
+
+_INFLOW_SIDES = {"x": 1, "X": 2, "y": 4, "Y": 8, "z": 16, "Z": 32}
+
+
+@plugin
+def setInflowBcs(vel, dir, value):
+    """extforces.cpp:171-182 -> KnSetInflow per character; a bad character raises after the characters before it were applied"""
+    _chk(vel, MACGrid, "MACGrid")
+    v = _to_vec3(value)
+    s = vel.parent
+    lib = _obstacles_lib(s, "setInflowBcs")
+    sides, bad = 0, False
+    for ch in str(dir):
+        if ch not in _INFLOW_SIDES:
+            bad = True
+            break
+        sides |= _INFLOW_SIDES[ch]
+    lib.call("mf_set_inflow_bcs", vel.sx, vel.sy, vel.sz, vel.ptr, sides, float(_f32(v.x)), float(_f32(v.y)), float(_f32(v.z)), s.stream)
+    if bad:
+        raise RuntimeError("invalid character in direction string. Only [xyzXYZ] allowed.")
+
+
+@plugin
+def addNoise(flags, density, noise, sdf=None, scale=1.0):
+    """initplugins.cpp:45-51 -> KnAddNoise"""
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(density, Grid, "Grid<Real>")
+    sdf = _opt(sdf, Grid, "Grid<Real>")
+    s = flags.parent
+    lib = _obstacles_lib(s, "addNoise")
+    lib.call("mf_add_noise", flags.sx, flags.sy, flags.sz, flags.ptr, density.ptr, None if sdf is None else sdf.ptr, _ptr(noise._tile),
+             noise._params(), float(_f32(scale)), s.stream)
 
 
 def _f32(x): return np.float32(x)
