@@ -115,7 +115,9 @@ int mf_grid_mult(int64_t n, float* me, const float* other, void* stream);
 /* ------------------------------------------------------------------------------------------------
  * Pressure projection
  * ---------------------------------------------------------------------------------------------- */
-/* ApplyMatrix / ApplyMatrix2D (sz==1), conjugategrad.h:118-151.  28 B/cell algorithmic traffic. */
+/* ApplyMatrix / ApplyMatrix2D (sz==1), conjugategrad.h:118-151.  28 B/cell algorithmic traffic.  Neighbours are indexed flat, as
+ * in the reference: a coupling across a row end (Ai at i = sx-1) or a plane end (Aj in row sy-1) reaches the first cell of the next
+ * row / plane; neighbours outside the grid count as 0. */
 int mf_apply_matrix(int sx, int sy, int sz, const int32_t* flags, float* dst, const float* src,
                     const float* A0, const float* Ai, const float* Aj, const float* Ak, void* stream);
 /* Optional accelerator for repeated mf_apply_matrix calls on one matrix: packs flags + Ai + Aj + Ak into one byte per cell
@@ -168,7 +170,9 @@ int mf_fix_pressure(int sx, int sy, int sz, int64_t fixPidx, float value, float*
  * InitPreconditionModifiedIncompCholesky2, conjugategrad.cpp:66-97 (3-D only).  Also records, for exactly these grids, which
  * 8x8 bundles of x-rows hold no fluid cell and have no coupling into them: mf_mic_apply leaves those out when it is called
  * with the same flags / Aprecond / Aj / Ak pointers (as GridCg does); with other pointers it sweeps everything.  Changing the
- * contents of these grids between mf_mic_init and mf_mic_apply is a caller error (the reference's Aprecond would be stale too). */
+ * contents of these grids between mf_mic_init and mf_mic_apply is a caller error (the reference's Aprecond would be stale too).
+ * The MIC entries and mf_cg_solve assume no coupling across row or plane ends (Ai = 0 at i = sx-1, Aj = 0 in row sy-1, Ak = 0 in
+ * plane sz-1 wherever the next cell is fluid), as in every matrix MakeLaplaceMatrix builds. */
 int mf_mic_init(int sx, int sy, int sz, const int32_t* flags, float* Aprecond, const float* A0,
                 const float* Ai, const float* Aj, const float* Ak, void* stream);
 /* Multi-GPU only (no reference counterpart): mf_mic_init for a preconditioner the caller has cut into independent blocks of
@@ -196,6 +200,7 @@ int mf_mic_apply_dot_dev(int sx, int sy, int sz, const int32_t* flags, float* ds
  *   Aprecond after the call are unspecified: with the MIC preconditioner and a row length that is not a multiple of 8 the loop
  *   runs on an internal copy of the system whose rows are padded with obstacle cells -- same iterates, 16-byte rows)
  *   pc = MF_PC_NONE | MF_PC_MICP; Aprecond: grid for the MIC factor (pca0), unused for PC_NONE
+ *   Like the MIC entries above, the solve assumes no coupling across row or plane ends.
  *   Liquid scenes (MIC-PCG): where 8 x 8 bundles of x-rows hold no fluid cell, or the fluid keeps to a part of the x-range, and rhs
  *   and the incoming work grids are +0 there -- checked on the device, once per call -- the kernels of an iteration leave those
  *   cells out: they stay +0, as they do in the reference.  A rhs that is not zero there is solved without the shortcut.

@@ -104,8 +104,11 @@ k_apply_matrix_v5(Dim d, const int32_t* __restrict__ flags, float* __restrict__ 
 	float4 sv[R + 2], ajv[R + 1], a0[R], ai[R], ak[R], akm[R], szm[R], szp[R];
 	float sl[R], al[R], sr[R];
 	// ---- loads (addresses clamped into the grid; out-of-domain neighbours are zeroed afterwards) ----
+	// The +-Y neighbours are flat, as in the reference (src[idx -+ Y]): at j = 0 the last row of the plane before, at j = sy-1 the first
+	// row of the plane after, zero only at the ends of the grid.  sv[0] / ajv[0] and sv[R + 1] hold them for the edge rows of a plane;
+	// with an odd sy the last thread of a plane has one row, and sv[R + 1] is still the row after it.  The interior loads are unchanged.
 	{
-		const int jm = (j0 > 0) ? -1 : 0;
+		const int jm = (rg > 0) ? -1 : 0;
 		sv[0] = *(const float4*)(src + row0 + jm * Y);
 		if (PACKED) ajv[0] = unpack_coef<4u>(*(const unsigned*)(pack + row0 + jm * Y));
 		else ajv[0] = *(const float4*)(Aj + row0 + jm * Y);
@@ -142,7 +145,7 @@ k_apply_matrix_v5(Dim d, const int32_t* __restrict__ flags, float* __restrict__ 
 		}
 	}
 	{
-		const int jr = (j0 + R < d.sy) ? R : (d.sy - 1 - j0);
+		const int jr = (j0 + R < d.sy) ? R : (d.sy - j0 - ((k < d.sz - 1) ? 0 : 1));
 		sv[R + 1] = *(const float4*)(src + row0 + jr * Y);
 	}
 	// ---- +-X neighbours: adjacent lanes hold the adjacent quads of the same row, except at row / wave edges ----
@@ -169,8 +172,8 @@ k_apply_matrix_v5(Dim d, const int32_t* __restrict__ flags, float* __restrict__ 
 		const float4 s = sv[r + 1];
 		float4 res = s;
 		if ((fl.x | fl.y | fl.z | fl.w) & MF_FLUID) {
-			const float4 sym = (j > 0) ? sv[r] : z4, ajm = (j > 0) ? ajv[r] : z4;
-			const float4 syp = (j < d.sy - 1) ? sv[r + 2] : z4, aj = ajv[r + 1];
+			const float4 sym = (j > 0 || k > 0) ? sv[r] : z4, ajm = (j > 0 || k > 0) ? ajv[r] : z4;
+			const float4 syp = (j < d.sy - 1) ? sv[r + 2] : (k < d.sz - 1) ? sv[R + 1] : z4, aj = ajv[r + 1];
 			float4 zm = z4, am = z4, zp = z4, akc = z4;
 			if (IS3D) {
 				akc = ak[r];
@@ -1036,11 +1039,13 @@ k_diffusion_matrix(int64_t n, const int32_t* __restrict__ flags, float* __restri
 static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const float* rhs, float* residual, float* search, float* tmp,
                          const float* A0, const float* Ai, const float* Aj, const float* Ak, float* Aprecond, int pc, float accuracy,
                          int maxIter, int useL2Norm, float* out_host, void* stream, const unsigned char* free_pack);
-// the system of mf_cg_solve with its rows padded from sx to px cells (pad cells: obstacle, zero coefficients, zero rhs), and back
+// the system of mf_cg_solve with its rows padded from sx to px cells (pad cells: obstacle, zero coefficients, zero rhs), plus the caller's
+// tmp (pad cells 0), and back
 __global__ void __launch_bounds__(BLOCK)
-k_pad_system(int sx, int px, int64_t np_, const int32_t* __restrict__ flags, const float* __restrict__ rhs, const float* __restrict__ A0,
-             const float* __restrict__ Ai, const float* __restrict__ Aj, const float* __restrict__ Ak, int32_t* __restrict__ pf, float* __restrict__ pr,
-             float* __restrict__ p0, float* __restrict__ pi, float* __restrict__ pj, float* __restrict__ pk) {
+k_pad_system(int sx, int px, int64_t np_, const int32_t* __restrict__ flags, const float* __restrict__ rhs, const float* __restrict__ tmp,
+             const float* __restrict__ A0, const float* __restrict__ Ai, const float* __restrict__ Aj, const float* __restrict__ Ak,
+             int32_t* __restrict__ pf, float* __restrict__ pr, float* __restrict__ pt, float* __restrict__ p0, float* __restrict__ pi,
+             float* __restrict__ pj, float* __restrict__ pk) {
 	for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < np_; q += (int64_t)gridDim.x * BLOCK) {
 		const int64_t row = q / px;
 		const int i = (int)(q - row * px);
@@ -1048,6 +1053,7 @@ k_pad_system(int sx, int px, int64_t np_, const int32_t* __restrict__ flags, con
 		const int64_t s = row * sx + i;
 		pf[q] = in ? flags[s] : MF_OBSTACLE;
 		pr[q] = in ? rhs[s] : 0.f;
+		pt[q] = in ? tmp[s] : 0.f;
 		p0[q] = in ? A0[s] : 0.f;
 		pi[q] = in ? Ai[s] : 0.f;
 		pj[q] = in ? Aj[s] : 0.f;
@@ -1283,13 +1289,13 @@ int mf_cg_solve(int sx, int sy, int sz, const int32_t* flags, float* dst, const 
 				const int64_t cap = (int64_t)(bytes / cell);
 				float *p_flags = b, *p_dst = b + cap, *p_rhs = b + 2 * cap, *p_res = b + 3 * cap, *p_search = b + 4 * cap, *p_tmp = b + 5 * cap,
 				      *p_A0 = b + 6 * cap, *p_Ai = b + 7 * cap, *p_Aj = b + 8 * cap, *p_Ak = b + 9 * cap, *p_Ap = b + 10 * cap;
-				// the work grids are fresh (zeroed) temp grids in solvePressureSystem, and the algorithm relies on it: the sweeps never
-				// write a non-fluid cell of tmp, ApplyMatrix copies search there, and the dots run over all cells
+				// doInit overwrites dst, residual and search, but not the non-fluid cells of tmp: the sweeps never write them,
+				// ApplyMatrix copies search there, and the dots run over all cells -- the caller's tmp goes in with the system
 				MF_HIP(hipMemsetAsync(p_dst, 0, sizeof(float) * np_, st));
-				MF_HIP(hipMemsetAsync(p_res, 0, sizeof(float) * (2 * cap + np_), st));      // residual, search, tmp
+				MF_HIP(hipMemsetAsync(p_res, 0, sizeof(float) * (cap + np_), st));      // residual, search
 				MF_HIP(hipMemsetAsync(p_Ap, 0, sizeof(float) * np_, st));
-				hipLaunchKernelGGL(k_pad_system, dim3(blocks_for(np_, BLOCK, 4096)), dim3(BLOCK), 0, st, sx, px, np_, flags, rhs, A0, Ai, Aj, Ak, (int32_t*)p_flags,
-				                   p_rhs, p_A0, p_Ai, p_Aj, p_Ak);
+				hipLaunchKernelGGL(k_pad_system, dim3(blocks_for(np_, BLOCK, 4096)), dim3(BLOCK), 0, st, sx, px, np_, flags, rhs, tmp, A0, Ai, Aj, Ak,
+				                   (int32_t*)p_flags, p_rhs, p_tmp, p_A0, p_Ai, p_Aj, p_Ak);
 				MF_LAUNCH_CHECK();
 				MF_TRY(mf_cg_solve(px, sy, sz, (const int32_t*)p_flags, p_dst, p_rhs, p_res, p_search, p_tmp, p_A0, p_Ai, p_Aj, p_Ak, p_Ap, pc, accuracy,
 				                   maxIter, useL2Norm, out_host, stream));

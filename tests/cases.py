@@ -116,10 +116,11 @@ def cg_rhs(dims, flags, seed):
     return rhs
 
 
-def run_cg_impl(impl, dims, flags, A, rhs, pc, accuracy, maxIter, useL2=0):
+def run_cg_impl(impl, dims, flags, A, rhs, pc, accuracy, maxIter, useL2=0, work=None):
+    """work: what the work grids hold when the solve starts, by name (dst, residual, search, tmp); zeros where not given"""
     sx, sy, sz = dims
-    z = lambda: impl.dev(np.zeros((sz, sy, sx), np.float32))
-    dst, residual, search, tmp, ap = z(), z(), z(), z(), z()
+    z = lambda name="": impl.dev(np.array((work or {}).get(name, np.zeros((sz, sy, sx), np.float32)), np.float32, copy=True))
+    dst, residual, search, tmp, ap = z("dst"), z("residual"), z("search"), z("tmp"), z()
     out = (ctypes.c_float * 3)()
     impl.call("mf_cg_solve", sx, sy, sz, impl.dev(flags), dst, impl.dev(rhs), residual, search, tmp,
               *[impl.dev(a) for a in A], ap, pc, accuracy, maxIter, useL2, out, None)
@@ -127,13 +128,123 @@ def run_cg_impl(impl, dims, flags, A, rhs, pc, accuracy, maxIter, useL2=0):
     return impl.host(dst), (int(out[0]), float(out[1]), float(out[2]))
 
 
-def run_cg_ref(dims, flags, A, rhs, pc, accuracy, maxIter, useL2=0):
+def run_cg_ref(dims, flags, A, rhs, pc, accuracy, maxIter, useL2=0, work=None):
     sx, sy, sz = dims
-    z = lambda: np.zeros((sz, sy, sx), np.float32)
-    dst, residual, search, tmp, ap = z(), z(), z(), z(), z()
+    z = lambda name="": np.array((work or {}).get(name, np.zeros((sz, sy, sx), np.float32)), np.float32, copy=True)
+    dst, residual, search, tmp, ap = z("dst"), z("residual"), z("search"), z("tmp"), z()
     out = np.zeros(3, np.float32)
     refcall("ref_cg_solve", sx, sy, sz, flags, dst, rhs, residual, search, tmp, *A, ap, pc, ctypes.c_float(accuracy), maxIter, useL2, out)
     return dst, (int(out[0]), float(out[1]), float(out[2]))
+
+
+# ---- the routes of mf_cg_solve, its liquid-scene shortcut, ApplyMatrix at the grid's ends ---------------------------------
+# (tests/test_gpu_pcg_routes.py compares the HIP library with the oracle on these inputs, tests/test_oracle_pcg_routes.py pins the
+# oracle to the reference on them).  The route mf_cg_solve takes with the MIC preconditioner, by shape (pressure.hip: mf_cg_solve,
+# pcg_setup, launch_apply_matrix); without a preconditioner no shape is padded, so sx % 4 != 0 means the scalar ApplyMatrix.
+PCG_ROUTES = [
+    ((13, 11, 9), "sx % 4 != 0, sx < 16: unpadded, scalar ApplyMatrix, n % 4 == 3 tails of the vector kernels"),
+    ((12, 10, 7), "sx % 8 != 0, sx < 16, sx % 4 == 0: unpadded, never trimmed, skip map (empty top bundle)"),
+    ((17, 9, 10), "sx % 8 != 0, sx >= 16: padded internal copy, pad 7 (pc 0: scalar ApplyMatrix, n % 4 == 2)"),
+    ((33, 20, 12), "padded, pad 7"),
+    ((63, 18, 10), "padded, pad 1"),
+    ((65, 24, 9), "padded, pad 7"),
+    ((16, 67, 5), "sx % 8 == 0: packed + skip map + x-range trim; sy odd (half last row pair of R = 2), sy % 8 != 0"),
+    ((24, 9, 70), "packed + skip map + x-range trim; sy odd, sz % 8 != 0"),
+    ((40, 4, 3), "packed; thin grid"),
+    ((37, 29, 1), "2-D, no preconditioner: scalar ApplyMatrix, n % 4 == 1"),
+    ((64, 33, 1), "2-D, no preconditioner: v5 2-D ApplyMatrix"),
+]
+# the three shapes of the shortcut premise tests and the liquid box fitted to each (x0, x1, y0, y1, z0, z1)
+LIQUID_SHORTCUT = [
+    ((64, 40, 24), (19, 45, 1, 22, 1, 23), "sx % 8 == 0: skip map + x-range trim"),
+    ((12, 40, 24), (1, 11, 1, 22, 1, 23), "sx % 8 != 0, sx < 16, sx % 4 == 0: skip map only, never trimmed"),
+    ((61, 40, 24), (21, 44, 1, 22, 1, 23), "sx % 8 != 0, sx >= 16: padded internal copy (64), skip map + trim there"),
+]
+
+
+def laplace_system(dims, flags):
+    """MakeLaplaceMatrix of flags, by the reference when available, else by the oracle (the two agree bit for bit)"""
+    if util.have_ref():
+        return run_laplace_ref(dims, flags, None)
+    return run_laplace_impl(util.Impl("oracle"), dims, flags, None)
+
+
+def liquid_box_system(dims, box, seed):
+    """the liquid scene of test_solve_pressure_liquid_shortcuts as a bare system: walls, empty cells, a box of fluid with an obstacle
+    inside; MakeLaplaceMatrix and a random rhs in the fluid cells"""
+    sx, sy, sz = dims
+    x0, x1, y0, y1, z0, z1 = box
+    flags = np.full((sz, sy, sx), util.EMPTY, np.int32)
+    flags[:, :, 0] = flags[:, :, -1] = flags[:, 0, :] = flags[:, -1, :] = util.OBS
+    flags[0] = flags[-1] = util.OBS
+    flags[z0:z1, y0:y1, x0:x1] = util.FLUID
+    flags[3:7, 3:9, x0 + 2:x0 + 6] = util.OBS
+    return flags, laplace_system(dims, flags), cg_rhs(dims, flags, seed)
+
+
+def liquid_variants(dims, box, flags):
+    """incoming values for mf_cg_solve on a liquid box system (name -> (rhs edit, work grids)): each puts something other than +0
+    where the liquid-scene shortcut needs +0, or leaves the premise intact (clean, tmp beside the fluid, search)"""
+    sx, sy, sz = dims
+    x0, x1, y0, y1, z0, z1 = box
+    shape = (sz, sy, sx)
+    nonfluid = (flags & util.FLUID) == 0
+    # a non-fluid cell in a bundle of 8 x 8 rows without fluid (rows j >= 24 hold no fluid: y1 <= 22)
+    far = (sz // 2, 30, sx // 2)
+    assert not (flags[:, 24:32, :] & util.FLUID).any()
+
+    def grid(cells, v):
+        g = np.zeros(shape, np.float32)
+        for c in cells:
+            g[c] = v
+        return g
+
+    # non-fluid cells next to the fluid: the column in front of the box, the obstacle inside it, the empty row above it
+    beside = [(z0 + 2, y0 + 3, x0 - 1), (4, 5, x0 + 3), (z0 + 5, y1, x0 + 2)]
+    assert all(nonfluid[c] for c in beside + [far])
+    out = {
+        "clean": (None, {}),
+        "rhs_empty_bundle": ({far: np.float32(1e-3)}, {}),
+        "rhs_minus_zero": ({far: np.float32(-0.0)}, {}),
+        "tmp_empty_bundle": (None, {"tmp": grid([far, (sz // 2 + 1, 33, 1)], 2e-3)}),
+        "tmp_beside_fluid": (None, {"tmp": grid(beside, -1.5e-3)}),
+        "search_nonfluid": (None, {"search": grid(beside + [far], 0.25)}),
+    }
+    if x1 + 9 < sx:
+        # outside the fluid's x-range, inside a bundle that holds fluid
+        out["rhs_outside_xrange"] = ({(z0 + 3, y0 + 4, sx - 2): np.float32(1e-3)}, {})
+    return out
+
+
+def apply_matrix_edge_inputs(dims, seed, packed=False):
+    """a caller-built system for ApplyMatrix with fluid up to the domain border (no walls) wherever the reference's flat indexing stays
+    inside the grid -- every cell but the planes k = 0 and sz-1 (3-D) or the rows j = 0 and sy-1 (2-D) -- and a few obstacle / empty
+    cells; coefficients everywhere, so also across row ends (Ai at i = sx-1, fluid at i = 0 of the next row) and plane ends (Aj in row
+    sy-1, fluid in row 0 of the next plane).  src holds large finite values and -0.0 in the non-fluid cells.  packed: off-diagonals
+    exactly +0 or -1 and an integer diagonal, what mf_pack_matrix packs (diagonal included)"""
+    sx, sy, sz = dims
+    shape = (sz, sy, sx)
+    rng = np.random.default_rng(seed)
+    flags = np.full(shape, util.FLUID, np.int32)
+    if sz > 1:
+        flags[0] = flags[-1] = util.OBS
+    else:
+        flags[:, 0] = flags[:, -1] = util.OBS
+    r = rng.random(shape)
+    inner = flags == util.FLUID
+    flags[inner & (r < 0.08)] = util.OBS
+    flags[inner & (r >= 0.08) & (r < 0.14)] = util.EMPTY
+    if packed:
+        A0 = rng.integers(0, 7, shape).astype(np.float32)
+        Ai, Aj, Ak = [np.where(rng.random(shape) < 0.7, -1.0, 0.0).astype(np.float32) for _ in range(3)]
+    else:
+        A0 = rng.uniform(0.5, 6.0, shape).astype(np.float32)
+        Ai, Aj, Ak = [rng.uniform(-1.0, 0.0, shape).astype(np.float32) for _ in range(3)]
+    src = util.rand_real(shape, seed + 1)
+    non = flags != util.FLUID
+    big = rng.choice(np.array([-3e18, 2.5e18, -0.0, 7.0e17], np.float32), size=shape)
+    src[non] = big[non]
+    return flags, [A0, Ai, Aj, Ak], src
 
 
 # ---------------------------------------------------------------------------------------------------------
