@@ -11,7 +11,7 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       setPartType, markIsolatedFluidCell, addForcePvel, updateVelocityFromDeltaPos, eulerStep,
                       interpolateGrid, interpolateGridVec3, interpolateMACGrid, computeEnergy, computeWaveletCoeffs,
                       vorticityConfinement, applyNoiseVec3, setOpenBound,
-                      updateFractions, setObstacleFlags, setInflowBcs, addNoise)
+                      updateFractions, setObstacleFlags, setInflowBcs, addNoise, releaseMG)
 
 from .scene import (Box, Cylinder, Gui, NoiseField, Shape, Sphere, densityInflow, sampleFlagsWithParticles,
                     sampleLevelsetWithParticles, sampleShapeWithParticles)

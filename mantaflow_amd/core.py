@@ -160,6 +160,7 @@ class SolverLib(object):
         self._lib, self._solver = lib, solver
         self.backend, self.device, self.cdll, self.path = lib.backend, lib.device, lib.cdll, lib.path
         self.obstacles = lib.obstacles
+        self.multigrid = lib.multigrid
 
     def call(self, name, *args):
         # set on every call: the window is thread-local state of the shared object, so a cache per Library object would go
@@ -202,6 +203,7 @@ class FluidSolver(PbClass):
         self.timePerFrame = 0.0
         self.mLockDt = False
         self._slab_window = (0, 0)
+        self._mg = None    # the GridMg of solvePressure(preconditioner=PcMGStatic | PcMGDynamic): one per solver (pressure.cpp:245-248)
         self.lib = SolverLib(_lib.get(), self)
         self.device = self.lib.device
         self._pool = {}    # dtype/ncomp -> list of free tensors  (GridStorage, fluidsolver.cpp:34-50)

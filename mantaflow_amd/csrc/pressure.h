@@ -43,7 +43,18 @@ struct MicSweep {
 	int ndot = 0;             // out: partials written to dotpart (0: the active mode cannot fuse the dot -- the caller runs its own)
 	bool tail_done = false;   // out: the tail was folded into the sweep
 };
+// a preconditioner that lives outside pressure.hip / mic.hip (multigrid.hip: PC_MGP).  init: once in doInit, before the first
+// apply (InitPrecondition...); apply: dst = M^-1 src on whole grids
+struct PcExternal {
+	int (*init)(void* ctx, const float* A0, const float* Ai, const float* Aj, const float* Ak, float accuracy, hipStream_t st);
+	int (*apply)(void* ctx, float* dst, const float* src, hipStream_t st);
+	void* ctx;
+};
 namespace mf {
+// mf_cg_solve's doInit + iterate loop (cg_solve_core: the same ApplyMatrix, fp64 dots and fused updates) around an external preconditioner
+int cg_solve_external(const Dim& d, const int32_t* flags, float* dst, const float* rhs, float* residual, float* search, float* tmp,
+                      const float* A0, const float* Ai, const float* Aj, const float* Ak, const PcExternal* ext, float accuracy, int maxIter,
+                      int useL2Norm, float* out_host, void* stream);
 // mode 0: InitPreconditionModifiedIncompCholesky2 (dst := Aprecond, var1 := A0); 1 / 2: forward / backward substitution
 // of ApplyPreconditionModifiedIncompCholesky2.  sc (nullable): skip when sc->done.  opt (nullable): see MicSweep
 int mic_sweep(int mode, const Dim& d, const int32_t* flags, float* dst, const float* var1, const float* Ap, const float* Ai,

@@ -1038,7 +1038,7 @@ k_diffusion_matrix(int64_t n, const int32_t* __restrict__ flags, float* __restri
 
 static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const float* rhs, float* residual, float* search, float* tmp,
                          const float* A0, const float* Ai, const float* Aj, const float* Ak, float* Aprecond, int pc, float accuracy,
-                         int maxIter, int useL2Norm, float* out_host, void* stream, const unsigned char* free_pack);
+                         int maxIter, int useL2Norm, float* out_host, void* stream, const unsigned char* free_pack, const PcExternal* ext = nullptr);
 // the system of mf_cg_solve with its rows padded from sx to px cells (pad cells: obstacle, zero coefficients, zero rhs), plus the caller's
 // tmp (pad cells 0), and back
 __global__ void __launch_bounds__(BLOCK)
@@ -1422,7 +1422,7 @@ static int pcg_setup(const Dim& d, const int32_t* flags, const float* rhs, const
 // only -- A0 / Ai / Aj / Ak are null, the MIC factor is already in Aprecond and the system is registered with the sweeps
 static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const float* rhs, float* residual, float* search, float* tmp,
                          const float* A0, const float* Ai, const float* Aj, const float* Ak, float* Aprecond, int pc, float accuracy,
-                         int maxIter, int useL2Norm, float* out_host, void* stream, const unsigned char* free_pack) {
+                         int maxIter, int useL2Norm, float* out_host, void* stream, const unsigned char* free_pack, const PcExternal* ext) {
 	const int sx = d.sx, sy = d.sy, sz = d.sz;
 	const int64_t n = d.n;
 	hipStream_t st = (hipStream_t)stream;
@@ -1441,6 +1441,10 @@ static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const f
 	if (pc == MF_PC_MICP) {
 		if (!free_pack) MF_TRY(mf_mic_init(sx, sy, sz, flags, Aprecond, A0, Ai, Aj, Ak, stream));
 		MF_TRY(mf_mic_apply(sx, sy, sz, flags, tmp, residual, Aprecond, Ai, Aj, Ak, stream));
+	} else if (ext) {
+		// PC_MGP: InitPreconditionMultigrid + ApplyPreconditionMultigrid, conjugategrad.cpp:229-231
+		MF_TRY(ext->init(ext->ctx, A0, Ai, Aj, Ak, accuracy, st));
+		MF_TRY(ext->apply(ext->ctx, tmp, residual, st));
 	} else {
 		MF_HIP(hipMemcpyAsync(tmp, residual, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
 	}
@@ -1468,7 +1472,9 @@ static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const f
 		MF_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
 	}
 	CgScalars* hslot = (CgScalars*)ws->host;   // two pinned slots
-	const int batch = (pc == MF_PC_MICP && mic_mode() == 0) ? 1 : 4;
+	// (an external preconditioner -- a multigrid V-cycle -- costs far more than a round trip and its kernels do not read `done`: the
+	// host then reads the scalars of every iteration before it queues the next)
+	const int batch = ((pc == MF_PC_MICP && mic_mode() == 0) || ext) ? 1 : 4;
 	const int be_nb = ((sy + 7) / 8) * ((sz + 7) / 8);      // the sweep's partials (one per bundle) come first, the nbs of the residual update behind them
 	int issued = 0, slot = 0, pending = -1;
 	while (issued < maxIter) {
@@ -1499,6 +1505,9 @@ static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const f
 					if (nsig != be_nb) return fail("mf_cg_solve: the backward sweep wrote %d dot partials, %d expected", nsig, be_nb);
 					nsig += nbs;
 				}
+			} else if (ext) {
+				hipLaunchKernelGGL((k_cg_axpy_r<false>), dim3(nbs), dim3(BLOCK), 0, st, n, sc, residual, tmp, p_mm, p_res);
+				MF_TRY(ext->apply(ext->ctx, tmp, residual, st));
 			} else {
 				hipLaunchKernelGGL((k_cg_axpy_r<true>), dim3(nbs), dim3(BLOCK), 0, st, n, sc, residual, tmp, p_mm, p_res);
 			}
@@ -1514,6 +1523,7 @@ static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const f
 		issued += todo;
 		MF_HIP(hipMemcpyAsync(&hslot[slot], sc, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
 		MF_HIP(hipEventRecord(ev[slot], st));
+		if (ext) pending = slot;
 		if (pending >= 0) {
 			MF_HIP(hipEventSynchronize(ev[pending]));
 			memcpy(&h, &hslot[pending], sizeof h);
@@ -1533,6 +1543,22 @@ static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const f
 	if (h.diverged) return fail("GridCg::iterate: The CG solver diverged, residual norm > 1e30, stopping.");
 	return 0;
 }
+
+namespace mf {
+int cg_solve_external(const Dim& d, const int32_t* flags, float* dst, const float* rhs, float* residual, float* search, float* tmp,
+                      const float* A0, const float* Ai, const float* Aj, const float* Ak, const PcExternal* ext, float accuracy, int maxIter,
+                      int useL2Norm, float* out_host, void* stream) {
+	if (!(al16(dst) && al16(rhs) && al16(residual) && al16(search) && al16(tmp))) return fail("cg_solve_external: work grids must be 16-byte aligned");
+	if (maxIter <= 0) {      // as mf_cg_solve: doInit never runs
+		out_host[0] = 0.f;
+		out_host[1] = 1e20f;
+		out_host[2] = 0.f;
+		return 0;
+	}
+	return cg_solve_core(d, flags, dst, rhs, residual, search, tmp, A0, Ai, Aj, Ak, nullptr, MF_PC_MGP, accuracy, maxIter, useL2Norm, out_host, stream,
+	                     nullptr, ext);
+}
+}  // namespace mf
 
 // ---- matrix-free set-up of a plain MakeLaplaceMatrix system (no fractions, no ghost fluid, no optional rhs terms): ONE pass over
 // flags and vel writes rhs (MakeRhs, pressure.cpp:32-84), the packed byte of every cell -- fluid bit, "Ai / Aj / Ak is -1" bits and the

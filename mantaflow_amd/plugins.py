@@ -208,6 +208,8 @@ def solvePressureSystem(rhs, vel, pressure, flags, cgAccuracy=1e-3, phi=None, pe
     s = flags.parent
     lib, st = s.lib, s.stream
     sx, sy, sz = flags.dims
+    if preconditioner in (PcMGDynamic, PcMGStatic):
+        _multigrid_lib(s, "solvePressureSystem")
     # reserve temp grids, pressure.cpp:332-338
     residual, search, A0, Ai, Aj, Ak, tmp = (Grid(s) for _ in range(7))
     lib.call("mf_make_laplace_matrix", sx, sy, sz, flags.ptr, A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr,
@@ -226,7 +228,27 @@ def solvePressureSystem(rhs, vel, pressure, flags, cgAccuracy=1e-3, phi=None, pe
             raise RuntimeError("GridCg<APPLYMAT>::setICPreconditioner: Invalid method specified.")
         pc = 2   # PC_mICP ; 2-D degrades to PC_None inside the solver (conjugategrad.cpp:315-321)
     elif preconditioner in (PcMGDynamic, PcMGStatic):
-        raise RuntimeError("solvePressure: multigrid preconditioners (source/multigrid.cpp) are outside the MI355X hot path")
+        # pressure.cpp:419-431, 452-454: one GridMg per solver; Dynamic releases an existing one first and its own after the solve,
+        # Static keeps it -- with its matrix: a later Static solve preconditions with the old hierarchy, whatever the flags are now
+        if s._mg is not None and preconditioner == PcMGDynamic:
+            _release_mg(s)
+        if s._mg is None:
+            s._mg = _MgHandle(lib, sx, sy, sz)
+            _mg_solvers.add(s)
+        out = (ctypes.c_float * 3)()
+        try:
+            lib.call("mf_mg_cg_solve", s._mg.handle, sx, sy, sz, flags.ptr, pressure.ptr, rhs.ptr, residual.ptr, search.ptr, tmp.ptr,
+                     A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr, float(cgAccuracy), 100, int(bool(useL2Norm)), out, st)   # maxIter = 100, :419
+        except RuntimeError as e:
+            if "diverged" in str(e):
+                # conjugategrad.cpp:287-291
+                print("GridCg::iterate: Warning - this diverging solve can be caused by the 'static' mode of the MG preconditioner. "
+                      "If the static mode is active, try switching to dynamic.")
+            raise
+        _last_cg["iterations"], _last_cg["residual"] = int(out[0]), float(out[1])
+        if preconditioner == PcMGDynamic:
+            _release_mg(s)
+        return
     else:
         maxIter, pc, pca0 = 0, 0, Grid(s)
     out = (ctypes.c_float * 3)()
@@ -269,6 +291,70 @@ def cgSolveDiffusion(flags, grid, alpha=0.25, cgMaxIterFac=1.0, cgAccuracy=1e-4)
             lib.call("mf_copy_f32", u.n, _ptr(grid.data[comp * grid.n:]), u.ptr, st)
     else:
         raise RuntimeError("cgSolveDiffusion: Grid Type is not supported (only Real, Vec3, MAC, or Levelset)")
+
+
+class _MgHandle(object):
+    """a multigrid hierarchy of the library (manta_hip_multigrid.h), destroyed with the object"""
+
+    def __init__(self, lib, sx, sy, sz):
+        self.lib = lib
+        h = ctypes.c_void_p()
+        lib.call("mf_mg_create", sx, sy, sz, ctypes.byref(h))
+        self.handle = h
+
+    def release(self):
+        if self.handle is not None:
+            h, self.handle = self.handle, None
+            self.lib.call("mf_mg_destroy", h)
+
+    def info(self):
+        """levels, set-ups so far, coarsest-CG iterations of the last V-cycle, per-level sizes and active vertices (mf_mg_info)"""
+        out = (ctypes.c_int64 * (8 + 4 * 16))()
+        self.lib.call("mf_mg_info", self.handle, out, len(out))
+        nl = int(out[0])
+        return dict(levels=nl, setups=int(out[1]), coarse_cg_iterations=int(out[2]), nonzero_stencil_sum=bool(out[3]),
+                    trivial_equations=bool(out[4]), tail_first_level=int(out[5]), setup_host_us=int(out[6]), setup_device_us=int(out[7]),
+                    sizes=[tuple(int(out[8 + 4 * l + c]) for c in range(3)) for l in range(nl)],
+                    active=[int(out[11 + 4 * l]) for l in range(nl)])
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+_mg_solvers = __import__("weakref").WeakSet()    # solvers that hold a hierarchy (gMapMG, pressure.cpp:248)
+
+
+def _multigrid_lib(s, name):
+    """refuse, before any grid is touched, what the multigrid preconditioner does not run on"""
+    lib = s.lib
+    if not lib.multigrid:
+        raise RuntimeError("%s: the '%s' backend does not implement the multigrid preconditioners PcMGStatic / PcMGDynamic "
+                           "(manta_hip_multigrid.h)" % (name, lib.backend))
+    if not s.is3D():
+        raise RuntimeError("%s: the multigrid preconditioners PcMGStatic / PcMGDynamic run on 3-D solvers only" % name)
+    if tuple(s._slab_window) != (0, 0):
+        raise RuntimeError("%s: the multigrid preconditioners PcMGStatic / PcMGDynamic do not run on a z-slab solver" % name)
+    return lib
+
+
+def _release_mg(solver):
+    mg, solver._mg = solver._mg, None
+    _mg_solvers.discard(solver)
+    if mg is not None:
+        mg.release()
+
+
+@plugin
+def releaseMG(solver=None):
+    """pressure.cpp:252-267: release the multigrid hierarchy PcMGStatic keeps on a solver (of every solver when none is given)"""
+    if solver is None or (isinstance(solver, int) and solver == 0):
+        for s in list(_mg_solvers):
+            _release_mg(s)
+        return
+    _release_mg(_chk(solver, core.FluidSolver, "FluidSolver"))
 
 
 def _fix_pressure(flags, rhs, A0, Ai, Aj, Ak):
@@ -318,6 +404,8 @@ def solvePressure(vel, pressure, flags, cgAccuracy=1e-3, phi=None, perCellCorr=N
                   cgMaxIterFac=1.5, precondition=True, preconditioner=PcMIC, enforceCompatibility=False, useL2Norm=False,
                   zeroPressureFixing=False, curv=None, surfTens=0., retRhs=None):
     _chk(vel, MACGrid, "MACGrid")
+    if precondition is not False and preconditioner in (PcMGDynamic, PcMGStatic):
+        _multigrid_lib(vel.parent, "solvePressure")
     if _plain_system(vel, pressure, flags, cgAccuracy, phi, perCellCorr, fractions, obvel, precondition, preconditioner,
                      enforceCompatibility, zeroPressureFixing, curv, surfTens):
         # the plain case (every smoke scene, FLIP without ghost fluid): rhs + packed matrix in one pass, MIC factor and PCG on the
