@@ -926,6 +926,25 @@ k_slab_axpy_r(int64_t n, const double* __restrict__ g, int world, CgScalars* __r
 		fpart[2 * blockIdx.x + 1] = hi;
 	}
 }
+// the residual update for views that do not start on a 16-byte boundary, behind k_slab_alpha_x: nothing once stopped (`done`), so that the
+// residual keeps its bits -- r + (-0) * tmp would turn a -0 into +0, and into NaN where tmp has overflowed
+__global__ void __launch_bounds__(BLOCK)
+k_slab_axpy_r_scalar(int64_t n, const CgScalars* __restrict__ sc, float* __restrict__ residual, const float* __restrict__ tmp, float* __restrict__ fpart) {
+	if (sc->done) return;
+	const float nalpha = sc->nalpha;
+	float lo = FLT_MAX, hi = -FLT_MAX;
+	for (int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+		const float r = residual[i] + nalpha * tmp[i];
+		residual[i] = r;
+		lo = fminf(lo, r);
+		hi = fmaxf(hi, r);
+	}
+	block_minmax(lo, hi);
+	if (threadIdx.x == 0) {
+		fpart[2 * blockIdx.x] = lo;
+		fpart[2 * blockIdx.x + 1] = hi;
+	}
+}
 __global__ void k_slab_beta_x(const double* __restrict__ g, int world, CgScalars* __restrict__ sc, float accuracy, int iter, int32_t* __restrict__ state) {
 	if (state && state[0]) return;
 	double acc = 0.0, mx = 0.0;
@@ -1676,9 +1695,13 @@ int mf_cg_slab_after_dp(const double* gathered, int world, void* scalars, const 
 			if (!d.is3d) return fail("mICP only supports 3D grids so far");
 			return mic_apply_dot_fold(d, flags, tmp, residual, Aprecond, Ai, Aj, Ak, dot_dev, nb, ws->fpartials, maxabs_dev, sc, st);
 		} else {
-			// views that do not start on a 16-byte boundary (odd plane sizes): the unfused sequence (alpha is 0 once stopped)
-			MF_TRY(mf_grid_scaled_add_dev(n_own, r, t, &sc->alpha, -1.f, stream));
-			MF_TRY(mf_grid_max_abs_dev_f64(n_own, r, maxabs_dev, stream));
+			// views that do not start on a 16-byte boundary (odd plane sizes), or no stop state: the unfused sequence (a no-op once stopped)
+			Workspace* ws;
+			MF_TRY(get_workspace(&ws));
+			const int nb = blocks_for(n_own, BLOCK, 2048);
+			hipLaunchKernelGGL(k_slab_axpy_r_scalar, dim3(nb), dim3(BLOCK), 0, st, n_own, sc, r, t, ws->fpartials);
+			hipLaunchKernelGGL(k_fin_maxabs, dim3(1), dim3(BLOCK), 0, st, nb, ws->fpartials, maxabs_dev);
+			MF_LAUNCH_CHECK();
 		}
 	}
 	return mf_mic_apply_dot_dev(sx, sy, sz, flags, tmp, residual, Aprecond, Ai, Aj, Ak, dot_dev, stream);
