@@ -11,7 +11,8 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       setPartType, markIsolatedFluidCell, addForcePvel, updateVelocityFromDeltaPos, eulerStep,
                       interpolateGrid, interpolateGridVec3, interpolateMACGrid, computeEnergy, computeWaveletCoeffs,
                       vorticityConfinement, applyNoiseVec3, setOpenBound,
-                      updateFractions, setObstacleFlags, setInflowBcs, addNoise, releaseMG)
+                      updateFractions, setObstacleFlags, setInflowBcs, addNoise, releaseMG,
+                      adjustNumber, combineGridVel)
 
 from .scene import (Box, Cylinder, Gui, NoiseField, Shape, Sphere, densityInflow, sampleFlagsWithParticles,
                     sampleLevelsetWithParticles, sampleShapeWithParticles)

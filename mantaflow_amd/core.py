@@ -161,6 +161,7 @@ class SolverLib(object):
         self.backend, self.device, self.cdll, self.path = lib.backend, lib.device, lib.cdll, lib.path
         self.obstacles = lib.obstacles
         self.multigrid = lib.multigrid
+        self.resample = lib.resample
 
     def call(self, name, *args):
         # set on every call: the window is thread-local state of the shared object, so a cache per Library object would go
@@ -346,6 +347,31 @@ class GridBase(PbClass):
         self.data, other.data = other.data, self.data
 
     def getDataPointer(self): return "%x" % self.data.data_ptr()
+
+    def setBoundNeumann(self, boundaryWidth):
+        """Grid<T>::setBoundNeumann -> knSetBoundaryNeumann, grid.cpp:640-669: every cell within boundaryWidth + 1 of a side takes
+        the value of the nearest cell inside (per component: the words are copied)"""
+        w = int(boundaryWidth)
+        lo = 2 * w + 3
+        if w < 0 or self.sx < lo or self.sy < lo or (self.is3D() and self.sz < lo):
+            raise RuntimeError("setBoundNeumann: grid [%d,%d,%d] too small for boundaryWidth %d" % (self.sx, self.sy, self.sz, w))
+        lib = self.parent.lib
+        if lib.resample:
+            for c in range(self._ncomp):
+                self._call("mf_grid_set_bound_neumann", self.sx, self.sy, self.sz, _ptr(self.data[c * self.n:]), w, self.parent.stream)
+            return
+        if lib.backend == "hip":
+            raise RuntimeError("setBoundNeumann: %s lacks the resampling extension (manta_hip_resample.h) -- rebuild the library" % lib.path)
+        # the CPU checker backend: the same separable index map as a torch expression
+        dev = self.data.device
+        def src(size):
+            i = torch.arange(size, device=dev)
+            i = torch.where(i <= w, torch.full_like(i, w + 1), i)
+            return torch.where(torch.arange(size, device=dev) >= size - 1 - w, torch.full_like(i, size - w - 2), i)
+        v = self.data.view(self._ncomp, self.sz, self.sy, self.sx)
+        if self.is3D():
+            v = v.index_select(1, src(self.sz))
+        self.data.copy_(v.index_select(2, src(self.sy)).index_select(3, src(self.sx)).reshape(-1))
 
     def save(self, name):
         """Grid<T>::save, grid.cpp:157-179 (.uni, .raw, .npz)"""
@@ -587,6 +613,20 @@ class LevelsetGrid(Grid):
         self._call("mf_levelset_subtract", self.n, self.ptr, o.ptr, None if flags is None else flags.ptr,
                    int(subtractType), self.parent.stream)
 
+    def initFromFlags(self, flags, ignoreWalls=False):
+        """LevelsetGrid::initFromFlags, levelset.cpp:231-238: -0.5 on fluid cells (and obstacle cells with ignoreWalls), else 0.5"""
+        if not isinstance(flags, FlagGrid):
+            raise RuntimeError("can't convert argument to FlagGrid*")
+        self._check_same(flags)
+        lib = self.parent.lib
+        if lib.resample:
+            self._call("mf_levelset_init_from_flags", self.n, self.ptr, flags.ptr, int(bool(ignoreWalls)), self.parent.stream)
+            return
+        if lib.backend == "hip":
+            raise RuntimeError("initFromFlags: %s lacks the resampling extension (manta_hip_resample.h) -- rebuild the library" % lib.path)
+        inside = (flags.data & (TypeFluid | (TypeObstacle if ignoreWalls else 0))) != 0
+        self.data.copy_(torch.where(inside, -0.5, 0.5).to(torch.float32))
+
     def createMesh(self, mesh):
         """marching-cubes surface extraction is GUI/mesh output, outside the solver hot path: accepted and ignored"""
         return None
@@ -682,6 +722,7 @@ class ParticleDataImpl(PbClass):
         self.sys = None
         self.data = torch.zeros(0, dtype=self._dtype, device=parent.device)
         self.cap = 0      # component stride (== pstride of the ABI)
+        self.mpGridSource, self.mGridSourceMAC = None, False     # setSource
 
     def _attach(self, sys):
         self.sys = sys
@@ -699,6 +740,15 @@ class ParticleDataImpl(PbClass):
     pyResize = resize
     @property
     def ptr(self): return _ptr(self.data)
+
+    def setSource(self, grid, isMAC=False):
+        """ParticleDataImpl<T>::setSource, particle.cpp:341-346: the grid new particles take their value from (adjustNumber's
+        insertion); None: new values are 0"""
+        if grid is not None and not isinstance(grid, self._source_type):
+            raise RuntimeError("can't convert argument to %s*" % self._source_name)
+        if isMAC and not isinstance(grid, MACGrid):
+            raise RuntimeError("Given grid is not a valid MAC grid")
+        self.mpGridSource, self.mGridSourceMAC = grid, bool(isMAC)
     def size(self): return self.sys.np if self.sys else 0
     def clear(self): self.data.zero_()
 
@@ -727,12 +777,17 @@ class ParticleDataImpl(PbClass):
 
 class PdataReal(ParticleDataImpl):
     _cname_py, _cname_cpp, _T = "PdataReal", "ParticleDataImpl", "Real"
+    _source_type, _source_name = Grid, "Grid<Real>"
     def setConst(self, v): self.data.fill_(float(v))
 
 
 class PdataInt(ParticleDataImpl):
     _dtype = torch.int32
     _cname_py, _cname_cpp, _T = "PdataInt", "ParticleDataImpl", "int"
+
+    def setSource(self, grid, isMAC=False):
+        raise RuntimeError("PdataInt.setSource: integer source grids are not implemented (no scene uses them)")
+
     def setConst(self, v): self.data.fill_(int(v))
 
     def setConstRange(self, s, begin, end):
@@ -743,6 +798,7 @@ class PdataInt(ParticleDataImpl):
 class PdataVec3(ParticleDataImpl):
     _ncomp = 3
     _cname_py, _cname_cpp, _T = "PdataVec3", "ParticleDataImpl", "Vec3"
+    _source_type, _source_name = VecGrid, "Grid<Vec3>"
 
     def setConst(self, v):
         v = _to_vec3(v)
@@ -783,6 +839,11 @@ class BasicParticleSystem(PbClass):
         self.pos = torch.zeros(0, dtype=torch.float32, device=dev)     # SoA [3][cap]
         self.flag = torch.zeros(0, dtype=torch.int32, device=dev)
         self.pdata = []
+        # ParticleSystem's delete bookkeeping, particle.h:171-173, 423-427: kill() counts mDeletes and, where mAllowCompress,
+        # compresses once mDeletes > mDeleteChunk.  Only addParticle, clear and compress change mDeleteChunk; set_positions (the
+        # samplers' buffered insertion) leaves both.  BasicParticleSystem's constructor clears mAllowCompress (particle.cpp:134-138),
+        # so its kills only count and doCompress() at the end of adjustNumber is the one compress of a call
+        self.mDeletes, self.mDeleteChunk, self.mAllowCompress = 0, 0, False
 
     def create(self, type, name="", **kw):
         """ParticleBase::create, particle.cpp:77-101: new pdata field sized like the system"""
@@ -813,7 +874,36 @@ class BasicParticleSystem(PbClass):
         for pd in self.pdata:
             pd.resize(n, self.cap)
 
-    def clear(self): self.resizeAll(0)
+    def clear(self):
+        """ParticleSystem::clear, particle.h:408-412"""
+        self.mDeleteChunk = self.mDeletes = 0
+        self.resizeAll(0)
+
+    def reserve(self, n):
+        """capacity for n particles in every array: grows geometrically, never shrinks"""
+        if n > self.cap:
+            self.resizeAll(self.np, max(n, 2 * self.cap))
+
+    def compress(self, planned=None):
+        """ParticleSystem::compress, particle.h:614-633: deleted slots are filled from the tail, every pdata channel moves along.
+        planned: (size, holes) of a plan the library holds already (mf_resample_round)"""
+        s = self.parent
+        if not s.lib.resample:
+            raise RuntimeError("compress: the '%s' backend does not implement particle resampling (manta_hip_resample.h)" % s.lib.backend)
+        if planned is None:
+            r = (ctypes.c_int64 * 2)()
+            s.lib.call("mf_particles_compress_plan", self.np, _ptr(self.flag), r, s.stream)
+            planned = (int(r[0]), int(r[1]))
+        size, holes = planned
+        for ncomp, t, cap in [(3, self.pos, self.cap), (1, self.flag, self.cap)] + [(pd._ncomp, pd.data, pd.cap) for pd in self.pdata]:
+            s.lib.call("mf_particles_compress_move", holes, ncomp, cap, _ptr(t), s.stream)
+        self.np = size
+        self.mDeletes, self.mDeleteChunk = 0, size // 20
+
+    def doCompress(self, bForce=False):
+        """particle.h:142-145"""
+        if bForce or self.mDeletes > self.mDeleteChunk:
+            self.compress()
 
     # numpy bridge: positions [np][3], flags [np]
     def set_positions(self, arr, flags=None):
@@ -849,6 +939,7 @@ class BasicParticleSystem(PbClass):
         old = self.get_positions()
         fl = self.get_flags()
         self.set_positions(np.concatenate([old, np.array([[p.x, p.y, p.z]], np.float32)]), np.concatenate([fl, [0]]))
+        self.mDeleteChunk = self.np // 20     # ParticleSystem::add, particle.h:414-420
 
     def advectInGrid(self, flags, vel, integrationMode, deleteInObstacle=True, stopInObstacle=True, skipNew=False,
                      ptype=None, exclude=0):

@@ -1,0 +1,486 @@
+// resample.hip -- particle resampling for narrow-band FLIP (include/manta_hip_resample.h): adjustNumber's particle loop in its
+// order-free form, the particle system's compress, the seeding loop with the buffered insertion, combineGridVel, and the grid
+// operations setBoundNeumann / initFromFlags.  Reference: source/plugin/flip.cpp, source/particle.{h,cpp}, source/grid.cpp,
+// source/levelset.cpp.  The formulation is stated in DESIGN.md ("Particle resampling").
+#include "common.h"
+#include "../../include/manta_hip_resample.h"
+#include <hipcub/hipcub.hpp>
+
+using namespace mf;
+
+namespace {
+
+constexpr int PNEW_ = 1, PDELETE_ = 1 << 10;
+// class of a particle in one round: not looked at (deleted already), killed whatever its cell holds, surface, normal
+constexpr int C_SKIP = 0, C_KILL = 1, C_SURF = 2, C_NORM = 3;
+
+static inline unsigned nblk_n(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
+
+#define CELL_IJK(d)                                                \
+	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x; \
+	if (idx >= (d).n) return;                                      \
+	const unsigned t_ = (unsigned)idx / (unsigned)(d).sx;          \
+	const int i = (int)((unsigned)idx - t_ * (unsigned)(d).sx);    \
+	const int j = (int)(t_ % (unsigned)(d).sy);                    \
+	const int k = (int)(t_ / (unsigned)(d).sy);
+
+// ---- the per-device arena: working arrays of a round and the compress plan; grows geometrically, never shrinks ----------------
+struct Arena {
+	char* p;
+	size_t cap;
+	int32_t *holes, *fillers;   // the current compress plan
+};
+Arena g_arena[16];
+
+static int arena(size_t need, Arena** out) {
+	int dev = 0;
+	MF_HIP(hipGetDevice(&dev));
+	if (dev < 0 || dev >= 16) return fail("device index %d out of range", dev);
+	Arena& a = g_arena[dev];
+	if (need > a.cap) {
+		size_t cap = a.cap * 2 > need ? a.cap * 2 : need;
+		MF_HIP(hipDeviceSynchronize());
+		if (a.p) MF_HIP(hipFree(a.p));
+		a.p = nullptr;
+		a.cap = 0;
+		a.holes = a.fillers = nullptr;
+		MF_HIP(hipMalloc((void**)&a.p, cap));
+		a.cap = cap;
+	}
+	*out = &a;
+	return 0;
+}
+static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// ---- grid operations ---------------------------------------------------------------------------------------------------------
+// knSetBoundaryNeumann, grid.cpp:640-669: the source cell lies strictly inside (the entry checks the sizes), so no thread reads a
+// cell another one writes
+__global__ __launch_bounds__(BLOCK) void k_set_bound_neumann(Dim d, uint32_t* __restrict__ g, int w) {
+	CELL_IJK(d)
+	int si = i, sj = j, sk = k;
+	bool set = false;
+	if (i <= w) { si = w + 1; set = true; }
+	if (i >= d.sx - 1 - w) { si = d.sx - 1 - w - 1; set = true; }
+	if (j <= w) { sj = w + 1; set = true; }
+	if (j >= d.sy - 1 - w) { sj = d.sy - 1 - w - 1; set = true; }
+	if (d.is3d) {
+		if (k <= w) { sk = w + 1; set = true; }
+		if (k >= d.sz - 1 - w) { sk = d.sz - 1 - w - 1; set = true; }
+	}
+	if (set) g[idx] = g[(int64_t)si + d.Y * sj + d.Z * sk];
+}
+
+// LevelsetGrid::initFromFlags, levelset.cpp:231-238
+__global__ __launch_bounds__(BLOCK) void k_init_from_flags(int64_t n, float* __restrict__ phi, const int32_t* __restrict__ flags,
+                                                           int ignoreWalls) {
+	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+	if (idx >= n) return;
+	const int f = flags[idx];
+	phi[idx] = ((f & MF_FLUID) || (ignoreWalls && (f & MF_OBSTACLE))) ? -0.5f : 0.5f;
+}
+
+// knCombineVels, plugin/flip.cpp:748-770
+__global__ __launch_bounds__(BLOCK) void k_combine_vels(Dim d, float* __restrict__ vel, const float* __restrict__ w,
+                                                        float* __restrict__ comb, const float* __restrict__ phi, float narrowBand,
+                                                        float thresh) {
+	CELL_IJK(d)
+#pragma unroll
+	for (int c = 0; c < 3; c++) {
+		const int64_t o = (int64_t)c * d.n + idx;
+		if (phi) {
+			float p[3] = {(float)i, (float)j, (float)k};
+			p[(c + 1) % 3] += 0.5f;
+			p[(c + 2) % 3] += 0.5f;
+			if (interpol1(d, phi, p[0], p[1], p[2]) < -narrowBand) {
+				vel[o] = 0.f;
+				continue;
+			}
+		}
+		if (w[o] > thresh) {
+			comb[o] = vel[o];
+			vel[o] = -1.f;
+		} else {
+			vel[o] = 0.f;
+		}
+	}
+}
+
+// ---- one round of adjustNumber's particle loop ----------------------------------------------------------------------------------
+// plugin/flip.cpp:215-227 for the particle t = i0 + q: its class, its cell as the sort key (nc for the ones no cell counts), and
+// the number of counted particles per cell
+__global__ __launch_bounds__(BLOCK) void k_classify(Dim d, const float* __restrict__ phi, int64_t m, int64_t ps,
+                                                    const float* __restrict__ pos, const int32_t* __restrict__ pflag, int64_t i0,
+                                                    float narrowBand, float surfLs, int32_t* __restrict__ keys,
+                                                    int32_t* __restrict__ vals, int32_t* __restrict__ cls, int32_t* __restrict__ cnt) {
+	const int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+	if (q >= m) return;
+	const int64_t t = i0 + q;
+	int key = (int)d.n, c = C_SKIP;
+	if (!(pflag[t] & PDELETE_)) {
+		const float x = pos[t], y = pos[ps + t], z = pos[2 * ps + t];
+		const int ix = (int)x, iy = (int)y, iz = (int)z;   // toVec3i: truncation
+		c = C_KILL;
+		if (ix >= 0 && iy >= 0 && iz >= 0 && ix < d.sx && iy < d.sy && iz < d.sz) {
+			const float phiv = interpol1(d, phi, x, y, z);
+			if (!(phiv > 0.f) && !(narrowBand > 0.f && phiv < -narrowBand)) {
+				c = phiv > surfLs ? C_SURF : C_NORM;
+				key = (int)((int64_t)ix + d.Y * iy + d.Z * iz);
+				atomicAdd(&cnt[key], 1);
+			}
+		}
+	}
+	keys[q] = key;
+	vals[q] = (int32_t)q;
+	cls[q] = c;
+}
+
+// p-th entry of the cell-sorted (stable in particle index) list: f = tmp(cell) + counted particles before it in the cell; a normal
+// particle is culled iff f > maxParticles (flip.cpp:228-235).  cls becomes the kill decision in bit 2.
+__global__ __launch_bounds__(BLOCK) void k_decide(int64_t m, int nc, const int32_t* __restrict__ skeys,
+                                                  const int32_t* __restrict__ svals, const int32_t* __restrict__ start,
+                                                  const int32_t* __restrict__ tmp, int maxParticles, const int32_t* __restrict__ cls,
+                                                  int32_t* __restrict__ kill) {
+	const int64_t p = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+	if (p >= m) return;
+	const int key = skeys[p], q = svals[p], c = cls[q];
+	int kl;
+	if (key == nc)
+		kl = c == C_KILL;
+	else
+		kl = c == C_NORM && tmp[key] + ((int)p - start[key]) > maxParticles;
+	kill[q] = kl;
+}
+
+// the first kill whose running count passes the chunk: the one the serial loop compresses at (particle.h:426)
+__global__ __launch_bounds__(BLOCK) void k_find(int64_t m, const int32_t* __restrict__ kill, const int32_t* __restrict__ pre,
+                                                int64_t md, int64_t chunk, int64_t* __restrict__ res) {
+	const int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+	if (q >= m || !kill[q]) return;
+	const int64_t c = md + pre[q];
+	if (c > chunk && (c - 1 <= chunk || pre[q] == 1)) res[0] = q;   // exactly one thread
+}
+
+// kills and counts of the particles up to and including the hit (all of them without one)
+__global__ __launch_bounds__(BLOCK) void k_apply(int64_t m, int64_t i0, const int32_t* __restrict__ keys,
+                                                 const int32_t* __restrict__ cls, const int32_t* __restrict__ kill,
+                                                 const int32_t* __restrict__ pre, int64_t* __restrict__ res,
+                                                 int32_t* __restrict__ pflag, int32_t* __restrict__ tmp) {
+	const int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+	if (q >= m) return;
+	const int64_t hit = res[0];
+	const int64_t last = hit >= 0 ? hit : m - 1;
+	if (q > last) return;
+	if (q == last) res[1] = pre[q];
+	if (kill[q])
+		pflag[i0 + q] |= PDELETE_;
+	else if (cls[q] >= C_SURF)
+		atomicAdd(&tmp[keys[q]], 1);
+}
+// idx* in particle indices
+__global__ void k_round_finish(int64_t i0, int64_t np, int64_t* res) {
+	if (res[0] >= 0)
+		res[0] += i0;
+	else {
+		res[2] = np;
+		res[3] = 0;
+	}
+}
+
+// ---- compress -----------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(BLOCK) void k_alive(int64_t np, const int32_t* __restrict__ pflag, int32_t* __restrict__ alive) {
+	const int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+	if (i < np) alive[i] = (pflag[i] & PDELETE_) ? 0 : 1;
+}
+// A: exclusive prefix of alive.  M = A[np-1] + alive[np-1]; hole i (deleted, i < M) has rank i - A[i]; filler i (kept, i >= M) has
+// the rank "kept slots after it" = M - A[i] - 1.  res[2] = M, res[3] = holes (when `active` allows: a round without a hit keeps its own)
+__global__ __launch_bounds__(BLOCK) void k_plan(int64_t np, const int32_t* __restrict__ pflag, const int32_t* __restrict__ A,
+                                                int32_t* __restrict__ holes, int32_t* __restrict__ fillers, int64_t* __restrict__ res,
+                                                int needs_hit) {
+	const int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+	if (i >= np) return;
+	if (needs_hit && res[0] < 0) return;
+	const int64_t M = (int64_t)A[np - 1] + ((pflag[np - 1] & PDELETE_) ? 0 : 1);
+	const bool dead = pflag[i] & PDELETE_;
+	if (i < M && dead) holes[i - A[i]] = (int32_t)i;
+	if (i >= M && !dead) fillers[M - A[i] - 1] = (int32_t)i;
+	if (i == 0) {
+		res[2] = M;
+		if (M == np) res[3] = 0;
+	}
+	if (i == M) res[3] = M - A[M];
+}
+__global__ __launch_bounds__(BLOCK) void k_move(int64_t H, const int32_t* __restrict__ holes, const int32_t* __restrict__ fillers,
+                                                int ncomp, int64_t ps, uint32_t* __restrict__ data) {
+	const int64_t k = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+	if (k >= H) return;
+	const int64_t h = holes[k], f = fillers[k];
+	for (int c = 0; c < ncomp; c++) data[c * ps + h] = data[c * ps + f];
+}
+
+static int plan_launch(Arena* a, int64_t np, const int32_t* pflag, int32_t* A, int32_t* holes, int32_t* fillers, void* cub,
+                       size_t cub_bytes, int64_t* res, int needs_hit, hipStream_t st) {
+	hipLaunchKernelGGL(k_alive, dim3(nblk_n(np)), dim3(BLOCK), 0, st, np, pflag, A);
+	MF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, A, A, (int)np, st));
+	hipLaunchKernelGGL(k_plan, dim3(nblk_n(np)), dim3(BLOCK), 0, st, np, pflag, A, holes, fillers, res, needs_hit);
+	MF_LAUNCH_CHECK();
+	a->holes = holes;
+	a->fillers = fillers;
+	return 0;
+}
+
+// ---- seeding ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(BLOCK) void k_clear_new(int64_t np, int32_t* __restrict__ pflag) {
+	const int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+	if (i < np) pflag[i] &= ~PNEW_;
+}
+// plugin/flip.cpp:241-250
+__global__ __launch_bounds__(BLOCK) void k_seed_need(int64_t n, const int32_t* __restrict__ flags, const float* __restrict__ phi,
+                                                     const float* __restrict__ exclude, const int32_t* __restrict__ tmp, int minP,
+                                                     float narrowBand, float surfLs, int32_t* __restrict__ need) {
+	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+	if (idx >= n) return;
+	const float p = phi[idx];
+	int nd = 0;
+	const bool skip = p > surfLs || (narrowBand > 0.f && p < -narrowBand) || (exclude && exclude[idx] < 0.f);
+	if (!skip && (flags[idx] & MF_FLUID)) {
+		nd = minP - tmp[idx];
+		if (nd < 0) nd = 0;
+	}
+	need[idx] = nd;
+}
+__global__ void k_seed_total(int64_t n, const int32_t* need, const int32_t* offsets, int64_t* res) {
+	res[0] = (int64_t)offsets[n - 1] + need[n - 1];
+}
+// plugin/flip.cpp:250-256 + particle.h:645-650
+__global__ __launch_bounds__(BLOCK) void k_seed_insert(Dim d, const int32_t* __restrict__ offsets, const float* __restrict__ reals,
+                                                       int64_t np, int64_t total, int64_t ps, float* __restrict__ pos,
+                                                       int32_t* __restrict__ pflag) {
+	CELL_IJK(d)
+	const int64_t first = offsets[idx];
+	const int64_t end = idx + 1 < d.n ? (int64_t)offsets[idx + 1] : total;
+	for (int64_t m = first; m < end; m++) {
+		const float* r = reals + 3 * m;
+		const int64_t s = np + m;
+		pos[s] = (float)i + r[0];
+		pos[ps + s] = (float)j + r[1];
+		pos[2 * ps + s] = d.is3d ? (float)k + r[2] : 0.5f;
+		pflag[s] = PNEW_;
+	}
+}
+
+// ParticleDataImpl<T>::initNewValue, particle.cpp:348-369
+__global__ __launch_bounds__(BLOCK) void k_pdata_init(Dim d, const float* __restrict__ grid, int mode, int ncomp, int64_t first,
+                                                      int64_t count, int64_t ps, const float* __restrict__ pos,
+                                                      float* __restrict__ data) {
+	const int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+	if (q >= count) return;
+	const int64_t t = first + q;
+	if (mode == 0) {
+		for (int c = 0; c < ncomp; c++) data[c * ps + t] = 0.f;   // the all-zero word, for int channels as well
+		return;
+	}
+	const float x = pos[t], y = pos[ps + t], z = pos[2 * ps + t];
+	if (mode == 2) {
+		float vx, vy, vz;
+		interpol_mac(d, grid, x, y, z, vx, vy, vz);
+		data[t] = vx;
+		data[ps + t] = vy;
+		data[2 * ps + t] = vz;
+	} else {
+		for (int c = 0; c < ncomp; c++) data[c * ps + t] = interpol1(d, grid + (int64_t)c * d.n, x, y, z);
+	}
+}
+
+static int bits_for(int64_t nc) {
+	int end_bit = 1;
+	while (end_bit < 31 && (((int64_t)1 << end_bit) <= nc)) end_bit++;
+	return end_bit;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mf_resample_abi_version(void) { return MF_RESAMPLE_ABI_VERSION; }
+
+int mf_grid_set_bound_neumann(int sx, int sy, int sz, void* data, int boundaryWidth, void* stream) {
+	MF_TRY(check_dim(sx, sy, sz));
+	const Dim d = mkdim(sx, sy, sz);
+	const int w = boundaryWidth, lo = 2 * w + 3;
+	if (w < 0) return fail("setBoundNeumann: boundaryWidth %d < 0", w);
+	if (sx < lo || sy < lo || (d.is3d && sz < lo))
+		return fail("setBoundNeumann: grid %dx%dx%d too small for boundaryWidth %d (needs %d cells per axis)", sx, sy, sz, w, lo);
+	hipLaunchKernelGGL(k_set_bound_neumann, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, (uint32_t*)data, w);
+	MF_LAUNCH_CHECK();
+	return 0;
+}
+
+int mf_levelset_init_from_flags(int64_t n, float* phi, const int32_t* flags, int ignoreWalls, void* stream) {
+	if (n <= 0) return 0;
+	hipLaunchKernelGGL(k_init_from_flags, dim3(nblk_n(n)), dim3(BLOCK), 0, (hipStream_t)stream, n, phi, flags, ignoreWalls);
+	MF_LAUNCH_CHECK();
+	return 0;
+}
+
+int mf_combine_grid_vel(int sx, int sy, int sz, float* vel, const float* weight, float* combineVel, const float* phi,
+                        float narrowBand, float thresh, void* stream) {
+	MF_TRY(check_dim(sx, sy, sz));
+	const Dim d = mkdim(sx, sy, sz);
+	hipLaunchKernelGGL(k_combine_vels, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, weight, combineVel, phi,
+	                   narrowBand, thresh);
+	MF_LAUNCH_CHECK();
+	return 0;
+}
+
+int mf_resample_round(int sx, int sy, int sz, const float* phi, int32_t* tmp, int64_t np, int64_t pstride, const float* pos,
+                      int32_t* pflag, int64_t i0, int maxParticles, float narrowBand, float surfaceLs, int64_t mDeletes,
+                      int64_t mDeleteChunk, int64_t* result_host, void* stream) {
+	MF_TRY(check_dim(sx, sy, sz));
+	const Dim d = mkdim(sx, sy, sz);
+	hipStream_t st = (hipStream_t)stream;
+	if (np >= ((int64_t)1 << 31)) return fail("adjustNumber: too many particles for 32-bit indices");
+	if (i0 < 0 || i0 > np || pstride < np) return fail("adjustNumber: bad particle range (i0 %lld, np %lld, stride %lld)", (long long)i0, (long long)np, (long long)pstride);
+	const int64_t m = np - i0;
+	if (m == 0) {
+		result_host[0] = -1;
+		result_host[1] = 0;
+		result_host[2] = np;
+		result_host[3] = 0;
+		return 0;
+	}
+	const int nc = (int)d.n, end_bit = bits_for(nc);
+	// arena: 6 arrays of np words (keys, sorted keys, vals, sorted vals, cls, kill; the prefix reuses sorted keys, the plan reuses
+	// keys / vals / sorted vals), cnt and start of nc + 1 words, the result block, the hipcub workspace
+	size_t scan_m = 0, scan_c = 0, scan_p = 0, sort_b = 0;
+	MF_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, scan_m, (int32_t*)nullptr, (int32_t*)nullptr, (int)m, st));
+	MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_c, (int32_t*)nullptr, (int32_t*)nullptr, nc + 1, st));
+	MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_p, (int32_t*)nullptr, (int32_t*)nullptr, (int)np, st));
+	MF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
+	                                          (int)m, 0, end_bit, st));
+	size_t cub_bytes = scan_m > scan_c ? scan_m : scan_c;
+	if (scan_p > cub_bytes) cub_bytes = scan_p;
+	if (sort_b > cub_bytes) cub_bytes = sort_b;
+	const size_t wp = al256(sizeof(int32_t) * (size_t)np), wc = al256(sizeof(int32_t) * ((size_t)nc + 1));
+	Arena* a;
+	MF_TRY(arena(6 * wp + 2 * wc + 256 + al256(cub_bytes), &a));
+	char* b = a->p;
+	int32_t* keys = (int32_t*)b;
+	int32_t* skeys = (int32_t*)(b + wp);
+	int32_t* vals = (int32_t*)(b + 2 * wp);
+	int32_t* svals = (int32_t*)(b + 3 * wp);
+	int32_t* cls = (int32_t*)(b + 4 * wp);
+	int32_t* kill = (int32_t*)(b + 5 * wp);
+	int32_t* cnt = (int32_t*)(b + 6 * wp);
+	int32_t* start = (int32_t*)(b + 6 * wp + wc);
+	int64_t* res = (int64_t*)(b + 6 * wp + 2 * wc);
+	void* cub = b + 6 * wp + 2 * wc + 256;
+	int32_t* pre = skeys;   // free once k_decide has read the sorted keys
+
+	MF_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * ((size_t)nc + 1), st));
+	MF_HIP(hipMemsetAsync(res, 0xff, sizeof(int64_t), st));          // res[0] = -1
+	MF_HIP(hipMemsetAsync(res + 1, 0, 3 * sizeof(int64_t), st));
+	const dim3 gm(nblk_n(m)), bl(BLOCK);
+	hipLaunchKernelGGL(k_classify, gm, bl, 0, st, d, phi, m, pstride, pos, pflag, i0, narrowBand, surfaceLs, keys, vals, cls, cnt);
+	MF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, scan_c, cnt, start, nc + 1, st));
+	MF_HIP(hipcub::DeviceRadixSort::SortPairs(cub, sort_b, keys, skeys, vals, svals, (int)m, 0, end_bit, st));
+	hipLaunchKernelGGL(k_decide, gm, bl, 0, st, m, nc, skeys, svals, start, tmp, maxParticles, cls, kill);
+	MF_HIP(hipcub::DeviceScan::InclusiveSum(cub, scan_m, kill, pre, (int)m, st));
+	hipLaunchKernelGGL(k_find, gm, bl, 0, st, m, kill, pre, mDeletes, mDeleteChunk, res);
+	hipLaunchKernelGGL(k_apply, gm, bl, 0, st, m, i0, keys, cls, kill, pre, res, pflag, tmp);
+	MF_LAUNCH_CHECK();
+	// the plan of the whole array; its kernels do nothing when the round had no hit
+	MF_TRY(plan_launch(a, np, pflag, svals, keys, vals, cub, scan_p, res, 1, st));
+	hipLaunchKernelGGL(k_round_finish, dim3(1), dim3(1), 0, st, i0, np, res);
+	MF_LAUNCH_CHECK();
+	MF_HIP(hipMemcpyAsync(result_host, res, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+	MF_HIP(hipStreamSynchronize(st));
+	return 0;
+}
+
+int mf_particles_compress_plan(int64_t np, const int32_t* pflag, int64_t* result_host, void* stream) {
+	hipStream_t st = (hipStream_t)stream;
+	if (np <= 0) {
+		result_host[0] = result_host[1] = 0;
+		return 0;
+	}
+	if (np >= ((int64_t)1 << 31)) return fail("compress: too many particles for 32-bit indices");
+	size_t scan_p = 0;
+	MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_p, (int32_t*)nullptr, (int32_t*)nullptr, (int)np, st));
+	const size_t wp = al256(sizeof(int32_t) * (size_t)np);
+	Arena* a;
+	MF_TRY(arena(3 * wp + 256 + al256(scan_p), &a));
+	char* b = a->p;
+	int64_t* res = (int64_t*)(b + 3 * wp);
+	MF_HIP(hipMemsetAsync(res, 0, 4 * sizeof(int64_t), st));
+	MF_TRY(plan_launch(a, np, pflag, (int32_t*)b, (int32_t*)(b + wp), (int32_t*)(b + 2 * wp), b + 3 * wp + 256, scan_p, res, 0, st));
+	MF_HIP(hipMemcpyAsync(result_host, res + 2, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+	MF_HIP(hipStreamSynchronize(st));
+	return 0;
+}
+
+int mf_particles_compress_move(int64_t holes, int ncomp, int64_t pstride, void* data, void* stream) {
+	if (holes <= 0) return 0;
+	Arena* a;
+	MF_TRY(arena(0, &a));
+	if (!a->holes) return fail("compress: no plan (mf_resample_round / mf_particles_compress_plan come first)");
+	if (ncomp < 1 || ncomp > 3) return fail("compress: %d components", ncomp);
+	hipLaunchKernelGGL(k_move, dim3(nblk_n(holes)), dim3(BLOCK), 0, (hipStream_t)stream, holes, a->holes, a->fillers, ncomp, pstride,
+	                   (uint32_t*)data);
+	MF_LAUNCH_CHECK();
+	return 0;
+}
+
+int mf_resample_seed_plan(int sx, int sy, int sz, const int32_t* flags, const float* phi, const float* exclude, const int32_t* tmp,
+                          int minParticles, float narrowBand, float surfaceLs, int64_t np, int32_t* pflag, int32_t* offsets,
+                          int64_t* total_host, void* stream) {
+	MF_TRY(check_dim(sx, sy, sz));
+	const Dim d = mkdim(sx, sy, sz);
+	hipStream_t st = (hipStream_t)stream;
+	size_t scan_c = 0;
+	MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_c, (int32_t*)nullptr, (int32_t*)nullptr, (int)d.n, st));
+	const size_t wc = al256(sizeof(int32_t) * (size_t)d.n);
+	// a compress plan is pending only between a round and its moves; seeding comes after them and takes the arena over
+	Arena* a;
+	MF_TRY(arena(wc + 256 + al256(scan_c), &a));
+	a->holes = a->fillers = nullptr;
+	char* b = a->p;
+	int32_t* need = (int32_t*)b;
+	int64_t* res = (int64_t*)(b + wc);
+	if (np > 0) hipLaunchKernelGGL(k_clear_new, dim3(nblk_n(np)), dim3(BLOCK), 0, st, np, pflag);
+	hipLaunchKernelGGL(k_seed_need, dim3(nblk_n(d.n)), dim3(BLOCK), 0, st, d.n, flags, phi, exclude, tmp, minParticles, narrowBand,
+	                   surfaceLs, need);
+	MF_HIP(hipcub::DeviceScan::ExclusiveSum(b + wc + 256, scan_c, need, offsets, (int)d.n, st));
+	hipLaunchKernelGGL(k_seed_total, dim3(1), dim3(1), 0, st, d.n, need, offsets, res);
+	MF_LAUNCH_CHECK();
+	MF_HIP(hipMemcpyAsync(total_host, res, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+	MF_HIP(hipStreamSynchronize(st));
+	return 0;
+}
+
+int mf_resample_seed_insert(int sx, int sy, int sz, const int32_t* offsets, const float* reals, int64_t np, int64_t total,
+                            int64_t pstride, float* pos, int32_t* pflag, void* stream) {
+	MF_TRY(check_dim(sx, sy, sz));
+	const Dim d = mkdim(sx, sy, sz);
+	if (total <= 0) return 0;
+	if (pstride < np + total) return fail("adjustNumber: particle capacity %lld below %lld", (long long)pstride, (long long)(np + total));
+	hipLaunchKernelGGL(k_seed_insert, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, offsets, reals, np, total, pstride, pos,
+	                   pflag);
+	MF_LAUNCH_CHECK();
+	return 0;
+}
+
+int mf_pdata_init_new(int sx, int sy, int sz, const float* grid, int mode, int ncomp, int64_t first, int64_t count, int64_t pstride,
+                      const float* pos, void* data, void* stream) {
+	MF_TRY(check_dim(sx, sy, sz));
+	const Dim d = mkdim(sx, sy, sz);
+	if (count <= 0) return 0;
+	if (mode < 0 || mode > 2 || (mode && !grid) || (mode == 2 && ncomp != 3) || (ncomp != 1 && ncomp != 3))
+		return fail("pdata init: bad mode %d / components %d", mode, ncomp);
+	if (first < 0 || first + count > pstride) return fail("pdata init: range past the capacity");
+	hipLaunchKernelGGL(k_pdata_init, dim3(nblk_n(count)), dim3(BLOCK), 0, (hipStream_t)stream, d, grid, mode, ncomp, first, count,
+	                   pstride, pos, (float*)data);
+	MF_LAUNCH_CHECK();
+	return 0;
+}
+
+}  // extern "C"

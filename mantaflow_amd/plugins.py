@@ -9,6 +9,8 @@ PYTHON() declarations; orchestration mirrors the reference function by function,
   updateFractions / setObstacleFlags / addNoise   source/plugin/initplugins.cpp:45-51, 351-474
   setWallBcs(fractions=, phiObs=) / setInflowBcs  source/plugin/extforces.cpp:163-182, 240-335
                                              (include/manta_hip_obstacles.h; not on z-slab solvers)
+  adjustNumber / combineGridVel              source/plugin/flip.cpp:204-262, 748-776
+                                             (include/manta_hip_resample.h; not on z-slab solvers)
 """
 import ctypes
 import functools
@@ -950,6 +952,113 @@ def addNoise(flags, density, noise, sdf=None, scale=1.0):
     lib = _obstacles_lib(s, "addNoise")
     lib.call("mf_add_noise", flags.sx, flags.sy, flags.sz, flags.ptr, density.ptr, None if sdf is None else sdf.ptr, _ptr(noise._tile),
              noise._params(), float(_f32(scale)), s.stream)
+
+
+# =========================================================================================================
+# particle resampling for narrow-band FLIP (include/manta_hip_resample.h)
+# =========================================================================================================
+def _resample_lib(s, name):
+    """the solver's library, if it implements the resampling extension (the CPU test backend does not)"""
+    lib = s.lib
+    if tuple(s._slab_window) != (0, 0):
+        raise RuntimeError("%s: particle resampling does not run on a z-slab solver" % name)
+    if not lib.resample:
+        raise RuntimeError("%s: the '%s' backend does not implement particle resampling (manta_hip_resample.h)" % (name, lib.backend))
+    return lib
+
+
+_seed_reals = {}     # device -> the first reals of RandomStream(9832), which every adjustNumber call restarts
+
+
+def _seed_table(device, n):
+    """at least n reals of the MT19937(9832) stream on the device: one table per process, lengthened when a call needs more"""
+    t = _seed_reals.get(device)
+    if t is None or t.numel() < n:
+        from .scene import RandomStream
+        m = max(n, 2 * (t.numel() if t is not None else 0), 1 << 16)
+        t = torch.from_numpy(RandomStream(9832).reals(m)).to(device)
+        _seed_reals[device] = t
+    return t
+
+
+def calculateRadiusFactor(grid, factor):
+    """flip.cpp:198-200: the particle radius that covers a cell's diagonal (double arithmetic, narrowed to Real)"""
+    return float(np.float32((np.sqrt(3.) if grid.is3D() else np.sqrt(2.)) * (float(np.float32(factor)) + .01)))
+
+
+adjustNumberStats = {}      # rounds / kills / inserted / compresses of the last adjustNumber call
+
+
+@plugin
+def adjustNumber(parts, vel, flags, minParticles, maxParticles, phi, radiusFactor=1., narrowBand=-1., exclude=None):
+    """plugin/flip.cpp:204-262: cull particles outside the liquid, below the band and in crowded cells, seed thin cells, with
+    ParticleSystem::kill's bookkeeping (particle.h:423-427: a mid-loop compress where parts.mAllowCompress, which a
+    BasicParticleSystem clears, so there the one compress is doCompress at the end) and insertBufferedParticles (particle.h:636-663).  The serial
+    particle loop runs as rounds of its order-free statement ("Particle resampling"): one scalar read-back per round
+    and one for the number of new particles; no particle or grid array crosses to the host."""
+    _chk(parts, core.BasicParticleSystem, "BasicParticleSystem"); _chk(vel, MACGrid, "MACGrid"); _chk(flags, FlagGrid, "FlagGrid")
+    _chk(phi, LevelsetGrid, "LevelsetGrid")
+    exclude = _opt(exclude, Grid, "Grid<Real>")
+    s = vel.parent
+    lib = _resample_lib(s, "adjustNumber")
+    minParticles, maxParticles = _coerce(minParticles, 0), _coerce(maxParticles, 0)
+    nb = float(np.float32(narrowBand))
+    sls = -calculateRadiusFactor(phi, radiusFactor)
+    dims = (flags.sx, flags.sy, flags.sz)
+    tmp = core.IntGrid(s)          # Grid<int> tmp(vel.getParent()): zeroed
+    res = (ctypes.c_int64 * 4)()
+    i0, rounds, kills, compresses = 0, 0, 0, 0
+    while i0 < parts.np:
+        # without mAllowCompress (a BasicParticleSystem as the reference builds it) no kill compresses: one round does the loop
+        chunk = parts.mDeleteChunk if parts.mAllowCompress else (1 << 62)
+        lib.call("mf_resample_round", *dims, phi.ptr, tmp.ptr, parts.np, parts.cap, _ptr(parts.pos), _ptr(parts.flag), i0,
+                 maxParticles, nb, sls, parts.mDeletes, chunk, res, s.stream)
+        rounds += 1
+        kills += int(res[1])
+        if res[0] < 0:
+            parts.mDeletes += int(res[1])
+            break
+        parts.compress(planned=(int(res[2]), int(res[3])))
+        compresses += 1
+        i0 = int(res[0]) + 1
+    if parts.mDeletes > parts.mDeleteChunk:     # doCompress, particle.h:142-145
+        parts.compress()
+        compresses += 1
+    offsets = core.IntGrid(s)
+    total = ctypes.c_int64(0)
+    lib.call("mf_resample_seed_plan", *dims, flags.ptr, phi.ptr, None if exclude is None else exclude.ptr, tmp.ptr, minParticles, nb, sls,
+             parts.np, _ptr(parts.flag), offsets.ptr, ctypes.byref(total), s.stream)
+    total = int(total.value)
+    if total:
+        old = parts.np
+        parts.reserve(old + total)
+        parts.resizeAll(old + total, parts.cap)
+        reals = _seed_table(s.device, 3 * total)
+        lib.call("mf_resample_seed_insert", *dims, offsets.ptr, _ptr(reals), old, total, parts.cap, _ptr(parts.pos), _ptr(parts.flag),
+                 s.stream)
+        for pd in parts.pdata:
+            src = pd.mpGridSource
+            mode = 0 if src is None else (2 if pd.mGridSourceMAC else 1)
+            if src is not None and (src.sx, src.sy, src.sz) != dims:
+                raise RuntimeError("adjustNumber: the source grid of a pdata channel has another resolution")
+            if pd.cap != parts.cap:
+                raise RuntimeError("adjustNumber: a pdata channel does not follow the capacity of its particle system")
+            lib.call("mf_pdata_init_new", *dims, None if src is None else src.ptr, mode, pd._ncomp, old, total, pd.cap, _ptr(parts.pos),
+                     pd.ptr, s.stream)
+    adjustNumberStats.clear()
+    adjustNumberStats.update(rounds=rounds, kills=kills, inserted=total, compresses=compresses)
+
+
+@plugin
+def combineGridVel(vel, weight, combineVel, phi=None, narrowBand=0.0, thresh=0.0):
+    """plugin/flip.cpp:748-776 -> knCombineVels: where the particles carry a velocity (weight > thresh) and the face is not deeper
+    than narrowBand, combineVel takes vel and vel becomes -1; elsewhere vel becomes 0"""
+    _chk(vel, MACGrid, "MACGrid"); _chk(weight, VecGrid, "Grid<Vec3>"); _chk(combineVel, MACGrid, "MACGrid")
+    phi = _opt(phi, LevelsetGrid, "LevelsetGrid")
+    s = vel.parent
+    lib = _resample_lib(s, "combineGridVel")
+    lib.call("mf_combine_grid_vel", vel.sx, vel.sy, vel.sz, vel.ptr, weight.ptr, combineVel.ptr, None if phi is None else phi.ptr,
+             float(np.float32(narrowBand)), float(np.float32(thresh)), s.stream)
 
 
 def _f32(x): return np.float32(x)

@@ -1,0 +1,141 @@
+"""Public surface of the narrow-band FLIP additions, on the CPU checker backend: names and signatures of the reference, the particle
+system's delete bookkeeping, the refusals, and the two plain grid operations against the model."""
+import inspect
+
+import numpy as np
+import pytest
+
+import nbflip_model as M
+import util
+
+
+def _params(fn):
+    return [(p.name, p.default) for p in inspect.signature(fn).parameters.values() if p.name != "self"]
+
+
+def test_public_names_and_signatures():
+    import manta as m
+    E = inspect.Parameter.empty
+    assert _params(m.adjustNumber) == [("parts", E), ("vel", E), ("flags", E), ("minParticles", E), ("maxParticles", E), ("phi", E),
+                                       ("radiusFactor", 1.), ("narrowBand", -1.), ("exclude", None)]
+    assert _params(m.combineGridVel) == [("vel", E), ("weight", E), ("combineVel", E), ("phi", None), ("narrowBand", 0.0), ("thresh", 0.0)]
+    for cls in (m.PdataReal, m.PdataVec3, m.PdataInt):
+        assert _params(inspect.unwrap(cls.setSource)) == [("grid", E), ("isMAC", False)]
+    for cls in (m.RealGrid, m.VecGrid, m.MACGrid, m.IntGrid, m.LevelsetGrid):
+        assert _params(inspect.unwrap(cls.setBoundNeumann)) == [("boundaryWidth", E)]
+    assert _params(inspect.unwrap(m.LevelsetGrid.initFromFlags)) == [("flags", E), ("ignoreWalls", False)]
+
+
+def test_header_declares_the_extension():
+    from mantaflow_amd import _lib
+    protos = _lib.parse_header(_lib.RESAMPLE_HEADER)
+    for n in ("mf_resample_abi_version", "mf_grid_set_bound_neumann", "mf_levelset_init_from_flags", "mf_combine_grid_vel",
+              "mf_resample_round", "mf_particles_compress_plan", "mf_particles_compress_move", "mf_resample_seed_plan",
+              "mf_resample_seed_insert", "mf_pdata_init_new"):
+        assert n in protos, n
+    assert not set(protos) & set(_lib.parse_header())
+    assert not set(protos) & set(_lib.parse_header(_lib.OBSTACLES_HEADER)) and not set(protos) & set(_lib.parse_header(_lib.MULTIGRID_HEADER))
+
+
+def test_delete_bookkeeping_of_the_particle_system(oracle_backend):
+    """(mDeletes, mDeleteChunk) start at (0, 0); only addParticle (size / 20) and clear (0, 0) change the chunk, set_positions (the
+    samplers' buffered insertion) leaves the pair alone; a BasicParticleSystem does not allow kill() to compress (particle.cpp:134-138)"""
+    import manta as m
+    s = m.Solver(name="b", gridSize=m.vec3(12, 10, 8), dim=3)
+    pp = s.create(m.BasicParticleSystem)
+    assert (pp.mDeletes, pp.mDeleteChunk, pp.mAllowCompress) == (0, 0, False)
+    pp.set_positions(np.random.RandomState(0).uniform(1, 7, (100, 3)))
+    assert (pp.mDeletes, pp.mDeleteChunk) == (0, 0)
+    pp.addParticle(m.vec3(2, 2, 2))
+    assert (pp.mDeletes, pp.mDeleteChunk) == (0, 101 // 20)
+    pp.mDeletes = 3
+    pp.set_positions(np.zeros((250, 3)) + 3)
+    assert (pp.mDeletes, pp.mDeleteChunk) == (3, 5)
+    pp.addParticle(m.vec3(2, 2, 2))
+    assert (pp.mDeletes, pp.mDeleteChunk) == (3, 251 // 20)
+    pp.clear()
+    assert (pp.mDeletes, pp.mDeleteChunk, pp.pySize()) == (0, 0, 0)
+
+
+def _objects(m, s):
+    pp = s.create(m.BasicParticleSystem)
+    pp.set_positions(np.random.RandomState(0).uniform(1, 7, (50, 3)))
+    return dict(pp=pp, vel=s.create(m.MACGrid), w=s.create(m.MACGrid), comb=s.create(m.MACGrid), flags=s.create(m.FlagGrid),
+                phi=s.create(m.LevelsetGrid))
+
+
+def _refused(m, o, pattern):
+    before = o["pp"].get_positions().copy()
+    o["vel"].setConst(m.vec3(1, 2, 3))
+    with pytest.raises(RuntimeError, match=r"adjustNumber: " + pattern):
+        m.adjustNumber(parts=o["pp"], vel=o["vel"], flags=o["flags"], minParticles=2, maxParticles=4, phi=o["phi"])
+    with pytest.raises(RuntimeError, match=r"combineGridVel: " + pattern):
+        m.combineGridVel(vel=o["vel"], weight=o["w"], combineVel=o["comb"], phi=o["phi"], narrowBand=2)
+    # nothing was touched
+    assert np.array_equal(o["pp"].get_positions(), before) and o["pp"].pySize() == 50
+    v = o["vel"].to_numpy()
+    assert (v[..., 0] == 1).all() and (v[..., 2] == 3).all() and (o["comb"].to_numpy() == 0).all()
+
+
+def test_cpu_backend_refuses_the_resampling_plugins(oracle_backend):
+    import manta as m
+    from mantaflow_amd import _lib
+    assert _lib.get().resample is False
+    s = m.Solver(name="o", gridSize=m.vec3(12, 10, 8), dim=3)
+    _refused(m, _objects(m, s), r"the 'oracle' backend does not implement particle resampling")
+
+
+def test_z_slab_solver_refuses_the_resampling_plugins(oracle_backend):
+    import manta as m
+    s = m.Solver(name="o", gridSize=m.vec3(12, 10, 8), dim=3)
+    o = _objects(m, s)
+    s._slab_window = (4, 40)      # what slab.SlabDomain gives the solver of a z-slab: (z offset, global sz)
+    try:
+        _refused(m, o, r"particle resampling does not run on a z-slab solver")
+    finally:
+        s._slab_window = (0, 0)
+
+
+def test_set_source_rules(oracle_backend):
+    import manta as m
+    s = m.Solver(name="o", gridSize=m.vec3(12, 10, 8), dim=3)
+    pp = s.create(m.BasicParticleSystem)
+    pv, pr, pi = pp.create(m.PdataVec3), pp.create(m.PdataReal), pp.create(m.PdataInt)
+    mac, vec, real, ints = s.create(m.MACGrid), s.create(m.VecGrid), s.create(m.RealGrid), s.create(m.IntGrid)
+    pv.setSource(mac, isMAC=True)
+    assert pv.mpGridSource is mac and pv.mGridSourceMAC is True
+    pv.setSource(vec)
+    assert pv.mpGridSource is vec and pv.mGridSourceMAC is False
+    pr.setSource(real)
+    assert pr.mpGridSource is real
+    with pytest.raises(RuntimeError, match="Given grid is not a valid MAC grid"):
+        pv.setSource(vec, isMAC=True)
+    with pytest.raises(RuntimeError, match="Given grid is not a valid MAC grid"):
+        pr.setSource(real, isMAC=True)
+    with pytest.raises(RuntimeError, match="can't convert argument"):
+        pr.setSource(vec)
+    with pytest.raises(RuntimeError, match="PdataInt.setSource"):
+        pi.setSource(ints)
+
+
+@pytest.mark.parametrize("which", list(M.NEUMANN_DIMS))
+def test_grid_ops_on_the_cpu_backend_equal_the_model(oracle_backend, which):
+    import manta as m
+    dims = M.NEUMANN_DIMS[which]
+    s = m.Solver(name="o", gridSize=m.vec3(*dims), dim=3 if dims[2] > 1 else 2)
+    r, v = M.neumann_inputs(which)
+    for w in (0, 1, 2):
+        for cls, arr in ((m.RealGrid, r), (m.VecGrid, v), (m.MACGrid, v), (m.IntGrid, r.view(np.int32)), (m.LevelsetGrid, r)):
+            g = s.create(cls)
+            g.from_numpy(arr)
+            g.setBoundNeumann(w)
+            util.assert_bitexact(g.to_numpy(), M.set_bound_neumann(arr, w), "%s w%d" % (cls.__name__, w))
+    g = s.create(m.RealGrid)
+    with pytest.raises(RuntimeError, match="setBoundNeumann: grid .* too small"):
+        g.setBoundNeumann(5)
+    fl = s.create(m.FlagGrid)
+    fl.from_numpy(M.flags_inputs(which))
+    for ig in (False, True):
+        phi = s.create(m.LevelsetGrid)
+        phi.initFromFlags(fl, ignoreWalls=ig)
+        util.assert_bitexact(phi.to_numpy(), M.init_from_flags(M.flags_inputs(which), ig), "initFromFlags %s" % ig)
