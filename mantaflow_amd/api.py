@@ -12,7 +12,8 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       interpolateGrid, interpolateGridVec3, interpolateMACGrid, computeEnergy, computeWaveletCoeffs,
                       vorticityConfinement, applyNoiseVec3, setOpenBound,
                       updateFractions, setObstacleFlags, setInflowBcs, addNoise, releaseMG,
-                      adjustNumber, combineGridVel)
+                      adjustNumber, combineGridVel,
+                      copyFlagsToFlags, markFluidAndBoundaryCells, mapMassToGrid, computeDeltaX, mapMACToPartPositions)
 
 from .scene import (Box, Cylinder, Gui, NoiseField, Shape, Sphere, densityInflow, sampleFlagsWithParticles,
                     sampleLevelsetWithParticles, sampleShapeWithParticles)

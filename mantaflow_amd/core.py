@@ -162,6 +162,7 @@ class SolverLib(object):
         self.obstacles = lib.obstacles
         self.multigrid = lib.multigrid
         self.resample = lib.resample
+        self.idp = lib.idp
 
     def call(self, name, *args):
         # set on every call: the window is thread-local state of the shared object, so a cache per Library object would go
@@ -261,7 +262,7 @@ class FluidSolver(PbClass):
         f32 = np.float32
         mvt = f32(maxVel) * f32(self.timestep)
         if not self.mLockDt:
-            dt = f32(f32(self.timestep) * f32(self.cfl / (float(mvt) + 1e-05)))
+            dt = f32(f32(self.timestep) * f32(float(f32(self.cfl)) / (float(mvt) + 1e-05)))      # mCflCond is a Real: Real / double
             dt = max(min(dt, f32(self.timestepMax)), f32(self.timestepMin))
             if (self.timePerFrame + float(dt) * 1.05) > self.frameLength:
                 dt = f32((self.frameLength - self.timePerFrame) + 1e-04)

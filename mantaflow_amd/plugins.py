@@ -11,6 +11,9 @@ PYTHON() declarations; orchestration mirrors the reference function by function,
                                              (include/manta_hip_obstacles.h; not on z-slab solvers)
   adjustNumber / combineGridVel              source/plugin/flip.cpp:204-262, 748-776
                                              (include/manta_hip_resample.h; not on z-slab solvers)
+  copyFlagsToFlags / markFluidAndBoundaryCells / mapMassToGrid / computeDeltaX / mapMACToPartPositions
+                                             source/plugin/implicitdensityprojection.cpp
+                                             (include/manta_hip_idp.h; not on z-slab solvers)
 """
 import ctypes
 import functools
@@ -1059,6 +1062,114 @@ def combineGridVel(vel, weight, combineVel, phi=None, narrowBand=0.0, thresh=0.0
     lib = _resample_lib(s, "combineGridVel")
     lib.call("mf_combine_grid_vel", vel.sx, vel.sy, vel.sz, vel.ptr, weight.ptr, combineVel.ptr, None if phi is None else phi.ptr,
              float(np.float32(narrowBand)), float(np.float32(thresh)), s.stream)
+
+
+# =========================================================================================================
+# implicit density projection: the position solve of IDP-FLIP / IDP-APIC (include/manta_hip_idp.h)
+# =========================================================================================================
+def _idp_lib(s, name):
+    """the solver's library, if it implements the density-projection extension (the CPU test backend does not)"""
+    lib = s.lib
+    if tuple(s._slab_window) != (0, 0):
+        raise RuntimeError("%s: implicit density projection does not run on a z-slab solver" % name)
+    if not lib.idp:
+        raise RuntimeError("%s: the '%s' backend does not implement implicit density projection (manta_hip_idp.h)" % (name, lib.backend))
+    return lib
+
+
+@plugin
+def copyFlagsToFlags(source, target):
+    """implicitdensityprojection.cpp:336-341: target = source, cell by cell (every backend)"""
+    _chk(source, FlagGrid, "FlagGrid"); _chk(target, FlagGrid, "FlagGrid")
+    target.copyFrom(source)
+
+
+def _mark_fluid_and_boundary(lib, s, particles, flags, deltaX, phiObs, ptype, exclude):
+    (np_, cap, pos, pfl), pt = _pargs(particles, ptype)
+    res = (ctypes.c_int64 * 2)()
+    lib.call("mf_idp_mark", flags.sx, flags.sy, flags.sz, flags.ptr, deltaX.ptr, phiObs.ptr, np_, cap, pos, pfl, pt, int(exclude),
+             res, s.stream)
+    return int(res[0]), int(res[1])
+
+
+markFluidAndBoundaryCellsStats = {}      # particles inside obstacle cells / of them pushing out, of the last call
+
+
+@plugin
+def markFluidAndBoundaryCells(particles, flags, deltaX, phiObs, ptype=None, exclude=0):
+    """implicitdensityprojection.cpp:29-79: fluid cells become empty, deltaX is cleared, every cell holding an active particle
+    (not excluded) becomes fluid, and a particle inside an obstacle cell with phiObs <= 0 proposes the displacement that pushes it
+    out on the faces of its cell; a face keeps the proposal of largest magnitude, among equal ones the lowest particle's (the
+    serial loop, stated order-free: DESIGN.md, "Implicit density projection").  In 2-D no z component is written.  Cells that
+    carry the obstacle bit together with the empty or fluid bit (no flag initialiser makes them) are marked and propose nothing.
+    One scalar read-back (two when a particle sits in an obstacle cell); no array crosses to the host."""
+    _chk(particles, core.BasicParticleSystem, "BasicParticleSystem"); _chk(flags, FlagGrid, "FlagGrid")
+    _chk(deltaX, MACGrid, "MACGrid"); _chk(phiObs, Grid, "Grid<Real>")
+    ptype = _opt(ptype, core.PdataInt, "ParticleDataImpl<int>")
+    s = flags.parent
+    lib = _idp_lib(s, "markFluidAndBoundaryCells")
+    inside, pushing = _mark_fluid_and_boundary(lib, s, particles, flags, deltaX, phiObs, ptype, exclude)
+    markFluidAndBoundaryCellsStats.clear()
+    markFluidAndBoundaryCellsStats.update(boundary_particles=inside, pushing=pushing)
+
+
+mapMassToGridStats = {}      # rounds / candidates / flipped cells / boundary particles / read-backs of the last mapMassToGrid call
+
+
+@plugin
+def mapMassToGrid(flags, density, parts, source, deltaX, phiObs, dt, particleMass, noDensityClamping=False):
+    """implicitdensityprojection.cpp:156-180: markFluidAndBoundaryCells (no ptype), density = the sum of the particles' trilinear
+    weights (the ordered, bit-exact particle->grid transfer; `source` only feeds the transfer's discarded value grid), then
+    knComputeDensity: 1 - density * particleMass minus the divergence of the push-out displacements and -- in 3-D -- the particle
+    deficiency of obstacle and empty neighbours; surface cells left positive become empty (flag TypeEmpty exactly, density 0);
+    the clamp to +-0.5 and the division by dt unless noDensityClamping; 0 in non-fluid cells.  The 3-D kernel of the reference
+    reads the flags it rewrites: the contract is its single-thread sweep (k outer, j, i inner), computed in rounds over the cells
+    whose flip depends on earlier flips ("Implicit density projection").  Fluid cells on the outermost layer of the
+    grid make the reference read out of bounds: the contract covers domains whose outermost layer is not fluid
+    (initDomain(boundaryWidth >= 1)); there a neighbour outside the grid counts as neither obstacle nor empty.  Scalar read-backs
+    only (mapMassToGridStats counts them); no grid or particle array crosses to the host."""
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(density, Grid, "Grid<Real>"); _chk(parts, core.BasicParticleSystem, "BasicParticleSystem")
+    _chk(source, core.PdataReal, "ParticleDataImpl<Real>"); _chk(deltaX, MACGrid, "MACGrid"); _chk(phiObs, Grid, "Grid<Real>")
+    s = flags.parent
+    lib = _idp_lib(s, "mapMassToGrid")
+    inside, pushing = _mark_fluid_and_boundary(lib, s, parts, flags, deltaX, phiObs, None, 0)
+    (np_, cap, pos, pfl), _ = _pargs(parts, None)
+    dims = (flags.sx, flags.sy, flags.sz)
+    if source.cap != parts.cap:
+        raise RuntimeError("mapMassToGrid: the source channel does not follow the capacity of its particle system")
+    lib.call("mf_idp_map_weights", *dims, density.ptr, np_, cap, pos, pfl, source.ptr, s.stream)
+    res = (ctypes.c_int64 * 4)()
+    lib.call("mf_idp_compute_density", *dims, density.ptr, flags.ptr, deltaX.ptr, float(np.float32(dt)), float(np.float32(particleMass)),
+             int(noDensityClamping), res, s.stream)
+    mapMassToGridStats.clear()
+    mapMassToGridStats.update(rounds=int(res[2]), candidates=int(res[0]), flipped=int(res[1]), boundary_particles=inside,
+                              pushing=pushing, readbacks=2 + (1 if inside else 0))
+
+
+@plugin
+def computeDeltaX(deltaX, Lambda, flags):
+    """implicitdensityprojection.cpp:184-205: Lambda = 0 in empty cells (one cell off the sides), then for every non-obstacle cell
+    each face component becomes the backward difference of Lambda where the lower neighbour is no obstacle; all other components
+    keep their value (the push-out displacements of the marking).  For a non-obstacle cell at i = 0, j = 0 or k = 0 the reference
+    reads before the row; here that neighbour counts as an obstacle."""
+    _chk(deltaX, MACGrid, "MACGrid"); _chk(Lambda, Grid, "Grid<Real>"); _chk(flags, FlagGrid, "FlagGrid")
+    s = flags.parent
+    lib = _idp_lib(s, "computeDeltaX")
+    lib.call("mf_idp_compute_delta_x", flags.sx, flags.sy, flags.sz, flags.ptr, deltaX.ptr, Lambda.ptr, s.stream)
+
+
+@plugin
+def mapMACToPartPositions(flags, deltaX, parts, dt, ptype=None, exclude=0, mapQuadratic=False):
+    """implicitdensityprojection.cpp:207-245: pos += deltaX.getInterpolated(pos) * dt for the active, not excluded particles, then
+    per component the clamp to [1.001, size - 1.001] (z of a 2-D solver: [-10.001, 10.001]); mapQuadratic is accepted and
+    ignored, as in the reference"""
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(deltaX, MACGrid, "MACGrid"); _chk(parts, core.BasicParticleSystem, "BasicParticleSystem")
+    ptype = _opt(ptype, core.PdataInt, "ParticleDataImpl<int>")
+    s = flags.parent
+    lib = _idp_lib(s, "mapMACToPartPositions")
+    (np_, cap, pos, pfl), pt = _pargs(parts, ptype)
+    lib.call("mf_idp_map_mac_to_positions", flags.sx, flags.sy, flags.sz, deltaX.ptr, np_, cap, pos, pfl, pt, int(exclude),
+             float(np.float32(dt)), s.stream)
 
 
 def _f32(x): return np.float32(x)
