@@ -99,7 +99,11 @@ __device__ __forceinline__ void p2g_component_grouped(float* __restrict__ ref, f
 	}
 #pragma unroll
 	for (int st = 1; st <= 4; st <<= 1) {
-		const bool take = (g + st < 8) && (dpp_shl_i(rid, st) == rid);
+		// the cross-lane read stays outside the lane-dependent condition: behind `&&` it runs with lanes g + st >= 8 switched
+		// off, a DPP read of a switched-off lane is invalid (the reader keeps -2), and the last st lanes of every group are
+		// then never merged into their run
+		const int rnext = dpp_shl_i(rid, st);
+		const bool take = (g + st < 8) & (rnext == rid);
 #pragma unroll
 		for (int q = 0; q < 8; q++) {
 			const float wn = dpp_shl(w[q], st), vn = dpp_shl(v[q], st);

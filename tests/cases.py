@@ -385,41 +385,43 @@ def run_flip_pkg(dims, flags, vel, velOld, pos, pflag, pvel, ptype=None, exclude
     from mantaflow_amd import core, plugins
     s = _mk_solver(dims)
     plugins.setDeterministicP2G(deterministic)
-    fl = soa_to_grid(core.FlagGrid(s), flags)
-    pp = _mk_parts(s, pos, pflag)
-    pv = _pd_vec3(s, pp, pvel)
-    pt = None
-    if ptype is not None:
-        pt = pp.create(core.PdataInt)
-        pt.data[:pp.np] = torch.from_numpy(ptype).to(pt.data.device)
-    out = {}
-    v, vo, w = core.MACGrid(s), core.MACGrid(s), core.VecGrid(s)
-    soa_to_grid(v, util.rand_vel(*dims, 99)); soa_to_grid(w, util.rand_vel(*dims, 98))     # must be cleared by the plugin
-    plugins.mapPartsToMAC(fl, v, vo, pp, pv, w, ptype=pt, exclude=exclude)
-    out["p2g_vel"], out["p2g_velOld"], out["p2g_weight"] = grid_to_soa(v), grid_to_soa(vo), grid_to_soa(w)
-    gv, gvo = soa_to_grid(core.MACGrid(s), vel), soa_to_grid(core.MACGrid(s), velOld)
-    pv2 = _pd_vec3(s, pp, pvel)
-    plugins.mapMACToParts(fl, gv, pp, pv2, ptype=pt, exclude=exclude)
-    out["pic"] = _pd_get(pv2, pp.np)
-    pv3 = _pd_vec3(s, pp, pvel)
-    plugins.flipVelocityUpdate(fl, gv, gvo, pp, pv3, 0.97, ptype=pt, exclude=exclude)
-    out["flip"] = _pd_get(pv3, pp.np)
-    tgt = core.Grid(s)
-    ps = pp.create(core.PdataReal)
-    ps.data[:pp.np] = torch.from_numpy(pvel[0]).to(ps.data.device)
-    plugins.mapPartsToGrid(fl, tgt, pp, ps)
-    out["p2g_real"] = grid_to_soa(tgt)
-    tv = core.VecGrid(s)
-    plugins.mapPartsToGridVec3(fl, tv, pp, pv)
-    out["p2g_vec3"] = grid_to_soa(tv)
-    pr = pp.create(core.PdataReal)
-    plugins.mapGridToParts(soa_to_grid(core.Grid(s), vel[0]), pp, pr)
-    out["g2p_real"] = _pd_get(pr, pp.np)
-    pv4 = _pd_vec3(s, pp, pvel)
-    plugins.mapGridToPartsVec3(soa_to_grid(core.VecGrid(s), vel), pp, pv4)
-    out["g2p_vec3"] = _pd_get(pv4, pp.np)
-    s.sync()
-    plugins.setDeterministicP2G(True)
+    try:       # the switch goes back to its default even when a call below raises
+        fl = soa_to_grid(core.FlagGrid(s), flags)
+        pp = _mk_parts(s, pos, pflag)
+        pv = _pd_vec3(s, pp, pvel)
+        pt = None
+        if ptype is not None:
+            pt = pp.create(core.PdataInt)
+            pt.data[:pp.np] = torch.from_numpy(ptype).to(pt.data.device)
+        out = {}
+        v, vo, w = core.MACGrid(s), core.MACGrid(s), core.VecGrid(s)
+        soa_to_grid(v, util.rand_vel(*dims, 99)); soa_to_grid(w, util.rand_vel(*dims, 98))     # must be cleared by the plugin
+        plugins.mapPartsToMAC(fl, v, vo, pp, pv, w, ptype=pt, exclude=exclude)
+        out["p2g_vel"], out["p2g_velOld"], out["p2g_weight"] = grid_to_soa(v), grid_to_soa(vo), grid_to_soa(w)
+        gv, gvo = soa_to_grid(core.MACGrid(s), vel), soa_to_grid(core.MACGrid(s), velOld)
+        pv2 = _pd_vec3(s, pp, pvel)
+        plugins.mapMACToParts(fl, gv, pp, pv2, ptype=pt, exclude=exclude)
+        out["pic"] = _pd_get(pv2, pp.np)
+        pv3 = _pd_vec3(s, pp, pvel)
+        plugins.flipVelocityUpdate(fl, gv, gvo, pp, pv3, 0.97, ptype=pt, exclude=exclude)
+        out["flip"] = _pd_get(pv3, pp.np)
+        tgt = core.Grid(s)
+        ps = pp.create(core.PdataReal)
+        ps.data[:pp.np] = torch.from_numpy(pvel[0]).to(ps.data.device)
+        plugins.mapPartsToGrid(fl, tgt, pp, ps)
+        out["p2g_real"] = grid_to_soa(tgt)
+        tv = core.VecGrid(s)
+        plugins.mapPartsToGridVec3(fl, tv, pp, pv)
+        out["p2g_vec3"] = grid_to_soa(tv)
+        pr = pp.create(core.PdataReal)
+        plugins.mapGridToParts(soa_to_grid(core.Grid(s), vel[0]), pp, pr)
+        out["g2p_real"] = _pd_get(pr, pp.np)
+        pv4 = _pd_vec3(s, pp, pvel)
+        plugins.mapGridToPartsVec3(soa_to_grid(core.VecGrid(s), vel), pp, pv4)
+        out["g2p_vec3"] = _pd_get(pv4, pp.np)
+        s.sync()
+    finally:
+        plugins.setDeterministicP2G(True)
     return out
 
 
@@ -862,6 +864,14 @@ def dam_setup(s, fl, phiS, pp, pT, res, zflow=False):
 
 def run_dam_pkg(res, steps, deterministic=True, zflow=False, cgacc=1e-3):
     """a ghost-fluid FLIP dam break with the call sequence of scenes/benchmark_dam.py's main loop (own set-up code)"""
+    from mantaflow_amd import plugins
+    try:
+        return _run_dam_pkg(res, steps, deterministic, zflow, cgacc)
+    finally:
+        plugins.setDeterministicP2G(True)
+
+
+def _run_dam_pkg(res, steps, deterministic, zflow, cgacc):
     from mantaflow_amd import core, plugins, scene
     FF, FE = 1, 4
     bnd, gs = dam_geometry(res, zflow)[:2]
@@ -905,7 +915,6 @@ def run_dam_pkg(res, steps, deterministic=True, zflow=False, cgacc=1e-3):
         plugins.setPartType(parts=pp, ptype=pT, mark=FE, stype=FF, flags=fl, cflag=FE)
         s.step()
     s.sync()
-    plugins.setDeterministicP2G(True)
     return dict(pos=_ppos(pp), pvel=np.ascontiguousarray(pV.to_numpy().T), ptype=pT.data[:pp.np].cpu().numpy().copy(),
                 flags=grid_to_soa(fl), phi=grid_to_soa(phi), vel=grid_to_soa(V), pres=grid_to_soa(P), iters=iters, gs=gs,
                 dt=float(s.timestep), rec=rec)
