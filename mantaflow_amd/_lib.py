@@ -10,7 +10,8 @@ extension ``include/manta_hip_obstacles.h`` (fill-fraction obstacle boundaries) 
 when the loaded library exports them (``Library.obstacles``), and a library without them still loads.  The same holds for
 ``include/manta_hip_multigrid.h`` (the multigrid preconditioner, ``Library.multigrid``) and for
 ``include/manta_hip_resample.h`` (particle resampling for narrow-band FLIP, ``Library.resample``) and for
-``include/manta_hip_idp.h`` (implicit density projection, ``Library.idp``).
+``include/manta_hip_idp.h`` (implicit density projection, ``Library.idp``) and for
+``include/manta_hip_partls.h`` (averaged and improved particle level sets, ``Library.partls``).
 """
 import ctypes
 import os
@@ -22,6 +23,7 @@ OBSTACLES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_ob
 MULTIGRID_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_multigrid.h")
 RESAMPLE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_resample.h")
 IDP_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_idp.h")
+PARTLS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_partls.h")
 DEFAULT_LIB = os.path.join(_HERE, "csrc", "libmanta_hip.so")
 
 _CTYPES = {
@@ -91,6 +93,7 @@ class Library:
         self.multigrid = self._bind_extension(path, MULTIGRID_HEADER, "mf_multigrid_abi_version", "MF_MULTIGRID_ABI_VERSION")
         self.resample = self._bind_extension(path, RESAMPLE_HEADER, "mf_resample_abi_version", "MF_RESAMPLE_ABI_VERSION")
         self.idp = self._bind_extension(path, IDP_HEADER, "mf_idp_abi_version", "MF_IDP_ABI_VERSION")
+        self.partls = self._bind_extension(path, PARTLS_HEADER, "mf_partls_abi_version", "MF_PARTLS_ABI_VERSION")
         # the z-slab window is thread-local state of the shared object (which stays loaded across Library instances): start
         # from "the grid is the whole domain"; solvers carry their own window and set it per call (core.SolverLib)
         self.cdll.mf_set_slab_window(0, 0)

@@ -13,7 +13,8 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       vorticityConfinement, applyNoiseVec3, setOpenBound,
                       updateFractions, setObstacleFlags, setInflowBcs, addNoise, releaseMG,
                       adjustNumber, combineGridVel,
-                      copyFlagsToFlags, markFluidAndBoundaryCells, mapMassToGrid, computeDeltaX, mapMACToPartPositions)
+                      copyFlagsToFlags, markFluidAndBoundaryCells, mapMassToGrid, computeDeltaX, mapMACToPartPositions,
+                      averagedParticleLevelset, improvedParticleLevelset)
 
 from .scene import (Box, Cylinder, Gui, NoiseField, Shape, Sphere, densityInflow, sampleFlagsWithParticles,
                     sampleLevelsetWithParticles, sampleShapeWithParticles)

@@ -14,6 +14,8 @@ PYTHON() declarations; orchestration mirrors the reference function by function,
   copyFlagsToFlags / markFluidAndBoundaryCells / mapMassToGrid / computeDeltaX / mapMACToPartPositions
                                              source/plugin/implicitdensityprojection.cpp
                                              (include/manta_hip_idp.h; not on z-slab solvers)
+  averagedParticleLevelset / improvedParticleLevelset   source/plugin/flip.cpp:365-581
+                                             (include/manta_hip_partls.h; not on z-slab solvers)
 """
 import ctypes
 import functools
@@ -1170,6 +1172,58 @@ def mapMACToPartPositions(flags, deltaX, parts, dt, ptype=None, exclude=0, mapQu
     (np_, cap, pos, pfl), pt = _pargs(parts, ptype)
     lib.call("mf_idp_map_mac_to_positions", flags.sx, flags.sy, flags.sz, deltaX.ptr, np_, cap, pos, pfl, pt, int(exclude),
              float(np.float32(dt)), s.stream)
+
+
+# =========================================================================================================
+# averaged and improved particle level sets (include/manta_hip_partls.h)
+# =========================================================================================================
+def _partls_lib(s, name):
+    """the solver's library, if it implements the particle level-set extension (the CPU test backend does not)"""
+    lib = s.lib
+    if tuple(s._slab_window) != (0, 0):
+        raise RuntimeError("%s: the smooth particle level sets do not run on a z-slab solver" % name)
+    if not lib.partls:
+        raise RuntimeError("%s: the '%s' backend does not implement the smooth particle level sets (manta_hip_partls.h)" % (name, lib.backend))
+    return lib
+
+
+def _particle_levelset(name, improved, parts, indexSys, flags, index, phi, radiusFactor, smoothen, smoothenNeg, t_low, t_high, ptype, exclude):
+    _chk(parts, core.BasicParticleSystem, "BasicParticleSystem"); _chk(indexSys, core.ParticleIndexSystem, "ParticleIndexSystem")
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(index, core.IntGrid, "Grid<int>"); _chk(phi, LevelsetGrid, "LevelsetGrid")
+    ptype = _opt(ptype, core.PdataInt, "ParticleDataImpl<int>")
+    s = flags.parent
+    lib = _partls_lib(s, name)
+    if ptype is not None and ptype.cap != parts.cap:
+        raise RuntimeError("%s: the ptype channel does not follow the capacity of its particle system" % name)
+    # Grid<Vec3> save_pAcc, Grid<Real> save_rAcc, LevelsetGrid tmp: from the solver's pool, every cell is written before it is read
+    pacc = _scratch_grid(s, VecGrid) if improved else None
+    racc = _scratch_grid(s) if improved else None
+    tmp = _scratch_grid(s) if (smoothen > 0 or smoothenNeg > 0) else None
+    lib.call("mf_partls_levelset", flags.sx, flags.sy, flags.sz, parts.np, parts.cap, _ptr(parts.pos), _ptr(indexSys.data),
+             int(indexSys.np), index.ptr, phi.ptr, float(np.float32(radiusFactor)), smoothen, smoothenNeg, int(improved),
+             float(np.float32(t_low)), float(np.float32(t_high)), None if ptype is None else ptype.ptr, int(exclude),
+             None if pacc is None else pacc.ptr, None if racc is None else racc.ptr, None if tmp is None else tmp.ptr, s.stream)
+
+
+@plugin
+def averagedParticleLevelset(parts, indexSys, flags, index, phi, radiusFactor=1., smoothen=1, smoothenNeg=1, ptype=None, exclude=0):
+    """flip.cpp:365-499 (Zhu & Bridson): per cell the particles of the (2r+1)^3 cells around it are averaged with the weights
+    max(0, 1 - |x - p|^2 / (4 radius^2)), summed in the reference's order; phi = |x - pAvg| - rAvg, or radius where the weights sum
+    to at most 1e-6; then max(smoothen, smoothenNeg) rounds of knSmoothGrid / knSmoothGridNeg and setBound(0.5, 0).  Bit-identical
+    to the reference.  Nothing is read back."""
+    _particle_levelset("averagedParticleLevelset", False, parts, indexSys, flags, index, phi, radiusFactor, smoothen, smoothenNeg,
+                       0.4, 3.5, ptype, exclude)
+
+
+@plugin
+def improvedParticleLevelset(parts, indexSys, flags, index, phi, radiusFactor=1., smoothen=1, smoothenNeg=1, t_low=0.4, t_high=3.5,
+                             ptype=None, exclude=0):
+    """flip.cpp:501-581 (Solenthaler et al.): the averaged level set, whose radius term is scaled down where the largest eigenvalue
+    of the Jacobian of the averaged positions reaches t_low (correctLevelset), before the smoothing rounds.  Bit-identical to the
+    reference up to the rounding of the device's fp64 pow / acos / cos / sin (README, "Averaged and improved particle level
+    sets").  Nothing is read back."""
+    _particle_levelset("improvedParticleLevelset", True, parts, indexSys, flags, index, phi, radiusFactor, smoothen, smoothenNeg,
+                       t_low, t_high, ptype, exclude)
 
 
 def _f32(x): return np.float32(x)

@@ -1,0 +1,124 @@
+"""Public surface of the two smooth particle level sets, without a GPU: names and signatures of the reference (plugin/flip.cpp:477-480,
+540-542), the refusals on the CPU checker backend and on a z-slab solver (before anything is touched), and the C ABI extension
+include/manta_hip_partls.h: it parses, shares no name with the other headers, and a library binds all of it or none."""
+import ctypes
+import inspect
+import os
+
+import numpy as np
+import pytest
+
+import util
+
+
+def _params(fn):
+    return [(p.name, p.default) for p in inspect.signature(fn).parameters.values()]
+
+
+def test_public_names_and_signatures():
+    import manta as m
+    E = inspect.Parameter.empty
+    assert _params(m.averagedParticleLevelset) == [("parts", E), ("indexSys", E), ("flags", E), ("index", E), ("phi", E), ("radiusFactor", 1.),
+                                                   ("smoothen", 1), ("smoothenNeg", 1), ("ptype", None), ("exclude", 0)]
+    assert _params(m.improvedParticleLevelset) == [("parts", E), ("indexSys", E), ("flags", E), ("index", E), ("phi", E), ("radiusFactor", 1.),
+                                                   ("smoothen", 1), ("smoothenNeg", 1), ("t_low", 0.4), ("t_high", 3.5), ("ptype", None),
+                                                   ("exclude", 0)]
+    ns = {}
+    exec("from manta import *", ns)
+    assert "averagedParticleLevelset" in ns and "improvedParticleLevelset" in ns
+
+
+def test_header_declares_the_extension():
+    from mantaflow_amd import _lib
+    protos = _lib.parse_header(_lib.PARTLS_HEADER)
+    assert set(protos) == {"mf_partls_abi_version", "mf_partls_levelset"}
+    restype, argtypes, argnames = protos["mf_partls_levelset"]
+    assert restype is ctypes.c_int and argtypes[:3] == [ctypes.c_int] * 3 and argtypes[3] is ctypes.c_int64
+    assert argnames[-1] == "stream" and argtypes[-1] is ctypes.c_void_p and len(argtypes) == 22
+    for other in (_lib.HEADER, _lib.OBSTACLES_HEADER, _lib.MULTIGRID_HEADER, _lib.RESAMPLE_HEADER, _lib.IDP_HEADER):
+        assert not set(protos) & set(_lib.parse_header(other))
+    # the frozen header stays as it is
+    assert "partls" not in open(_lib.HEADER).read()
+
+
+def test_product_library_exports_the_whole_extension():
+    from mantaflow_amd import _lib
+    assert os.path.exists(util.HIP_LIB), "%s missing -- run __graft_entry__.build()" % util.HIP_LIB
+    L = ctypes.CDLL(util.HIP_LIB)          # loads without a GPU; no compute call is made here
+    for name in _lib.parse_header(_lib.PARTLS_HEADER):
+        assert hasattr(L, name), name
+    want = int(__import__("re").search(r"#define\s+MF_PARTLS_ABI_VERSION\s+(\d+)", open(_lib.PARTLS_HEADER).read()).group(1))
+    assert L.mf_partls_abi_version() == want
+
+
+def test_extension_binds_as_a_whole_or_not_at_all(oracle_backend):
+    from mantaflow_amd import _lib
+    lib = _lib.get()
+    assert lib.partls is False          # the CPU checker has none of it, and still loads
+    hip = ctypes.CDLL(util.HIP_LIB)
+
+    class Part(object):
+        """a library that exports one entry of the extension only"""
+        mf_partls_abi_version = hip.mf_partls_abi_version
+
+    saved = lib.cdll
+    lib.cdll = Part()
+    try:
+        with pytest.raises(RuntimeError, match=r"implements part of manta_hip_partls.h, lacks: mf_partls_levelset"):
+            lib._bind_extension("x.so", _lib.PARTLS_HEADER, "mf_partls_abi_version", "MF_PARTLS_ABI_VERSION")
+        lib.cdll = hip
+        assert lib._bind_extension("x.so", _lib.PARTLS_HEADER, "mf_partls_abi_version", "MF_PARTLS_ABI_VERSION") is True
+    finally:
+        lib.cdll = saved
+
+
+def _objects(m, s, dims):
+    pp = s.create(m.BasicParticleSystem)
+    pp.set_positions(np.random.RandomState(0).uniform(1, 7, (50, 3)) * (1, 1, 1 if dims[2] > 1 else 0))
+    o = dict(pp=pp, pindex=s.create(m.ParticleIndexSystem), flags=s.create(m.FlagGrid), gpi=s.create(m.IntGrid), phi=s.create(m.LevelsetGrid))
+    o["flags"].initDomain(boundaryWidth=1)
+    o["phi"].setConst(4.25)
+    m.gridParticleIndex(parts=pp, flags=o["flags"], indexSys=o["pindex"], index=o["gpi"])
+    return o
+
+
+def _refused(m, o, pattern):
+    before = o["phi"].to_numpy().copy()
+    live = o["flags"].parent._live
+    for name in ("averagedParticleLevelset", "improvedParticleLevelset"):
+        with pytest.raises(RuntimeError, match=name + ": " + pattern):
+            getattr(m, name)(o["pp"], o["pindex"], o["flags"], o["gpi"], o["phi"], 1.0, 1, 1)
+    assert np.array_equal(o["phi"].to_numpy(), before) and (before == np.float32(4.25)).all()
+    assert o["flags"].parent._live == live          # no scratch grid was taken
+
+
+@pytest.mark.parametrize("dims", [(12, 10, 8), (15, 12, 1)])
+def test_cpu_backend_refuses_the_plugins(oracle_backend, dims):
+    import manta as m
+    s = m.Solver(name="o", gridSize=m.vec3(*dims), dim=3 if dims[2] > 1 else 2)
+    _refused(m, _objects(m, s, dims), r"the 'oracle' backend does not implement the smooth particle level sets")
+
+
+def test_z_slab_solver_refuses_the_plugins(oracle_backend):
+    import manta as m
+    s = m.Solver(name="o", gridSize=m.vec3(12, 10, 8), dim=3)
+    o = _objects(m, s, (12, 10, 8))
+    s._slab_window = (4, 40)      # what slab.SlabDomain gives the solver of a z-slab: (z offset, global sz)
+    try:
+        _refused(m, o, r"the smooth particle level sets do not run on a z-slab solver")
+    finally:
+        s._slab_window = (0, 0)
+
+
+def test_argument_types_are_checked(oracle_backend):
+    import manta as m
+    s = m.Solver(name="o", gridSize=m.vec3(12, 10, 8), dim=3)
+    o = _objects(m, s, (12, 10, 8))
+    with pytest.raises(RuntimeError, match="can't convert argument to LevelsetGrid"):
+        m.averagedParticleLevelset(o["pp"], o["pindex"], o["flags"], o["gpi"], o["flags"])
+    with pytest.raises(RuntimeError, match="can't convert argument to Grid<int>"):
+        m.improvedParticleLevelset(o["pp"], o["pindex"], o["flags"], o["phi"], o["phi"])
+    with pytest.raises(RuntimeError, match="argument is not an int"):
+        m.improvedParticleLevelset(o["pp"], o["pindex"], o["flags"], o["gpi"], o["phi"], smoothen=1.5)
+    with pytest.raises(RuntimeError, match="unknown"):
+        m.averagedParticleLevelset(o["pp"], o["pindex"], o["flags"], o["gpi"], o["phi"], t_low=0.4)
