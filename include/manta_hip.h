@@ -60,7 +60,11 @@ int mf_abi_version(void);
 
 /* z-slab window (multi-GPU, no reference counterpart): subsequent calls on this thread treat every grid as the
  * planes [zoff, zoff+sz) of a global grid with gsz planes -- positions handed to the interpolators are global
- * coordinates, so a slab reproduces the undivided domain bit for bit.  (0, 0) restores the default (whole domain). */
+ * coordinates, so a slab reproduces the undivided domain bit for bit.  (0, 0) restores the default (whole domain).
+ * Particle positions stay global.  A per-particle entry point leaves a particle whose cell is outside the window untouched
+ * (bounds are tested in global z against gsz, the plane k - zoff must lie in [0, sz)), unless its comment says otherwise: the
+ * interpolating transfers and mf_advect_in_grid clamp the planes they read into the window instead, so their result for such a
+ * particle is not the undivided one. */
 int mf_set_slab_window(int zoff, int gsz);
 /* the window of the SOURCE grid of the calls that read a grid of another size (mf_interpolate_grid, mf_interpolate_mac_grid,
  * the weight grid of mf_apply_noise_vec3): in a two-resolution scene each solver's slab has its own window */

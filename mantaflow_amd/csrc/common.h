@@ -366,7 +366,8 @@ __device__ __forceinline__ float interpol_cubic(const Dim& d, const float* __res
 #pragma unroll
 	for (int c = 0; c < 4; c++) {
 		if (c < nzp) {
-			const float* base = data + (d.is3d ? d.Z * (int64_t)(z0 + c - d.zoff) : 0) + x0;
+			// a stencil plane outside the slab window (a cell of the ghost fringe, whose result is discarded) stays addressable
+			const float* base = data + (d.is3d ? d.Z * (int64_t)local_z(d, z0 + c, 0) : 0) + x0;
 			float rows[4];
 #pragma unroll
 			for (int b = 0; b < 4; b++) {
@@ -462,7 +463,7 @@ __device__ __forceinline__ ApicFace apic_face(const Dim& d, float px, float py, 
 			a.W[q][1] = w;
 		}
 	}
-	a.gidx = b[0] + b[1] * d.Y + b[2] * d.Z;
+	a.gidx = b[0] + b[1] * d.Y + (b[2] - d.zoff) * d.Z;  // positions are global: the plane inside the slab window
 	return a;
 }
 }  // namespace mf

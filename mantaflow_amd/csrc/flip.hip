@@ -390,7 +390,12 @@ __device__ __forceinline__ bool in_bounds_pos(const Dim& d, float x, float y, fl
 __device__ __forceinline__ int flag_at(const Dim& d, const int32_t* __restrict__ flags, float x, float y, float z) {
 	int k = (int)z - d.zoff;                     // plane inside the slab window (identity without a window)
 	k = k < 0 ? 0 : (k > d.sz - 1 ? d.sz - 1 : k);
-	return flags[(int64_t)(int)x + d.Y * (int)y + d.Z * k];  // FlagGrid::getAt, grid.h:324
+	// FlagGrid::getAt, grid.h:324: flat and unchecked in x / y, as in the reference (a position beside the domain reads a
+	// neighbouring row).  Only an index that leaves the array -- a position beside the domain in the last plane of the grid or
+	// of a slab window, where the reference reads past its grid -- is brought back to the nearest cell.
+	int64_t idx = (int64_t)(int)x + d.Y * (int)y + d.Z * k;
+	idx = idx < 0 ? 0 : (idx > d.n - 1 ? d.n - 1 : idx);
+	return flags[idx];
 }
 struct AdvArgs {
 	float dt;

@@ -287,8 +287,9 @@ __global__ void __launch_bounds__(BLOCK) k_reset_outflow_parts(Dim d, const int3
 	if (p >= np) return;
 	const int pf = pflag[p];
 	if (pf & MF_PDELETE) return;
-	const int i = (int)pos[p], j = (int)pos[ps + p], k = (int)pos[2 * ps + p];
-	if (i < 0 || j < 0 || k < 0 || i >= d.sx || j >= d.sy || k >= d.sz) return;
+	// positions are global: bounds against the domain, the plane inside the slab window
+	const int i = (int)pos[p], j = (int)pos[ps + p], kg = (int)pos[2 * ps + p], k = kg - d.zoff;
+	if (i < 0 || j < 0 || kg < 0 || i >= d.sx || j >= d.sy || kg >= d.gsz || k < 0 || k >= d.sz) return;
 	if (flags[i + d.Y * j + d.Z * k] & MF_OUTFLOW) pflag[p] = pf | MF_PDELETE;
 }
 __global__ void __launch_bounds__(BLOCK) k_reset_outflow(int64_t n, int32_t* __restrict__ flags, float* __restrict__ phi, float* __restrict__ real) {

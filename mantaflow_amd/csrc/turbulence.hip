@@ -28,7 +28,8 @@ __global__ void __launch_bounds__(BLOCK) k_compute_energy(Dim d, const int32_t* 
 	if (flags[idx] & MF_FLUID) {
 		const int64_t n = d.n;
 		const float v0 = half_of(vel[idx] + vel[idx + 1]), v1 = half_of(vel[n + idx] + vel[n + idx + d.Y]);
-		const float v2 = d.is3d ? half_of(vel[2 * n + idx] + vel[2 * n + idx + d.Z]) : 0.f;
+		// the last plane has no face above it inside the array (the top ghost plane of a slab window may hold fluid)
+		const float v2 = d.is3d ? half_of(vel[2 * n + idx] + (idx + d.Z < n ? vel[2 * n + idx + d.Z] : 0.f)) : 0.f;
 		e = half_of(v0 * v0 + v1 * v1 + v2 * v2);
 	}
 	energy[idx] = e;

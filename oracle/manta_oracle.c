@@ -828,7 +828,8 @@ static inline float interpol_cubic(const Dim* d, const float* data, float x, flo
 	float planes[4];
 	const int nzp = d->is3d ? 4 : 1;
 	for (int c = 0; c < nzp; c++) {
-		const int64_t zb = d->is3d ? d->Z * (int64_t)(z0 + c - d->zoff) : 0;
+		/* a stencil plane outside the slab window (a cell of the ghost fringe, whose result is discarded) stays addressable */
+		const int64_t zb = d->is3d ? d->Z * (int64_t)local_z(d, z0 + c, 0) : 0;
 		float rows[4];
 		for (int b = 0; b < 4; b++) {
 			const float* r = data + zb + d->Y * (int64_t)(y0 + b) + x0;
@@ -870,7 +871,8 @@ static inline void get_centered(const Dim* d, const float* vel, int64_t idx, flo
 	v[0] = 0.5 * (vel[idx] + vel[idx + 1]);
 	v[1] = 0.5 * (vel[n + idx] + vel[n + idx + d->sx]);
 	v[2] = 0.;
-	if (d->is3d) v[2] = 0.5 * (vel[2 * n + idx] + vel[2 * n + idx + d->Z]);
+	/* the last plane has no face above it inside the array (the top ghost plane of a slab window may hold fluid) */
+	if (d->is3d) v[2] = 0.5 * (vel[2 * n + idx] + (idx + d->Z < n ? vel[2 * n + idx + d->Z] : 0.f));
 }
 static inline void get_at_mac_x(const Dim* d, const float* vel, int64_t idx, float v[3]) {
 	const int64_t n = d->n, sx = d->sx, Z = d->Z;
@@ -1453,7 +1455,7 @@ int mf_apic_map_parts_to_mac(int sx, int sy, int sz, float* vel, float* mass, in
 			int64_t b[3];
 			float gpos[3], W[3][2];
 			apic_face(&a, comp, b, gpos, W);
-			const int64_t gidx = b[0] + b[1] * d.Y + b[2] * d.Z;
+			const int64_t gidx = b[0] + b[1] * d.Y + (b[2] - d.zoff) * d.Z; /* positions are global: the plane inside the slab window */
 			if (gidx < 0 || gidx >= n) continue;
 			const float c0 = cp[comp][p], c1 = cp[comp][ps + p], c2 = cp[comp][2 * ps + p];
 			const float vc = pvel[comp * ps + p];
@@ -1497,7 +1499,7 @@ int mf_apic_map_mac_to_parts(int sx, int sy, int sz, const float* vel, int64_t n
 				int64_t b[3];
 				float gpos[3], W[3][2];
 				apic_face(&a, comp, b, gpos, W);
-				const int64_t gidx = b[0] + b[1] * d.Y + b[2] * d.Z;
+				const int64_t gidx = b[0] + b[1] * d.Y + (b[2] - d.zoff) * d.Z; /* positions are global: the plane inside the slab window */
 				for (int i = 0; i < 2; i++)
 					for (int j = 0; j < 2; j++)
 						for (int k = 0; k < 2; k++) {
@@ -1607,7 +1609,11 @@ static inline int in_bounds_pos(const Dim* d, float x, float y, float z, int bnd
 static inline int flag_at(const Dim* d, const int32_t* flags, float x, float y, float z) { /* FlagGrid::getAt, grid.h:324 */
 	int k = (int)z - d->zoff; /* plane inside the slab window (identity without a window) */
 	k = k < 0 ? 0 : (k > d->sz - 1 ? d->sz - 1 : k);
-	return flags[IDX(*d, (int)x, (int)y, k)];
+	/* flat and unchecked in x / y, as in the reference; an index that leaves the array (a position beside the domain in the last
+	 * plane of the grid or of a slab window, where the reference reads past its grid) is brought back to the nearest cell */
+	int64_t idx = IDX(*d, (int)x, (int)y, k);
+	idx = idx < 0 ? 0 : (idx > d->n - 1 ? d->n - 1 : idx);
+	return flags[idx];
 }
 /* GridAdvectKernel, particle.h:458-481 */
 static void grid_advect_kernel(const Dim* d, const int32_t* flags, const float* vel, int64_t np, int64_t ps,
@@ -2260,8 +2266,8 @@ int mf_reset_outflow(int sx, int sy, int sz, int32_t* flags, float* phi, float* 
 	if (pos && pflag)
 		for (int64_t p = 0; p < np; p++) {
 			if (pflag[p] & MF_PDELETE) continue;
-			const int i = (int)pos[p], j = (int)pos[ps + p], k = (int)pos[2 * ps + p];
-			if (i < 0 || j < 0 || k < 0 || i >= sx || j >= sy || k >= sz) continue;
+			int i, j, k; /* positions are global: bounds against the domain, the plane inside the slab window */
+			if (!cell_of(&d, pos[p], pos[ps + p], pos[2 * ps + p], &i, &j, &k)) continue;
 			if (flags[IDX(d, i, j, k)] & MF_OUTFLOW) pflag[p] |= MF_PDELETE;
 		}
 	for (int64_t idx = 0; idx < d.n; idx++)
@@ -2355,6 +2361,8 @@ int mf_set_part_type(int sx, int sy, int sz, const int32_t* flags, int64_t np, i
 	Dim d = mkdim(sx, sy, sz);
 	for (int64_t p = 0; p < np; p++) {
 		const float x = pos[p], y = pos[ps + p], z = pos[2 * ps + p];
+		const int k = (int)z - d.zoff; /* a particle whose cell lies outside the slab window is left alone */
+		if (d.is3d && (k < 0 || k >= d.sz)) continue;
 		if (in_bounds_pos(&d, x, y, z, 0) && (flag_at(&d, flags, x, y, z) & cflag) && (ptype[p] & stype)) ptype[p] = mark;
 	}
 	return 0;
