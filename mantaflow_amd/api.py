@@ -14,7 +14,8 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       updateFractions, setObstacleFlags, setInflowBcs, addNoise, releaseMG,
                       adjustNumber, combineGridVel,
                       copyFlagsToFlags, markFluidAndBoundaryCells, mapMassToGrid, computeDeltaX, mapMACToPartPositions,
-                      averagedParticleLevelset, improvedParticleLevelset)
+                      averagedParticleLevelset, improvedParticleLevelset,
+                      PD_fluid_guiding, releaseBlurPrecomp, lastGuidingStats, getSpiralVelocity, setGradientYWeight)
 
 from .scene import (Box, Cylinder, Gui, NoiseField, Shape, Sphere, densityInflow, sampleFlagsWithParticles,
                     sampleLevelsetWithParticles, sampleShapeWithParticles)

@@ -16,6 +16,8 @@ PYTHON() declarations; orchestration mirrors the reference function by function,
                                              (include/manta_hip_idp.h; not on z-slab solvers)
   averagedParticleLevelset / improvedParticleLevelset   source/plugin/flip.cpp:365-581
                                              (include/manta_hip_partls.h; not on z-slab solvers)
+  PD_fluid_guiding / releaseBlurPrecomp / getSpiralVelocity / setGradientYWeight   source/plugin/fluidguiding.cpp
+                                             (include/manta_hip_guiding.h; the solve not on z-slab solvers)
 """
 import ctypes
 import functools
@@ -1253,3 +1255,147 @@ def addGravity(flags, vel, gravity, exclude=None, scale=True):
 
 @plugin
 def addGravityNoScale(flags, vel, gravity, exclude=None): addGravity(flags, vel, gravity, exclude, False, notiming=True)
+
+
+# =========================================================================================================
+# primal-dual fluid guiding (include/manta_hip_guiding.h), source/plugin/fluidguiding.cpp
+# =========================================================================================================
+_blur_precomp = {"radius": -1, "weights": None, "dev": {}}    # gBlurPrecomputed / gBlurKernelRadius / gBlurKernel, :23-25
+_last_guiding = {}
+
+
+def _guiding_lib(s, name):
+    """the solver's library, if it implements the guiding extension (the CPU test backend does not)"""
+    lib = s.lib
+    if tuple(s._slab_window) != (0, 0):
+        raise RuntimeError("%s: fluid guiding does not run on a z-slab solver" % name)
+    if not lib.guiding:
+        raise RuntimeError("%s: the '%s' backend does not implement fluid guiding (manta_hip_guiding.h)" % (name, lib.backend))
+    return lib
+
+
+def _blur_weights(lib, s, blurRadius):
+    """ADMM_precompute_Separable, :217-226: one blur kernel for the whole process; the weights come from the library's host code
+    and are uploaded once per device"""
+    if _blur_precomp["radius"] < 0:
+        if blurRadius < 0:
+            raise RuntimeError("PD_fluid_guiding: invalid blur radius %d" % blurRadius)
+        w = np.zeros(2 * blurRadius + 1, np.float32)
+        lib.call("mf_guiding_weights", int(blurRadius), w.ctypes.data_as(ctypes.c_void_p))
+        _blur_precomp.update(radius=int(blurRadius), weights=w, dev={})
+    key = str(s.device)
+    if key not in _blur_precomp["dev"]:
+        _blur_precomp["dev"][key] = torch.from_numpy(_blur_precomp["weights"]).to(s.device)
+    return _blur_precomp["dev"][key]
+
+
+def _guiding_blur2(lib, s, flags, grid, s1, s2, w_dev):
+    """applySeparableGaussianBlur twice (:233-234, :246-247)"""
+    lib.call("mf_guiding_blur", flags.sx, flags.sy, flags.sz, flags.ptr, grid.ptr, s1.ptr, None if s2 is None else s2.ptr, _ptr(w_dev),
+             _blur_precomp["radius"], 2, s.stream)
+
+
+@plugin
+def PD_fluid_guiding(vel, velT, pressure, flags, weight, blurRadius=5, theta=1.0, tau=1.0, sigma=1.0, epsRel=1e-3, epsAbs=1e-3,
+                     maxIters=200, phi=None, perCellCorr=None, fractions=None, obvel=None, gfClamp=1e-04, cgMaxIterFac=1.5,
+                     cgAccuracy=1e-3, preconditioner=1, zeroPressureFixing=False, curv=None, surfTens=0.):
+    """fluidguiding.cpp:294-353 (Inglis et al., "Primal-Dual Optimization for Fluids"): up to maxIters primal-dual iterations, each
+    an x update (two separable Gaussian blurs between two fused element-wise kernels), the package's own solvePressure on the
+    slack grid z, and a y update whose kernel also yields the two maxima of the stop test -- the one read-back of an iteration.
+    Bit-identical to the reference as far as the inner solve is.  lastGuidingStats() has the iteration counts."""
+    _chk(vel, MACGrid, "MACGrid"); _chk(velT, MACGrid, "MACGrid"); _chk(pressure, Grid, "Grid<Real>")
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(weight, Grid, "Grid<Real>")
+    s = vel.parent
+    if _blur_precomp["radius"] >= 0 and _blur_precomp["radius"] != blurRadius:
+        raise RuntimeError("More than a single blur radius not supported at the moment.")
+    lib = _guiding_lib(s, "PD_fluid_guiding")
+    if preconditioner in (PcMGDynamic, PcMGStatic):
+        _multigrid_lib(s, "PD_fluid_guiding")               # the inner solve would refuse, but only after the set-up
+    for g in (velT, pressure, flags, weight):
+        vel._check_same(g)
+    w_dev = _blur_weights(lib, s, blurRadius)
+    n, is3d = vel.n, s.is3D()
+    sig, ta, th = _f32(sigma), _f32(tau), _f32(theta)
+    inv_sigma = _f32(1.0 / float(sig))                      # x.multConst(1.0 / sigma): a double quotient, rounded by Vec3(double)
+    # velC, Q, invA and the per-iteration temporaries: from the solver's pool, every cell is written before it is read
+    velC, Q, xv, vn, s1 = (_scratch_grid(s, MACGrid) for _ in range(5))
+    s2 = _scratch_grid(s, MACGrid) if flags.sz > 1 else None
+    invA = _scratch_grid(s)
+    x, y, z, zn = MACGrid(s), MACGrid(s), MACGrid(s), _scratch_grid(s, MACGrid)
+    velC.copyFrom(vel)
+    # precomputeQ, :243-250
+    Q.copyFrom(velT)
+    Q.sub(velC)
+    _guiding_blur2(lib, s, flags, Q, s1, s2, w_dev)
+    Q.multConst(vec3(2.0))
+    Q.addScaled(velC, vec3(float(-sig)))
+    lib.call("mf_guiding_inv_a", n, weight.ptr, float(sig), invA.ptr, s.stream)
+    cg_its = []
+    it = 0
+    out = (ctypes.c_float * 2)()
+    for it in range(maxIters):
+        lib.call("mf_guiding_pre", n, x.ptr, y.ptr, Q.ptr, invA.ptr, xv.ptr, vn.ptr, float(inv_sigma), float(sig), s.stream)
+        _guiding_blur2(lib, s, flags, vn, s1, s2, w_dev)
+        lib.call("mf_guiding_mid", n, x.ptr, y.ptr, xv.ptr, vn.ptr, invA.ptr, velC.ptr, z.ptr, zn.ptr, float(sig), float(ta), s.stream)
+        z, zn = zn, z                                       # zn now holds z0
+        solvePressure(z, pressure, flags, cgAccuracy, phi, perCellCorr, fractions, obvel, gfClamp, cgMaxIterFac, True, preconditioner,
+                      False, False, zeroPressureFixing, curv, surfTens, notiming=True)
+        cg_its.append(_last_cg.get("iterations"))
+        lib.call("mf_guiding_post", n, z.ptr, zn.ptr, y.ptr, float(th), out, s.stream)
+        rnorm, zmax = _f32(out[0]), _f32(out[1])
+        # getEpsDual, :165-168: sqrt(3.0 or 2.0) * eps_abs in double, eps_rel * getMaxAbs() a Real product, the sum rounded to Real
+        epsDual = _f32(np.sqrt(3.0 if is3d else 2.0) * float(_f32(epsAbs)) + float(_f32(epsRel) * zmax))
+        if (it > 0 and rnorm < epsDual) or it == maxIters - 1:
+            break
+    vel.copyFrom(z)
+    _last_guiding.clear()
+    _last_guiding.update(iterations=int(it), cg_iterations=cg_its, rnorm=float(out[0]), epsDual=float(epsDual) if cg_its else 0.0)
+
+
+@plugin
+def releaseBlurPrecomp():
+    """fluidguiding.cpp:356-360"""
+    _blur_precomp.update(radius=-1, weights=None, dev={})
+
+
+def lastGuidingStats():
+    """of the most recent PD_fluid_guiding: `iterations`, the value the reference prints at :352 (the index of the last primal-dual
+    iteration), and `cg_iterations`, the CG iteration count of each inner solve"""
+    d = dict(_last_guiding)
+    d["cg_iterations"] = list(d.get("cg_iterations", []))
+    return d
+
+
+@plugin
+def getSpiralVelocity(flags, vel, strength=1.0, with3D=False):
+    """fluidguiding.cpp:171-191: set-up code, on the host (every backend)"""
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(vel, MACGrid, "MACGrid")
+    nx, ny, nz = flags.sx, flags.sy, (flags.sz if with3D else 1)
+    midX, midY = _f32(0.5 * float(_f32(nx - 1))), _f32(0.5 * float(_f32(ny - 1)))
+    diffX = (midX - np.arange(nx, dtype=np.float32))[None, :]
+    diffY = (midY - np.arange(ny, dtype=np.float32))[:, None]
+    hyp = np.sqrt(diffX * diffX + diffY * diffY)
+    ok = hyp > 0
+    safe = np.where(ok, hyp, _f32(1))
+    v = vel.to_numpy()
+    v[:nz, :, :, 0] = np.where(ok, diffY / safe, v[:nz, :, :, 0])
+    v[:nz, :, :, 1] = np.where(ok, -diffX / safe, v[:nz, :, :, 1])
+    vel.from_numpy(v)
+    vel.multConst(vec3(float(_f32(strength))))
+
+
+@plugin
+def setGradientYWeight(W, minY, maxY, valAtMin, valAtMax):
+    """fluidguiding.cpp:194-205: set-up code, on the host (every backend)"""
+    _chk(W, Grid, "Grid<Real>")
+    minY, maxY = _coerce(minY, 0), _coerce(maxY, 0)
+    vmin, vmax = _f32(valAtMin), _f32(valAtMax)
+    a = W.to_numpy()
+    for j in range(max(minY, 0), min(maxY, W.sy - 1) + 1):
+        val = vmin
+        if vmax != vmin:
+            with np.errstate(all="ignore"):
+                ratio = _f32(j - minY) / _f32(maxY - minY)
+                val = _f32(float(ratio * vmax) + (1.0 - float(ratio)) * float(vmin))   # Real product + double product
+        a[:, j, :] = val
+    W.from_numpy(a)

@@ -1,0 +1,234 @@
+"""Public surface of fluid guiding, without a GPU: names and signatures of the reference (plugin/fluidguiding.cpp:171-205, 294-360),
+the C ABI extension include/manta_hip_guiding.h, the single-radius rule and releaseBlurPrecomp, the refusals of PD_fluid_guiding on
+the CPU checker backend and on a z-slab solver (before anything is touched), and the two set-up plugins, which run on every backend,
+against the reference's recorded results."""
+import ctypes
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+import guiding_model as M
+import util
+from util import assert_bitexact
+
+
+def _params(fn):
+    return [(p.name, p.default) for p in inspect.signature(fn).parameters.values()]
+
+
+def test_public_names_and_signatures():
+    import manta as m
+    E = inspect.Parameter.empty
+    assert _params(m.PD_fluid_guiding) == [
+        ("vel", E), ("velT", E), ("pressure", E), ("flags", E), ("weight", E), ("blurRadius", 5), ("theta", 1.0), ("tau", 1.0), ("sigma", 1.0),
+        ("epsRel", 1e-3), ("epsAbs", 1e-3), ("maxIters", 200), ("phi", None), ("perCellCorr", None), ("fractions", None), ("obvel", None),
+        ("gfClamp", 1e-04), ("cgMaxIterFac", 1.5), ("cgAccuracy", 1e-3), ("preconditioner", 1), ("zeroPressureFixing", False), ("curv", None),
+        ("surfTens", 0.)]
+    assert _params(m.releaseBlurPrecomp) == []
+    assert _params(m.getSpiralVelocity) == [("flags", E), ("vel", E), ("strength", 1.0), ("with3D", False)]
+    assert _params(m.setGradientYWeight) == [("W", E), ("minY", E), ("maxY", E), ("valAtMin", E), ("valAtMax", E)]
+    assert _params(m.lastGuidingStats) == []
+    ns = {}
+    exec("from manta import *", ns)
+    for name in ("PD_fluid_guiding", "releaseBlurPrecomp", "getSpiralVelocity", "setGradientYWeight", "lastGuidingStats"):
+        assert name in ns, name
+
+
+def test_header_declares_the_extension():
+    from mantaflow_amd import _lib
+    protos = _lib.parse_header(_lib.GUIDING_HEADER)
+    assert set(protos) == {"mf_guiding_abi_version", "mf_guiding_weights", "mf_guiding_blur", "mf_guiding_inv_a", "mf_guiding_pre",
+                           "mf_guiding_mid", "mf_guiding_post"}
+    for name in ("mf_guiding_blur", "mf_guiding_inv_a", "mf_guiding_pre", "mf_guiding_mid", "mf_guiding_post"):
+        restype, argtypes, argnames = protos[name]
+        assert restype is ctypes.c_int and argnames[-1] == "stream" and argtypes[-1] is ctypes.c_void_p, name
+    assert protos["mf_guiding_weights"][2] == ["radius", "w_host"]
+    for other in (_lib.HEADER, _lib.OBSTACLES_HEADER, _lib.MULTIGRID_HEADER, _lib.RESAMPLE_HEADER, _lib.IDP_HEADER, _lib.PARTLS_HEADER):
+        assert not set(protos) & set(_lib.parse_header(other))
+    assert "guiding" not in open(_lib.HEADER).read()          # the frozen header stays as it is
+
+
+def test_product_library_exports_the_whole_extension():
+    from mantaflow_amd import _lib
+    assert os.path.exists(util.HIP_LIB), "%s missing -- run __graft_entry__.build()" % util.HIP_LIB
+    L = ctypes.CDLL(util.HIP_LIB)          # loads without a GPU; no compute call is made here
+    for name in _lib.parse_header(_lib.GUIDING_HEADER):
+        assert hasattr(L, name), name
+    want = int(re.search(r"#define\s+MF_GUIDING_ABI_VERSION\s+(\d+)", open(_lib.GUIDING_HEADER).read()).group(1))
+    assert L.mf_guiding_abi_version() == want
+
+
+def test_extension_binds_as_a_whole_or_not_at_all(oracle_backend):
+    from mantaflow_amd import _lib
+    lib = _lib.get()
+    assert lib.guiding is False          # the CPU checker has none of it, and still loads
+    hip = ctypes.CDLL(util.HIP_LIB)
+
+    class Part(object):
+        """a library that exports one entry of the extension only"""
+        mf_guiding_abi_version = hip.mf_guiding_abi_version
+
+    saved = lib.cdll
+    lib.cdll = Part()
+    try:
+        with pytest.raises(RuntimeError, match=r"implements part of manta_hip_guiding.h, lacks: "):
+            lib._bind_extension("x.so", _lib.GUIDING_HEADER, "mf_guiding_abi_version", "MF_GUIDING_ABI_VERSION")
+        lib.cdll = hip
+        assert lib._bind_extension("x.so", _lib.GUIDING_HEADER, "mf_guiding_abi_version", "MF_GUIDING_ABI_VERSION") is True
+    finally:
+        lib.cdll = saved
+
+
+def _objects(m, s):
+    o = dict(vel=s.create(m.MACGrid), velT=s.create(m.MACGrid), pressure=s.create(m.RealGrid), flags=s.create(m.FlagGrid), W=s.create(m.RealGrid))
+    o["flags"].initDomain(boundaryWidth=1)
+    o["flags"].fillGrid()
+    o["vel"].setConst(m.vec3(0.25, -0.5, 0.125))
+    o["velT"].setConst(m.vec3(1, 2, 3))
+    o["pressure"].setConst(7.5)
+    o["W"].setConst(2.0)
+    return o
+
+
+def _refused(m, o, pattern, **kw):
+    before = {k: g.to_numpy().copy() for k, g in o.items()}
+    live = o["flags"].parent._live
+    stats = m.lastGuidingStats()
+    with pytest.raises(RuntimeError, match=pattern):
+        m.PD_fluid_guiding(vel=o["vel"], velT=o["velT"], pressure=o["pressure"], flags=o["flags"], weight=o["W"], **kw)
+    for k, g in o.items():
+        assert np.array_equal(g.to_numpy(), before[k]), k
+    assert o["flags"].parent._live == live          # no scratch grid was taken
+    assert m.lastGuidingStats() == stats
+
+
+@pytest.fixture
+def no_blur_precomp():
+    import manta as m
+    m.releaseBlurPrecomp()
+    yield
+    m.releaseBlurPrecomp()
+
+
+@pytest.mark.parametrize("dims", [(12, 10, 8), (15, 12, 1)])
+def test_cpu_backend_refuses_the_plugin(oracle_backend, no_blur_precomp, dims):
+    import manta as m
+    from mantaflow_amd import plugins
+    s = m.Solver(name="o", gridSize=m.vec3(*dims), dim=3 if dims[2] > 1 else 2)
+    _refused(m, _objects(m, s), r"PD_fluid_guiding: the 'oracle' backend does not implement fluid guiding", blurRadius=2)
+    assert plugins._blur_precomp["radius"] == -1          # a refused call fixes no radius
+
+
+def test_z_slab_solver_refuses_the_plugin(oracle_backend, no_blur_precomp):
+    import manta as m
+    s = m.Solver(name="o", gridSize=m.vec3(12, 10, 8), dim=3)
+    o = _objects(m, s)
+    s._slab_window = (4, 40)      # what slab.SlabDomain gives the solver of a z-slab: (z offset, global sz)
+    try:
+        _refused(m, o, r"PD_fluid_guiding: fluid guiding does not run on a z-slab solver")
+    finally:
+        s._slab_window = (0, 0)
+
+
+def test_single_radius_rule_and_release(oracle_backend, no_blur_precomp):
+    """the reference keeps one blur kernel per process: once a radius is fixed, a call with another one raises its message before
+    anything else happens; releaseBlurPrecomp() forgets the radius"""
+    import manta as m
+    from mantaflow_amd import plugins
+    s = m.Solver(name="o", gridSize=m.vec3(12, 10, 8), dim=3)
+    o = _objects(m, s)
+    plugins._blur_precomp.update(radius=2, weights=M.weights(2), dev={})     # what a first call with blurRadius=2 leaves
+    _refused(m, o, r"More than a single blur radius not supported at the moment\.", blurRadius=3)
+    _refused(m, o, r"More than a single blur radius not supported at the moment\.")            # the default radius is 5
+    _refused(m, o, r"the 'oracle' backend does not implement fluid guiding", blurRadius=2)   # the fixed radius passes the rule
+    m.releaseBlurPrecomp()
+    assert plugins._blur_precomp["radius"] == -1 and plugins._blur_precomp["weights"] is None
+    _refused(m, o, r"the 'oracle' backend does not implement fluid guiding", blurRadius=3)
+
+
+def test_argument_types_are_checked(oracle_backend, no_blur_precomp):
+    import manta as m
+    s = m.Solver(name="o", gridSize=m.vec3(12, 10, 8), dim=3)
+    o = _objects(m, s)
+    with pytest.raises(RuntimeError, match="can't convert argument to MACGrid"):
+        m.PD_fluid_guiding(o["pressure"], o["velT"], o["pressure"], o["flags"], o["W"])
+    with pytest.raises(RuntimeError, match="can't convert argument to FlagGrid"):
+        m.PD_fluid_guiding(o["vel"], o["velT"], o["pressure"], o["W"], o["W"])
+    with pytest.raises(RuntimeError, match="argument is not an int"):
+        m.PD_fluid_guiding(o["vel"], o["velT"], o["pressure"], o["flags"], o["W"], blurRadius=2.5)
+    with pytest.raises(RuntimeError, match="argument is not a boolean"):
+        m.PD_fluid_guiding(o["vel"], o["velT"], o["pressure"], o["flags"], o["W"], zeroPressureFixing=1)
+    with pytest.raises(RuntimeError, match="unknown"):
+        m.PD_fluid_guiding(o["vel"], o["velT"], o["pressure"], o["flags"], o["W"], precondition=True)
+
+
+@pytest.mark.parametrize("name", [k for k in M.SETUP if k.startswith("spiral")])
+def test_get_spiral_velocity(oracle_backend, name):
+    import manta as m
+    dims, strength, with3D = M.SETUP[name]
+    s = m.Solver(name="o", gridSize=m.vec3(*dims), dim=3 if dims[2] > 1 else 2)
+    flags, vel = s.create(m.FlagGrid), s.create(m.MACGrid)
+    a = M.setup_input(name)
+    vel.from_numpy(a)
+    m.getSpiralVelocity(flags=flags, vel=vel, strength=strength, with3D=with3D)
+    got, want = vel.to_numpy(), M.golden()[name + "/out"]
+    assert_bitexact(got, want, name)
+    st = np.float32(strength)
+    assert_bitexact(got[..., 2], a[..., 2] * st, "z components are scaled only")
+    if dims[2] > 1 and not with3D:
+        assert_bitexact(got[1:], a[1:] * st, "planes above 0 are scaled only")
+    if dims[0] % 2 and dims[1] % 2:
+        c = (slice(0, dims[2] if with3D else 1), dims[1] // 2, dims[0] // 2)
+        assert_bitexact(got[c], a[c] * st, "the centre column (hypotenuse 0) is scaled only")
+
+
+@pytest.mark.parametrize("name", [k for k in M.SETUP if k.startswith("grad")])
+def test_set_gradient_y_weight(oracle_backend, name):
+    import manta as m
+    dims, minY, maxY, vmin, vmax = M.SETUP[name]
+    s = m.Solver(name="o", gridSize=m.vec3(*dims), dim=3 if dims[2] > 1 else 2)
+    W = s.create(m.RealGrid)
+    a = M.setup_input(name)
+    W.from_numpy(a)
+    m.setGradientYWeight(W=W, minY=minY, maxY=maxY, valAtMin=vmin, valAtMax=vmax)
+    got = W.to_numpy()
+    assert_bitexact(got, M.golden()[name + "/out"], name)
+    rows = np.arange(dims[1])
+    inside = (rows >= minY) & (rows <= maxY)
+    assert_bitexact(got[:, ~inside, :], a[:, ~inside, :], "rows outside minY..maxY stay")
+    assert (got[:, minY, :] == np.float32(vmin)).all()                     # both ends are inside
+    if maxY < dims[1]:
+        assert (got[:, maxY, :] == np.float32(vmax)).all()
+
+
+def test_set_gradient_y_weight_takes_the_scene_floats(oracle_backend):
+    """test_1050_guiding2d.py passes res/2, a float: an int parameter takes a float that is an integer"""
+    import manta as m
+    s = m.Solver(name="o", gridSize=m.vec3(6, 8, 1), dim=2)
+    W = s.create(m.RealGrid)
+    m.setGradientYWeight(W=W, minY=0, maxY=8 / 2, valAtMin=1, valAtMax=1)
+    m.setGradientYWeight(W=W, minY=8 / 2, maxY=8, valAtMin=5, valAtMax=5)
+    got = W.to_numpy()
+    assert (got[:, :4] == 1).all() and (got[:, 4:] == 5).all()
+    assert_bitexact(M.box_weight(), _box_weight_through_the_plugin(m), "the box case's weight")
+
+
+def _box_weight_through_the_plugin(m):
+    sx, sy, sz = M.BOX["dims"]
+    s = m.Solver(name="b", gridSize=m.vec3(sx, sy, sz), dim=3)
+    W = s.create(m.RealGrid)
+    W.setConst(1.0)
+    m.setGradientYWeight(W, *M.box_inputs()["grad"])
+    return W.to_numpy()
+
+
+@pytest.mark.parametrize("radius", list(M.RADII))
+def test_library_weights_are_host_code(radius):
+    """mf_guiding_weights touches no device: the product library's weights equal the reference's here too"""
+    L = ctypes.CDLL(util.HIP_LIB)
+    w = np.full(2 * radius + 1, np.nan, np.float32)
+    assert L.mf_guiding_weights(radius, w.ctypes.data_as(ctypes.c_void_p)) == 0
+    assert_bitexact(w, M.golden()["weights/%d" % radius], "weights of radius %d" % radius)
