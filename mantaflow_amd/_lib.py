@@ -12,7 +12,8 @@ when the loaded library exports them (``Library.obstacles``), and a library with
 ``include/manta_hip_resample.h`` (particle resampling for narrow-band FLIP, ``Library.resample``) and for
 ``include/manta_hip_idp.h`` (implicit density projection, ``Library.idp``) and for
 ``include/manta_hip_partls.h`` (averaged and improved particle level sets, ``Library.partls``) and for
-``include/manta_hip_guiding.h`` (primal-dual fluid guiding, ``Library.guiding``).
+``include/manta_hip_guiding.h`` (primal-dual fluid guiding, ``Library.guiding``) and for
+``include/manta_hip_secparts.h`` (secondary particles: spray, foam, bubbles, ``Library.secparts``).
 """
 import ctypes
 import os
@@ -26,6 +27,7 @@ RESAMPLE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_res
 IDP_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_idp.h")
 PARTLS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_partls.h")
 GUIDING_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_guiding.h")
+SECPARTS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_secparts.h")
 DEFAULT_LIB = os.path.join(_HERE, "csrc", "libmanta_hip.so")
 
 _CTYPES = {
@@ -97,6 +99,7 @@ class Library:
         self.idp = self._bind_extension(path, IDP_HEADER, "mf_idp_abi_version", "MF_IDP_ABI_VERSION")
         self.partls = self._bind_extension(path, PARTLS_HEADER, "mf_partls_abi_version", "MF_PARTLS_ABI_VERSION")
         self.guiding = self._bind_extension(path, GUIDING_HEADER, "mf_guiding_abi_version", "MF_GUIDING_ABI_VERSION")
+        self.secparts = self._bind_extension(path, SECPARTS_HEADER, "mf_secparts_abi_version", "MF_SECPARTS_ABI_VERSION")
         # the z-slab window is thread-local state of the shared object (which stays loaded across Library instances): start
         # from "the grid is the whole domain"; solvers carry their own window and set it per call (core.SolverLib)
         self.cdll.mf_set_slab_window(0, 0)

@@ -15,6 +15,8 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       adjustNumber, combineGridVel,
                       copyFlagsToFlags, markFluidAndBoundaryCells, mapMassToGrid, computeDeltaX, mapMACToPartPositions,
                       averagedParticleLevelset, improvedParticleLevelset,
+                      flipComputeSecondaryParticlePotentials, flipSampleSecondaryParticles, flipUpdateSecondaryParticles,
+                      flipDeleteParticlesInObstacle, setFlagsFromLevelset, setMACFromLevelset, resetSecondaryParticleStreams,
                       PD_fluid_guiding, releaseBlurPrecomp, lastGuidingStats, getSpiralVelocity, setGradientYWeight)
 
 from .scene import (Box, Cylinder, Gui, NoiseField, Shape, Sphere, densityInflow, sampleFlagsWithParticles,

@@ -165,6 +165,7 @@ class SolverLib(object):
         self.idp = lib.idp
         self.partls = lib.partls
         self.guiding = lib.guiding
+        self.secparts = lib.secparts
 
     def call(self, name, *args):
         # set on every call: the window is thread-local state of the shared object, so a cache per Library object would go

@@ -18,6 +18,9 @@ PYTHON() declarations; orchestration mirrors the reference function by function,
                                              (include/manta_hip_partls.h; not on z-slab solvers)
   PD_fluid_guiding / releaseBlurPrecomp / getSpiralVelocity / setGradientYWeight   source/plugin/fluidguiding.cpp
                                              (include/manta_hip_guiding.h; the solve not on z-slab solvers)
+  flipComputeSecondaryParticlePotentials / flipSampleSecondaryParticles / flipUpdateSecondaryParticles /
+  flipDeleteParticlesInObstacle / setFlagsFromLevelset / setMACFromLevelset   source/plugin/secondaryparticles.cpp
+                                             (include/manta_hip_secparts.h; not on z-slab solvers)
 """
 import ctypes
 import functools
@@ -1226,6 +1229,215 @@ def improvedParticleLevelset(parts, indexSys, flags, index, phi, radiusFactor=1.
     sets").  Nothing is read back."""
     _particle_levelset("improvedParticleLevelset", True, parts, indexSys, flags, index, phi, radiusFactor, smoothen, smoothenNeg,
                        t_low, t_high, ptype, exclude)
+
+
+# =========================================================================================================
+# secondary particles: spray, foam, bubbles (include/manta_hip_secparts.h)
+# =========================================================================================================
+def _secparts_lib(s, name):
+    """the solver's library, if it implements the secondary-particle extension (the CPU test backend does not)"""
+    lib = s.lib
+    if tuple(s._slab_window) != (0, 0):
+        raise RuntimeError("%s: the secondary particles do not run on a z-slab solver" % name)
+    if not lib.secparts:
+        raise RuntimeError("%s: the '%s' backend does not implement the secondary particles (manta_hip_secparts.h)" % (name, lib.backend))
+    return lib
+
+
+class _SecondaryStream(object):
+    """the `static RandomStream mRand(9832)` of one sampling kernel (secondaryparticles.cpp:118, 175): one per process and mode,
+    never restarted by a call; `cursor` counts the reals drawn so far"""
+
+    def __init__(self):
+        self.seek(0)
+
+    def seek(self, cursor):
+        from .scene import RandomStream
+        self.rs, self.cursor = RandomStream(9832), 0
+        while self.cursor < cursor:         # MT19937 has no cheap jump: draw and drop
+            self.take(min(cursor - self.cursor, 1 << 20))
+
+    def take(self, n):
+        self.cursor += n
+        return self.rs.reals(n)
+
+
+_secondary_streams = {}      # mode -> _SecondaryStream
+
+
+def _secondary_stream(mode):
+    if mode not in _secondary_streams:
+        _secondary_streams[mode] = _SecondaryStream()
+    return _secondary_streams[mode]
+
+
+def resetSecondaryParticleStreams():
+    """restart the random streams of both sampling modes, as a fresh process of the reference has them (no reference counterpart)"""
+    _secondary_streams.clear()
+
+
+def _set_secondary_stream_cursor(mode, cursor):
+    """test hook: the stream of `mode` as it is after `cursor` reals"""
+    _secondary_stream(mode).seek(int(cursor))
+
+
+_FLAG_FLUID, _FLAG_OBSTACLE, _FLAG_INFLOW, _FLAG_OUTFLOW = 1, 2, 8, 16
+_PTRACER = 16
+
+flipSampleSecondaryParticlesStats = {}     # spawned / reals / stream cursor after the last flipSampleSecondaryParticles call
+
+
+@plugin
+def flipComputeSecondaryParticlePotentials(potTA, potWC, potKE, neighborRatio, flags, v, normal, phi, radius, tauMinTA, tauMaxTA,
+                                           tauMinWC, tauMaxWC, tauMinKE, tauMaxKE, scaleFromManta, itype=_FLAG_FLUID,
+                                           jtype=_FLAG_OBSTACLE | _FLAG_OUTFLOW | _FLAG_INFLOW):
+    """secondaryparticles.cpp:24-103: the four outputs are cleared, normal = GradientOp(phi) on the interior, and every itype cell at
+    least `radius` cells from the sides gets the trapped-air, wave-crest and kinetic-energy potentials and the fluid-neighbour
+    ratio of its (2 radius + 1)^3 neighbourhood (jtype cells and the outermost layer do not count).  Bit-identical to the
+    reference.  A streaming pass writes the per-cell terms into pool scratch, the gather reads only those; nothing is read back.
+    radius < 1 is refused (the reference would read outside the grid)."""
+    for g in (potTA, potWC, potKE, neighborRatio):
+        _chk(g, Grid, "Grid<Real>")
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(v, MACGrid, "MACGrid"); _chk(normal, VecGrid, "Grid<Vec3>"); _chk(phi, Grid, "Grid<Real>")
+    s = flags.parent
+    lib = _secparts_lib(s, "flipComputeSecondaryParticlePotentials")
+    radius = _coerce(radius, 0)
+    if radius < 1:
+        raise RuntimeError("flipComputeSecondaryParticlePotentials: radius %d < 1" % radius)
+    sv, sn, sc = _scratch_grid(s, VecGrid), _scratch_grid(s, VecGrid), _scratch_grid(s, core.IntGrid)
+    f = lambda x: float(np.float32(x))
+    lib.call("mf_secparts_potentials", flags.sx, flags.sy, flags.sz, potTA.ptr, potWC.ptr, potKE.ptr, neighborRatio.ptr, flags.ptr, v.ptr,
+             normal.ptr, phi.ptr, radius, f(tauMinTA), f(tauMaxTA), f(tauMinWC), f(tauMaxWC), f(tauMinKE), f(tauMaxKE), f(scaleFromManta),
+             int(itype), int(jtype), sv.ptr, sn.ptr, sc.ptr, 3, s.stream)
+
+
+def _secondary_dt(s, dt):
+    """float timestep = dt; if (dt <= 0) timestep = parent->getDt()"""
+    return float(np.float32(dt)) if dt > 0 else float(np.float32(s.getDt()))
+
+
+def _follows(parts, name, **channels):
+    for what, pd in channels.items():
+        if pd.sys is not parts or pd.cap != parts.cap:
+            raise RuntimeError("%s: %s is not a channel of the particle system" % (name, what))
+
+
+@plugin
+def flipSampleSecondaryParticles(mode, flags, v, pts_sec, v_sec, l_sec, lMin, lMax, potTA, potWC, potKE, neighborRatio, c_s, c_b, k_ta,
+                                 k_wc, dt=0., itype=_FLAG_FLUID):
+    """secondaryparticles.cpp:105-220: every itype cell ("single") or each of its 8 sub-cylinders ("multiple") spawns
+    int(KE * (k_ta * TA + k_wc * WC) * dt) particles in a cylinder along the local velocity, typed by the cell's neighbour ratio.
+    The reference's serial loop over all cells with one process-wide random stream per mode is restated order-free: a count
+    kernel, a scan that gives every entry its particle and stream offset, one read-back of the two totals, the host draws that
+    window of the stream (which continues from call to call; resetSecondaryParticleStreams restarts it), and an emit kernel with
+    one thread per new particle.  Counts, order, flags, lifetimes and stream consumption are bit-identical; positions and
+    velocities are within 4 r 2^-23 + 3 ulp (cos / sin of the azimuth: README, "Secondary particles").  Every other pdata channel
+    of pts_sec gets a zero entry."""
+    if mode not in ("single", "multiple"):
+        raise ValueError("Unknown mode: use \"single\" or \"multiple\" instead!")
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(v, MACGrid, "MACGrid"); _chk(pts_sec, core.BasicParticleSystem, "BasicParticleSystem")
+    _chk(v_sec, core.PdataVec3, "ParticleDataImpl<Vec3>"); _chk(l_sec, core.PdataReal, "ParticleDataImpl<Real>")
+    for g in (potTA, potWC, potKE, neighborRatio):
+        _chk(g, Grid, "Grid<Real>")
+    s = flags.parent
+    lib = _secparts_lib(s, "flipSampleSecondaryParticles")
+    _follows(pts_sec, "flipSampleSecondaryParticles", v_sec=v_sec, l_sec=l_sec)
+    multiple = int(mode == "multiple")
+    f = lambda x: float(np.float32(x))
+    step = _secondary_dt(s, dt)
+    dims = (flags.sx, flags.sy, flags.sz)
+    entries = flags.n * (8 if multiple else 1)
+    nbytes = ctypes.c_int64(0)
+    lib.call("mf_secparts_scan_bytes", entries, ctypes.byref(nbytes))
+    dev = s.device
+    nraw = torch.empty(entries, dtype=torch.int32, device=dev)
+    poff = torch.empty(entries, dtype=torch.int64, device=dev)
+    roff = torch.empty(entries, dtype=torch.int64, device=dev)
+    tmp = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+    totals = (ctypes.c_int64 * 2)()
+    lib.call("mf_secparts_sample_plan", *dims, multiple, flags.ptr, potTA.ptr, potWC.ptr, potKE.ptr, f(k_ta), f(k_wc), step, int(itype),
+             _ptr(nraw), _ptr(poff), _ptr(roff), _ptr(tmp), int(nbytes.value), totals, s.stream)
+    total, nreals = int(totals[0]), int(totals[1])
+    stream = _secondary_stream(mode)
+    reals = stream.take(nreals)
+    if total:
+        old = pts_sec.np
+        pts_sec.reserve(old + total)
+        pts_sec.resizeAll(old + total, pts_sec.cap)
+        for pd in pts_sec.pdata:          # add() -> addEntry(): a default entry in every channel, no setSource initialisation
+            for c in range(pd._ncomp):
+                pd.data[c * pd.cap + old:c * pd.cap + old + total] = 0
+        rdev = torch.from_numpy(reals).to(dev)
+        lib.call("mf_secparts_sample_emit", *dims, multiple, v.ptr, potTA.ptr, potWC.ptr, potKE.ptr, neighborRatio.ptr, _ptr(nraw),
+                 _ptr(poff), _ptr(roff), _ptr(rdev), nreals, old, total, pts_sec.cap, _ptr(pts_sec.pos), _ptr(pts_sec.flag), v_sec.ptr,
+                 l_sec.ptr, f(lMin), f(lMax), f(c_s), f(c_b), step, s.stream)
+        pts_sec.mDeleteChunk = pts_sec.np // 20      # ParticleSystem::add, particle.h:414-420
+    flipSampleSecondaryParticlesStats.clear()
+    flipSampleSecondaryParticlesStats.update(spawned=total, reals=nreals, cursor=stream.cursor)
+
+
+@plugin
+def flipUpdateSecondaryParticles(mode, pts_sec, v_sec, l_sec, f_sec, flags, v, neighborRatio, radius, gravity, k_b, k_d, c_s, c_b, dt=0.,
+                                 scale=True, exclude=_PTRACER, antitunneling=0, itype=_FLAG_FLUID):
+    """secondaryparticles.cpp:225-447: the active, not excluded particles are typed by the neighbour ratio of their cell and advanced:
+    spray ballistically, bubbles by buoyancy and drag towards the fluid velocity, foam with the fluid velocity -- "linear": the
+    interpolated MAC velocity, "cubic": a cubic-spline average of the centred velocities of the itype cells within `radius`.
+    Particles outside the grid, tunnelling into an obstacle at one of the `antitunneling` - 1 samples of their path, or out of
+    lifetime are killed; the call ends with doCompress().  Bit-identical to the reference in every slot of every channel.  One
+    scalar (the kill count) is read back."""
+    if mode not in ("linear", "cubic"):
+        raise ValueError("Unknown mode: use \"linear\" or \"cubic\" instead!")
+    _chk(pts_sec, core.BasicParticleSystem, "BasicParticleSystem"); _chk(v_sec, core.PdataVec3, "ParticleDataImpl<Vec3>")
+    _chk(l_sec, core.PdataReal, "ParticleDataImpl<Real>"); _chk(f_sec, core.PdataVec3, "ParticleDataImpl<Vec3>")
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(v, MACGrid, "MACGrid"); _chk(neighborRatio, Grid, "Grid<Real>")
+    s = flags.parent
+    lib = _secparts_lib(s, "flipUpdateSecondaryParticles")
+    _follows(pts_sec, "flipUpdateSecondaryParticles", v_sec=v_sec, l_sec=l_sec, f_sec=f_sec)
+    radius = _coerce(radius, 0)
+    f = lambda x: float(np.float32(x))
+    g = _to_vec3(gravity)
+    gscale = np.float32(s.getDx()) if scale else np.float32(1)      # float gridScale = scale ? getDx() : 1
+    gx, gy, gz = (float(np.float32(c) / gscale) for c in (g.x, g.y, g.z))
+    kills = ctypes.c_int64(0)
+    lib.call("mf_secparts_update", flags.sx, flags.sy, flags.sz, int(mode == "cubic"), pts_sec.np, pts_sec.cap, _ptr(pts_sec.pos),
+             _ptr(pts_sec.flag), v_sec.ptr, l_sec.ptr, f_sec.ptr, flags.ptr, v.ptr, neighborRatio.ptr, radius, gx, gy, gz, f(k_b), f(k_d),
+             f(c_s), f(c_b), _secondary_dt(s, dt), int(exclude), int(antitunneling), int(itype), ctypes.byref(kills), s.stream)
+    pts_sec.mDeletes += int(kills.value)
+    pts_sec.doCompress()
+
+
+@plugin
+def flipDeleteParticlesInObstacle(pts, flags):
+    """secondaryparticles.cpp:450-476: active particles outside the grid or inside an obstacle or outflow cell are killed, then
+    doCompress().  Bit-identical; one scalar (the kill count) is read back."""
+    _chk(pts, core.BasicParticleSystem, "BasicParticleSystem"); _chk(flags, FlagGrid, "FlagGrid")
+    s = flags.parent
+    lib = _secparts_lib(s, "flipDeleteParticlesInObstacle")
+    kills = ctypes.c_int64(0)
+    lib.call("mf_secparts_delete_in_obstacle", flags.sx, flags.sy, flags.sz, pts.np, pts.cap, _ptr(pts.pos), _ptr(pts.flag), flags.ptr,
+             ctypes.byref(kills), s.stream)
+    pts.mDeletes += int(kills.value)
+    pts.doCompress()
+
+
+@plugin
+def setFlagsFromLevelset(flags, phi, exclude=_FLAG_OBSTACLE, itype=_FLAG_FLUID):
+    """secondaryparticles.cpp:512-522: a cell with phi < 0 and no `exclude` bit becomes itype (the whole flag word)"""
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(phi, Grid, "Grid<Real>")
+    s = flags.parent
+    lib = _secparts_lib(s, "setFlagsFromLevelset")
+    lib.call("mf_secparts_flags_from_levelset", flags.n, flags.ptr, phi.ptr, int(exclude), int(itype), s.stream)
+
+
+@plugin
+def setMACFromLevelset(v, phi, c):
+    """secondaryparticles.cpp:524-533: v = c in every cell where phi, interpolated at the cell's corner Vec3(i, j, k), is positive"""
+    _chk(v, MACGrid, "MACGrid"); _chk(phi, Grid, "Grid<Real>")
+    c = _to_vec3(c)
+    s = v.parent
+    lib = _secparts_lib(s, "setMACFromLevelset")
+    lib.call("mf_secparts_mac_from_levelset", v.sx, v.sy, v.sz, v.ptr, phi.ptr, float(np.float32(c.x)), float(np.float32(c.y)),
+             float(np.float32(c.z)), s.stream)
 
 
 def _f32(x): return np.float32(x)
