@@ -5,15 +5,11 @@ library is missing or cannot be loaded the import of any hot-path function raise
 the test-suite can drive the *same* host code with another implementation of the same ABI (the plain-C oracle
 restatement, host pointers) -- nothing in this package ever loads anything from ``oracle/`` by itself.
 
-Prototypes are parsed from the header itself, so the binding cannot drift from ``include/manta_hip.h``.  The optional
-extension ``include/manta_hip_obstacles.h`` (fill-fraction obstacle boundaries) is parsed the same way: its entries are bound
-when the loaded library exports them (``Library.obstacles``), and a library without them still loads.  The same holds for
-``include/manta_hip_multigrid.h`` (the multigrid preconditioner, ``Library.multigrid``) and for
-``include/manta_hip_resample.h`` (particle resampling for narrow-band FLIP, ``Library.resample``) and for
-``include/manta_hip_idp.h`` (implicit density projection, ``Library.idp``) and for
-``include/manta_hip_partls.h`` (averaged and improved particle level sets, ``Library.partls``) and for
-``include/manta_hip_guiding.h`` (primal-dual fluid guiding, ``Library.guiding``) and for
-``include/manta_hip_secparts.h`` (secondary particles: spray, foam, bubbles, ``Library.secparts``).
+Prototypes are parsed from the header itself, so the binding cannot drift from ``include/manta_hip.h``.
+
+An *extension* is one row of ``EXTENSIONS`` below: an optional header ``include/manta_hip_<name>.h`` that is parsed the same way.
+Its entries are bound when the loaded library exports them (``Library.<name>`` is then True, and ``mf_<name>_abi_version()`` must
+equal the header's ``MF_<NAME>_ABI_VERSION``); a library without them still loads, and the plugins of that extension refuse it.
 """
 import ctypes
 import os
@@ -21,14 +17,41 @@ import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip.h")
-OBSTACLES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_obstacles.h")
-MULTIGRID_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_multigrid.h")
-RESAMPLE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_resample.h")
-IDP_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_idp.h")
-PARTLS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_partls.h")
-GUIDING_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_guiding.h")
-SECPARTS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_secparts.h")
 DEFAULT_LIB = os.path.join(_HERE, "csrc", "libmanta_hip.so")
+
+
+class Extension(object):
+    """One optional extension of the ABI.  ``name`` is the attribute on Library / SolverLib and fixes the header, the version
+    function and the version macro; ``what`` is the phrase the refusals use and ``verb`` the "does" / "do" it takes."""
+
+    def __init__(self, name, what, verb):
+        self.name, self.what, self.verb = name, what, verb
+        self.header = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_%s.h" % name)
+        self.version_fn = "mf_%s_abi_version" % name
+        self.version_macro = "MF_%s_ABI_VERSION" % name.upper()
+
+    def not_implemented(self, who, backend):
+        """the refusal of a library that lacks this extension (the CPU test backend lacks all of them)"""
+        return "%s: the '%s' backend does not implement %s (manta_hip_%s.h)" % (who, backend, self.what, self.name)
+
+
+EXTENSIONS = (
+    Extension("obstacles", "the fill-fraction obstacle plugins", "do"),
+    Extension("multigrid", "the multigrid preconditioners PcMGStatic / PcMGDynamic", "do"),
+    Extension("resample", "particle resampling", "does"),
+    Extension("idp", "implicit density projection", "does"),
+    Extension("partls", "the smooth particle level sets", "do"),
+    Extension("guiding", "fluid guiding", "does"),
+    Extension("secparts", "the secondary particles", "do"),
+)
+for _ext in EXTENSIONS:    # OBSTACLES_HEADER ... SECPARTS_HEADER
+    globals()[_ext.name.upper() + "_HEADER"] = _ext.header
+
+
+def extension(name):
+    """the row of EXTENSIONS with that attribute name"""
+    return next(e for e in EXTENSIONS if e.name == name)
+
 
 _CTYPES = {
     "int": ctypes.c_int,
@@ -93,13 +116,8 @@ class Library:
         if got != want:
             raise RuntimeError("mantaflow_amd: %s implements ABI revision %d, include/manta_hip.h declares %d -- rebuild the library"
                                % (path, got, want))
-        self.obstacles = self._bind_extension(path, OBSTACLES_HEADER, "mf_obstacles_abi_version", "MF_OBSTACLES_ABI_VERSION")
-        self.multigrid = self._bind_extension(path, MULTIGRID_HEADER, "mf_multigrid_abi_version", "MF_MULTIGRID_ABI_VERSION")
-        self.resample = self._bind_extension(path, RESAMPLE_HEADER, "mf_resample_abi_version", "MF_RESAMPLE_ABI_VERSION")
-        self.idp = self._bind_extension(path, IDP_HEADER, "mf_idp_abi_version", "MF_IDP_ABI_VERSION")
-        self.partls = self._bind_extension(path, PARTLS_HEADER, "mf_partls_abi_version", "MF_PARTLS_ABI_VERSION")
-        self.guiding = self._bind_extension(path, GUIDING_HEADER, "mf_guiding_abi_version", "MF_GUIDING_ABI_VERSION")
-        self.secparts = self._bind_extension(path, SECPARTS_HEADER, "mf_secparts_abi_version", "MF_SECPARTS_ABI_VERSION")
+        for ext in EXTENSIONS:
+            setattr(self, ext.name, self._bind_extension(path, ext.header, ext.version_fn, ext.version_macro))
         # the z-slab window is thread-local state of the shared object (which stays loaded across Library instances): start
         # from "the grid is the whole domain"; solvers carry their own window and set it per call (core.SolverLib)
         self.cdll.mf_set_slab_window(0, 0)

@@ -159,13 +159,8 @@ class SolverLib(object):
     def __init__(self, lib, solver):
         self._lib, self._solver = lib, solver
         self.backend, self.device, self.cdll, self.path = lib.backend, lib.device, lib.cdll, lib.path
-        self.obstacles = lib.obstacles
-        self.multigrid = lib.multigrid
-        self.resample = lib.resample
-        self.idp = lib.idp
-        self.partls = lib.partls
-        self.guiding = lib.guiding
-        self.secparts = lib.secparts
+        for ext in _lib.EXTENSIONS:
+            setattr(self, ext.name, getattr(lib, ext.name))
 
     def call(self, name, *args):
         # set on every call: the window is thread-local state of the shared object, so a cache per Library object would go
@@ -893,7 +888,7 @@ class BasicParticleSystem(PbClass):
         planned: (size, holes) of a plan the library holds already (mf_resample_round)"""
         s = self.parent
         if not s.lib.resample:
-            raise RuntimeError("compress: the '%s' backend does not implement particle resampling (manta_hip_resample.h)" % s.lib.backend)
+            raise RuntimeError(_lib.extension("resample").not_implemented("compress", s.lib.backend))
         if planned is None:
             r = (ctypes.c_int64 * 2)()
             s.lib.call("mf_particles_compress_plan", self.np, _ptr(self.flag), r, s.stream)

@@ -10,15 +10,7 @@ using namespace mf;
 
 // blocks are dealt round-robin over the 8 XCDs: give every XCD one contiguous range of cells (a z-slab), so that the planes a
 // gather reaches stay in that XCD's L2 instead of being fetched from HBM by all eight (xcd_swizzle: speed only)
-#define CELL_IJK(d)                                                               \
-	const int64_t idx = xcd_swizzle((int)blockIdx.x, (int)gridDim.x) * (int64_t)BLOCK + threadIdx.x; \
-	if (idx >= (d).n) return;                                                     \
-	const int i = (int)(idx % (d).sx);                                            \
-	const int j = (int)((idx / (d).sx) % (d).sy);                                 \
-	const int k = (int)(idx / ((int64_t)(d).sx * (d).sy));                        \
-	(void)i; (void)j; (void)k;
-#define INTERIOR(d) (i >= 1 && i < (d).sx - 1 && j >= 1 && j < (d).sy - 1 && (!(d).is3d || (k >= 1 && k < (d).sz - 1)))
-static inline unsigned nblk(const Dim& d) { return (unsigned)((d.n + BLOCK - 1) / BLOCK); }
+#define XCD_CELL_IJK(d) CELL_IJK_BLOCK(d, xcd_swizzle((int)blockIdx.x, (int)gridDim.x))
 
 struct __attribute__((packed, aligned(4))) F2u {
 	float a, b;
@@ -30,7 +22,7 @@ __device__ __forceinline__ F2u ld2(const float* __restrict__ p) { return *(const
 template <int NCOMP, int OS>
 __global__ void __launch_bounds__(BLOCK)
 k_semi_lagrange(Dim d, const float* __restrict__ vel, float* __restrict__ dst, const float* __restrict__ src, float dt, int orderTrace) {
-	CELL_IJK(d)
+	XCD_CELL_IJK(d)
 	if (!INTERIOR(d)) {
 		// KERNEL(bnd=1) leaves the boundary of a fresh (cleared) temp grid alone: written here, so that the caller need not clear dst
 #pragma unroll
@@ -141,7 +133,7 @@ __device__ __forceinline__ float mac_component_hi(const Dim& d, const float* __r
 template <int OS>
 __global__ void __launch_bounds__(BLOCK)
 k_semi_lagrange_mac(Dim d, const float* __restrict__ vel, float* __restrict__ dst, const float* __restrict__ src, float dt, int orderTrace) {
-	CELL_IJK(d)
+	XCD_CELL_IJK(d)
 	if (!INTERIOR(d)) {
 		dst[idx] = dst[d.n + idx] = dst[2 * d.n + idx] = 0.f;      // boundary zeros of a cleared temp grid
 		return;
@@ -203,7 +195,7 @@ k_maccormack_correct(Dim d, const int32_t* __restrict__ flags, float* __restrict
 __global__ void __launch_bounds__(BLOCK)
 k_maccormack_correct_mac(Dim d, const int32_t* __restrict__ flags, float* __restrict__ dst, const float* __restrict__ old,
                          const float* __restrict__ fwd, const float* __restrict__ bwd, float strength) {
-	CELL_IJK(d)
+	XCD_CELL_IJK(d)
 	bool s0 = false, s1 = false, s2 = false;
 	if (!(flags[idx] & MF_FLUID)) s0 = s1 = s2 = true;
 	if ((i > 0) && !(flags[idx - 1] & MF_FLUID)) s0 = true;
@@ -227,7 +219,7 @@ template <int NCOMP>
 __global__ void __launch_bounds__(BLOCK)
 k_maccormack_clamp(Dim d, const int32_t* __restrict__ flags, const float* __restrict__ vel, float* __restrict__ dst,
                    const float* __restrict__ orig, const float* __restrict__ fwd, float dt, int clampMode) {
-	CELL_IJK(d)
+	XCD_CELL_IJK(d)
 	if (!INTERIOR(d)) return;
 	float vx, vy, vz;
 	get_centered(d, vel, idx, vx, vy, vz);
@@ -340,7 +332,7 @@ __device__ __forceinline__ float clamp_component_mac(const Dim& d, int c, const 
 __global__ void __launch_bounds__(BLOCK)
 k_maccormack_clamp_mac(Dim d, const int32_t* __restrict__ flags, const float* __restrict__ vel, float* __restrict__ dst,
                        const float* __restrict__ orig, const float* __restrict__ fwd, float dt, int clampMode) {
-	CELL_IJK(d)
+	XCD_CELL_IJK(d)
 	if (!INTERIOR(d)) return;
 	float vx, vy, vz;
 	get_at_mac_x(d, vel, idx, vx, vy, vz);
@@ -446,7 +438,7 @@ __global__ void __launch_bounds__(BLOCK)
 k_mc_correct_clamp(Dim d, const int32_t* __restrict__ flags, const float* __restrict__ vel, float* __restrict__ dst,
                    const float* __restrict__ orig, const float* __restrict__ fwd, const float* __restrict__ bwd, float strength, float dt,
                    int clampMode) {
-	CELL_IJK(d)
+	XCD_CELL_IJK(d)
 	const bool fl = flags[idx] & MF_FLUID;
 	const double sh = (double)strength * 0.5;
 	float fw[NCOMP], dv[NCOMP];
@@ -479,7 +471,7 @@ __global__ void __launch_bounds__(BLOCK)
 k_mc_correct_clamp_mac(Dim d, const int32_t* __restrict__ flags, const float* __restrict__ vel, float* __restrict__ dst,
                        const float* __restrict__ orig, const float* __restrict__ fwd, const float* __restrict__ bwd, float strength, float dt,
                        int clampMode) {
-	CELL_IJK(d)
+	XCD_CELL_IJK(d)
 	bool s0 = false, s1 = false, s2 = false;
 	if (!(flags[idx] & MF_FLUID)) s0 = s1 = s2 = true;
 	if ((i > 0) && !(flags[idx - 1] & MF_FLUID)) s0 = true;
@@ -517,7 +509,7 @@ __device__ __forceinline__ bool inb(const Dim& d, int i, int j, int k) { return 
 __global__ void __launch_bounds__(BLOCK)
 k_outflow_extrapolate(Dim d, const int32_t* __restrict__ flags, const float* __restrict__ vel, float* __restrict__ velDst,
                       const float* __restrict__ velPrev, float timeStep) {
-	CELL_IJK(d)
+	XCD_CELL_IJK(d)
 	if (!(flags[idx] & MF_OUTFLOW)) return;
 	const int64_t n = d.n;
 	float avg[3] = {0.f, 0.f, 0.f};
@@ -607,13 +599,13 @@ int mf_semi_lagrange_real(int sx, int sy, int sz, const float* vel, float* dst, 
 	if (orderSpace != 1 && orderSpace != 2) return fail("Unknown interpolation order %d", orderSpace);
 	const Dim d = mkdim(sx, sy, sz);
 	if (orderSpace == 2)
-		hipLaunchKernelGGL((k_semi_lagrange<1, 2>), dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, dst, src, dt, orderTrace);
+		hipLaunchKernelGGL((k_semi_lagrange<1, 2>), dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, dst, src, dt, orderTrace);
 	else
 		if (d.is3d && orderTrace == 1 && !slz_off()) {
 		const int64_t nthreads = (int64_t)d.sx * d.sy * ((d.sz + SLZ - 1) / SLZ);
 		hipLaunchKernelGGL((k_semi_lagrange_zmarch<1>), dim3((unsigned)((nthreads + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, dst, src, dt);
 	} else
-		hipLaunchKernelGGL((k_semi_lagrange<1, 1>), dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, dst, src, dt, orderTrace);
+		hipLaunchKernelGGL((k_semi_lagrange<1, 1>), dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, dst, src, dt, orderTrace);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -624,13 +616,13 @@ int mf_semi_lagrange_vec3(int sx, int sy, int sz, const float* vel, float* dst, 
 	if (orderSpace != 1 && orderSpace != 2) return fail("Unknown interpolation order %d", orderSpace);
 	const Dim d = mkdim(sx, sy, sz);
 	if (orderSpace == 2)
-		hipLaunchKernelGGL((k_semi_lagrange<3, 2>), dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, dst, src, dt, orderTrace);
+		hipLaunchKernelGGL((k_semi_lagrange<3, 2>), dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, dst, src, dt, orderTrace);
 	else
 		if (d.is3d && orderTrace == 1 && !slz_off()) {
 		const int64_t nthreads = (int64_t)d.sx * d.sy * ((d.sz + SLZ - 1) / SLZ);
 		hipLaunchKernelGGL((k_semi_lagrange_zmarch<3>), dim3((unsigned)((nthreads + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, dst, src, dt);
 	} else
-		hipLaunchKernelGGL((k_semi_lagrange<3, 1>), dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, dst, src, dt, orderTrace);
+		hipLaunchKernelGGL((k_semi_lagrange<3, 1>), dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, dst, src, dt, orderTrace);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -641,9 +633,9 @@ int mf_semi_lagrange_mac(int sx, int sy, int sz, const float* vel, float* dst, c
 	if (orderSpace != 1 && orderSpace != 2) return fail("Unknown interpolation order %d", orderSpace);
 	const Dim d = mkdim(sx, sy, sz);
 	if (orderSpace == 2)
-		hipLaunchKernelGGL((k_semi_lagrange_mac<2>), dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, dst, src, dt, orderTrace);
+		hipLaunchKernelGGL((k_semi_lagrange_mac<2>), dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, dst, src, dt, orderTrace);
 	else
-		hipLaunchKernelGGL((k_semi_lagrange_mac<1>), dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, dst, src, dt, orderTrace);
+		hipLaunchKernelGGL((k_semi_lagrange_mac<1>), dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, dst, src, dt, orderTrace);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -652,9 +644,9 @@ int mf_maccormack_correct(int sx, int sy, int sz, int ncomp, const int32_t* flag
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
 	if (ncomp == 1)
-		hipLaunchKernelGGL((k_maccormack_correct<1>), dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, dst, old, fwd, bwd, strength);
+		hipLaunchKernelGGL((k_maccormack_correct<1>), dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, dst, old, fwd, bwd, strength);
 	else if (ncomp == 3)
-		hipLaunchKernelGGL((k_maccormack_correct<3>), dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, dst, old, fwd, bwd, strength);
+		hipLaunchKernelGGL((k_maccormack_correct<3>), dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, dst, old, fwd, bwd, strength);
 	else
 		return fail("ncomp must be 1 or 3");
 	MF_LAUNCH_CHECK();
@@ -664,7 +656,7 @@ int mf_maccormack_correct_mac(int sx, int sy, int sz, const int32_t* flags, floa
                               const float* bwd, float strength, void* stream) {
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_maccormack_correct_mac, dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, dst, old, fwd, bwd, strength);
+	hipLaunchKernelGGL(k_maccormack_correct_mac, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, dst, old, fwd, bwd, strength);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -673,9 +665,9 @@ int mf_maccormack_clamp(int sx, int sy, int sz, int ncomp, const int32_t* flags,
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
 	if (ncomp == 1)
-		hipLaunchKernelGGL((k_maccormack_clamp<1>), dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, dst, orig, fwd, dt, clampMode);
+		hipLaunchKernelGGL((k_maccormack_clamp<1>), dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, dst, orig, fwd, dt, clampMode);
 	else if (ncomp == 3)
-		hipLaunchKernelGGL((k_maccormack_clamp<3>), dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, dst, orig, fwd, dt, clampMode);
+		hipLaunchKernelGGL((k_maccormack_clamp<3>), dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, dst, orig, fwd, dt, clampMode);
 	else
 		return fail("ncomp must be 1 or 3");
 	MF_LAUNCH_CHECK();
@@ -685,7 +677,7 @@ int mf_maccormack_clamp_mac(int sx, int sy, int sz, const int32_t* flags, const 
                             const float* fwd, float dt, int clampMode, void* stream) {
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_maccormack_clamp_mac, dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, dst, orig, fwd, dt, clampMode);
+	hipLaunchKernelGGL(k_maccormack_clamp_mac, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, dst, orig, fwd, dt, clampMode);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -695,9 +687,9 @@ int mf_maccormack_correct_clamp(int sx, int sy, int sz, int ncomp, const int32_t
 	const Dim d = mkdim(sx, sy, sz);
 	if (dst == orig || dst == fwd || dst == bwd) return fail("mf_maccormack_correct_clamp: dst must not alias orig / fwd / bwd");
 	if (ncomp == 1)
-		hipLaunchKernelGGL((k_mc_correct_clamp<1>), dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, dst, orig, fwd, bwd, strength, dt, clampMode);
+		hipLaunchKernelGGL((k_mc_correct_clamp<1>), dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, dst, orig, fwd, bwd, strength, dt, clampMode);
 	else if (ncomp == 3)
-		hipLaunchKernelGGL((k_mc_correct_clamp<3>), dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, dst, orig, fwd, bwd, strength, dt, clampMode);
+		hipLaunchKernelGGL((k_mc_correct_clamp<3>), dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, dst, orig, fwd, bwd, strength, dt, clampMode);
 	else
 		return fail("ncomp must be 1 or 3");
 	MF_LAUNCH_CHECK();
@@ -708,7 +700,7 @@ int mf_maccormack_correct_clamp_mac(int sx, int sy, int sz, const int32_t* flags
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
 	if (dst == orig || dst == fwd || dst == bwd) return fail("mf_maccormack_correct_clamp_mac: dst must not alias orig / fwd / bwd");
-	hipLaunchKernelGGL(k_mc_correct_clamp_mac, dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, dst, orig, fwd, bwd, strength, dt, clampMode);
+	hipLaunchKernelGGL(k_mc_correct_clamp_mac, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, dst, orig, fwd, bwd, strength, dt, clampMode);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -719,8 +711,8 @@ int mf_apply_outflow_bc(int sx, int sy, int sz, const int32_t* flags, float* vel
 	// applyOutflowBC(double timeStep) hands max(1.0, timeStep*4) to a Real parameter, advection.cpp:388-391
 	const double t4 = (double)dtIn * 4;
 	const float timeStep = (float)(1.0 > t4 ? 1.0 : t4);
-	hipLaunchKernelGGL(k_outflow_extrapolate, dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, velDst, velPrev, timeStep);
-	hipLaunchKernelGGL(k_copy_changed_vels, dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, velDst, vel);
+	hipLaunchKernelGGL(k_outflow_extrapolate, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, velDst, velPrev, timeStep);
+	hipLaunchKernelGGL(k_copy_changed_vels, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, velDst, vel);
 	MF_LAUNCH_CHECK();
 	return 0;
 }

@@ -109,6 +109,38 @@ __device__ __forceinline__ int xcd_swizzle(int b, int nb) {
 	return (b & 7) * (nb >> 3) + (b >> 3);
 }
 
+// ---- one thread per cell / per particle: the preamble of every such kernel and launch --------------------------------
+// idx of block `blk` and its cell coordinates, with 32-bit unsigned divisions: exact because check_dim keeps n below 2^31 and
+// idx < n after the guard (64-bit divisions dominated the cheap sweeps).  Every entry that launches such a kernel has passed
+// check_dim.
+#define CELL_IJK_BLOCK(d, blk)                                          \
+	const int64_t idx = (blk) * (int64_t)BLOCK + threadIdx.x;           \
+	if (idx >= (d).n) return;                                           \
+	const unsigned t_ = (unsigned)idx / (unsigned)(d).sx;               \
+	const int i = (int)((unsigned)idx - t_ * (unsigned)(d).sx);         \
+	const int j = (int)(t_ % (unsigned)(d).sy);                         \
+	const int k = (int)(t_ / (unsigned)(d).sy);                         \
+	(void)i; (void)j; (void)k;
+#define CELL_IJK(d) CELL_IJK_BLOCK(d, blockIdx.x)
+// the cells of KERNEL(bnd = b); the complement of INTERIOR is the set of setBound(value, 0)
+#define INTERIOR_B(d, b) (i >= (b) && i < (d).sx - (b) && j >= (b) && j < (d).sy - (b) && (!(d).is3d || (k >= (b) && k < (d).sz - (b))))
+#define INTERIOR(d) INTERIOR_B(d, 1)
+__device__ __forceinline__ bool in_grid(const Dim& d, int i, int j, int k) {
+	return i >= 0 && j >= 0 && k >= 0 && i < d.sx && j < d.sy && k < d.sz;
+}
+// blocks of BLOCK threads for n items (cells or particles), at least one: a launch of zero blocks is an invalid configuration
+static inline unsigned nblk(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK > 0 ? (n + BLOCK - 1) / BLOCK : 1); }
+
+// ---- growable per-device scratch: each user keeps its own `static Arena g_x[16]` (blocks are not shared between files) ----
+struct Arena {
+	char* p;
+	size_t cap;
+};
+static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+// *out = the current device's block, grown to max(2 * cap, need) bytes where need > cap (after hipDeviceSynchronize; the old
+// contents are gone, *regrown says so, also on the error return of a failed allocation, which leaves p / cap at nullptr / 0).
+int arena_reserve(Arena* per_device, size_t need, Arena** out, bool* regrown = nullptr);
+
 // ---- wave / block reductions (wave = 64 lanes) ---------------------------------------------------------
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

@@ -7,8 +7,6 @@
 
 using namespace mf;
 
-static inline unsigned nblk_n(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK > 0 ? (n + BLOCK - 1) / BLOCK : 1); }
-
 __device__ __forceinline__ bool skip_particle(const int32_t* __restrict__ pflag, const int32_t* __restrict__ ptype, int exclude, int64_t p) {
 	// !p.isActive(idx) || (ptype && ((*ptype)[idx] & exclude)), flip.cpp:630,712,727
 	return (pflag[p] & MF_PDELETE) || (ptype && (ptype[p] & exclude));
@@ -515,9 +513,9 @@ int mf_map_parts_to_mac_accum(int sx, int sy, int sz, float* vel, float* weight,
 		else if (deterministic)
 			hipLaunchKernelGGL(k_p2g_mac_sequential, dim3(1), dim3(64), 0, st, d, vel, weight, np, ps, pos, pflag, pvel, ptype, exclude);
 		else if (3 * d.n < ((int64_t)1 << 31) && !getenv("MF_P2G_NOLDS"))
-			hipLaunchKernelGGL(k_p2g_mac_lds, dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, vel, weight, np, ps, pos, pflag, pvel, ptype, exclude);
+			hipLaunchKernelGGL(k_p2g_mac_lds, dim3(nblk(np)), dim3(BLOCK), 0, st, d, vel, weight, np, ps, pos, pflag, pvel, ptype, exclude);
 		else
-			hipLaunchKernelGGL(k_p2g_mac_atomic, dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, vel, weight, np, ps, pos, pflag, pvel, ptype, exclude);
+			hipLaunchKernelGGL(k_p2g_mac_atomic, dim3(nblk(np)), dim3(BLOCK), 0, st, d, vel, weight, np, ps, pos, pflag, pvel, ptype, exclude);
 	}
 	MF_LAUNCH_CHECK();
 	return 0;
@@ -554,7 +552,7 @@ int mf_apic_map_mac_to_parts(int sx, int sy, int sz, const float* vel, int64_t n
 	MF_TRY(check_dim(sx, sy, sz));
 	if (np <= 0) return 0;
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_g2p_apic, dim3(nblk_n(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, np, ps, pos, pflag, pvel, cpx, cpy, cpz, ptype, exclude);
+	hipLaunchKernelGGL(k_g2p_apic, dim3(nblk(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, np, ps, pos, pflag, pvel, cpx, cpy, cpz, ptype, exclude);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -563,7 +561,7 @@ int mf_map_mac_to_parts(int sx, int sy, int sz, const float* vel, int64_t np, in
 	MF_TRY(check_dim(sx, sy, sz));
 	if (np <= 0) return 0;
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_g2p_pic, dim3(nblk_n(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, np, ps, pos, pflag, pvel, ptype, exclude);
+	hipLaunchKernelGGL(k_g2p_pic, dim3(nblk(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, np, ps, pos, pflag, pvel, ptype, exclude);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -573,7 +571,7 @@ int mf_flip_velocity_update(int sx, int sy, int sz, const float* vel, const floa
 	MF_TRY(check_dim(sx, sy, sz));
 	if (np <= 0) return 0;
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_g2p_flip, dim3(nblk_n(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, velOld, np, ps, pos, pflag, pvel, flipRatio, ptype, exclude);
+	hipLaunchKernelGGL(k_g2p_flip, dim3(nblk(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, velOld, np, ps, pos, pflag, pvel, flipRatio, ptype, exclude);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -596,9 +594,9 @@ int mf_map_parts_to_grid(int sx, int sy, int sz, int ncomp, float* target, float
 				hipLaunchKernelGGL((k_p2g_cell_sequential<3>), dim3(1), dim3(64), 0, st, d, target, wtmp, np, ps, pos, pflag, psrc);
 		} else {
 			if (ncomp == 1)
-				hipLaunchKernelGGL((k_p2g_cell_atomic<1>), dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, target, wtmp, np, ps, pos, pflag, psrc);
+				hipLaunchKernelGGL((k_p2g_cell_atomic<1>), dim3(nblk(np)), dim3(BLOCK), 0, st, d, target, wtmp, np, ps, pos, pflag, psrc);
 			else
-				hipLaunchKernelGGL((k_p2g_cell_atomic<3>), dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, target, wtmp, np, ps, pos, pflag, psrc);
+				hipLaunchKernelGGL((k_p2g_cell_atomic<3>), dim3(nblk(np)), dim3(BLOCK), 0, st, d, target, wtmp, np, ps, pos, pflag, psrc);
 		}
 	}
 	if (ncomp == 1)
@@ -615,9 +613,9 @@ int mf_map_grid_to_parts(int sx, int sy, int sz, int ncomp, const float* source,
 	if (np <= 0) return 0;
 	const Dim d = mkdim(sx, sy, sz);
 	if (ncomp == 1)
-		hipLaunchKernelGGL((k_g2p_cell<1>), dim3(nblk_n(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, source, np, ps, pos, pflag, ptarget);
+		hipLaunchKernelGGL((k_g2p_cell<1>), dim3(nblk(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, source, np, ps, pos, pflag, ptarget);
 	else
-		hipLaunchKernelGGL((k_g2p_cell<3>), dim3(nblk_n(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, source, np, ps, pos, pflag, ptarget);
+		hipLaunchKernelGGL((k_g2p_cell<3>), dim3(nblk(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, source, np, ps, pos, pflag, ptarget);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -635,7 +633,7 @@ int mf_advect_in_grid(int sx, int sy, int sz, const int32_t* flags, const float*
 	a.stopInObstacle = stopInObstacle;
 	a.skipNew = skipNew;
 	a.exclude = exclude;
-	hipLaunchKernelGGL(k_advect_in_grid, dim3(nblk_n(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, np, ps, pos, pflag, a, integrationMode, ptype);
+	hipLaunchKernelGGL(k_advect_in_grid, dim3(nblk(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, np, ps, pos, pflag, a, integrationMode, ptype);
 	MF_LAUNCH_CHECK();
 	return 0;
 }

@@ -4,16 +4,6 @@
 
 using namespace mf;
 
-#define CELL_IJK(d)                                                               \
-	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x;                \
-	if (idx >= (d).n) return;                                                     \
-	const int i = (int)(idx % (d).sx);                                            \
-	const int j = (int)((idx / (d).sx) % (d).sy);                                 \
-	const int k = (int)(idx / ((int64_t)(d).sx * (d).sy));                        \
-	(void)i; (void)j; (void)k;
-#define INTERIOR(d) (i >= 1 && i < (d).sx - 1 && j >= 1 && j < (d).sy - 1 && (!(d).is3d || (k >= 1 && k < (d).sz - 1)))
-static inline unsigned nblk(const Dim& d) { return (unsigned)((d.n + BLOCK - 1) / BLOCK); }
-
 // KnSetWallBcs, extforces.cpp:187-237 (KERNEL(): every cell; each thread writes only its own cell)
 __global__ void __launch_bounds__(BLOCK)
 k_set_wall_bcs(Dim d, const int32_t* __restrict__ flags, float* __restrict__ vel, const float* __restrict__ obvel) {
@@ -297,17 +287,17 @@ int mf_extrapolate_mac_simple(int sx, int sy, int sz, const int32_t* flags, floa
 	hipStream_t st = (hipStream_t)stream;
 	const int dim = d.is3d ? 3 : 2;
 	for (int c = 0; c < dim; c++) {
-		hipLaunchKernelGGL(k_extrap_mark, dim3(nblk(d)), dim3(BLOCK), 0, st, d, flags, tmp, c, intoObs);
+		hipLaunchKernelGGL(k_extrap_mark, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d, flags, tmp, c, intoObs);
 		const bool quads = d.is3d && ((((uintptr_t)tmp) & 15) == 0);
 		for (int dd = 1; dd < 1 + distance; dd++) {
 			if (quads)
 				hipLaunchKernelGGL(k_extrap_simple4, dim3((unsigned)((d.n / 4 + BLOCK) / BLOCK)), dim3(BLOCK), 0, st, d, vel + c * d.n, tmp, dd);
 			else
-				hipLaunchKernelGGL(k_extrap_simple, dim3(nblk(d)), dim3(BLOCK), 0, st, d, vel + c * d.n, tmp, dd);
+				hipLaunchKernelGGL(k_extrap_simple, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d, vel + c * d.n, tmp, dd);
 		}
 	}
 	MF_HIP(hipMemcpyAsync(velTmp, vel, sizeof(float) * 3 * d.n, hipMemcpyDeviceToDevice, st));
-	hipLaunchKernelGGL(k_extrap_into_bnd, dim3(nblk(d)), dim3(BLOCK), 0, st, d, flags, vel, velTmp);
+	hipLaunchKernelGGL(k_extrap_into_bnd, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d, flags, vel, velTmp);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -317,9 +307,9 @@ int mf_extrapolate_mac_from_weight(int sx, int sy, int sz, float* vel, float* we
 	hipStream_t st = (hipStream_t)stream;
 	const int dim = d.is3d ? 3 : 2;
 	for (int c = 0; c < dim; c++) {
-		hipLaunchKernelGGL(k_weight_reset, dim3(nblk(d)), dim3(BLOCK), 0, st, d, weight + c * d.n);
+		hipLaunchKernelGGL(k_weight_reset, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d, weight + c * d.n);
 		for (int dd = 1; dd < 1 + distance; dd++)
-			hipLaunchKernelGGL(k_extrap_weight, dim3(nblk(d)), dim3(BLOCK), 0, st, d, vel + c * d.n, weight + c * d.n, dd);
+			hipLaunchKernelGGL(k_extrap_weight, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d, vel + c * d.n, weight + c * d.n, dd);
 	}
 	MF_LAUNCH_CHECK();
 	return 0;
@@ -329,13 +319,13 @@ int mf_mark_fluid_cells(int sx, int sy, int sz, int32_t* flags, int64_t np, int6
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
 	hipStream_t st = (hipStream_t)stream;
-	hipLaunchKernelGGL(k_clear_fluid_flags, dim3(nblk(d)), dim3(BLOCK), 0, st, d, flags);
+	hipLaunchKernelGGL(k_clear_fluid_flags, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d, flags);
 	if (np > 0)
 		hipLaunchKernelGGL(k_mark_fluid, dim3((unsigned)((np + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, d, flags, np, ps, pos, pflag, ptype, exclude);
 	if (phiObs) {
 		// FlagGrid tmp(flags); knSetNbObstacle(tmp, flags, phiObs); flags.swap(tmp)
 		MF_HIP(hipMemcpyAsync(ftmp, flags, sizeof(int32_t) * d.n, hipMemcpyDeviceToDevice, st));
-		hipLaunchKernelGGL(k_set_nb_obstacle, dim3(nblk(d)), dim3(BLOCK), 0, st, d, ftmp, flags, phiObs);
+		hipLaunchKernelGGL(k_set_nb_obstacle, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d, ftmp, flags, phiObs);
 		MF_HIP(hipMemcpyAsync(flags, ftmp, sizeof(int32_t) * d.n, hipMemcpyDeviceToDevice, st));
 	}
 	MF_LAUNCH_CHECK();
@@ -344,14 +334,14 @@ int mf_mark_fluid_cells(int sx, int sy, int sz, int32_t* flags, int64_t np, int6
 int mf_set_wall_bcs(int sx, int sy, int sz, const int32_t* flags, float* vel, const float* obvel, void* stream) {
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_set_wall_bcs, dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, obvel);
+	hipLaunchKernelGGL(k_set_wall_bcs, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, obvel);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
 int mf_add_buoyancy(int sx, int sy, int sz, const int32_t* flags, const float* density, float* vel, float fx, float fy, float fz, void* stream) {
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_add_buoyancy, dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, density, vel, fx, fy, fz);
+	hipLaunchKernelGGL(k_add_buoyancy, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, density, vel, fx, fy, fz);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -359,7 +349,7 @@ int mf_apply_force(int sx, int sy, int sz, const int32_t* flags, float* vel, flo
                    int additive, void* stream) {
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_apply_force, dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, fx, fy, fz, exclude, additive);
+	hipLaunchKernelGGL(k_apply_force, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, fx, fy, fz, exclude, additive);
 	MF_LAUNCH_CHECK();
 	return 0;
 }

@@ -10,41 +10,7 @@ using namespace mf;
 
 namespace {
 
-static inline unsigned nblk_n(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
-#define CELL_IJK(d)                                                \
-	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x; \
-	if (idx >= (d).n) return;                                      \
-	const unsigned t_ = (unsigned)idx / (unsigned)(d).sx;          \
-	const int i = (int)((unsigned)idx - t_ * (unsigned)(d).sx);    \
-	const int j = (int)(t_ % (unsigned)(d).sy);                    \
-	const int k = (int)(t_ / (unsigned)(d).sy);
-
-// ---- the per-device arena: grows geometrically, never shrinks -----------------------------------------------------------------
-struct Arena {
-	char* p;
-	size_t cap;
-};
-Arena g_arena[16];
-
-static int arena(size_t need, Arena** out) {
-	int dev = 0;
-	MF_HIP(hipGetDevice(&dev));
-	if (dev < 0 || dev >= 16) return fail("device index %d out of range", dev);
-	Arena& a = g_arena[dev];
-	if (need > a.cap) {
-		size_t cap = a.cap * 2 > need ? a.cap * 2 : need;
-		MF_HIP(hipDeviceSynchronize());
-		if (a.p) MF_HIP(hipFree(a.p));
-		a.p = nullptr;
-		a.cap = 0;
-		MF_HIP(hipMalloc((void**)&a.p, cap));
-		a.cap = cap;
-	}
-	*out = &a;
-	return 0;
-}
-static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+Arena g_arena[16];   // this file's per-device scratch (arena_reserve): grows geometrically, never shrinks
 
 // relaxed agent-scope accesses for words that one kernel writes and reads (the rounds of the density sweep)
 __device__ __forceinline__ int ld_agent(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -135,9 +101,6 @@ __global__ __launch_bounds__(BLOCK) void k_push(Dim d, const float* __restrict__
 }
 
 // ---- density -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool in_grid(const Dim& d, int i, int j, int k) {
-	return i >= 0 && j >= 0 && k >= 0 && i < d.sx && j < d.sy && k < d.sz;
-}
 // a flag / a MAC component at a cell that may lie outside the grid (fluid on the outermost layer is outside the contract; it must
 // not fault): nothing there
 __device__ __forceinline__ int flag_at(const Dim& d, const int32_t* __restrict__ f, int i, int j, int k) {
@@ -346,21 +309,21 @@ int mf_idp_mark(int sx, int sy, int sz, int32_t* flags, float* deltaX, const flo
 	if (np < 0 || pstride < np || np >= ((int64_t)1 << 31)) return fail("markFluidAndBoundaryCells: bad particle range (np %lld, stride %lld)", (long long)np, (long long)pstride);
 	const size_t wl = al256(sizeof(int32_t) * (size_t)(np > 0 ? np : 1)), wo = al256(sizeof(int32_t) * 3 * (size_t)d.n);
 	Arena* a;
-	MF_TRY(arena(256 + wl + wo, &a));
+	MF_TRY(arena_reserve(g_arena, 256 + wl + wo, &a));
 	unsigned long long* cnt = (unsigned long long*)a->p;
 	int32_t* list = (int32_t*)(a->p + 256);
 	int32_t* owner = (int32_t*)(a->p + 256 + wl);
 	MF_HIP(hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned long long), st));
 	MF_HIP(hipMemsetAsync(deltaX, 0, sizeof(float) * 3 * d.n, st));
-	hipLaunchKernelGGL(k_clear_fluid, dim3(nblk_n(d.n)), dim3(BLOCK), 0, st, d.n, flags);
-	if (np > 0) hipLaunchKernelGGL(k_mark, dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, flags, np, pstride, pos, pflag, ptype, exclude, list, cnt);
+	hipLaunchKernelGGL(k_clear_fluid, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d.n, flags);
+	if (np > 0) hipLaunchKernelGGL(k_mark, dim3(nblk(np)), dim3(BLOCK), 0, st, d, flags, np, pstride, pos, pflag, ptype, exclude, list, cnt);
 	MF_LAUNCH_CHECK();
 	MF_HIP(hipMemcpyAsync(result_host, cnt, sizeof(int64_t), hipMemcpyDeviceToHost, st));
 	MF_HIP(hipStreamSynchronize(st));
 	const int64_t nb = result_host[0];
 	result_host[1] = 0;
 	if (nb > 0) {
-		const dim3 g(nblk_n(nb)), b(BLOCK);
+		const dim3 g(nblk(nb)), b(BLOCK);
 		hipLaunchKernelGGL((k_push<0>), g, b, 0, st, d, phiObs, nb, list, pstride, pos, deltaX, owner, cnt);
 		hipLaunchKernelGGL((k_push<1>), g, b, 0, st, d, phiObs, nb, list, pstride, pos, deltaX, owner, cnt);
 		hipLaunchKernelGGL((k_push<2>), g, b, 0, st, d, phiObs, nb, list, pstride, pos, deltaX, owner, cnt);
@@ -381,7 +344,7 @@ int mf_idp_map_weights(int sx, int sy, int sz, float* density, int64_t np, int64
 	if (np <= 0) return 0;
 	// the value grid of the transfer (knMapLinear's `tmp` role swapped: it receives the weighted sources) is discarded
 	Arena* a;
-	MF_TRY(arena(al256(sizeof(float) * (size_t)d.n), &a));
+	MF_TRY(arena_reserve(g_arena, al256(sizeof(float) * (size_t)d.n), &a));
 	return p2g_ordered_cell(d, 1, (float*)a->p, density, np, pstride, pos, pflag, psrc, st);
 }
 
@@ -392,14 +355,14 @@ int mf_idp_compute_density(int sx, int sy, int sz, float* density, int32_t* flag
 	hipStream_t st = (hipStream_t)stream;
 	const size_t wc = al256(sizeof(int32_t) * (size_t)d.n);
 	Arena* a;
-	MF_TRY(arena(256 + 4 * wc, &a));
+	MF_TRY(arena_reserve(g_arena, 256 + 4 * wc, &a));
 	unsigned long long* cnt = (unsigned long long*)a->p;
 	int32_t* f0 = (int32_t*)(a->p + 256);
 	int32_t* state = (int32_t*)(a->p + 256 + wc);
 	int32_t* cand = (int32_t*)(a->p + 256 + 2 * wc);   // 2 n words: the list, and its copy that keeps the cell of a decided slot
 	MF_HIP(hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned long long), st));
 	MF_HIP(hipMemcpyAsync(f0, flags, sizeof(int32_t) * d.n, hipMemcpyDeviceToDevice, st));   // FlagGrid flagsTmp(flags), :162
-	const dim3 g(nblk_n(d.n)), b(BLOCK);
+	const dim3 g(nblk(d.n)), b(BLOCK);
 	if (d.is3d) {
 		hipLaunchKernelGGL(k_density_candidates, g, b, 0, st, d, density, f0, deltaX, mass, state, cand, cnt);
 		hipLaunchKernelGGL(k_copy_cand, dim3(256), b, 0, st, cand, cnt);
@@ -415,7 +378,7 @@ int mf_idp_compute_density(int sx, int sy, int sz, float* density, int32_t* flag
 int mf_idp_compute_delta_x(int sx, int sy, int sz, const int32_t* flags, float* deltaX, float* Lambda, void* stream) {
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_compute_delta_x, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, deltaX, Lambda);
+	hipLaunchKernelGGL(k_compute_delta_x, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, deltaX, Lambda);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -426,7 +389,7 @@ int mf_idp_map_mac_to_positions(int sx, int sy, int sz, const float* deltaX, int
 	const Dim d = mkdim(sx, sy, sz);
 	if (np <= 0) return 0;
 	if (pstride < np) return fail("mapMACToPartPositions: particle stride %lld below %lld", (long long)pstride, (long long)np);
-	hipLaunchKernelGGL(k_map_positions, dim3(nblk_n(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, deltaX, np, pstride, pos, pflag, ptype,
+	hipLaunchKernelGGL(k_map_positions, dim3(nblk(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, deltaX, np, pstride, pos, pflag, ptype,
 	                   exclude, dt);
 	MF_LAUNCH_CHECK();
 	return 0;

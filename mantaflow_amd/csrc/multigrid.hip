@@ -472,7 +472,6 @@ Mg* as_mg(void* h) {
 	Mg* m = (Mg*)h;
 	return (m && m->magic == MG_MAGIC) ? m : nullptr;
 }
-int nblk(int n) { return (n + BLOCK - 1) / BLOCK; }
 
 // The bucket min-heap of genCoarseGrid (NKMinHeap, multigrid.cpp:57-186): one doubly linked list per key; set_key puts an ID at
 // the HEAD of its new key's list and pop_min takes the head of the smallest non-empty key -- among equal keys the vertex whose

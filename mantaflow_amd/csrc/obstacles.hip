@@ -8,16 +8,6 @@ using namespace mf;
 
 namespace {
 
-// cell coordinates with 32-bit divisions (check_dim keeps n below 2^31; 64-bit divisions dominated these sweeps)
-#define CELL_IJK(d)                                                               \
-	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x;                \
-	if (idx >= (d).n) return;                                                     \
-	const unsigned t_ = (unsigned)idx / (unsigned)(d).sx;                         \
-	const int i = (int)((unsigned)idx - t_ * (unsigned)(d).sx);                   \
-	const int j = (int)(t_ % (unsigned)(d).sy);                                   \
-	const int k = (int)(t_ / (unsigned)(d).sy);
-static inline unsigned nblk(const Dim& d) { return (unsigned)((d.n + BLOCK - 1) / BLOCK); }
-
 constexpr int OPENISH = MF_INFLOW | MF_OUTFLOW | MF_OPEN;
 
 // the cells a KERNEL(bnd=b) visits (KernelBase::KernelBase, kernel.cpp:21-30, and the generated run(): the k loop runs
@@ -263,7 +253,7 @@ int mf_update_fractions(int sx, int sy, int sz, const int32_t* flags, const floa
 	MF_TRY(check_dim(sx, sy, sz));
 	if (sz == 2) return fail("mf_update_fractions: a 3-D grid needs sz >= 3");
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_update_fractions, dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, phiObs, fractions,
+	hipLaunchKernelGGL(k_update_fractions, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, phiObs, fractions,
 	                   boundaryWidth, fracThreshold);
 	MF_LAUNCH_CHECK();
 	return 0;
@@ -276,7 +266,7 @@ int mf_set_obstacle_flags(int sx, int sy, int sz, int32_t* flags, const float* p
 		return fail("setObstacleFlags: boundaryWidth %d %s", boundaryWidth,
 		            boundaryWidth < 0 ? "is negative" : "with fractions reads faces outside the grid (needs >= 1)");
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_set_obstacle_flags, dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, phiObs, fractions, phiOut,
+	hipLaunchKernelGGL(k_set_obstacle_flags, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, phiObs, fractions, phiOut,
 	                   phiIn, boundaryWidth);
 	MF_LAUNCH_CHECK();
 	return 0;
@@ -298,8 +288,8 @@ int mf_set_wall_bcs_frac(int sx, int sy, int sz, const int32_t* flags, float* ve
 	unsigned long long* mask = (unsigned long long*)scratch;
 	float* vals = (float*)(scratch + 6 * ((d.n + 63) >> 6));
 	hipStream_t st = (hipStream_t)stream;
-	hipLaunchKernelGGL(k_wall_bcs_frac_collect, dim3(nblk(d)), dim3(BLOCK), 0, st, d, flags, vel, phiObs, vals, mask);
-	hipLaunchKernelGGL(k_wall_bcs_frac_apply, dim3(nblk(d)), dim3(BLOCK), 0, st, d, vel, vals, mask);
+	hipLaunchKernelGGL(k_wall_bcs_frac_collect, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d, flags, vel, phiObs, vals, mask);
+	hipLaunchKernelGGL(k_wall_bcs_frac_apply, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d, vel, vals, mask);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -309,7 +299,7 @@ int mf_set_inflow_bcs(int sx, int sy, int sz, float* vel, int sides, float vx, f
 	if (sides & ~63) return fail("mf_set_inflow_bcs: unknown side bits 0x%x", sides);
 	const Dim d = mkdim(sx, sy, sz);
 	if (sides == 0) return 0;
-	hipLaunchKernelGGL(k_set_inflow, dim3(nblk(d)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, sides, vx, vy, vz);
+	hipLaunchKernelGGL(k_set_inflow, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, sides, vx, vy, vz);
 	MF_LAUNCH_CHECK();
 	return 0;
 }

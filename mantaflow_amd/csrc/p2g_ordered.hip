@@ -25,8 +25,6 @@ using namespace mf;
 
 namespace {
 
-static inline unsigned nblk_n(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK > 0 ? (n + BLOCK - 1) / BLOCK : 1); }
-
 constexpr int PBITS = 28;                          // particle index bits of a payload word; e lives above
 constexpr unsigned PMASK = (1u << PBITS) - 1u;
 constexpr int SMALL_RUN = 32;                      // longest run the per-cell insertion sort takes
@@ -780,12 +778,12 @@ int bin_particles(const Dim& d, int64_t np, int64_t ps, const float* pos, const 
 	const int nsb = (int)((n1 + BLOCK * SCAN_ITEMS - 1) / (BLOCK * SCAN_ITEMS));
 	MF_HIP(hipMemsetAsync(s->counts, 0, sizeof(int32_t) * n1, st));
 	MF_HIP(hipMemsetAsync(s->nbig, 0, sizeof(int32_t), st));
-	hipLaunchKernelGGL((k_bin_keys<KEYMODE>), dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, np, ps, pos, pflag, ptype, exclude, s->keys, s->counts);
+	hipLaunchKernelGGL((k_bin_keys<KEYMODE>), dim3(nblk(np)), dim3(BLOCK), 0, st, d, np, ps, pos, pflag, ptype, exclude, s->keys, s->counts);
 	hipLaunchKernelGGL(k_scan_sums, dim3(nsb), dim3(BLOCK), 0, st, n1, s->counts, s->sums);
 	hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(BLOCK), 0, st, nsb, s->sums);
 	hipLaunchKernelGGL(k_scan_blocks, dim3(nsb), dim3(BLOCK), 0, st, n1, s->counts, s->sums, s->start);
-	hipLaunchKernelGGL(k_bin_place, dim3(nblk_n(np)), dim3(BLOCK), 0, st, d.n, np, s->keys, s->start, s->counts, s->order);
-	hipLaunchKernelGGL(k_bin_sort_cells, dim3(nblk_n(d.n)), dim3(BLOCK), 0, st, d.n, s->start, s->order, s->nbig, s->big);
+	hipLaunchKernelGGL(k_bin_place, dim3(nblk(np)), dim3(BLOCK), 0, st, d.n, np, s->keys, s->start, s->counts, s->order);
+	hipLaunchKernelGGL(k_bin_sort_cells, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d.n, s->start, s->order, s->nbig, s->big);
 	hipLaunchKernelGGL(k_bin_sort_big, dim3(256), dim3(BLOCK), 0, st, s->start, s->order, s->nbig, s->big, s->tmp);
 	MF_LAUNCH_CHECK();
 	return 0;
@@ -803,7 +801,7 @@ int run_apic(const Dim& d, int64_t np, int64_t ps, const float* pos, const int32
 	Scratch* s;
 	MF_TRY(get_scratch(np, d.n, &s));
 	MF_TRY((bin_particles<10 + COMP>(d, np, ps, pos, pflag, ptype, exclude, s, st)));
-	hipLaunchKernelGGL((k_gather_apic<COMP>), dim3(nblk_n(d.n)), dim3(BLOCK), 0, st, d, ps, pos, pvc, cp, s->order, s->start, vel, mass);
+	hipLaunchKernelGGL((k_gather_apic<COMP>), dim3(nblk(d.n)), dim3(BLOCK), 0, st, d, ps, pos, pvc, cp, s->order, s->start, vel, mass);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -824,8 +822,8 @@ int p2g_ordered_mac(const Dim& d, float* vel, float* weight, int64_t np, int64_t
 	uint32_t* link = (uint32_t*)(s->pay + 12 * cp);
 	// the number of binned particles is start[n], known on the device only: the payload kernels are launched over np slots and
 	// bound themselves
-	hipLaunchKernelGGL((k_bin_payload<3>), dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, s->start, ps, pos, pvel, ps, s->order, true, rec, (float*)nullptr, cp, s->spe);
-	hipLaunchKernelGGL(k_bin_links, dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, s->start, s->keys, s->spe, true, cp, link);
+	hipLaunchKernelGGL((k_bin_payload<3>), dim3(nblk(np)), dim3(BLOCK), 0, st, d, s->start, ps, pos, pvel, ps, s->order, true, rec, (float*)nullptr, cp, s->spe);
+	hipLaunchKernelGGL(k_bin_links, dim3(nblk(np)), dim3(BLOCK), 0, st, d, s->start, s->keys, s->spe, true, cp, link);
 	const int ntx = d.is3d ? (d.sx + GX - 1) / GX : (d.sx + GX * GZ - 1) / (GX * GZ), nty = (d.sy + GY - 1) / GY, ntz = d.is3d ? (d.sz + GZ - 1) / GZ : 1;
 	const unsigned nb = (unsigned)(ntx * nty * ntz);
 	if (d.is3d) {
@@ -854,10 +852,10 @@ int p2g_ordered_cell(const Dim& d, int ncomp, float* target, float* wsum, int64_
 	const int ntx = d.is3d ? (d.sx + GX - 1) / GX : (d.sx + GX * GZ - 1) / (GX * GZ), nty = (d.sy + GY - 1) / GY, ntz = d.is3d ? (d.sz + GZ - 1) / GZ : 1;
 	const unsigned nb = (unsigned)(ntx * nty * ntz);
 	if (ncomp == 1)
-		hipLaunchKernelGGL((k_bin_payload<1>), dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, s->start, ps, pos, psrc, ps, s->order, false, rec, sv, cp, s->spe);
+		hipLaunchKernelGGL((k_bin_payload<1>), dim3(nblk(np)), dim3(BLOCK), 0, st, d, s->start, ps, pos, psrc, ps, s->order, false, rec, sv, cp, s->spe);
 	else
-		hipLaunchKernelGGL((k_bin_payload<3>), dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, s->start, ps, pos, psrc, ps, s->order, false, rec, sv, cp, s->spe);
-	hipLaunchKernelGGL(k_bin_links, dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, s->start, s->keys, s->spe, false, cp, link);
+		hipLaunchKernelGGL((k_bin_payload<3>), dim3(nblk(np)), dim3(BLOCK), 0, st, d, s->start, ps, pos, psrc, ps, s->order, false, rec, sv, cp, s->spe);
+	hipLaunchKernelGGL(k_bin_links, dim3(nblk(np)), dim3(BLOCK), 0, st, d, s->start, s->keys, s->spe, false, cp, link);
 	if (ncomp == 1 && d.is3d)
 		hipLaunchKernelGGL((k_gather_wave<3>), dim3(nb), dim3(GBLOCK), 0, st, d, ntx, nty, rec, link, s->start, target, wsum);
 	else if (ncomp == 1)

@@ -10,18 +10,6 @@ using namespace mf;
 
 namespace {
 
-#define CELL_IJK(d)                                                \
-	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x; \
-	if (idx >= (d).n) return;                                      \
-	const int i = (int)(idx % (d).sx);                             \
-	const int j = (int)((idx / (d).sx) % (d).sy);                  \
-	const int k = (int)(idx / ((int64_t)(d).sx * (d).sy));
-
-// the cells of KERNEL(bnd=1)'s complement, which are also those of setBound(value, 0)
-__device__ __forceinline__ bool on_border(const Dim& d, int i, int j, int k) {
-	return i <= 0 || i >= d.sx - 1 || j <= 0 || j >= d.sy - 1 || (d.is3d && (k <= 0 || k >= d.sz - 1));
-}
-
 // fabs(norm(g - p)), vectorbase.h:385-389: 0 up to a squared length of 1e-12, 1 within 1e-12 of 1
 __device__ __forceinline__ float dist(float gx, float gy, float gz, float px, float py, float pz) {
 	const float dx = gx - px, dy = gy - py, dz = gz - pz;
@@ -41,7 +29,7 @@ k_partls_gather(Dim d, int64_t np, int64_t ps, const float* __restrict__ pos, co
                 const int32_t* __restrict__ index, float* __restrict__ phi, float* __restrict__ pAcc, float* __restrict__ rAcc,
                 float radius, float sradiusInv, const int32_t* __restrict__ ptype, int exclude, int final) {
 	CELL_IJK(d)
-	if (final && on_border(d, i, j, k)) {
+	if (final && !INTERIOR(d)) {
 		phi[idx] = 0.5f;
 		return;
 	}
@@ -147,7 +135,7 @@ __global__ void __launch_bounds__(BLOCK)
 k_partls_correct(Dim d, float* __restrict__ phi, const float* __restrict__ pAcc, const float* __restrict__ rAcc, float radius, float t_low,
                  float t_high, int final) {
 	CELL_IJK(d)
-	if (on_border(d, i, j, k)) {
+	if (!INTERIOR(d)) {
 		if (final) phi[idx] = 0.5f;
 		return;
 	}
@@ -177,7 +165,7 @@ k_partls_correct(Dim d, float* __restrict__ phi, const float* __restrict__ pAcc,
 __global__ void __launch_bounds__(BLOCK)
 k_partls_smooth(Dim d, const float* __restrict__ me, float* __restrict__ out, float factor, int mode, int final) {
 	CELL_IJK(d)
-	if (on_border(d, i, j, k)) {
+	if (!INTERIOR(d)) {
 		if (final) out[idx] = 0.5f;
 		else if (mode != 1) out[idx] = 0.f;
 		return;
@@ -221,7 +209,7 @@ int mf_partls_levelset(int sx, int sy, int sz, int64_t np, int64_t pstride, cons
 	const float radius = (float)(0.5 * (double)rf);
 	const float sradiusInv = (float)(1. / (4. * (double)radius * (double)radius));
 	const float factor = (float)(1. / (d.is3d ? 7. : 5.));
-	const dim3 grid((unsigned)((d.n + BLOCK - 1) / BLOCK)), block(BLOCK);
+	const dim3 grid(nblk(d.n)), block(BLOCK);
 	// every pass moves the level set to the other buffer: start where an even number of moves ends in phi
 	float* cur = (passes & 1) ? tmp : phi;
 	float* oth = (passes & 1) ? phi : tmp;

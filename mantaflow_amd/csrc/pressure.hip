@@ -302,15 +302,6 @@ static int launch_apply_matrix(const Dim& d, const int32_t* flags, float* dst, c
 // =========================================================================================================
 // assembly kernels (one thread per cell, bnd = 1 unless noted)
 // =========================================================================================================
-#define CELL_IJK(d)                                                               \
-	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x;                \
-	if (idx >= (d).n) return;                                                     \
-	const int i = (int)(idx % (d).sx);                                            \
-	const int j = (int)((idx / (d).sx) % (d).sy);                                 \
-	const int k = (int)(idx / ((int64_t)(d).sx * (d).sy));                        \
-	(void)i; (void)j; (void)k;
-#define INTERIOR(d) (i >= 1 && i < (d).sx - 1 && j >= 1 && j < (d).sy - 1 && (!(d).is3d || (k >= 1 && k < (d).sz - 1)))
-
 // MakeLaplaceMatrix, conjugategrad.h:154-187
 __global__ void __launch_bounds__(BLOCK)
 k_make_laplace(Dim d, const int32_t* __restrict__ flags, float* __restrict__ A0, float* __restrict__ Ai,

@@ -14,43 +14,22 @@ constexpr int PNEW_ = 1, PDELETE_ = 1 << 10;
 // class of a particle in one round: not looked at (deleted already), killed whatever its cell holds, surface, normal
 constexpr int C_SKIP = 0, C_KILL = 1, C_SURF = 2, C_NORM = 3;
 
-static inline unsigned nblk_n(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
-#define CELL_IJK(d)                                                \
-	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x; \
-	if (idx >= (d).n) return;                                      \
-	const unsigned t_ = (unsigned)idx / (unsigned)(d).sx;          \
-	const int i = (int)((unsigned)idx - t_ * (unsigned)(d).sx);    \
-	const int j = (int)(t_ % (unsigned)(d).sy);                    \
-	const int k = (int)(t_ / (unsigned)(d).sy);
-
-// ---- the per-device arena: working arrays of a round and the compress plan; grows geometrically, never shrinks ----------------
-struct Arena {
-	char* p;
-	size_t cap;
-	int32_t *holes, *fillers;   // the current compress plan
-};
+// this file's per-device scratch (arena_reserve): the working arrays of a round and the compress plan, which stays in the block
+// between a round and its moves -- no other entry may take the block over.  Grows geometrically, never shrinks.
 Arena g_arena[16];
-
-static int arena(size_t need, Arena** out) {
-	int dev = 0;
-	MF_HIP(hipGetDevice(&dev));
-	if (dev < 0 || dev >= 16) return fail("device index %d out of range", dev);
-	Arena& a = g_arena[dev];
-	if (need > a.cap) {
-		size_t cap = a.cap * 2 > need ? a.cap * 2 : need;
-		MF_HIP(hipDeviceSynchronize());
-		if (a.p) MF_HIP(hipFree(a.p));
-		a.p = nullptr;
-		a.cap = 0;
-		a.holes = a.fillers = nullptr;
-		MF_HIP(hipMalloc((void**)&a.p, cap));
-		a.cap = cap;
-	}
-	*out = &a;
+struct Plan {
+	int32_t *holes, *fillers;   // the current compress plan, inside the block
+};
+Plan g_plan[16];
+// the block of `need` bytes and the device's plan; the plan of a block that had to be regrown is gone with it
+static int arena(size_t need, Arena** out, Plan** plan) {
+	bool regrown = false;
+	const int rc = arena_reserve(g_arena, need, out, &regrown);
+	if (regrown) g_plan[*out - g_arena] = Plan{nullptr, nullptr};   // also where the new allocation failed
+	if (rc) return rc;
+	*plan = &g_plan[*out - g_arena];
 	return 0;
 }
-static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---- grid operations ---------------------------------------------------------------------------------------------------------
 // knSetBoundaryNeumann, grid.cpp:640-669: the source cell lies strictly inside (the entry checks the sizes), so no thread reads a
@@ -217,14 +196,14 @@ __global__ __launch_bounds__(BLOCK) void k_move(int64_t H, const int32_t* __rest
 	for (int c = 0; c < ncomp; c++) data[c * ps + h] = data[c * ps + f];
 }
 
-static int plan_launch(Arena* a, int64_t np, const int32_t* pflag, int32_t* A, int32_t* holes, int32_t* fillers, void* cub,
+static int plan_launch(Plan* plan, int64_t np, const int32_t* pflag, int32_t* A, int32_t* holes, int32_t* fillers, void* cub,
                        size_t cub_bytes, int64_t* res, int needs_hit, hipStream_t st) {
-	hipLaunchKernelGGL(k_alive, dim3(nblk_n(np)), dim3(BLOCK), 0, st, np, pflag, A);
+	hipLaunchKernelGGL(k_alive, dim3(nblk(np)), dim3(BLOCK), 0, st, np, pflag, A);
 	MF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, A, A, (int)np, st));
-	hipLaunchKernelGGL(k_plan, dim3(nblk_n(np)), dim3(BLOCK), 0, st, np, pflag, A, holes, fillers, res, needs_hit);
+	hipLaunchKernelGGL(k_plan, dim3(nblk(np)), dim3(BLOCK), 0, st, np, pflag, A, holes, fillers, res, needs_hit);
 	MF_LAUNCH_CHECK();
-	a->holes = holes;
-	a->fillers = fillers;
+	plan->holes = holes;
+	plan->fillers = fillers;
 	return 0;
 }
 
@@ -310,14 +289,14 @@ int mf_grid_set_bound_neumann(int sx, int sy, int sz, void* data, int boundaryWi
 	if (w < 0) return fail("setBoundNeumann: boundaryWidth %d < 0", w);
 	if (sx < lo || sy < lo || (d.is3d && sz < lo))
 		return fail("setBoundNeumann: grid %dx%dx%d too small for boundaryWidth %d (needs %d cells per axis)", sx, sy, sz, w, lo);
-	hipLaunchKernelGGL(k_set_bound_neumann, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, (uint32_t*)data, w);
+	hipLaunchKernelGGL(k_set_bound_neumann, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, (uint32_t*)data, w);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
 
 int mf_levelset_init_from_flags(int64_t n, float* phi, const int32_t* flags, int ignoreWalls, void* stream) {
 	if (n <= 0) return 0;
-	hipLaunchKernelGGL(k_init_from_flags, dim3(nblk_n(n)), dim3(BLOCK), 0, (hipStream_t)stream, n, phi, flags, ignoreWalls);
+	hipLaunchKernelGGL(k_init_from_flags, dim3(nblk(n)), dim3(BLOCK), 0, (hipStream_t)stream, n, phi, flags, ignoreWalls);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -326,7 +305,7 @@ int mf_combine_grid_vel(int sx, int sy, int sz, float* vel, const float* weight,
                         float narrowBand, float thresh, void* stream) {
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_combine_vels, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, weight, combineVel, phi,
+	hipLaunchKernelGGL(k_combine_vels, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, weight, combineVel, phi,
 	                   narrowBand, thresh);
 	MF_LAUNCH_CHECK();
 	return 0;
@@ -362,7 +341,8 @@ int mf_resample_round(int sx, int sy, int sz, const float* phi, int32_t* tmp, in
 	if (sort_b > cub_bytes) cub_bytes = sort_b;
 	const size_t wp = al256(sizeof(int32_t) * (size_t)np), wc = al256(sizeof(int32_t) * ((size_t)nc + 1));
 	Arena* a;
-	MF_TRY(arena(6 * wp + 2 * wc + 256 + al256(cub_bytes), &a));
+	Plan* plan;
+	MF_TRY(arena(6 * wp + 2 * wc + 256 + al256(cub_bytes), &a, &plan));
 	char* b = a->p;
 	int32_t* keys = (int32_t*)b;
 	int32_t* skeys = (int32_t*)(b + wp);
@@ -379,7 +359,7 @@ int mf_resample_round(int sx, int sy, int sz, const float* phi, int32_t* tmp, in
 	MF_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * ((size_t)nc + 1), st));
 	MF_HIP(hipMemsetAsync(res, 0xff, sizeof(int64_t), st));          // res[0] = -1
 	MF_HIP(hipMemsetAsync(res + 1, 0, 3 * sizeof(int64_t), st));
-	const dim3 gm(nblk_n(m)), bl(BLOCK);
+	const dim3 gm(nblk(m)), bl(BLOCK);
 	hipLaunchKernelGGL(k_classify, gm, bl, 0, st, d, phi, m, pstride, pos, pflag, i0, narrowBand, surfaceLs, keys, vals, cls, cnt);
 	MF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, scan_c, cnt, start, nc + 1, st));
 	MF_HIP(hipcub::DeviceRadixSort::SortPairs(cub, sort_b, keys, skeys, vals, svals, (int)m, 0, end_bit, st));
@@ -389,7 +369,7 @@ int mf_resample_round(int sx, int sy, int sz, const float* phi, int32_t* tmp, in
 	hipLaunchKernelGGL(k_apply, gm, bl, 0, st, m, i0, keys, cls, kill, pre, res, pflag, tmp);
 	MF_LAUNCH_CHECK();
 	// the plan of the whole array; its kernels do nothing when the round had no hit
-	MF_TRY(plan_launch(a, np, pflag, svals, keys, vals, cub, scan_p, res, 1, st));
+	MF_TRY(plan_launch(plan, np, pflag, svals, keys, vals, cub, scan_p, res, 1, st));
 	hipLaunchKernelGGL(k_round_finish, dim3(1), dim3(1), 0, st, i0, np, res);
 	MF_LAUNCH_CHECK();
 	MF_HIP(hipMemcpyAsync(result_host, res, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -408,11 +388,12 @@ int mf_particles_compress_plan(int64_t np, const int32_t* pflag, int64_t* result
 	MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_p, (int32_t*)nullptr, (int32_t*)nullptr, (int)np, st));
 	const size_t wp = al256(sizeof(int32_t) * (size_t)np);
 	Arena* a;
-	MF_TRY(arena(3 * wp + 256 + al256(scan_p), &a));
+	Plan* plan;
+	MF_TRY(arena(3 * wp + 256 + al256(scan_p), &a, &plan));
 	char* b = a->p;
 	int64_t* res = (int64_t*)(b + 3 * wp);
 	MF_HIP(hipMemsetAsync(res, 0, 4 * sizeof(int64_t), st));
-	MF_TRY(plan_launch(a, np, pflag, (int32_t*)b, (int32_t*)(b + wp), (int32_t*)(b + 2 * wp), b + 3 * wp + 256, scan_p, res, 0, st));
+	MF_TRY(plan_launch(plan, np, pflag, (int32_t*)b, (int32_t*)(b + wp), (int32_t*)(b + 2 * wp), b + 3 * wp + 256, scan_p, res, 0, st));
 	MF_HIP(hipMemcpyAsync(result_host, res + 2, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
 	MF_HIP(hipStreamSynchronize(st));
 	return 0;
@@ -421,10 +402,11 @@ int mf_particles_compress_plan(int64_t np, const int32_t* pflag, int64_t* result
 int mf_particles_compress_move(int64_t holes, int ncomp, int64_t pstride, void* data, void* stream) {
 	if (holes <= 0) return 0;
 	Arena* a;
-	MF_TRY(arena(0, &a));
-	if (!a->holes) return fail("compress: no plan (mf_resample_round / mf_particles_compress_plan come first)");
+	Plan* plan;
+	MF_TRY(arena(0, &a, &plan));
+	if (!plan->holes) return fail("compress: no plan (mf_resample_round / mf_particles_compress_plan come first)");
 	if (ncomp < 1 || ncomp > 3) return fail("compress: %d components", ncomp);
-	hipLaunchKernelGGL(k_move, dim3(nblk_n(holes)), dim3(BLOCK), 0, (hipStream_t)stream, holes, a->holes, a->fillers, ncomp, pstride,
+	hipLaunchKernelGGL(k_move, dim3(nblk(holes)), dim3(BLOCK), 0, (hipStream_t)stream, holes, plan->holes, plan->fillers, ncomp, pstride,
 	                   (uint32_t*)data);
 	MF_LAUNCH_CHECK();
 	return 0;
@@ -441,13 +423,14 @@ int mf_resample_seed_plan(int sx, int sy, int sz, const int32_t* flags, const fl
 	const size_t wc = al256(sizeof(int32_t) * (size_t)d.n);
 	// a compress plan is pending only between a round and its moves; seeding comes after them and takes the arena over
 	Arena* a;
-	MF_TRY(arena(wc + 256 + al256(scan_c), &a));
-	a->holes = a->fillers = nullptr;
+	Plan* plan;
+	MF_TRY(arena(wc + 256 + al256(scan_c), &a, &plan));
+	plan->holes = plan->fillers = nullptr;
 	char* b = a->p;
 	int32_t* need = (int32_t*)b;
 	int64_t* res = (int64_t*)(b + wc);
-	if (np > 0) hipLaunchKernelGGL(k_clear_new, dim3(nblk_n(np)), dim3(BLOCK), 0, st, np, pflag);
-	hipLaunchKernelGGL(k_seed_need, dim3(nblk_n(d.n)), dim3(BLOCK), 0, st, d.n, flags, phi, exclude, tmp, minParticles, narrowBand,
+	if (np > 0) hipLaunchKernelGGL(k_clear_new, dim3(nblk(np)), dim3(BLOCK), 0, st, np, pflag);
+	hipLaunchKernelGGL(k_seed_need, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d.n, flags, phi, exclude, tmp, minParticles, narrowBand,
 	                   surfaceLs, need);
 	MF_HIP(hipcub::DeviceScan::ExclusiveSum(b + wc + 256, scan_c, need, offsets, (int)d.n, st));
 	hipLaunchKernelGGL(k_seed_total, dim3(1), dim3(1), 0, st, d.n, need, offsets, res);
@@ -463,7 +446,7 @@ int mf_resample_seed_insert(int sx, int sy, int sz, const int32_t* offsets, cons
 	const Dim d = mkdim(sx, sy, sz);
 	if (total <= 0) return 0;
 	if (pstride < np + total) return fail("adjustNumber: particle capacity %lld below %lld", (long long)pstride, (long long)(np + total));
-	hipLaunchKernelGGL(k_seed_insert, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, offsets, reals, np, total, pstride, pos,
+	hipLaunchKernelGGL(k_seed_insert, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, offsets, reals, np, total, pstride, pos,
 	                   pflag);
 	MF_LAUNCH_CHECK();
 	return 0;
@@ -477,7 +460,7 @@ int mf_pdata_init_new(int sx, int sy, int sz, const float* grid, int mode, int n
 	if (mode < 0 || mode > 2 || (mode && !grid) || (mode == 2 && ncomp != 3) || (ncomp != 1 && ncomp != 3))
 		return fail("pdata init: bad mode %d / components %d", mode, ncomp);
 	if (first < 0 || first + count > pstride) return fail("pdata init: range past the capacity");
-	hipLaunchKernelGGL(k_pdata_init, dim3(nblk_n(count)), dim3(BLOCK), 0, (hipStream_t)stream, d, grid, mode, ncomp, first, count,
+	hipLaunchKernelGGL(k_pdata_init, dim3(nblk(count)), dim3(BLOCK), 0, (hipStream_t)stream, d, grid, mode, ncomp, first, count,
 	                   pstride, pos, (float*)data);
 	MF_LAUNCH_CHECK();
 	return 0;

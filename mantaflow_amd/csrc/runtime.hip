@@ -35,6 +35,28 @@ int get_workspace(Workspace** out) {
 	*out = &g_ws[dev];
 	return 0;
 }
+
+int arena_reserve(Arena* per_device, size_t need, Arena** out, bool* regrown) {
+	if (regrown) *regrown = false;
+	int dev = 0;
+	MF_HIP(hipGetDevice(&dev));
+	if (dev < 0 || dev >= 16) return fail("device index %d out of range", dev);
+	Arena& a = per_device[dev];
+	*out = &a;
+	if (need > a.cap) {
+		const size_t cap = a.cap * 2 > need ? a.cap * 2 : need;
+		MF_HIP(hipDeviceSynchronize());
+		if (regrown) *regrown = true;
+		if (a.p) MF_HIP(hipFree(a.p));
+		a.p = nullptr;
+		a.cap = 0;
+		char* p = nullptr;
+		MF_HIP(hipMalloc((void**)&p, cap));
+		a.p = p;
+		a.cap = cap;
+	}
+	return 0;
+}
 }  // namespace mf
 
 using namespace mf;

@@ -14,15 +14,6 @@ namespace {
 
 constexpr int PSPRAY_ = 1 << 1, PBUBBLE_ = 1 << 2, PFOAM_ = 1 << 3, PDELETE_ = 1 << 10;
 
-static inline unsigned nblk_n(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
-#define CELL_IJK(d)                                                \
-	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x; \
-	if (idx >= (d).n) return;                                      \
-	const int i = (int)(idx % (d).sx);                             \
-	const int j = (int)((idx / (d).sx) % (d).sy);                  \
-	const int k = (int)(idx / ((int64_t)(d).sx * (d).sy));
-
 struct V3 {
 	float x, y, z;
 };
@@ -444,7 +435,7 @@ int mf_secparts_potentials(int sx, int sy, int sz, float* potTA, float* potWC, f
 	if (!sv || !sn || !sc) return fail("mf_secparts_potentials: needs its scratch arrays");
 	const Dim d = mkdim(sx, sy, sz);
 	hipStream_t st = (hipStream_t)stream;
-	const dim3 grid(nblk_n(d.n)), block(BLOCK);
+	const dim3 grid(nblk(d.n)), block(BLOCK);
 	// Real h = !is3D ? 1.414 * radius : 1.732 * radius
 	const float h = (float)(d.is3d ? 1.732 * radius : 1.414 * radius);
 	if (passes & 1) {
@@ -482,7 +473,7 @@ int mf_secparts_sample_plan(int sx, int sy, int sz, int multiple, const int32_t*
 	int64_t* res = (int64_t*)tmp;
 	void* cub = (char*)tmp + 256;
 	size_t cub_bytes = (size_t)(need - 256);
-	hipLaunchKernelGGL(k_secparts_plan, dim3(nblk_n(entries)), dim3(BLOCK), 0, st, d, multiple, entries, flags, potTA, potWC, potKE, k_ta,
+	hipLaunchKernelGGL(k_secparts_plan, dim3(nblk(entries)), dim3(BLOCK), 0, st, d, multiple, entries, flags, potTA, potWC, potKE, k_ta,
 	                   k_wc, dt, itype, nraw, poff, roff);
 	MF_LAUNCH_CHECK();
 	MF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, poff, poff, (int)entries, st));
@@ -507,7 +498,7 @@ int mf_secparts_sample_emit(int sx, int sy, int sz, int multiple, const float* v
 	if (np_old + total >= ((int64_t)1 << 31)) return fail("flipSampleSecondaryParticles: too many particles for 32-bit indices");
 	const Dim d = mkdim(sx, sy, sz);
 	const int64_t entries = multiple ? 8 * d.n : d.n;
-	hipLaunchKernelGGL(k_secparts_emit, dim3(nblk_n(total)), dim3(BLOCK), 0, (hipStream_t)stream, d, multiple, entries, vel, potTA, potWC,
+	hipLaunchKernelGGL(k_secparts_emit, dim3(nblk(total)), dim3(BLOCK), 0, (hipStream_t)stream, d, multiple, entries, vel, potTA, potWC,
 	                   potKE, neighborRatio, nraw, poff, roff, reals, nreals, np_old, total, pstride, pos, pflag, v_sec, l_sec, lMin, lMax,
 	                   c_s, c_b, dt);
 	MF_LAUNCH_CHECK();
@@ -530,10 +521,10 @@ int mf_secparts_update(int sx, int sy, int sz, int cubic, int64_t np, int64_t ps
 	MF_TRY(kills_begin(&cnt, st));
 	const V3 g = {gx, gy, gz};
 	if (cubic)
-		hipLaunchKernelGGL(k_secparts_update<true>, dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, np, pstride, pos, pflag, v_sec, l_sec, f_sec,
+		hipLaunchKernelGGL(k_secparts_update<true>, dim3(nblk(np)), dim3(BLOCK), 0, st, d, np, pstride, pos, pflag, v_sec, l_sec, f_sec,
 		                   flags, vel, neighborRatio, radius, g, k_b, k_d, c_s, c_b, dt, exclude, antitunneling, itype, cnt);
 	else
-		hipLaunchKernelGGL(k_secparts_update<false>, dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, np, pstride, pos, pflag, v_sec, l_sec, f_sec,
+		hipLaunchKernelGGL(k_secparts_update<false>, dim3(nblk(np)), dim3(BLOCK), 0, st, d, np, pstride, pos, pflag, v_sec, l_sec, f_sec,
 		                   flags, vel, neighborRatio, radius, g, k_b, k_d, c_s, c_b, dt, exclude, antitunneling, itype, cnt);
 	return kills_end(cnt, kills_host, st);
 }
@@ -549,13 +540,13 @@ int mf_secparts_delete_in_obstacle(int sx, int sy, int sz, int64_t np, int64_t p
 	hipStream_t st = (hipStream_t)stream;
 	unsigned long long* cnt;
 	MF_TRY(kills_begin(&cnt, st));
-	hipLaunchKernelGGL(k_secparts_delete, dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, np, pstride, pos, pflag, flags, cnt);
+	hipLaunchKernelGGL(k_secparts_delete, dim3(nblk(np)), dim3(BLOCK), 0, st, d, np, pstride, pos, pflag, flags, cnt);
 	return kills_end(cnt, kills_host, st);
 }
 
 int mf_secparts_flags_from_levelset(int64_t n, int32_t* flags, const float* phi, int exclude, int itype, void* stream) {
 	if (n <= 0) return 0;
-	hipLaunchKernelGGL(k_flags_from_levelset, dim3(nblk_n(n)), dim3(BLOCK), 0, (hipStream_t)stream, n, flags, phi, exclude, itype);
+	hipLaunchKernelGGL(k_flags_from_levelset, dim3(nblk(n)), dim3(BLOCK), 0, (hipStream_t)stream, n, flags, phi, exclude, itype);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -564,7 +555,7 @@ int mf_secparts_mac_from_levelset(int sx, int sy, int sz, float* vel, const floa
 	MF_TRY(check_dim(sx, sy, sz));
 	if (g_slab_gsz > 0) return fail("mf_secparts_mac_from_levelset: not available inside a z-slab window");
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_mac_from_levelset, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, phi, cx, cy, cz);
+	hipLaunchKernelGGL(k_mac_from_levelset, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, vel, phi, cx, cy, cz);
 	MF_LAUNCH_CHECK();
 	return 0;
 }

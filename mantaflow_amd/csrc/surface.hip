@@ -7,10 +7,6 @@
 
 using namespace mf;
 
-static inline unsigned nblk_n(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK > 0 ? (n + BLOCK - 1) / BLOCK : 1); }
-__device__ __forceinline__ bool in_bounds(const Dim& d, int i, int j, int k) {
-	return i >= 0 && j >= 0 && k >= 0 && i < d.sx && j < d.sy && k < d.sz;
-}
 __device__ __forceinline__ int64_t cidx(const Dim& d, int i, int j, int k) { return (int64_t)i + d.Y * j + d.Z * k; }
 // Particle positions are GLOBAL grid coordinates; a z-slab window (mf_set_slab_window) holds planes [zoff, zoff + sz) of gsz.
 // cell_of: cell of a position, k as the plane inside the window; false when the cell is outside the domain or the window
@@ -24,14 +20,6 @@ __device__ __forceinline__ bool cell_of(const Dim& d, float x, float y, float z,
 }
 // domain-boundary test in global planes (a slab's outer ghost plane is not a domain wall)
 __device__ __forceinline__ bool z_wall(const Dim& d, int k, int w) { return d.is3d && (k + d.zoff <= w || k + d.zoff >= d.gsz - 1 - w); }
-#define CELL_IJK(d)                                                               \
-	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x;                \
-	if (idx >= (d).n) return;                                                     \
-	const int i = (int)(idx % (d).sx);                                            \
-	const int j = (int)((idx / (d).sx) % (d).sy);                                 \
-	const int k = (int)(idx / ((int64_t)(d).sx * (d).sy));                        \
-	(void)i; (void)j; (void)k;
-#define INTERIOR_B(d, b) (i >= (b) && i < (d).sx - (b) && j >= (b) && j < (d).sy - (b) && (!(d).is3d || (k >= (b) && k < (d).sz - (b))))
 
 // KnProjectOutOfBnd, particle.h:579-590 (std::max(pos, bnd) / std::min(pos, size - bnd))
 __global__ void __launch_bounds__(BLOCK)
@@ -126,24 +114,7 @@ k_gpi_keys(Dim d, int64_t np, int64_t ps, const float* __restrict__ pos, const i
 	keys[p] = key;
 	vals[p] = (int)p;
 }
-struct SortScratch {
-	void* tmp = nullptr;
-	size_t cap = 0;
-};
-static SortScratch g_sort[16];
-static int sort_scratch(size_t need, void** out) {
-	int dev = 0;
-	MF_HIP(hipGetDevice(&dev));
-	SortScratch& s = g_sort[dev];
-	if (need > s.cap) {
-		MF_HIP(hipDeviceSynchronize());
-		if (s.tmp) MF_HIP(hipFree(s.tmp));
-		MF_HIP(hipMalloc(&s.tmp, need));
-		s.cap = need;
-	}
-	*out = s.tmp;
-	return 0;
-}
+static Arena g_sort[16];   // gridParticleIndex's hipcub workspace, per device (arena_reserve)
 
 // ComputeUnionLevelsetPindex, plugin/flip.cpp:322-353 (+ setBound(0.5, 0) fused: the boundary test of knSetBoundary with w=0)
 __global__ void __launch_bounds__(BLOCK)
@@ -165,7 +136,7 @@ k_union_levelset(Dim d, int64_t ps, const float* __restrict__ pos, const int32_t
 	const int xlo = i - r < 0 ? 0 : i - r, xhi = i + r > d.sx - 1 ? d.sx - 1 : i + r;
 	for (int zj = k - rZ; zj <= k + rZ; zj++)
 		for (int yj = j - r; yj <= j + r; yj++) {
-				if (!in_bounds(d, xlo, yj, zj)) continue;
+				if (!in_grid(d, xlo, yj, zj)) continue;
 				const int64_t c0 = cidx(d, xlo, yj, zj), c1 = cidx(d, xhi, yj, zj);
 				const int64_t pStart = index[c0];
 				const int64_t pEnd = (c1 + 1 < d.n) ? (int64_t)index[c1 + 1] : n_indexed;
@@ -458,9 +429,9 @@ int mf_interpolate_grid(int tsx, int tsy, int tsz, float* target, int ssx, int s
 	if (orderSpace != 1 && orderSpace != 2) return fail("Unknown interpolation order %d", orderSpace);
 	const Dim t = mkdim(tsx, tsy, tsz), s = mkdim_src(ssx, ssy, ssz);   // each grid under its own slab window
 	if (orderSpace == 2)
-		hipLaunchKernelGGL((k_interpolate_grid<false, 2>), dim3(nblk_n(t.n)), dim3(BLOCK), 0, (hipStream_t)stream, t, target, s, source, ncomp, sfx, sfy, sfz, ox, oy, oz);
+		hipLaunchKernelGGL((k_interpolate_grid<false, 2>), dim3(nblk(t.n)), dim3(BLOCK), 0, (hipStream_t)stream, t, target, s, source, ncomp, sfx, sfy, sfz, ox, oy, oz);
 	else
-		hipLaunchKernelGGL((k_interpolate_grid<false, 1>), dim3(nblk_n(t.n)), dim3(BLOCK), 0, (hipStream_t)stream, t, target, s, source, ncomp, sfx, sfy, sfz, ox, oy, oz);
+		hipLaunchKernelGGL((k_interpolate_grid<false, 1>), dim3(nblk(t.n)), dim3(BLOCK), 0, (hipStream_t)stream, t, target, s, source, ncomp, sfx, sfy, sfz, ox, oy, oz);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -471,9 +442,9 @@ int mf_interpolate_mac_grid(int tsx, int tsy, int tsz, float* target, int ssx, i
 	if (orderSpace != 1 && orderSpace != 2) return fail("Unknown interpolation order %d", orderSpace);
 	const Dim t = mkdim(tsx, tsy, tsz), s = mkdim_src(ssx, ssy, ssz);   // each grid under its own slab window
 	if (orderSpace == 2)
-		hipLaunchKernelGGL((k_interpolate_grid<true, 2>), dim3(nblk_n(t.n)), dim3(BLOCK), 0, (hipStream_t)stream, t, target, s, source, 3, sfx, sfy, sfz, ox, oy, oz);
+		hipLaunchKernelGGL((k_interpolate_grid<true, 2>), dim3(nblk(t.n)), dim3(BLOCK), 0, (hipStream_t)stream, t, target, s, source, 3, sfx, sfy, sfz, ox, oy, oz);
 	else
-		hipLaunchKernelGGL((k_interpolate_grid<true, 1>), dim3(nblk_n(t.n)), dim3(BLOCK), 0, (hipStream_t)stream, t, target, s, source, 3, sfx, sfy, sfz, ox, oy, oz);
+		hipLaunchKernelGGL((k_interpolate_grid<true, 1>), dim3(nblk(t.n)), dim3(BLOCK), 0, (hipStream_t)stream, t, target, s, source, 3, sfx, sfy, sfz, ox, oy, oz);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -483,7 +454,7 @@ int mf_project_out_of_bnd(int sx, int sy, int sz, int64_t np, int64_t pstride, f
 	MF_TRY(check_dim(sx, sy, sz));
 	if (np <= 0) return 0;
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_project_out_of_bnd, dim3(nblk_n(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, np, pstride, pos, pflag, bnd, axis, ptype, exclude);
+	hipLaunchKernelGGL(k_project_out_of_bnd, dim3(nblk(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, np, pstride, pos, pflag, bnd, axis, ptype, exclude);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -493,7 +464,7 @@ int mf_push_out_of_obs(int sx, int sy, int sz, int64_t np, int64_t pstride, floa
 	MF_TRY(check_dim(sx, sy, sz));
 	if (np <= 0) return 0;
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_push_out_of_obs, dim3(nblk_n(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, np, pstride, pos, pflag, phiObs, shift, thresh, ptype, exclude);
+	hipLaunchKernelGGL(k_push_out_of_obs, dim3(nblk(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, np, pstride, pos, pflag, phiObs, shift, thresh, ptype, exclude);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -507,7 +478,7 @@ int mf_grid_particle_index(int sx, int sy, int sz, int64_t np, int64_t pstride, 
 	hipStream_t st = (hipStream_t)stream;
 	MF_HIP(hipMemsetAsync(counter, 0, sizeof(int32_t) * d.n, st));
 	if (np > 0) {
-		hipLaunchKernelGGL(k_gpi_keys, dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, np, pstride, pos, pflag, keys, vals, counter);
+		hipLaunchKernelGGL(k_gpi_keys, dim3(nblk(np)), dim3(BLOCK), 0, st, d, np, pstride, pos, pflag, keys, vals, counter);
 		MF_LAUNCH_CHECK();
 	}
 	// index = exclusive prefix sum of the per-cell counts
@@ -516,8 +487,9 @@ int mf_grid_particle_index(int sx, int sy, int sz, int64_t np, int64_t pstride, 
 	int end_bit = 1;
 	while (end_bit < 31 && (((int64_t)1 << end_bit) <= d.n)) end_bit++;
 	if (np > 0) MF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys, keys + np, vals, vals + np, (int)np, 0, end_bit, st));
-	void* tmp = nullptr;
-	MF_TRY(sort_scratch((scan_bytes > sort_bytes ? scan_bytes : sort_bytes) + 256, &tmp));
+	Arena* a;
+	MF_TRY(arena_reserve(g_sort, (scan_bytes > sort_bytes ? scan_bytes : sort_bytes) + 256, &a));
+	void* tmp = a->p;
 	MF_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, counter, index, (int)d.n, st));
 	if (np > 0) {
 		MF_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, keys, keys + np, vals, vals + np, (int)np, 0, end_bit, st));
@@ -543,7 +515,7 @@ int mf_union_particle_levelset(int sx, int sy, int sz, int64_t np, int64_t pstri
 	// calculateRadiusFactor (flip.cpp:198-200) in double, returned as Real; radius = 0.5 * that, rounded to Real
 	const float rf = (float)((d.is3d ? sqrt(3.) : sqrt(2.)) * ((double)radiusFactor + .01));
 	const float radius = (float)(0.5 * (double)rf);
-	hipLaunchKernelGGL(k_union_levelset, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, pstride, pos, indexSys, n_indexed, index, phi, radius, ptype, exclude);
+	hipLaunchKernelGGL(k_union_levelset, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, pstride, pos, indexSys, n_indexed, index, phi, radius, ptype, exclude);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -551,7 +523,7 @@ int mf_union_particle_levelset(int sx, int sy, int sz, int64_t np, int64_t pstri
 int mf_grid_set_bound(int sx, int sy, int sz, float* grid, float value, int boundaryWidth, void* stream) {
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_set_bound, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, grid, value, boundaryWidth);
+	hipLaunchKernelGGL(k_set_bound, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, grid, value, boundaryWidth);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -582,7 +554,7 @@ int mf_shape_apply_to_grid(int sx, int sy, int sz, int kind, const float* params
 	const Dim d = mkdim(sx, sy, sz);
 	ShapeParams P;
 	for (int q = 0; q < 12; q++) P.q[q] = params_host[q];
-	hipLaunchKernelGGL(k_shape_apply, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, kind, P, gridkind, (float*)grid, value_host[0], value_host[1],
+	hipLaunchKernelGGL(k_shape_apply, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, kind, P, gridkind, (float*)grid, value_host[0], value_host[1],
 	                   value_host[2], respectFlags);
 	MF_LAUNCH_CHECK();
 	return 0;
@@ -593,7 +565,7 @@ int mf_shape_levelset(int sx, int sy, int sz, int kind, const float* params_host
 	const Dim d = mkdim(sx, sy, sz);
 	ShapeParams P;
 	for (int q = 0; q < 12; q++) P.q[q] = params_host[q];
-	hipLaunchKernelGGL(k_shape_levelset, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, kind, P, phi);
+	hipLaunchKernelGGL(k_shape_levelset, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, kind, P, phi);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -603,8 +575,8 @@ int mf_reset_outflow(int sx, int sy, int sz, int32_t* flags, float* phi, float* 
 	const Dim d = mkdim(sx, sy, sz);
 	hipStream_t st = (hipStream_t)stream;
 	if (np > 0 && pos && pflag)
-		hipLaunchKernelGGL(k_reset_outflow_parts, dim3(nblk_n(np)), dim3(BLOCK), 0, st, d, flags, np, ps, pos, pflag);
-	hipLaunchKernelGGL(k_reset_outflow, dim3(nblk_n(d.n)), dim3(BLOCK), 0, st, d.n, flags, phi, real);
+		hipLaunchKernelGGL(k_reset_outflow_parts, dim3(nblk(np)), dim3(BLOCK), 0, st, d, flags, np, ps, pos, pflag);
+	hipLaunchKernelGGL(k_reset_outflow, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d.n, flags, phi, real);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -614,7 +586,7 @@ int mf_extrapolate_ls_simple(int sx, int sy, int sz, float* phi, int distance, i
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
 	hipStream_t st = (hipStream_t)stream;
-	const unsigned nb = nblk_n(d.n);
+	const unsigned nb = nblk(d.n);
 	const float direction = inside ? -1.f : 1.f;
 	hipLaunchKernelGGL(k_els_mark, dim3(nb), dim3(BLOCK), 0, st, d, phi, tmp, inside, (inside && include_walls) ? 0 : 1);
 	hipLaunchKernelGGL(k_els_first, dim3(nb), dim3(BLOCK), 0, st, d, tmp);
@@ -629,7 +601,7 @@ int mf_set_part_type(int sx, int sy, int sz, const int32_t* flags, int64_t np, i
 	MF_TRY(check_dim(sx, sy, sz));
 	if (np <= 0) return 0;
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_set_part_type, dim3(nblk_n(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, np, pstride, pos, ptype, mark, stype, cflag);
+	hipLaunchKernelGGL(k_set_part_type, dim3(nblk(np)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, np, pstride, pos, ptype, mark, stype, cflag);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -637,7 +609,7 @@ int mf_set_part_type(int sx, int sy, int sz, const int32_t* flags, int64_t np, i
 int mf_mark_isolated_fluid_cell(int sx, int sy, int sz, int32_t* flags, int mark, void* stream) {
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_mark_isolated, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, mark);
+	hipLaunchKernelGGL(k_mark_isolated, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, mark);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -646,7 +618,7 @@ int mf_add_force_pvel(int64_t np, int64_t pstride, float* pvel, float ax, float 
                       int exclude, void* stream) {
 	if (np <= 0) return 0;
 	const float dx = ax * dt, dy = ay * dt, dz = az * dt;
-	hipLaunchKernelGGL(k_add_force_pvel, dim3(nblk_n(np)), dim3(BLOCK), 0, (hipStream_t)stream, np, pstride, pvel, dx, dy, dz, ptype, exclude);
+	hipLaunchKernelGGL(k_add_force_pvel, dim3(nblk(np)), dim3(BLOCK), 0, (hipStream_t)stream, np, pstride, pvel, dx, dy, dz, ptype, exclude);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -655,7 +627,7 @@ int mf_update_velocity_from_delta_pos(int64_t np, int64_t pstride, const float* 
                                       const int32_t* ptype, int exclude, void* stream) {
 	if (np <= 0) return 0;
 	const float over_dt = (float)(1.0 / (double)dt);
-	hipLaunchKernelGGL(k_vel_from_delta_pos, dim3(nblk_n(np)), dim3(BLOCK), 0, (hipStream_t)stream, np, pstride, pos, pvel, xprev, over_dt, ptype, exclude);
+	hipLaunchKernelGGL(k_vel_from_delta_pos, dim3(nblk(np)), dim3(BLOCK), 0, (hipStream_t)stream, np, pstride, pos, pvel, xprev, over_dt, ptype, exclude);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -663,20 +635,20 @@ int mf_update_velocity_from_delta_pos(int64_t np, int64_t pstride, const float* 
 int mf_euler_step(int64_t np, int64_t pstride, float* pos, const float* pvel, float dt, const int32_t* ptype, int exclude,
                   void* stream) {
 	if (np <= 0) return 0;
-	hipLaunchKernelGGL(k_euler_step, dim3(nblk_n(np)), dim3(BLOCK), 0, (hipStream_t)stream, np, pstride, pos, pvel, dt, ptype, exclude);
+	hipLaunchKernelGGL(k_euler_step, dim3(nblk(np)), dim3(BLOCK), 0, (hipStream_t)stream, np, pstride, pos, pvel, dt, ptype, exclude);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
 
 int mf_levelset_join(int64_t n, float* phi, const float* other, void* stream) {
 	if (n <= 0) return 0;
-	hipLaunchKernelGGL(k_ls_join, dim3(nblk_n(n)), dim3(BLOCK), 0, (hipStream_t)stream, n, phi, other);
+	hipLaunchKernelGGL(k_ls_join, dim3(nblk(n)), dim3(BLOCK), 0, (hipStream_t)stream, n, phi, other);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
 int mf_levelset_subtract(int64_t n, float* phi, const float* other, const int32_t* flags, int subtractType, void* stream) {
 	if (n <= 0) return 0;
-	hipLaunchKernelGGL(k_ls_subtract, dim3(nblk_n(n)), dim3(BLOCK), 0, (hipStream_t)stream, n, phi, other, flags, subtractType);
+	hipLaunchKernelGGL(k_ls_subtract, dim3(nblk(n)), dim3(BLOCK), 0, (hipStream_t)stream, n, phi, other, flags, subtractType);
 	MF_LAUNCH_CHECK();
 	return 0;
 }

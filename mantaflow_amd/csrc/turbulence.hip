@@ -8,16 +8,6 @@ using namespace mf;
 
 namespace {
 
-inline unsigned nblk_n(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK > 0 ? (n + BLOCK - 1) / BLOCK : 1); }
-#define CELL_IJK(d)                                                               \
-	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x;                \
-	if (idx >= (d).n) return;                                                     \
-	const int i = (int)(idx % (d).sx);                                            \
-	const int j = (int)((idx / (d).sx) % (d).sy);                                 \
-	const int k = (int)(idx / ((int64_t)(d).sx * (d).sy));                        \
-	(void)i; (void)j; (void)k;
-#define INTERIOR(d) (i >= 1 && i < (d).sx - 1 && j >= 1 && j < (d).sy - 1 && (!(d).is3d || (k >= 1 && k < (d).sz - 1)))
-
 // `0.5 * x` with a double literal: exact halving, written as the reference writes it
 __device__ __forceinline__ float half_of(float x) { return (float)(0.5 * (double)x); }
 
@@ -308,7 +298,7 @@ extern "C" {
 int mf_compute_energy(int sx, int sy, int sz, const int32_t* flags, const float* vel, float* energy, void* stream) {
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
-	hipLaunchKernelGGL(k_compute_energy, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, energy);
+	hipLaunchKernelGGL(k_compute_energy, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, vel, energy);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -318,7 +308,7 @@ int mf_vorticity_confinement(int sx, int sy, int sz, float* vel, const int32_t* 
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
 	hipStream_t st = (hipStream_t)stream;
-	const unsigned nb = nblk_n(d.n);
+	const unsigned nb = nblk(d.n);
 	MF_HIP(hipMemsetAsync(velCenter, 0, sizeof(float) * 3 * d.n, st));
 	MF_HIP(hipMemsetAsync(curl, 0, sizeof(float) * 3 * d.n, st));
 	MF_HIP(hipMemsetAsync(force, 0, sizeof(float) * 3 * d.n, st));
@@ -341,8 +331,8 @@ int mf_compute_wavelet_coeffs(int sx, int sy, int sz, float* input, float* temp1
 	hipLaunchKernelGGL(k_wavelet_lines, dim3((unsigned)((lx + 63) / 64)), dim3(64), 0, st, d, 0, input, temp1, temp2);
 	hipLaunchKernelGGL(k_wavelet_lines, dim3((unsigned)((ly + 63) / 64)), dim3(64), 0, st, d, 1, temp2, temp1, temp2);
 	if (d.is3d) hipLaunchKernelGGL(k_wavelet_lines, dim3((unsigned)((lz + 63) / 64)), dim3(64), 0, st, d, 2, temp2, temp1, temp2);
-	hipLaunchKernelGGL(k_wavelet_residual, dim3(nblk_n(d.n)), dim3(BLOCK), 0, st, d.n, input, temp2, temp1);
-	hipLaunchKernelGGL(k_wavelet_smooth, dim3(nblk_n(d.n)), dim3(BLOCK), 0, st, d, input, temp1, d.is3d ? (float)(1. / 6.) : (float)(1. / 4.));
+	hipLaunchKernelGGL(k_wavelet_residual, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d.n, input, temp2, temp1);
+	hipLaunchKernelGGL(k_wavelet_smooth, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d, input, temp1, d.is3d ? (float)(1. / 6.) : (float)(1. / 4.));
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -383,7 +373,7 @@ int mf_apply_noise_vec3(int sx, int sy, int sz, const int32_t* flags, float* tar
 	P.clamp = params[15];
 	P.clampNeg = params[16];
 	P.clampPos = params[17];
-	hipLaunchKernelGGL(k_apply_noise_vec3, dim3(nblk_n(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, target, tile, P, scale, scaleSpatial, weight, wd, interp, sf[0], sf[1], sf[2], uv);
+	hipLaunchKernelGGL(k_apply_noise_vec3, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, target, tile, P, scale, scaleSpatial, weight, wd, interp, sf[0], sf[1], sf[2], uv);
 	MF_LAUNCH_CHECK();
 	return 0;
 }

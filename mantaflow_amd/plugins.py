@@ -29,7 +29,7 @@ import time
 import numpy as np
 import torch
 
-from . import core
+from . import _lib, core
 from .core import (FlagGrid, Grid, GridBase, LevelsetGrid, MACGrid, VecGrid, _ptr, _to_vec3, vec3)
 
 PcNone, PcMIC, PcMGDynamic, PcMGStatic = 0, 1, 2, 3
@@ -339,16 +339,22 @@ class _MgHandle(object):
 _mg_solvers = __import__("weakref").WeakSet()    # solvers that hold a hierarchy (gMapMG, pressure.cpp:248)
 
 
+def _extension_lib(s, name, ext):
+    """the solver's library, if plugin `name` of extension `ext` (a row of _lib.EXTENSIONS, by name) can run on it; refused before
+    any grid is touched: a z-slab solver first, then a backend without the extension (the CPU test backend has none)"""
+    ext = _lib.extension(ext)
+    if tuple(s._slab_window) != (0, 0):
+        raise RuntimeError("%s: %s %s not run on a z-slab solver" % (name, ext.what, ext.verb))
+    if not getattr(s.lib, ext.name):
+        raise RuntimeError(ext.not_implemented(name, s.lib.backend))
+    return s.lib
+
+
 def _multigrid_lib(s, name):
     """refuse, before any grid is touched, what the multigrid preconditioner does not run on"""
-    lib = s.lib
-    if not lib.multigrid:
-        raise RuntimeError("%s: the '%s' backend does not implement the multigrid preconditioners PcMGStatic / PcMGDynamic "
-                           "(manta_hip_multigrid.h)" % (name, lib.backend))
+    lib = _extension_lib(s, name, "multigrid")
     if not s.is3D():
         raise RuntimeError("%s: the multigrid preconditioners PcMGStatic / PcMGDynamic run on 3-D solvers only" % name)
-    if tuple(s._slab_window) != (0, 0):
-        raise RuntimeError("%s: the multigrid preconditioners PcMGStatic / PcMGDynamic do not run on a z-slab solver" % name)
     return lib
 
 
@@ -877,7 +883,7 @@ def setWallBcs(flags, vel, obvel=None, fractions=None, phiObs=None, boundaryWidt
     fractions, phiObs = _opt(fractions, MACGrid, "MACGrid"), _opt(phiObs, Grid, "Grid<Real>")
     if fractions is not None and phiObs is not None:
         # KnSetWallBcsFrac + vel.swap(tmpvel), extforces.cpp:240-335 (obvel and boundaryWidth unused there as well); in place
-        lib = _obstacles_lib(s, "setWallBcs")
+        lib = _extension_lib(s, "setWallBcs", "obstacles")
         scratch = _wall_frac_scratch(s)
         lib.call("mf_set_wall_bcs_frac", flags.sx, flags.sy, flags.sz, flags.ptr, vel.ptr, phiObs.ptr, _ptr(scratch), scratch.numel(),
                  s.stream)
@@ -888,17 +894,6 @@ def setWallBcs(flags, vel, obvel=None, fractions=None, phiObs=None, boundaryWidt
 # =========================================================================================================
 # fill-fraction obstacle boundaries (include/manta_hip_obstacles.h)
 # =========================================================================================================
-def _obstacles_lib(s, name):
-    """the solver's library, if it implements the obstacle extension (the CPU test backend does not)"""
-    lib = s.lib
-    if not lib.obstacles:
-        raise RuntimeError("%s: the '%s' backend does not implement the fill-fraction obstacle plugins (manta_hip_obstacles.h)"
-                           % (name, lib.backend))
-    if tuple(s._slab_window) != (0, 0):
-        raise RuntimeError("%s: the fill-fraction obstacle plugins do not run on a z-slab solver" % name)
-    return lib
-
-
 def _wall_frac_scratch(s):
     """per-solver scratch of mf_set_wall_bcs_frac (new face values + one bit per face), allocated once; never initialised"""
     sc = getattr(s, "_wall_frac_scratch", None)
@@ -915,7 +910,7 @@ def updateFractions(flags, phiObs, fractions, boundaryWidth=0, fracThreshold=0.0
     """initplugins.cpp:436-440: fractions.setConst(0) + KnUpdateFractions (the serial-sweep result)"""
     _chk(flags, FlagGrid, "FlagGrid"); _chk(phiObs, Grid, "Grid<Real>"); _chk(fractions, MACGrid, "MACGrid")
     s = flags.parent
-    lib = _obstacles_lib(s, "updateFractions")
+    lib = _extension_lib(s, "updateFractions", "obstacles")
     lib.call("mf_update_fractions", flags.sx, flags.sy, flags.sz, flags.ptr, phiObs.ptr, fractions.ptr, int(boundaryWidth),
              float(np.float32(fracThreshold)), s.stream)
 
@@ -927,7 +922,7 @@ def setObstacleFlags(flags, phiObs, fractions=None, phiOut=None, phiIn=None, bou
     fractions = _opt(fractions, MACGrid, "MACGrid")
     phiOut, phiIn = _opt(phiOut, Grid, "Grid<Real>"), _opt(phiIn, Grid, "Grid<Real>")
     s = flags.parent
-    lib = _obstacles_lib(s, "setObstacleFlags")
+    lib = _extension_lib(s, "setObstacleFlags", "obstacles")
     lib.call("mf_set_obstacle_flags", flags.sx, flags.sy, flags.sz, flags.ptr, phiObs.ptr, None if fractions is None else fractions.ptr,
              None if phiOut is None else phiOut.ptr, None if phiIn is None else phiIn.ptr, int(boundaryWidth), s.stream)
 
@@ -941,7 +936,7 @@ def setInflowBcs(vel, dir, value):
     _chk(vel, MACGrid, "MACGrid")
     v = _to_vec3(value)
     s = vel.parent
-    lib = _obstacles_lib(s, "setInflowBcs")
+    lib = _extension_lib(s, "setInflowBcs", "obstacles")
     sides, bad = 0, False
     for ch in str(dir):
         if ch not in _INFLOW_SIDES:
@@ -959,7 +954,7 @@ def addNoise(flags, density, noise, sdf=None, scale=1.0):
     _chk(flags, FlagGrid, "FlagGrid"); _chk(density, Grid, "Grid<Real>")
     sdf = _opt(sdf, Grid, "Grid<Real>")
     s = flags.parent
-    lib = _obstacles_lib(s, "addNoise")
+    lib = _extension_lib(s, "addNoise", "obstacles")
     lib.call("mf_add_noise", flags.sx, flags.sy, flags.sz, flags.ptr, density.ptr, None if sdf is None else sdf.ptr, _ptr(noise._tile),
              noise._params(), float(_f32(scale)), s.stream)
 
@@ -967,16 +962,6 @@ def addNoise(flags, density, noise, sdf=None, scale=1.0):
 # =========================================================================================================
 # particle resampling for narrow-band FLIP (include/manta_hip_resample.h)
 # =========================================================================================================
-def _resample_lib(s, name):
-    """the solver's library, if it implements the resampling extension (the CPU test backend does not)"""
-    lib = s.lib
-    if tuple(s._slab_window) != (0, 0):
-        raise RuntimeError("%s: particle resampling does not run on a z-slab solver" % name)
-    if not lib.resample:
-        raise RuntimeError("%s: the '%s' backend does not implement particle resampling (manta_hip_resample.h)" % (name, lib.backend))
-    return lib
-
-
 _seed_reals = {}     # device -> the first reals of RandomStream(9832), which every adjustNumber call restarts
 
 
@@ -1010,7 +995,7 @@ def adjustNumber(parts, vel, flags, minParticles, maxParticles, phi, radiusFacto
     _chk(phi, LevelsetGrid, "LevelsetGrid")
     exclude = _opt(exclude, Grid, "Grid<Real>")
     s = vel.parent
-    lib = _resample_lib(s, "adjustNumber")
+    lib = _extension_lib(s, "adjustNumber", "resample")
     minParticles, maxParticles = _coerce(minParticles, 0), _coerce(maxParticles, 0)
     nb = float(np.float32(narrowBand))
     sls = -calculateRadiusFactor(phi, radiusFactor)
@@ -1066,7 +1051,7 @@ def combineGridVel(vel, weight, combineVel, phi=None, narrowBand=0.0, thresh=0.0
     _chk(vel, MACGrid, "MACGrid"); _chk(weight, VecGrid, "Grid<Vec3>"); _chk(combineVel, MACGrid, "MACGrid")
     phi = _opt(phi, LevelsetGrid, "LevelsetGrid")
     s = vel.parent
-    lib = _resample_lib(s, "combineGridVel")
+    lib = _extension_lib(s, "combineGridVel", "resample")
     lib.call("mf_combine_grid_vel", vel.sx, vel.sy, vel.sz, vel.ptr, weight.ptr, combineVel.ptr, None if phi is None else phi.ptr,
              float(np.float32(narrowBand)), float(np.float32(thresh)), s.stream)
 
@@ -1074,16 +1059,6 @@ def combineGridVel(vel, weight, combineVel, phi=None, narrowBand=0.0, thresh=0.0
 # =========================================================================================================
 # implicit density projection: the position solve of IDP-FLIP / IDP-APIC (include/manta_hip_idp.h)
 # =========================================================================================================
-def _idp_lib(s, name):
-    """the solver's library, if it implements the density-projection extension (the CPU test backend does not)"""
-    lib = s.lib
-    if tuple(s._slab_window) != (0, 0):
-        raise RuntimeError("%s: implicit density projection does not run on a z-slab solver" % name)
-    if not lib.idp:
-        raise RuntimeError("%s: the '%s' backend does not implement implicit density projection (manta_hip_idp.h)" % (name, lib.backend))
-    return lib
-
-
 @plugin
 def copyFlagsToFlags(source, target):
     """implicitdensityprojection.cpp:336-341: target = source, cell by cell (every backend)"""
@@ -1114,7 +1089,7 @@ def markFluidAndBoundaryCells(particles, flags, deltaX, phiObs, ptype=None, excl
     _chk(deltaX, MACGrid, "MACGrid"); _chk(phiObs, Grid, "Grid<Real>")
     ptype = _opt(ptype, core.PdataInt, "ParticleDataImpl<int>")
     s = flags.parent
-    lib = _idp_lib(s, "markFluidAndBoundaryCells")
+    lib = _extension_lib(s, "markFluidAndBoundaryCells", "idp")
     inside, pushing = _mark_fluid_and_boundary(lib, s, particles, flags, deltaX, phiObs, ptype, exclude)
     markFluidAndBoundaryCellsStats.clear()
     markFluidAndBoundaryCellsStats.update(boundary_particles=inside, pushing=pushing)
@@ -1138,7 +1113,7 @@ def mapMassToGrid(flags, density, parts, source, deltaX, phiObs, dt, particleMas
     _chk(flags, FlagGrid, "FlagGrid"); _chk(density, Grid, "Grid<Real>"); _chk(parts, core.BasicParticleSystem, "BasicParticleSystem")
     _chk(source, core.PdataReal, "ParticleDataImpl<Real>"); _chk(deltaX, MACGrid, "MACGrid"); _chk(phiObs, Grid, "Grid<Real>")
     s = flags.parent
-    lib = _idp_lib(s, "mapMassToGrid")
+    lib = _extension_lib(s, "mapMassToGrid", "idp")
     inside, pushing = _mark_fluid_and_boundary(lib, s, parts, flags, deltaX, phiObs, None, 0)
     (np_, cap, pos, pfl), _ = _pargs(parts, None)
     dims = (flags.sx, flags.sy, flags.sz)
@@ -1161,7 +1136,7 @@ def computeDeltaX(deltaX, Lambda, flags):
     reads before the row; here that neighbour counts as an obstacle."""
     _chk(deltaX, MACGrid, "MACGrid"); _chk(Lambda, Grid, "Grid<Real>"); _chk(flags, FlagGrid, "FlagGrid")
     s = flags.parent
-    lib = _idp_lib(s, "computeDeltaX")
+    lib = _extension_lib(s, "computeDeltaX", "idp")
     lib.call("mf_idp_compute_delta_x", flags.sx, flags.sy, flags.sz, flags.ptr, deltaX.ptr, Lambda.ptr, s.stream)
 
 
@@ -1173,7 +1148,7 @@ def mapMACToPartPositions(flags, deltaX, parts, dt, ptype=None, exclude=0, mapQu
     _chk(flags, FlagGrid, "FlagGrid"); _chk(deltaX, MACGrid, "MACGrid"); _chk(parts, core.BasicParticleSystem, "BasicParticleSystem")
     ptype = _opt(ptype, core.PdataInt, "ParticleDataImpl<int>")
     s = flags.parent
-    lib = _idp_lib(s, "mapMACToPartPositions")
+    lib = _extension_lib(s, "mapMACToPartPositions", "idp")
     (np_, cap, pos, pfl), pt = _pargs(parts, ptype)
     lib.call("mf_idp_map_mac_to_positions", flags.sx, flags.sy, flags.sz, deltaX.ptr, np_, cap, pos, pfl, pt, int(exclude),
              float(np.float32(dt)), s.stream)
@@ -1182,22 +1157,12 @@ def mapMACToPartPositions(flags, deltaX, parts, dt, ptype=None, exclude=0, mapQu
 # =========================================================================================================
 # averaged and improved particle level sets (include/manta_hip_partls.h)
 # =========================================================================================================
-def _partls_lib(s, name):
-    """the solver's library, if it implements the particle level-set extension (the CPU test backend does not)"""
-    lib = s.lib
-    if tuple(s._slab_window) != (0, 0):
-        raise RuntimeError("%s: the smooth particle level sets do not run on a z-slab solver" % name)
-    if not lib.partls:
-        raise RuntimeError("%s: the '%s' backend does not implement the smooth particle level sets (manta_hip_partls.h)" % (name, lib.backend))
-    return lib
-
-
 def _particle_levelset(name, improved, parts, indexSys, flags, index, phi, radiusFactor, smoothen, smoothenNeg, t_low, t_high, ptype, exclude):
     _chk(parts, core.BasicParticleSystem, "BasicParticleSystem"); _chk(indexSys, core.ParticleIndexSystem, "ParticleIndexSystem")
     _chk(flags, FlagGrid, "FlagGrid"); _chk(index, core.IntGrid, "Grid<int>"); _chk(phi, LevelsetGrid, "LevelsetGrid")
     ptype = _opt(ptype, core.PdataInt, "ParticleDataImpl<int>")
     s = flags.parent
-    lib = _partls_lib(s, name)
+    lib = _extension_lib(s, name, "partls")
     if ptype is not None and ptype.cap != parts.cap:
         raise RuntimeError("%s: the ptype channel does not follow the capacity of its particle system" % name)
     # Grid<Vec3> save_pAcc, Grid<Real> save_rAcc, LevelsetGrid tmp: from the solver's pool, every cell is written before it is read
@@ -1234,16 +1199,6 @@ def improvedParticleLevelset(parts, indexSys, flags, index, phi, radiusFactor=1.
 # =========================================================================================================
 # secondary particles: spray, foam, bubbles (include/manta_hip_secparts.h)
 # =========================================================================================================
-def _secparts_lib(s, name):
-    """the solver's library, if it implements the secondary-particle extension (the CPU test backend does not)"""
-    lib = s.lib
-    if tuple(s._slab_window) != (0, 0):
-        raise RuntimeError("%s: the secondary particles do not run on a z-slab solver" % name)
-    if not lib.secparts:
-        raise RuntimeError("%s: the '%s' backend does not implement the secondary particles (manta_hip_secparts.h)" % (name, lib.backend))
-    return lib
-
-
 class _SecondaryStream(object):
     """the `static RandomStream mRand(9832)` of one sampling kernel (secondaryparticles.cpp:118, 175): one per process and mode,
     never restarted by a call; `cursor` counts the reals drawn so far"""
@@ -1300,7 +1255,7 @@ def flipComputeSecondaryParticlePotentials(potTA, potWC, potKE, neighborRatio, f
         _chk(g, Grid, "Grid<Real>")
     _chk(flags, FlagGrid, "FlagGrid"); _chk(v, MACGrid, "MACGrid"); _chk(normal, VecGrid, "Grid<Vec3>"); _chk(phi, Grid, "Grid<Real>")
     s = flags.parent
-    lib = _secparts_lib(s, "flipComputeSecondaryParticlePotentials")
+    lib = _extension_lib(s, "flipComputeSecondaryParticlePotentials", "secparts")
     radius = _coerce(radius, 0)
     if radius < 1:
         raise RuntimeError("flipComputeSecondaryParticlePotentials: radius %d < 1" % radius)
@@ -1340,7 +1295,7 @@ def flipSampleSecondaryParticles(mode, flags, v, pts_sec, v_sec, l_sec, lMin, lM
     for g in (potTA, potWC, potKE, neighborRatio):
         _chk(g, Grid, "Grid<Real>")
     s = flags.parent
-    lib = _secparts_lib(s, "flipSampleSecondaryParticles")
+    lib = _extension_lib(s, "flipSampleSecondaryParticles", "secparts")
     _follows(pts_sec, "flipSampleSecondaryParticles", v_sec=v_sec, l_sec=l_sec)
     multiple = int(mode == "multiple")
     f = lambda x: float(np.float32(x))
@@ -1391,7 +1346,7 @@ def flipUpdateSecondaryParticles(mode, pts_sec, v_sec, l_sec, f_sec, flags, v, n
     _chk(l_sec, core.PdataReal, "ParticleDataImpl<Real>"); _chk(f_sec, core.PdataVec3, "ParticleDataImpl<Vec3>")
     _chk(flags, FlagGrid, "FlagGrid"); _chk(v, MACGrid, "MACGrid"); _chk(neighborRatio, Grid, "Grid<Real>")
     s = flags.parent
-    lib = _secparts_lib(s, "flipUpdateSecondaryParticles")
+    lib = _extension_lib(s, "flipUpdateSecondaryParticles", "secparts")
     _follows(pts_sec, "flipUpdateSecondaryParticles", v_sec=v_sec, l_sec=l_sec, f_sec=f_sec)
     radius = _coerce(radius, 0)
     f = lambda x: float(np.float32(x))
@@ -1412,7 +1367,7 @@ def flipDeleteParticlesInObstacle(pts, flags):
     doCompress().  Bit-identical; one scalar (the kill count) is read back."""
     _chk(pts, core.BasicParticleSystem, "BasicParticleSystem"); _chk(flags, FlagGrid, "FlagGrid")
     s = flags.parent
-    lib = _secparts_lib(s, "flipDeleteParticlesInObstacle")
+    lib = _extension_lib(s, "flipDeleteParticlesInObstacle", "secparts")
     kills = ctypes.c_int64(0)
     lib.call("mf_secparts_delete_in_obstacle", flags.sx, flags.sy, flags.sz, pts.np, pts.cap, _ptr(pts.pos), _ptr(pts.flag), flags.ptr,
              ctypes.byref(kills), s.stream)
@@ -1425,7 +1380,7 @@ def setFlagsFromLevelset(flags, phi, exclude=_FLAG_OBSTACLE, itype=_FLAG_FLUID):
     """secondaryparticles.cpp:512-522: a cell with phi < 0 and no `exclude` bit becomes itype (the whole flag word)"""
     _chk(flags, FlagGrid, "FlagGrid"); _chk(phi, Grid, "Grid<Real>")
     s = flags.parent
-    lib = _secparts_lib(s, "setFlagsFromLevelset")
+    lib = _extension_lib(s, "setFlagsFromLevelset", "secparts")
     lib.call("mf_secparts_flags_from_levelset", flags.n, flags.ptr, phi.ptr, int(exclude), int(itype), s.stream)
 
 
@@ -1435,7 +1390,7 @@ def setMACFromLevelset(v, phi, c):
     _chk(v, MACGrid, "MACGrid"); _chk(phi, Grid, "Grid<Real>")
     c = _to_vec3(c)
     s = v.parent
-    lib = _secparts_lib(s, "setMACFromLevelset")
+    lib = _extension_lib(s, "setMACFromLevelset", "secparts")
     lib.call("mf_secparts_mac_from_levelset", v.sx, v.sy, v.sz, v.ptr, phi.ptr, float(np.float32(c.x)), float(np.float32(c.y)),
              float(np.float32(c.z)), s.stream)
 
@@ -1476,16 +1431,6 @@ _blur_precomp = {"radius": -1, "weights": None, "dev": {}}    # gBlurPrecomputed
 _last_guiding = {}
 
 
-def _guiding_lib(s, name):
-    """the solver's library, if it implements the guiding extension (the CPU test backend does not)"""
-    lib = s.lib
-    if tuple(s._slab_window) != (0, 0):
-        raise RuntimeError("%s: fluid guiding does not run on a z-slab solver" % name)
-    if not lib.guiding:
-        raise RuntimeError("%s: the '%s' backend does not implement fluid guiding (manta_hip_guiding.h)" % (name, lib.backend))
-    return lib
-
-
 def _blur_weights(lib, s, blurRadius):
     """ADMM_precompute_Separable, :217-226: one blur kernel for the whole process; the weights come from the library's host code
     and are uploaded once per device"""
@@ -1520,7 +1465,7 @@ def PD_fluid_guiding(vel, velT, pressure, flags, weight, blurRadius=5, theta=1.0
     s = vel.parent
     if _blur_precomp["radius"] >= 0 and _blur_precomp["radius"] != blurRadius:
         raise RuntimeError("More than a single blur radius not supported at the moment.")
-    lib = _guiding_lib(s, "PD_fluid_guiding")
+    lib = _extension_lib(s, "PD_fluid_guiding", "guiding")
     if preconditioner in (PcMGDynamic, PcMGStatic):
         _multigrid_lib(s, "PD_fluid_guiding")               # the inner solve would refuse, but only after the set-up
     for g in (velT, pressure, flags, weight):

@@ -46,7 +46,7 @@ def test_header_declares_the_extension():
         restype, argtypes, argnames = protos[name]
         assert restype is ctypes.c_int and argnames[-1] == "stream" and argtypes[-1] is ctypes.c_void_p, name
     assert protos["mf_guiding_weights"][2] == ["radius", "w_host"]
-    for other in (_lib.HEADER, _lib.OBSTACLES_HEADER, _lib.MULTIGRID_HEADER, _lib.RESAMPLE_HEADER, _lib.IDP_HEADER, _lib.PARTLS_HEADER):
+    for other in [_lib.HEADER] + [e.header for e in _lib.EXTENSIONS if e.name != "guiding"]:
         assert not set(protos) & set(_lib.parse_header(other))
     assert "guiding" not in open(_lib.HEADER).read()          # the frozen header stays as it is
 

@@ -39,7 +39,7 @@ def test_header_declares_the_extension():
     for n in ("mf_idp_abi_version", "mf_idp_mark", "mf_idp_map_weights", "mf_idp_compute_density", "mf_idp_compute_delta_x",
               "mf_idp_map_mac_to_positions"):
         assert n in protos, n
-    for other in (_lib.HEADER, _lib.OBSTACLES_HEADER, _lib.MULTIGRID_HEADER, _lib.RESAMPLE_HEADER):
+    for other in [_lib.HEADER] + [e.header for e in _lib.EXTENSIONS if e.name != "idp"]:
         assert not set(protos) & set(_lib.parse_header(other))
 
 

@@ -33,8 +33,8 @@ def test_header_declares_the_extension():
               "mf_resample_round", "mf_particles_compress_plan", "mf_particles_compress_move", "mf_resample_seed_plan",
               "mf_resample_seed_insert", "mf_pdata_init_new"):
         assert n in protos, n
-    assert not set(protos) & set(_lib.parse_header())
-    assert not set(protos) & set(_lib.parse_header(_lib.OBSTACLES_HEADER)) and not set(protos) & set(_lib.parse_header(_lib.MULTIGRID_HEADER))
+    for other in [_lib.HEADER] + [e.header for e in _lib.EXTENSIONS if e.name != "resample"]:
+        assert not set(protos) & set(_lib.parse_header(other))
 
 
 def test_delete_bookkeeping_of_the_particle_system(oracle_backend):
