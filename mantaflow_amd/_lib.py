@@ -7,7 +7,8 @@ restatement, host pointers) -- nothing in this package ever loads anything from 
 
 Prototypes are parsed from the header itself, so the binding cannot drift from ``include/manta_hip.h``.
 
-An *extension* is one row of ``EXTENSIONS`` below: an optional header ``include/manta_hip_<name>.h`` that is parsed the same way.
+An *extension* is one row of ``EXTENSIONS`` or ``MORE_EXTENSIONS`` below: an optional header ``include/manta_hip_<name>.h`` (first
+table) or ``include/ext/manta_hip_<name>.h`` (second table) that is parsed the same way.
 Its entries are bound when the loaded library exports them (``Library.<name>`` is then True, and ``mf_<name>_abi_version()`` must
 equal the header's ``MF_<NAME>_ABI_VERSION``); a library without them still loads, and the plugins of that extension refuse it.
 """
@@ -22,11 +23,12 @@ DEFAULT_LIB = os.path.join(_HERE, "csrc", "libmanta_hip.so")
 
 class Extension(object):
     """One optional extension of the ABI.  ``name`` is the attribute on Library / SolverLib and fixes the header, the version
-    function and the version macro; ``what`` is the phrase the refusals use and ``verb`` the "does" / "do" it takes."""
+    function and the version macro; ``what`` is the phrase the refusals use and ``verb`` the "does" / "do" it takes; ``subdir`` is
+    the directory under include/ that holds the header (none: include/ itself)."""
 
-    def __init__(self, name, what, verb):
+    def __init__(self, name, what, verb, subdir=""):
         self.name, self.what, self.verb = name, what, verb
-        self.header = os.path.join(os.path.dirname(_HERE), "include", "manta_hip_%s.h" % name)
+        self.header = os.path.join(os.path.dirname(_HERE), "include", subdir, "manta_hip_%s.h" % name)
         self.version_fn = "mf_%s_abi_version" % name
         self.version_macro = "MF_%s_ABI_VERSION" % name.upper()
 
@@ -44,13 +46,19 @@ EXTENSIONS = (
     Extension("guiding", "fluid guiding", "does"),
     Extension("secparts", "the secondary particles", "do"),
 )
-for _ext in EXTENSIONS:    # OBSTACLES_HEADER ... SECPARTS_HEADER
+MORE_EXTENSIONS = (
+    Extension("turbulence", "the turbulence model", "does", "ext"),
+)
+"""The second table.  EXTENSIONS above is frozen: tests/test_extensions_api.py pins its seven names and the set of headers
+include/manta_hip_*.h, so it cannot grow.  Every later extension is a row here, with its header under include/ext/; the two tables
+are treated alike everywhere (binding, SolverLib, build()'s symbol check, the *_HEADER names, plugins._extension_lib)."""
+for _ext in EXTENSIONS + MORE_EXTENSIONS:    # OBSTACLES_HEADER ... SECPARTS_HEADER, TURBULENCE_HEADER
     globals()[_ext.name.upper() + "_HEADER"] = _ext.header
 
 
 def extension(name):
-    """the row of EXTENSIONS with that attribute name"""
-    return next(e for e in EXTENSIONS if e.name == name)
+    """the row of EXTENSIONS or MORE_EXTENSIONS with that attribute name"""
+    return next(e for e in EXTENSIONS + MORE_EXTENSIONS if e.name == name)
 
 
 _CTYPES = {
@@ -116,7 +124,7 @@ class Library:
         if got != want:
             raise RuntimeError("mantaflow_amd: %s implements ABI revision %d, include/manta_hip.h declares %d -- rebuild the library"
                                % (path, got, want))
-        for ext in EXTENSIONS:
+        for ext in EXTENSIONS + MORE_EXTENSIONS:
             setattr(self, ext.name, self._bind_extension(path, ext.header, ext.version_fn, ext.version_macro))
         # the z-slab window is thread-local state of the shared object (which stays loaded across Library instances): start
         # from "the grid is the whole domain"; solvers carry their own window and set it per call (core.SolverLib)

@@ -3,7 +3,8 @@
 import sys
 
 from .core import (BasicParticleSystem, FlagGrid, FluidSolver, Grid, IntGrid, LevelsetGrid, MACGrid, Mesh, ParticleIndexSystem,
-                   PdataInt, PdataReal, PdataVec3, RealGrid, Solver, Vec3Grid, VecGrid, vec3, vec4)
+                   PdataInt, PdataReal, PdataVec3, RealGrid, Solver, TurbulenceParticleSystem, Vec3Grid, VecGrid, resetTurbulenceParticleState,
+                   vec3, vec4)
 from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, resetOutflow, apicMapPartsToMAC, apicMapMACGridToParts, extrapolateMACFromWeight, extrapolateMACSimple, markFluidCells, addBuoyancy, addGravity, addGravityNoScale, advectSemiLagrange, computePressureRhs,
                       correctVelocity, flipVelocityUpdate, lastCgStats, mapGridToParts, mapGridToPartsVec3, mapMACToParts,
                       mapPartsToGrid, mapPartsToGridVec3, mapPartsToMAC, setDeterministicP2G, setWallBcs, solvePressure,
@@ -17,9 +18,11 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       averagedParticleLevelset, improvedParticleLevelset,
                       flipComputeSecondaryParticlePotentials, flipSampleSecondaryParticles, flipUpdateSecondaryParticles,
                       flipDeleteParticlesInObstacle, setFlagsFromLevelset, setMACFromLevelset, resetSecondaryParticleStreams,
+                      KEpsilonComputeProduction, KEpsilonSources, KEpsilonBcs, KEpsilonGradientDiffusion, computeStrainRateMag,
+                      computeVorticity, getCurl,
                       PD_fluid_guiding, releaseBlurPrecomp, lastGuidingStats, getSpiralVelocity, setGradientYWeight)
 
-from .scene import (Box, Cylinder, Gui, NoiseField, Shape, Sphere, densityInflow, sampleFlagsWithParticles,
+from .scene import (Box, Checkbox, Cylinder, Gui, NoiseField, Shape, Slider, Sphere, densityInflow, sampleFlagsWithParticles,
                     sampleLevelsetWithParticles, sampleShapeWithParticles)
 
 # module constants, registry.cpp:390-421

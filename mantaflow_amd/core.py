@@ -159,7 +159,7 @@ class SolverLib(object):
     def __init__(self, lib, solver):
         self._lib, self._solver = lib, solver
         self.backend, self.device, self.cdll, self.path = lib.backend, lib.device, lib.cdll, lib.path
-        for ext in _lib.EXTENSIONS:
+        for ext in _lib.EXTENSIONS + _lib.MORE_EXTENSIONS:
             setattr(self, ext.name, getattr(lib, ext.name))
 
     def call(self, name, *args):
@@ -953,3 +953,208 @@ class BasicParticleSystem(PbClass):
                    _ptr(self.pos), _ptr(self.flag), s.getDt(), int(integrationMode), int(bool(deleteInObstacle)),
                    int(bool(stopInObstacle)), int(bool(skipNew)), None if ptype is None else ptype.ptr, int(exclude),
                    _ptr(scratch), s.stream)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# turbulence particles, turbulencepart.{h,cpp} (include/ext/manta_hip_turbulence.h)
+# ---------------------------------------------------------------------------------------------------------
+class _TurbulenceState(object):
+    """what the reference keeps in function statics, one per process: seed()'s `static RandomStream rand(34894231)` (cursor: the
+    reals drawn so far) and synthesize()'s `static Real ctime` and `static Vec3 inflow`.  Reals are drawn in blocks and handed out
+    one attempt at a time, so the cursor counts exactly three per attempt."""
+
+    SEED = 34894231
+
+    def __init__(self):
+        self.seek(0)
+        self.ctime = np.float32(0)
+        self.inflow = np.zeros(3, np.float32)
+
+    def seek(self, cursor):
+        from .scene import RandomStream
+        self.rs, self.cursor, self.ahead = RandomStream(self.SEED), 0, np.zeros(0, np.float32)
+        while self.cursor < cursor:         # MT19937 has no cheap jump: draw and drop
+            self.take(min(cursor - self.cursor, 1 << 20))
+
+    def take(self, n):
+        if self.ahead.size < n:
+            self.ahead = np.concatenate([self.ahead, self.rs.reals(max(n - self.ahead.size, 3072))])
+        r, self.ahead = self.ahead[:n], self.ahead[n:]
+        self.cursor += n
+        return r
+
+
+_turbulence_state = _TurbulenceState()
+
+
+def resetTurbulenceParticleState():
+    """restart seed()'s random stream and synthesize()'s clock and inflow offset, as a fresh process of the reference has them (no
+    reference counterpart)"""
+    global _turbulence_state
+    _turbulence_state = _TurbulenceState()
+
+
+def _set_turbulence_particle_state(cursor, ctime, inflow):
+    """test hook: the process-wide state as it is after `cursor` reals, with this clock and inflow offset"""
+    _turbulence_state.seek(int(cursor))
+    _turbulence_state.ctime = np.float32(ctime)
+    _turbulence_state.inflow = np.asarray(inflow, np.float32).reshape(3).copy()
+
+
+def _hsv2rgb(h, s, v):
+    """turbulencepart.cpp:35-55 in fp32; `int i = (int)(h * 6)` truncates, so h = 1 gives i = 6 and `i % 6` case 0"""
+    f32 = np.float32
+    h, s, v = h.astype(f32), f32(s), f32(v)
+    h6 = h * f32(6)
+    i = h6.astype(np.int32)                    # truncation toward zero, like the C cast
+    f = h6 - i.astype(f32)
+    one = f32(1)
+    p = np.full(h.shape, v * (one - s), f32)
+    q = v * (one - f * s)
+    t = v * (one - (one - f) * s)
+    vv = np.full(h.shape, v, f32)
+    sel = np.fmod(i, 6)                        # C's %: the sign of the dividend; a negative case matches none and leaves (0, 0, 0)
+    table = [(vv, t, p), (q, vv, p), (p, vv, t), (p, q, vv), (t, p, vv), (vv, p, q)]
+    rgb = np.zeros(h.shape + (3,), f32)
+    for case, cols in enumerate(table):
+        m = sel == case
+        for c in range(3):
+            rgb[m, c] = cols[c][m]
+    return rgb
+
+
+class TurbulenceParticleSystem(BasicParticleSystem):
+    """TurbulenceParticleSystem, turbulencepart.h:25-48: particles with a colour and two texture coordinates that the wavelet noise
+    moves.  Storage is BasicParticleSystem's (SoA pos, flag) with three internal Vec3 channels color, tex0, tex1, so advectInGrid and
+    compress() apply as they are: compress() fills deleted slots from the tail and every channel moves along.  seed(),
+    resetTexCoords() on an empty system and the process-wide state run on every backend; synthesize() and deleteInObstacle() need
+    the turbulence extension and a whole-domain solver."""
+    _cname_py, _cname_cpp, _T = "TurbulenceParticleSystem", "TurbulenceParticleSystem", ""
+
+    def __init__(self, parent, noise=None, name="", **kw):
+        from .scene import NoiseField
+        if not isinstance(noise, NoiseField):
+            raise RuntimeError("can't convert argument to WaveletNoiseField*")
+        BasicParticleSystem.__init__(self, parent, name)
+        self.noise = noise
+        self.mAllowCompress = True      # ParticleSystem's default; BasicParticleSystem's constructor is the one that clears it
+        self.color, self.tex0, self.tex1 = (self.create(PdataVec3) for _ in range(3))
+
+    def _extension_lib(self, who):
+        """plugins._extension_lib for a method: z-slab first, then a backend without the extension"""
+        from . import plugins
+        return plugins._extension_lib(self.parent, "TurbulenceParticleSystem::" + who, "turbulence")
+
+    def _append(self, pos, color):
+        n0, m = self.np, pos.shape[0]
+        self.reserve(n0 + m)
+        self.resizeAll(n0 + m, self.cap)
+        dev = self.pos.device
+        for c in range(3):
+            col = torch.from_numpy(np.ascontiguousarray(pos[:, c])).to(dev)
+            for t, cap in ((self.pos, self.cap), (self.tex0.data, self.tex0.cap), (self.tex1.data, self.tex1.cap)):
+                t[c * cap + n0:c * cap + n0 + m] = col
+            self.color.data[c * self.color.cap + n0:c * self.color.cap + n0 + m] = torch.from_numpy(np.ascontiguousarray(color[:, c])).to(dev)
+        self.flag[n0:n0 + m] = 0
+        for pd in self.pdata:               # addEntry(): every other channel gets a zero entry
+            if pd not in (self.color, self.tex0, self.tex1):
+                for c in range(pd._ncomp):
+                    pd.data[c * pd.cap + n0:c * pd.cap + n0 + m] = 0
+        self.mDeleteChunk = self.np // 20   # ParticleSystem::add, particle.h:414-420
+
+    def seed(self, shape, num):
+        """turbulencepart.cpp:57-68 (host): rejection sampling in the shape's bounding box with the process-wide stream, three reals
+        per attempt, x then y then z; colour from the height inside the box"""
+        f32 = np.float32
+        if not (hasattr(shape, "getExtent") and hasattr(shape, "getCenter") and hasattr(shape, "_inside")):
+            raise RuntimeError("can't convert argument to Shape*")
+        num = int(num)
+        ext, cen = shape.getExtent(), shape.getCenter()
+        sz = np.array([ext.x, ext.y, ext.z], f32)
+        p0 = np.array([cen.x, cen.y, cen.z], f32) - sz * f32(0.5)
+        st = _turbulence_state
+        out = np.zeros((num, 3), f32)
+        got = 0
+        while got < num:
+            want = num - got
+            m = max(want + want // 2, 16)
+            r = st.take(3 * m).reshape(m, 3)
+            p = r * sz + p0
+            ok = np.nonzero(shape._inside(p[:, 0], p[:, 1], p[:, 2]))[0]
+            if ok.size >= want:             # the attempt that yields the last particle ends the call: hand the rest back
+                used = int(ok[want - 1]) + 1
+                st.ahead = np.concatenate([r[used:].reshape(-1), st.ahead])
+                st.cursor -= 3 * (m - used)
+                ok = ok[:want]
+            out[got:got + ok.size] = p[ok]
+            got += ok.size
+        if num <= 0:
+            return
+        with np.errstate(all="ignore"):
+            z = (out[:, 2] - p0[2]) / sz[2]
+        self._append(out, _hsv2rgb(z, 0.75, 1.0))
+
+    def resetTexCoords(self, num, inflow):
+        """turbulencepart.cpp:70-76: tex0 (num == 0) or tex1 = pos - inflow"""
+        v = _to_vec3(inflow)
+        if self.np == 0:
+            return
+        lib = self._extension_lib("resetTexCoords")
+        tex = self.tex0 if int(num) == 0 else self.tex1
+        lib.call("mf_turbulence_reset_tex", self.np, self.cap, _ptr(self.pos), tex.ptr, float(np.float32(v.x)), float(np.float32(v.y)),
+                 float(np.float32(v.z)), self.parent.stream)
+
+    def synthesize(self, flags, k, octaves=2, switchLength=10.0, L0=0.1, scale=1.0, inflowBias=0.0):
+        """turbulencepart.cpp:112-131: the host half (process-wide clock and inflow offset, the texture resets) and one kernel with a
+        thread per slot"""
+        f32 = np.float32
+        if not isinstance(flags, FlagGrid):
+            raise RuntimeError("can't convert argument to FlagGrid*")
+        if not isinstance(k, Grid):
+            raise RuntimeError("can't convert argument to Grid<Real>*")
+        s = self.parent
+        lib = self._extension_lib("synthesize")
+        st = _turbulence_state
+        bias = _to_vec3(inflowBias)
+        dt, sl = f32(s.getDt()), f32(switchLength)
+        st.inflow = st.inflow + np.array([bias.x, bias.y, bias.z], f32) * dt
+        old_alpha = f32(2.0) * _nmod1(st.ctime / sl)
+        st.ctime = f32(st.ctime + dt)
+        alpha = f32(2.0) * _nmod1(st.ctime / sl)
+        if old_alpha < f32(1.0) and alpha >= f32(1.0):
+            self.resetTexCoords(0, vec3(*st.inflow))
+        if old_alpha > alpha:
+            self.resetTexCoords(1, vec3(*st.inflow))
+        alpha = f32(1.0)                    # `alpha = 1.0;` overrides the hat function, as written
+        if self.np == 0:
+            return
+        kmin = f32(1.5 * (0.1 * 0.1))       # 1.5*square(0.1): doubles, rounded into the Real parameter
+        lib.call("mf_turbulence_synthesize", k.sx, k.sy, k.sz, k.ptr, _ptr(self.noise._tile), self.noise._params(), self.np, self.cap,
+                 _ptr(self.pos), self.tex0.ptr, self.tex1.ptr, float(alpha), float(dt), int(octaves), float(f32(scale)),
+                 float(f32(1.0) / f32(L0)), float(kmin), s.stream)
+
+    def deleteInObstacle(self, flags):
+        """turbulencepart.cpp:133-138: mark every slot inside an obstacle cell, then compress() -- always, not the chunked
+        doCompress().  Every position must lie inside the grid (the reference reads the flag grid unchecked)."""
+        if not isinstance(flags, FlagGrid):
+            raise RuntimeError("can't convert argument to FlagGrid*")
+        s = self.parent
+        lib = self._extension_lib("deleteInObstacle")
+        lib.call("mf_turbulence_mark_in_obstacle", flags.sx, flags.sy, flags.sz, flags.ptr, self.np, self.cap, _ptr(self.pos), _ptr(self.flag),
+                 s.stream)
+        self.compress()
+
+    def projectOutside(self, gradient):
+        raise RuntimeError("TurbulenceParticleSystem::projectOutside: not implemented (it needs obstacleGradient, i.e. reinitMarching, and "
+                           "draws from another process-wide random stream)")
+
+    def channels_to_numpy(self):
+        """{pos, color, tex0, tex1, flag} of the live slots"""
+        return dict(pos=self.get_positions(), color=self.color.to_numpy(), tex0=self.tex0.to_numpy(), tex1=self.tex1.to_numpy(),
+                    flag=self.get_flags())
+
+
+def _nmod1(a):
+    """nmod(a, Real(1.0)), general.h:145: fmod (exact) and one conditional add"""
+    c = np.fmod(np.float32(a), np.float32(1.0))
+    return np.float32(c + np.float32(1.0)) if c < 0 else np.float32(c)

@@ -2,6 +2,7 @@
 // computeEnergy, vorticityConfinement, computeWaveletCoeffs, applyNoiseVec3.
 // Reference: source/plugin/waveletturbulence.cpp, plugin/extforces.cpp:24-43, 409-428, commonkernels.h, noisefield.{h,cpp}.
 #include "common.h"
+#include "wavelet_noise_vec.h"
 #include <math.h>
 
 using namespace mf;
@@ -175,82 +176,7 @@ __global__ void __launch_bounds__(BLOCK) k_wavelet_smooth(Dim d, float* __restri
 	input[idx] = res * smoothing;
 }
 
-// ---- applyNoiseVec3 ----
-struct NoiseParams {
-	float gsInv[3], seedOff[3], time, posScale[3], posOffset[3], valOffset, valScale, clamp, clampNeg, clampPos;
-};
-// WNoiseVec, noisefield.h:210-310
-__device__ void wnoise_vec(float p0, float p1, float p2, const float* __restrict__ data, float out[3]) {
-	const float p[3] = {p0, p1, p2};
-	int mid[3];
-	float t[3], w[3][3], dw[3][3], nb[3][3][3];
-#pragma unroll
-	for (int c = 0; c < 3; c++) {
-		mid[c] = (int)ceil((double)(p[c] - 0.5f));
-		t[c] = (float)mid[c] - (p[c] - 0.5f);
-	}
-#pragma unroll
-	for (int z = -1; z <= 1; z++)
-#pragma unroll
-		for (int y = -1; y <= 1; y++)
-#pragma unroll
-			for (int x = -1; x <= 1; x++) {
-				const int xC = (mid[0] + x) & 127, yC = (mid[1] + y) & 127, zC = (mid[2] + z) & 127;
-				nb[x + 1][y + 1][z + 1] = data[zC * 128 * 128 + yC * 128 + xC];
-			}
-#pragma unroll
-	for (int c = 0; c < 3; c++) {
-		dw[c][0] = -t[c];
-		dw[c][2] = (1.f - t[c]);
-		dw[c][1] = 2.0f * t[c] - 1.0f;
-		w[c][0] = t[c] * t[c] * 0.5f;
-		w[c][2] = (1.f - t[c]) * (1.f - t[c]) * 0.5f;
-		w[c][1] = 1.f - w[c][0] - w[c][2];
-	}
-#pragma unroll
-	for (int comp = 0; comp < 3; comp++) {
-		float result = 0.0f;
-#pragma unroll
-		for (int z = -1; z <= 1; z++)
-#pragma unroll
-			for (int y = -1; y <= 1; y++)
-#pragma unroll
-				for (int x = -1; x <= 1; x++) {
-					const float a = (comp == 0) ? dw[0][x + 1] : w[0][x + 1];
-					const float b = (comp == 1) ? dw[1][y + 1] : w[1][y + 1];
-					const float c = (comp == 2) ? dw[2][z + 1] : w[2][z + 1];
-					const float weight = a * b * c;
-					result += weight * nb[x + 1][y + 1][z + 1];
-				}
-		out[comp] = result;
-	}
-}
-// WaveletNoiseField::evaluateVec, noisefield.h:338-364
-__device__ void noise_evaluate_vec(const NoiseParams& P, const float* __restrict__ tile, float x, float y, float z, int t, float v[3]) {
-	float pos[3] = {x, y, z};
-#pragma unroll
-	for (int c = 0; c < 3; c++) pos[c] *= P.gsInv[c];
-#pragma unroll
-	for (int c = 0; c < 3; c++) pos[c] += P.seedOff[c];
-#pragma unroll
-	for (int c = 0; c < 3; c++) pos[c] += P.time;
-#pragma unroll
-	for (int c = 0; c < 3; c++) pos[c] *= P.posScale[c];
-#pragma unroll
-	for (int c = 0; c < 3; c++) pos[c] += P.posOffset[c];
-	wnoise_vec(pos[0], pos[1], pos[2], tile + (int64_t)t * 128 * 128 * 128, v);
-#pragma unroll
-	for (int c = 0; c < 3; c++) v[c] += P.valOffset;
-#pragma unroll
-	for (int c = 0; c < 3; c++) v[c] *= P.valScale;
-	if (P.clamp != 0.f) {
-#pragma unroll
-		for (int c = 0; c < 3; c++) {
-			if (v[c] < P.clampNeg) v[c] = P.clampNeg;
-			if (v[c] > P.clampPos) v[c] = P.clampPos;
-		}
-	}
-}
+// ---- applyNoiseVec3 ---- (NoiseParams, wnoise_vec, noise_evaluate_vec: wavelet_noise_vec.h)
 // (Measured, not kept: one fused evaluation of the six derivatives the curl needs, each tile's pair accumulated as a float2 with
 // v_pk_mul_f32 / v_pk_add_f32 and the index / weight set-up shared -- bit-exact, 1026 instead of 1187 VALU instructions in the kernel,
 // and 4.88 instead of 3.93 ms per 512^3 call: the packed fp32 operations bought no issue slots here and the three long accumulation
@@ -360,19 +286,7 @@ int mf_apply_noise_vec3(int sx, int sy, int sz, const int32_t* flags, float* tar
 		sf[1] = (float)wsy / sy;
 		sf[2] = (float)wd.gsz / d.gsz;
 	}
-	NoiseParams P;
-	for (int c = 0; c < 3; c++) {
-		P.gsInv[c] = params[c];
-		P.seedOff[c] = params[3 + c];
-		P.posScale[c] = params[7 + c];
-		P.posOffset[c] = params[10 + c];
-	}
-	P.time = params[6];
-	P.valOffset = params[13];
-	P.valScale = params[14];
-	P.clamp = params[15];
-	P.clampNeg = params[16];
-	P.clampPos = params[17];
+	const NoiseParams P = noise_params_vec(params);
 	hipLaunchKernelGGL(k_apply_noise_vec3, dim3(nblk(d.n)), dim3(BLOCK), 0, (hipStream_t)stream, d, flags, target, tile, P, scale, scaleSpatial, weight, wd, interp, sf[0], sf[1], sf[2], uv);
 	MF_LAUNCH_CHECK();
 	return 0;

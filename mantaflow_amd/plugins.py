@@ -21,6 +21,9 @@ PYTHON() declarations; orchestration mirrors the reference function by function,
   flipComputeSecondaryParticlePotentials / flipSampleSecondaryParticles / flipUpdateSecondaryParticles /
   flipDeleteParticlesInObstacle / setFlagsFromLevelset / setMACFromLevelset   source/plugin/secondaryparticles.cpp
                                              (include/manta_hip_secparts.h; not on z-slab solvers)
+  KEpsilonComputeProduction / KEpsilonSources / KEpsilonBcs / KEpsilonGradientDiffusion   source/plugin/kepsilon.cpp
+  computeStrainRateMag / computeVorticity / getCurl   source/plugin/waveletturbulence.cpp:204-236, 310-316
+                                             (include/ext/manta_hip_turbulence.h; not on z-slab solvers)
 """
 import ctypes
 import functools
@@ -1556,3 +1559,97 @@ def setGradientYWeight(W, minY, maxY, valAtMin, valAtMax):
                 val = _f32(float(ratio * vmax) + (1.0 - float(ratio)) * float(vmin))   # Real product + double product
         a[:, j, :] = val
     W.from_numpy(a)
+
+
+# =========================================================================================================
+# the k-epsilon turbulence model, source/plugin/kepsilon.cpp, and the diagnostics of plugin/waveletturbulence.cpp that share its
+# stencil (include/ext/manta_hip_turbulence.h; whole-domain solvers only).  Bit-identical; DESIGN.md section 14.
+# =========================================================================================================
+@plugin
+def KEpsilonComputeProduction(vel, k, eps, prod, nuT, strain=None, pscale=1.0):
+    """kepsilon.cpp:86-99 in one kernel: KnTurbulenceClamp on every cell (k and eps rewritten), prod / nuT / strain on the interior
+    from the clamped values with the centred velocity formed on the fly.  The reference reads the planes k +- 1 unconditionally, so
+    a 2-D solver is refused (first: that refusal holds on every backend)."""
+    _chk(vel, MACGrid, "MACGrid")
+    for g in (k, eps, prod, nuT):
+        _chk(g, Grid, "Grid<Real>")
+    strain = _opt(strain, Grid, "Grid<Real>")
+    s = k.parent
+    if not s.is3D():
+        raise RuntimeError("KEpsilonComputeProduction: 3-D solvers only")
+    lib = _extension_lib(s, "KEpsilonComputeProduction", "turbulence")
+    lib.call("mf_turbulence_production", k.sx, k.sy, k.sz, vel.ptr, k.ptr, eps.ptr, prod.ptr, nuT.ptr, None if strain is None else strain.ptr,
+             float(pscale), s.stream)
+
+
+@plugin
+def KEpsilonSources(k, eps, prod):
+    """kepsilon.cpp:102-126: the source terms over one solver step, both pre-clamps and KnTurbulenceClamp, one kernel"""
+    for g in (k, eps, prod):
+        _chk(g, Grid, "Grid<Real>")
+    s = k.parent
+    lib = _extension_lib(s, "KEpsilonSources", "turbulence")
+    lib.call("mf_turbulence_sources", k.n, k.ptr, eps.ptr, prod.ptr, s.getDt(), s.stream)
+
+
+@plugin
+def KEpsilonBcs(flags, k, eps, intensity, nu, fillArea):
+    """kepsilon.cpp:129-140: k = 1.5 intensity^2 and eps = Cmu k^2 / nu in every cell (fillArea) or in the obstacle cells"""
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(k, Grid, "Grid<Real>"); _chk(eps, Grid, "Grid<Real>")
+    if not isinstance(fillArea, bool):
+        raise RuntimeError("argument is not a boolean")
+    s = k.parent
+    lib = _extension_lib(s, "KEpsilonBcs", "turbulence")
+    lib.call("mf_turbulence_bcs", k.n, flags.ptr, k.ptr, eps.ptr, float(intensity), float(nu), int(fillArea), s.stream)
+
+
+@plugin
+def KEpsilonGradientDiffusion(k, eps, nuT, sigmaU=4.0, vel=None):
+    """kepsilon.cpp:143-179: f += LaplaceOp(f) * nuT * (dt / sigma) for k (sigma 1), eps (sigma 1.3) and, where given, the three
+    components of vel (sigmaU): three launches.  The stencil reads neighbours of the field it updates, so each launch writes a
+    scratch grid of the solver's pool and the two grids swap their storage."""
+    for g in (k, eps, nuT):
+        _chk(g, Grid, "Grid<Real>")
+    vel = _opt(vel, MACGrid, "MACGrid")
+    s = k.parent
+    lib = _extension_lib(s, "KEpsilonGradientDiffusion", "turbulence")
+    dt = _f32(s.getDt())
+    coef = (ctypes.c_float * 5)(*[float(dt / _f32(sg)) for sg in (1.0, 1.3, sigmaU, sigmaU, sigmaU)])   # Real dt / Real sigma
+    tmp = _scratch_grid(s)
+    for npass, f in enumerate((k, eps)):
+        lib.call("mf_turbulence_grad_diff", f.sx, f.sy, f.sz, 1, f.ptr, tmp.ptr, nuT.ptr, npass, coef, s.stream)
+        f.swap(tmp)
+    if vel is not None:
+        tmp3 = _scratch_grid(s, VecGrid)
+        lib.call("mf_turbulence_grad_diff", vel.sx, vel.sy, vel.sz, 3, vel.ptr, tmp3.ptr, nuT.ptr, 2, coef, s.stream)
+        vel.swap(tmp3)
+
+
+@plugin
+def computeStrainRateMag(vel, mag):
+    """waveletturbulence.cpp:212-236: mag = S^2 on the interior; the centred velocity of a border cell is 0"""
+    _chk(vel, MACGrid, "MACGrid"); _chk(mag, Grid, "Grid<Real>")
+    s = vel.parent
+    lib = _extension_lib(s, "computeStrainRateMag", "turbulence")
+    lib.call("mf_turbulence_strain_mag", vel.sx, vel.sy, vel.sz, vel.ptr, mag.ptr, s.stream)
+
+
+@plugin
+def computeVorticity(vel, vorticity, norm=None):
+    """waveletturbulence.cpp:204-209: the curl of the centred velocity on the interior (the border of `vorticity` keeps its values)
+    and, where given, its norm in every cell"""
+    _chk(vel, MACGrid, "MACGrid"); _chk(vorticity, VecGrid, "Grid<Vec3>")
+    norm = _opt(norm, Grid, "Grid<Real>")
+    s = vel.parent
+    lib = _extension_lib(s, "computeVorticity", "turbulence")
+    lib.call("mf_turbulence_vorticity", vel.sx, vel.sy, vel.sz, vel.ptr, vorticity.ptr, None if norm is None else norm.ptr, s.stream)
+
+
+@plugin
+def getCurl(vel, vort, comp):
+    """waveletturbulence.cpp:310-316: one component of the curl of the centred velocity, 0 in the border cells"""
+    _chk(vel, MACGrid, "MACGrid"); _chk(vort, Grid, "Grid<Real>")
+    comp = _coerce(comp, 0)
+    s = vel.parent
+    lib = _extension_lib(s, "getCurl", "turbulence")
+    lib.call("mf_turbulence_curl_component", vel.sx, vel.sy, vel.sz, vel.ptr, vort.ptr, comp, s.stream)
