@@ -7,8 +7,9 @@ restatement, host pointers) -- nothing in this package ever loads anything from 
 
 Prototypes are parsed from the header itself, so the binding cannot drift from ``include/manta_hip.h``.
 
-An *extension* is one row of ``EXTENSIONS`` or ``MORE_EXTENSIONS`` below: an optional header ``include/manta_hip_<name>.h`` (first
-table) or ``include/ext/manta_hip_<name>.h`` (second table) that is parsed the same way.
+An *extension* is one row of ``EXTENSIONS``, ``MORE_EXTENSIONS`` or ``OPEN_EXTENSIONS`` below: an optional header
+``include/manta_hip_<name>.h`` (first table), ``include/ext/manta_hip_<name>.h`` (second table) or ``include/open/manta_hip_<name>.h``
+(third table) that is parsed the same way.
 Its entries are bound when the loaded library exports them (``Library.<name>`` is then True, and ``mf_<name>_abi_version()`` must
 equal the header's ``MF_<NAME>_ABI_VERSION``); a library without them still loads, and the plugins of that extension refuse it.
 """
@@ -52,13 +53,27 @@ MORE_EXTENSIONS = (
 """The second table.  EXTENSIONS above is frozen: tests/test_extensions_api.py pins its seven names and the set of headers
 include/manta_hip_*.h, so it cannot grow.  Every later extension is a row here, with its header under include/ext/; the two tables
 are treated alike everywhere (binding, SolverLib, build()'s symbol check, the *_HEADER names, plugins._extension_lib)."""
-for _ext in EXTENSIONS + MORE_EXTENSIONS:    # OBSTACLES_HEADER ... SECPARTS_HEADER, TURBULENCE_HEADER
+OPEN_EXTENSIONS = (
+    Extension("fields", "the fire, wave-equation and uv-grid plugins", "do", "open"),
+)
+"""The third table, and the last one.  MORE_EXTENSIONS is frozen as well: tests/test_turbulence_api.py pins its one name and the set of
+headers include/ext/manta_hip_*.h.  This table is open: the next extension appends a row here, puts its header under include/open/
+and brings its own test file.  No test may pin the tuple of names or its length -- a test may only ask that the headers under
+include/open/ are exactly the rows' headers and that its own row is found -- so nothing has to move again."""
+
+
+def all_extensions():
+    """the three tables, in order: every place that walks the extensions walks this"""
+    return EXTENSIONS + MORE_EXTENSIONS + OPEN_EXTENSIONS
+
+
+for _ext in all_extensions():    # OBSTACLES_HEADER ... SECPARTS_HEADER, TURBULENCE_HEADER, FIELDS_HEADER
     globals()[_ext.name.upper() + "_HEADER"] = _ext.header
 
 
 def extension(name):
-    """the row of EXTENSIONS or MORE_EXTENSIONS with that attribute name"""
-    return next(e for e in EXTENSIONS + MORE_EXTENSIONS if e.name == name)
+    """the row of the three tables with that attribute name"""
+    return next(e for e in all_extensions() if e.name == name)
 
 
 _CTYPES = {
@@ -124,7 +139,7 @@ class Library:
         if got != want:
             raise RuntimeError("mantaflow_amd: %s implements ABI revision %d, include/manta_hip.h declares %d -- rebuild the library"
                                % (path, got, want))
-        for ext in EXTENSIONS + MORE_EXTENSIONS:
+        for ext in all_extensions():
             setattr(self, ext.name, self._bind_extension(path, ext.header, ext.version_fn, ext.version_macro))
         # the z-slab window is thread-local state of the shared object (which stays loaded across Library instances): start
         # from "the grid is the whole domain"; solvers carry their own window and set it per call (core.SolverLib)

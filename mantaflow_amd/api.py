@@ -20,6 +20,8 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       flipDeleteParticlesInObstacle, setFlagsFromLevelset, setMACFromLevelset, resetSecondaryParticleStreams,
                       KEpsilonComputeProduction, KEpsilonSources, KEpsilonBcs, KEpsilonGradientDiffusion, computeStrainRateMag,
                       computeVorticity, getCurl,
+                      processBurn, updateFlame, calcSecDeriv2d, totalSum, normalizeSumTo, cgSolveWE, resetUvGrid, updateUvWeight,
+                      getUvWeight, extrapolateSimpleFlags, initVortexVelocity,
                       PD_fluid_guiding, releaseBlurPrecomp, lastGuidingStats, getSpiralVelocity, setGradientYWeight)
 
 from .scene import (Box, Checkbox, Cylinder, Gui, NoiseField, Shape, Slider, Sphere, densityInflow, sampleFlagsWithParticles,

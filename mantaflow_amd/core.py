@@ -159,7 +159,7 @@ class SolverLib(object):
     def __init__(self, lib, solver):
         self._lib, self._solver = lib, solver
         self.backend, self.device, self.cdll, self.path = lib.backend, lib.device, lib.cdll, lib.path
-        for ext in _lib.EXTENSIONS + _lib.MORE_EXTENSIONS:
+        for ext in _lib.all_extensions():
             setattr(self, ext.name, getattr(lib, ext.name))
 
     def call(self, name, *args):

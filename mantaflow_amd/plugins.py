@@ -24,6 +24,12 @@ PYTHON() declarations; orchestration mirrors the reference function by function,
   KEpsilonComputeProduction / KEpsilonSources / KEpsilonBcs / KEpsilonGradientDiffusion   source/plugin/kepsilon.cpp
   computeStrainRateMag / computeVorticity / getCurl   source/plugin/waveletturbulence.cpp:204-236, 310-316
                                              (include/ext/manta_hip_turbulence.h; not on z-slab solvers)
+  processBurn / updateFlame                   source/plugin/fire.cpp
+  calcSecDeriv2d / totalSum / normalizeSumTo / cgSolveWE   source/plugin/waves.cpp
+  resetUvGrid / updateUvWeight / getUvWeight  source/grid.cpp:573-627
+  extrapolateSimpleFlags                      source/plugin/waveletturbulence.cpp:239-307
+  initVortexVelocity                          source/plugin/initplugins.cpp:478-503
+                                             (include/open/manta_hip_fields.h; not on z-slab solvers)
 """
 import ctypes
 import functools
@@ -1653,3 +1659,212 @@ def getCurl(vel, vort, comp):
     s = vel.parent
     lib = _extension_lib(s, "getCurl", "turbulence")
     lib.call("mf_turbulence_curl_component", vel.sx, vel.sy, vel.sz, vel.ptr, vort.ptr, comp, s.stream)
+
+
+# =========================================================================================================
+# fire (source/plugin/fire.cpp), the wave equation (source/plugin/waves.cpp), uv grids (source/grid.cpp:573-627) and
+# extrapolateSimpleFlags (source/plugin/waveletturbulence.cpp:239-307): include/open/manta_hip_fields.h, whole-domain solvers only;
+# initVortexVelocity (source/plugin/initplugins.cpp:478-503) is host code of the same extension.  DESIGN.md section 15.
+# =========================================================================================================
+@plugin
+def processBurn(fuel, density, react, red=None, green=None, blue=None, heat=None, burningRate=0.75, flameSmoke=1.0, ignitionTemp=1.25,
+                maxTemp=1.75, flameSmokeColor=vec3(0.7, 0.7, 0.7)):
+    """fire.cpp:22-75, one kernel on the interior: fuel burns down by burningRate * dt, react follows it, the burnt fuel emits smoke
+    into density (which is NOT clamped: the reference drops clamp()'s result), heat takes the flame temperature profile and the
+    colours mix; red / green / blue / heat are each optional"""
+    for g in (fuel, density, react):
+        _chk(g, Grid, "Grid<Real>")
+    red, green, blue, heat = (_opt(g, Grid, "Grid<Real>") for g in (red, green, blue, heat))
+    c = _to_vec3(flameSmokeColor)
+    s = fuel.parent
+    lib = _extension_lib(s, "processBurn", "fields")
+    p = lambda g: None if g is None else g.ptr
+    lib.call("mf_fields_process_burn", fuel.sx, fuel.sy, fuel.sz, fuel.ptr, density.ptr, react.ptr, p(red), p(green), p(blue), p(heat),
+             float(burningRate), float(flameSmoke), float(ignitionTemp), float(maxTemp), s.getDt(), float(c.x), float(c.y), float(c.z), s.stream)
+
+
+@plugin
+def updateFlame(react, flame):
+    """fire.cpp:78-90: flame = sqrt(react) where react > 0, else 0, on the interior"""
+    _chk(react, Grid, "Grid<Real>"); _chk(flame, Grid, "Grid<Real>")
+    s = react.parent
+    lib = _extension_lib(s, "updateFlame", "fields")
+    lib.call("mf_fields_update_flame", react.sx, react.sy, react.sz, react.ptr, flame.ptr, s.stream)
+
+
+@plugin
+def calcSecDeriv2d(v, curv):
+    """waves.cpp:32-41: the 2-D five-point second derivative on the interior (of every plane of a 3-D grid)"""
+    _chk(v, Grid, "Grid<Real>"); _chk(curv, Grid, "Grid<Real>")
+    s = v.parent
+    lib = _extension_lib(s, "calcSecDeriv2d", "fields")
+    lib.call("mf_fields_sec_deriv_2d", v.sx, v.sy, v.sz, v.ptr, curv.ptr, s.stream)
+
+
+@plugin
+def totalSum(height):
+    """waves.cpp:46-53: the fp64 sum of the interior, returned as a Real (one scalar read-back)"""
+    _chk(height, Grid, "Grid<Real>")
+    s = height.parent
+    lib = _extension_lib(s, "totalSum", "fields")
+    out = ctypes.c_float(0.0)
+    lib.call("mf_fields_total_sum", height.sx, height.sy, height.sz, height.ptr, ctypes.byref(out), s.stream)
+    return float(out.value)
+
+
+@plugin
+def normalizeSumTo(height, target):
+    """waves.cpp:56-60: height *= Real(target / sum of the interior) in every cell; the factor is formed on the device, nothing is
+    read back"""
+    _chk(height, Grid, "Grid<Real>")
+    s = height.parent
+    lib = _extension_lib(s, "normalizeSumTo", "fields")
+    lib.call("mf_fields_normalize_sum", height.sx, height.sy, height.sz, height.ptr, float(target), s.stream)
+
+
+@plugin
+def cgSolveWE(flags, ut, utm1, out, crankNic=False, cSqr=0.25, cgMaxIterFac=1.5, cgAccuracy=1e-5):
+    """waves.cpp:87-147: one implicit step of the wave equation, (I + s L) out = 2 ut - utm1 (+ s L ut with crankNic),
+    s = dt^2 cSqr / 2, by the unpreconditioned GridCg<ApplyMatrix/2D> with the L2 norm; then utm1 <-> ut and ut = out.
+    lastCgStats() reports the solve."""
+    _chk(flags, FlagGrid, "FlagGrid")
+    for g in (ut, utm1, out):
+        _chk(g, Grid, "Grid<Real>")
+    s = flags.parent
+    lib = _extension_lib(s, "cgSolveWE", "fields")
+    st = s.stream
+    sx, sy, sz = flags.dims
+    residual, search, tmp = (Grid(s) for _ in range(3))
+    rhs = _scratch_grid(s)                      # written in every cell by the set-up kernel
+    A0, Ai, Aj, Ak = (Grid(s) for _ in range(4))
+    out.clear()
+    lib.call("mf_make_laplace_matrix", sx, sy, sz, flags.ptr, A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr, None, st)
+    dt = _f32(s.getDt())
+    sc = _f32(float(dt * dt * _f32(cSqr)) * 0.5)            # Real s = dt*dt*cSqr * 0.5: an fp32 product, halved in double
+    lib.call("mf_fields_wave_system", sx, sy, sz, A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr, rhs.ptr, ut.ptr, utm1.ptr, float(sc), int(crankNic), st)
+    maxIter = int(_f32(cgMaxIterFac) * _f32(max(sx, sy, sz))) * (1 if flags.is3D() else 4)
+    res = (ctypes.c_float * 3)()
+    none = Grid(s)
+    lib.call("mf_cg_solve", sx, sy, sz, flags.ptr, out.ptr, rhs.ptr, residual.ptr, search.ptr, tmp.ptr, A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr,
+             none.ptr, PcNone, float(cgAccuracy), int(maxIter), 1, res, st)     # GridCgInterface() : mUseL2Norm(true), conjugategrad.h:31
+    _last_cg["iterations"], _last_cg["residual"] = int(res[0]), float(res[1])
+    utm1.swap(ut)
+    ut.copyFrom(out)
+
+
+def _uv_offset(offset):
+    if offset is None or (isinstance(offset, int) and not isinstance(offset, bool) and offset == 0):
+        return (0.0, 0.0, 0.0)                  # (Real)i + 0 is (Real)i: NULL and a zero offset write the same words
+    v = _to_vec3(offset)
+    return tuple(float(_f32(c)) for c in (v.x, v.y, v.z))
+
+
+@plugin
+def resetUvGrid(target, offset=None):
+    """grid.cpp:591-600: every cell takes its own coordinates (plus offset)"""
+    _chk(target, VecGrid, "Grid<Vec3>")
+    off = _uv_offset(offset)
+    s = target.parent
+    lib = _extension_lib(s, "resetUvGrid", "fields")
+    lib.call("mf_fields_reset_uv", target.sx, target.sy, target.sz, target.ptr, off[0], off[1], off[2], s.stream)
+
+
+@plugin
+def getUvWeight(uv):
+    """grid.cpp:576: the x component of cell 0 (one 4-byte read-back)"""
+    _chk(uv, VecGrid, "Grid<Vec3>")
+    s = uv.parent
+    lib = _extension_lib(s, "getUvWeight", "fields")
+    out = ctypes.c_float(0.0)
+    lib.call("mf_fields_get_uv_weight", uv.ptr, ctypes.byref(out), s.stream)
+    return float(out.value)
+
+
+def _uv_grid_time(t, resetTime):
+    """computeUvGridTime, grid.cpp:581-583: fmod(t / resetTime, 1) in fp32 (fmodf is exact)"""
+    with np.errstate(all="ignore"):
+        return _f32(np.fmod(_f32(t) / _f32(resetTime), _f32(1.0)))
+
+
+def _uv_ramp(t):
+    """computeUvRamp, grid.cpp:585-589: `2. * t` and `2. - w` are double expressions rounded once"""
+    w = _f32(2.0 * float(t))
+    if float(w) > 1.0:
+        w = _f32(2.0 - float(w))
+    return w
+
+
+def _uv_weight_scalars(t, dt, resetTime, index, numUvs):
+    """the host half of updateUvWeight, grid.cpp:603-616, in fp32 as written: (weight, reset?)"""
+    with np.errstate(all="ignore"):
+        t, dt, resetTime = _f32(t), _f32(dt), _f32(resetTime)
+        timeOff = resetTime / _f32(numUvs)
+        lastt = _uv_grid_time(t + _f32(index) * timeOff - dt, resetTime)
+        currt = _uv_grid_time(t + _f32(index) * timeOff, resetTime)
+        w = _uv_ramp(currt)
+        total = _f32(0.0)
+        for i in range(numUvs):
+            total = _f32(total + _uv_ramp(_uv_grid_time(t + _f32(i) * timeOff, resetTime)))
+        if total <= _f32(1e-6):
+            w = _f32(1.0)
+        else:
+            w = _f32(w / total)
+    return w, bool(currt < lastt)
+
+
+@plugin
+def updateUvWeight(resetTime, index, numUvs, uv, offset=None):
+    """grid.cpp:601-627: the hat-function weight of uv grid `index` of `numUvs` at the solver's time, normalised over all of them,
+    goes into cell 0; the grid is reset when its normalised time wrapped during the last step.  Scalars on the host in fp32, the
+    reset and the cell-0 write are kernels."""
+    index, numUvs = _coerce(index, 0), _coerce(numUvs, 0)
+    _chk(uv, VecGrid, "Grid<Vec3>")
+    off = _uv_offset(offset)
+    s = uv.parent
+    w, reset = _uv_weight_scalars(s.timeTotal, s.getDt(), resetTime, index, numUvs)
+    lib = _extension_lib(s, "updateUvWeight", "fields")
+    if reset:
+        lib.call("mf_fields_reset_uv", uv.sx, uv.sy, uv.sz, uv.ptr, off[0], off[1], off[2], s.stream)
+    lib.call("mf_fields_set_uv_weight", uv.n, uv.ptr, float(w), s.stream)
+
+
+@plugin
+def extrapolateSimpleFlags(flags, val, distance=4, flagFrom=_FLAG_FLUID, flagTo=_FLAG_OBSTACLE):
+    """waveletturbulence.cpp:239-307: val spreads from the cells with flagFrom into the cells with flagTo, `distance` layers deep,
+    each new cell the average of its neighbours of the previous layer.  One mark launch and one launch per layer, in place: the
+    reference's serial loop is order-free.  Nothing is read back; without target cells no pass can write."""
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(val, GridBase, "GridBase")
+    t = val.getType()
+    if t & GridBase.TypeReal:
+        ncomp, is_int = 1, 0
+    elif t & GridBase.TypeInt:
+        ncomp, is_int = 1, 1
+    elif t & GridBase.TypeVec3:
+        ncomp, is_int = 3, 0
+    else:
+        raise RuntimeError("extrapolateSimpleFlags: Grid Type is not supported (only int, Real, Vec3)")
+    s = flags.parent
+    lib = _extension_lib(s, "extrapolateSimpleFlags", "fields")
+    flags._check_same(val)
+    tmp = _scratch_grid(s, core.IntGrid)        # the mark pass writes every cell
+    lib.call("mf_fields_extrapolate_mark", flags.n, flags.ptr, tmp.ptr, int(flagFrom), s.stream)
+    for d in range(1, 1 + distance):
+        lib.call("mf_fields_extrapolate_pass", flags.sx, flags.sy, flags.sz, flags.ptr, tmp.ptr, val.ptr, ncomp, is_int, d, int(flagTo), s.stream)
+
+
+@plugin
+def initVortexVelocity(phiObs, vel, center, radius):
+    """initplugins.cpp:478-503, set-up code of test_1040_secOrderBnd.py: a solid-body vortex around `center` in the x and y
+    components of every cell with phiObs >= -1.  Host code of the library in fp32 with the C library's sqrtf / atan2f / sinf /
+    cosf; phiObs comes down, vel goes down and up again."""
+    _chk(phiObs, Grid, "Grid<Real>"); _chk(vel, MACGrid, "MACGrid")
+    c = _to_vec3(center)
+    s = vel.parent
+    lib = _extension_lib(s, "initVortexVelocity", "fields")
+    phiObs._check_same(vel)
+    s.sync()
+    phi = np.ascontiguousarray(phiObs.data.detach().cpu().numpy())
+    v = np.ascontiguousarray(vel.data.detach().cpu().numpy()).copy()
+    lib.call("mf_fields_vortex_velocity", vel.sx, vel.sy, vel.sz, phi.ctypes.data_as(ctypes.c_void_p), v.ctypes.data_as(ctypes.c_void_p),
+             float(_f32(c.x)), float(_f32(c.y)), float(_f32(radius)))
+    vel.data.copy_(torch.from_numpy(v).to(vel.data.device))
