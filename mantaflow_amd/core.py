@@ -11,7 +11,11 @@ the hot path goes through the C ABI (mantaflow_amd._lib).  Grids are dense, x fa
 vectors are structure-of-arrays ([3][N]); the reference's AoS [z][y][x][3] view exists only at the numpy bridge.
 """
 import ctypes
+import ctypes.util
+import gzip
 import math
+import re
+import struct
 
 import functools
 import types
@@ -626,9 +630,48 @@ class LevelsetGrid(Grid):
         inside = (flags.data & (TypeFluid | (TypeObstacle if ignoreWalls else 0))) != 0
         self.data.copy_(torch.where(inside, -0.5, 0.5).to(torch.float32))
 
+    _create_mesh_told = False
+
     def createMesh(self, mesh):
-        """marching-cubes surface extraction is GUI/mesh output, outside the solver hot path: accepted and ignored"""
-        return None
+        """LevelsetGrid::createMesh, levelset.cpp:330-415: marching cubes on the device (include/open/manta_hip_mesh.h, DESIGN.md
+        section 16) -- classify, count, two scans, one 16-byte read-back of the totals, emit.  On the CPU checker backend and on a
+        z-slab solver the call is accepted and the mesh is left as it was."""
+        s = self.parent
+        lib = s.lib
+        if lib.backend != "hip" or tuple(s._slab_window) != (0, 0):
+            if not LevelsetGrid._create_mesh_told:
+                LevelsetGrid._create_mesh_told = True
+                from . import api
+                api.mantaMsg("createMesh: not run on %s; the mesh is left as it was"
+                             % ("a z-slab solver" if lib.backend == "hip" else "the '%s' backend" % lib.backend), 1)
+            return None
+        if not isinstance(mesh, Mesh):
+            raise RuntimeError("can't convert argument to Mesh")
+        if not lib.mesh:
+            raise RuntimeError("createMesh: %s lacks the mesh extension (manta_hip_mesh.h) -- rebuild the library" % lib.path)
+        if not self.is3D():
+            raise RuntimeError("Only 3D grids supported so far")
+        mesh.clear()
+        need = ctypes.c_int64(0)
+        lib.call("mf_mesh_scan_bytes", self.sx, self.sy, self.sz, ctypes.byref(need))
+        # scratch from the solver's pool: the two scans, and one grid that holds the 16-bit owned masks followed by the cube bytes
+        node_off, tri_off, marks = (s._alloc("int", zero=False) for _ in range(3))
+        pooled_tmp = need.value <= 4 * self.n
+        tmp = s._alloc("int", zero=False) if pooled_tmp else torch.empty(need.value, dtype=torch.uint8, device=s.device)
+        try:
+            totals = (ctypes.c_int64 * 2)()
+            cube = ctypes.c_void_p(marks.data_ptr() + 2 * self.n)
+            lib.call("mf_mesh_create_plan", self.sx, self.sy, self.sz, self.ptr, cube, _ptr(marks), _ptr(node_off), _ptr(tri_off),
+                     _ptr(tmp), tmp.numel() * tmp.element_size(), totals, s.stream)
+            nn, nt = int(totals[0]), int(totals[1])
+            mesh._reserve_nodes(nn, keep=False)
+            mesh._reserve_tris(nt, keep=False)
+            lib.call("mf_mesh_create_emit", self.sx, self.sy, self.sz, self.ptr, cube, _ptr(marks), _ptr(node_off), _ptr(tri_off), nn, nt,
+                     mesh.ncap, _ptr(mesh.pos), _ptr(mesh.normal), _ptr(mesh.nflag), mesh.tcap, _ptr(mesh.tri), _ptr(mesh.tflag), s.stream)
+            mesh.nn, mesh.nt = nn, nt
+        finally:
+            for t in (node_off, tri_off, marks) + ((tmp,) if pooled_tmp else ()):
+                s._release("int", t)
 
 
 class FlagGrid(IntGrid):
@@ -820,12 +863,366 @@ class ParticleIndexSystem(PbClass):
     def to_numpy(self): return self.data[:self.np].detach().cpu().numpy().copy()
 
 
+_libm = None
+
+
+def _c_sincos(lib, theta):
+    """sinf / cosf of the C library, as `sin(Real)` resolves to in mesh.cpp: the library's host entry, or libm itself where the loaded
+    library lacks the mesh extension (the CPU test backend)"""
+    global _libm
+    if lib.mesh:
+        sn, cs = ctypes.c_float(0), ctypes.c_float(0)
+        lib.call("mf_mesh_sincos", float(theta), ctypes.byref(sn), ctypes.byref(cs))
+        return sn.value, cs.value
+    if _libm is None:
+        _libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+        for fn in (_libm.sinf, _libm.cosf):
+            fn.restype, fn.argtypes = ctypes.c_float, [ctypes.c_float]
+    return float(_libm.sinf(float(theta))), float(_libm.cosf(float(theta)))
+
+
+def _vertex_normals(pos, tris):
+    """Mesh::computeVertexNormals, mesh.cpp:604-622, on host arrays pos[n][3] float32, tris[t][3]: the three contributions of a
+    triangle are `nm * (1.0 / (l * l'))` -- a double factor, each product rounded once -- and are summed into the nodes in fp32 in
+    triangle order (ufunc.at adds one index after the other); normalize(), vectorbase.h:421-434, sends NaN to the zero vector"""
+    f32, f64 = np.float32, np.float64
+    nrm = np.zeros((pos.shape[0], 3), f32)
+    with np.errstate(all="ignore"):
+        if tris.shape[0]:
+            p0, p1, p2 = pos[tris[:, 0]], pos[tris[:, 1]], pos[tris[:, 2]]
+            n0, n1, n2 = p0 - p1, p1 - p2, p2 - p0
+            l0, l1, l2 = [v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1] + v[:, 2] * v[:, 2] for v in (n0, n1, n2)]
+            nm = np.stack([n0[:, 1] * n1[:, 2] - n0[:, 2] * n1[:, 1], n0[:, 2] * n1[:, 0] - n0[:, 0] * n1[:, 2],
+                           n0[:, 0] * n1[:, 1] - n0[:, 1] * n1[:, 0]], 1)
+            w = np.stack([1.0 / (l0 * l2).astype(f64), 1.0 / (l0 * l1).astype(f64), 1.0 / (l1 * l2).astype(f64)], 1)     # [t][corner]
+            contrib = (nm.astype(f64)[:, None, :] * w[:, :, None]).astype(f32)
+            np.add.at(nrm, tris.reshape(-1), contrib.reshape(-1, 3))
+        l = nrm[:, 0] * nrm[:, 0] + nrm[:, 1] * nrm[:, 1] + nrm[:, 2] * nrm[:, 2]
+        eps2 = f32(VECTOR_EPSILON) * f32(VECTOR_EPSILON)
+        one = np.abs(l.astype(f64) - 1.0) < f64(eps2)
+        scaled = ~one & (l > eps2)
+        fac = (1.0 / np.sqrt(l.astype(f64)).astype(f32).astype(f64)).astype(f32)
+        nrm[scaled] = nrm[scaled] * fac[scaled, None]
+        nrm[~one & ~scaled] = 0
+    return nrm
+
+
+def _atoi(s):
+    m = re.match(r"\s*[+-]?\d+", s)
+    return int(m.group(0)) if m else 0
+
+
 class Mesh(PbClass):
-    """placeholder so that scenes which create a Mesh for the GUI keep running; meshes are outside the hot path"""
+    """Mesh, mesh.{h,cpp}: a triangle mesh resident on the solver's device.  Nodes are structure-of-arrays -- pos[3][ncap],
+    normal[3][ncap], flags[ncap] -- and triangles c[3][tcap] (int32 node numbers) with flags[tcap]; the buffers grow geometrically and
+    are reused from call to call.  createMesh (LevelsetGrid), advectInGrid and the node transforms are kernels of
+    include/open/manta_hip_mesh.h; save / load are host code.  No Mdata channels, corner tables or 1-ring lookups."""
     _cname_py, _cname_cpp, _T = "Mesh", "Mesh", ""
+    NfNone, NfFixed, NfMarked, NfKillme, NfCollide = 0, 1, 2, 4, 8
+    FfNone, FfDoubled, FfMarked = 0, 1, 2
+    m_color, m_b2D = vec3(-1, -1, -1), False        # the fork's statics, mesh.cpp:317-318: stored, no effect without a GUI
 
     def __init__(self, parent, name="", **kw):
         PbClass.__init__(self, parent, name)
+        dev = parent.device
+        self.nn, self.ncap, self.nt, self.tcap = 0, 0, 0, 0
+        self.pos = torch.zeros(0, dtype=torch.float32, device=dev)
+        self.normal = torch.zeros(0, dtype=torch.float32, device=dev)
+        self.nflag = torch.zeros(0, dtype=torch.int32, device=dev)
+        self.tri = torch.zeros(0, dtype=torch.int32, device=dev)
+        self.tflag = torch.zeros(0, dtype=torch.int32, device=dev)
+        self._saved_pos, self._saved_n = None, 0
+
+    # --- storage ---
+    def _reserve_nodes(self, n, keep=True):
+        if n <= self.ncap:
+            return
+        cap, dev = max(n, 2 * self.ncap), self.parent.device
+        pos = torch.zeros(3 * cap, dtype=torch.float32, device=dev)
+        normal = torch.zeros(3 * cap, dtype=torch.float32, device=dev)
+        nflag = torch.zeros(cap, dtype=torch.int32, device=dev)
+        if keep and self.nn:
+            for c in range(3):
+                pos[c * cap:c * cap + self.nn] = self.pos[c * self.ncap:c * self.ncap + self.nn]
+                normal[c * cap:c * cap + self.nn] = self.normal[c * self.ncap:c * self.ncap + self.nn]
+            nflag[:self.nn] = self.nflag[:self.nn]
+        self.pos, self.normal, self.nflag, self.ncap = pos, normal, nflag, cap
+
+    def _reserve_tris(self, n, keep=True):
+        if n <= self.tcap:
+            return
+        cap, dev = max(n, 2 * self.tcap), self.parent.device
+        tri = torch.zeros(3 * cap, dtype=torch.int32, device=dev)
+        tflag = torch.zeros(cap, dtype=torch.int32, device=dev)
+        if keep and self.nt:
+            for c in range(3):
+                tri[c * cap:c * cap + self.nt] = self.tri[c * self.tcap:c * self.tcap + self.nt]
+            tflag[:self.nt] = self.tflag[:self.nt]
+        self.tri, self.tflag, self.tcap = tri, tflag, cap
+
+    def _rows(self, t, cap, n):
+        """[3][cap] device planes -> host [n][3]"""
+        self.parent.sync()
+        return np.ascontiguousarray(t.view(3, cap)[:, :n].detach().cpu().numpy().T)
+
+    def numNodes(self): return self.nn
+    def numTris(self): return self.nt
+    def size(self): return self.nn
+    def getSizeSlow(self): return self.nn
+
+    def nodes_numpy(self):
+        """-> pos[n][3], normal[n][3], flags[n]"""
+        n = self.nn
+        if n == 0:
+            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros(0, np.int32)
+        return self._rows(self.pos, self.ncap, n), self._rows(self.normal, self.ncap, n), self.nflag[:n].detach().cpu().numpy().copy()
+
+    def tris_numpy(self):
+        """-> c[t][3], flags[t]"""
+        n = self.nt
+        if n == 0:
+            return np.zeros((0, 3), np.int32), np.zeros(0, np.int32)
+        return self._rows(self.tri, self.tcap, n), self.tflag[:n].detach().cpu().numpy().copy()
+
+    def set_numpy(self, pos, normal=None, flags=None, tris=None, triFlags=None):
+        """replace the mesh by host arrays (absent normals and flags are zero, absent triangles none)"""
+        pos = np.asarray(pos, np.float32).reshape(-1, 3)
+        n = pos.shape[0]
+        normal = np.zeros((n, 3), np.float32) if normal is None else np.asarray(normal, np.float32).reshape(-1, 3)
+        flags = np.zeros(n, np.int32) if flags is None else np.asarray(flags, np.int32).reshape(-1)
+        tris = np.zeros((0, 3), np.int32) if tris is None else np.asarray(tris, np.int32).reshape(-1, 3)
+        t = tris.shape[0]
+        triFlags = np.zeros(t, np.int32) if triFlags is None else np.asarray(triFlags, np.int32).reshape(-1)
+        if normal.shape[0] != n or flags.shape[0] != n or triFlags.shape[0] != t:
+            raise RuntimeError("Mesh::set_numpy: array lengths do not match")
+        self.nn = self.nt = 0
+        self._reserve_nodes(n, keep=False)
+        self._reserve_tris(t, keep=False)
+        dev = self.parent.device
+        for c in range(3):
+            self.pos[c * self.ncap:c * self.ncap + n] = torch.from_numpy(np.array(pos[:, c])).to(dev)
+            self.normal[c * self.ncap:c * self.ncap + n] = torch.from_numpy(np.array(normal[:, c])).to(dev)
+            self.tri[c * self.tcap:c * self.tcap + t] = torch.from_numpy(np.array(tris[:, c])).to(dev)
+        self.nflag[:n] = torch.from_numpy(np.array(flags)).to(dev)
+        self.tflag[:t] = torch.from_numpy(np.array(triFlags)).to(dev)
+        self.nn, self.nt = n, t
+
+    def _set_normals(self, normal):
+        dev = self.parent.device
+        for c in range(3):
+            self.normal[c * self.ncap:c * self.ncap + self.nn] = torch.from_numpy(np.ascontiguousarray(normal[:, c])).to(dev)
+
+    # --- plugins of the reference ---
+    def clear(self):
+        """Mesh::clear, mesh.cpp:143-160 (the buffers stay)"""
+        self.nn = self.nt = 0
+
+    def _not_implemented(self, what, why):
+        raise RuntimeError("Mesh::%s: not implemented in mantaflow_amd (%s)" % (what, why))
+
+    def fromShape(self, shape=None, append=False): self._not_implemented("fromShape", "no Shape::generateMesh")
+    def computeVelocity(self, oldMesh=None, vel=None): self._not_implemented("computeVelocity", "no mesh velocities")
+    def computeLevelset(self, levelset=None, sigma=None, cutoff=-1.): self._not_implemented("computeLevelset", "meshSDF is not part of the mesh extension")
+    def getLevelset(self, sigma=None, cutoff=-1.): self._not_implemented("getLevelset", "meshSDF is not part of the mesh extension")
+    def applyMeshToGrid(self, grid=None, respectFlags=None, cutoff=-1., meshSigma=2.): self._not_implemented("applyMeshToGrid", "meshSDF is not part of the mesh extension")
+    def create(self, type=None, name="", **kw): self._not_implemented("create", "no Mdata channels")
+    def getNodesDataPointer(self): self._not_implemented("getNodesDataPointer", "nodes are structure-of-arrays device buffers")
+    def getTrisDataPointer(self): self._not_implemented("getTrisDataPointer", "triangles are structure-of-arrays device buffers")
+
+    @staticmethod
+    def set_color(c): Mesh.m_color = _to_vec3(c)
+    @staticmethod
+    def set_2D(b2D): Mesh.m_b2D = bool(b2D)
+    def get_name(self): return self.getName()
+    def set_name(self, s): self.setName(s)
+
+    def advectInGrid(self, flags, vel, integrationMode):
+        """Mesh::advectInGrid, mesh.cpp:301-315: one kernel, no clamp, no obstacle test, no delete"""
+        from . import plugins
+        s = self.parent
+        lib = plugins._extension_lib(s, "Mesh::advectInGrid", "mesh")
+        if not isinstance(flags, FlagGrid):
+            raise RuntimeError("can't convert argument to FlagGrid*")
+        if not isinstance(vel, MACGrid):
+            raise RuntimeError("can't convert argument to MACGrid*")
+        if int(integrationMode) not in (0, 1, 2):
+            raise RuntimeError("unknown integration type")
+        lib.call("mf_mesh_advect", flags.sx, flags.sy, flags.sz, vel.ptr, self.nn, self.ncap, _ptr(self.pos), _ptr(self.nflag), s.getDt(),
+                 int(integrationMode), s.stream)
+
+    def _elementwise(self, entry, v, torch_op):
+        """pos (op)= v per component: the kernel, or torch on a backend without the extension (the same single fp32 operation)"""
+        s = self.parent
+        v = _to_vec3(v)
+        if self.nn == 0:
+            return
+        if s.lib.mesh:
+            s.lib.call(entry, self.nn, self.ncap, _ptr(self.pos), float(v.x), float(v.y), float(v.z), s.stream)
+            return
+        if s.lib.backend == "hip":
+            raise RuntimeError("Mesh: %s lacks the mesh extension (manta_hip_mesh.h) -- rebuild the library" % s.lib.path)
+        for c, x in enumerate(v):
+            torch_op(self.pos[c * self.ncap:c * self.ncap + self.nn], float(np.float32(x)))
+
+    def scale(self, s):
+        """mesh.cpp:332-336"""
+        self._elementwise("mf_mesh_scale", s, lambda t, x: t.mul_(x))
+
+    def offset(self, o):
+        """mesh.cpp:338-341"""
+        self._elementwise("mf_mesh_offset", o, lambda t, x: t.add_(x))
+
+    def rotate(self, thetas):
+        """mesh.cpp:343-373: about x, then y, then z; a zero angle is skipped; sin and cos are the C library's float functions"""
+        s = self.parent
+        lib = s.lib
+        th = _to_vec3(thetas)
+        if not lib.mesh and lib.backend == "hip":
+            raise RuntimeError("Mesh: %s lacks the mesh extension (manta_hip_mesh.h) -- rebuild the library" % lib.path)
+        for theta, (a, b) in zip(th, ((1, 2), (0, 2), (0, 1))):
+            theta = float(np.float32(theta))
+            if theta == 0.0:
+                continue
+            sin_t, cos_t = _c_sincos(lib, theta)
+            if (a, b) == (0, 2):
+                sin_t = -sin_t
+            if self.nn == 0:
+                continue
+            if lib.mesh:
+                lib.call("mf_mesh_rotate_pair", self.nn, self.ncap, _ptr(self.pos), a, b, sin_t, cos_t, s.stream)
+            else:
+                pa, pb = self.pos[a * self.ncap:a * self.ncap + self.nn], self.pos[b * self.ncap:b * self.ncap + self.nn]
+                fa, fb = pa.clone(), pb.clone()
+                pa.copy_(fa * cos_t - fb * sin_t)      # each product and the difference are single fp32 operations
+                pb.copy_(fb * cos_t + fa * sin_t)
+
+    def save_pos(self):
+        """mesh.cpp:320-324"""
+        self._saved_n = self.nn
+        self._saved_pos = self.pos.view(3, self.ncap)[:, :self.nn].clone() if self.nn else None
+
+    def load_pos(self):
+        """mesh.cpp:326-330"""
+        if self._saved_n != self.nn:
+            raise RuntimeError("# of mesh nodes has changed")
+        if self.nn:
+            self.pos.view(3, self.ncap)[:, :self.nn].copy_(self._saved_pos)
+
+    # --- file I/O, fileio/iomeshes.cpp:125-388 (host) ---
+    @staticmethod
+    def _extension(name):
+        p = name.rfind(".")
+        if p < 0:
+            raise RuntimeError("file '" + name + "' does not have an extension")
+        return name[p:]
+
+    def _unit_cube(self, pos):
+        """grid space -> the unit cube around 0, iomeshes.cpp:204-207: pos -= gs * 0.5 ; pos *= dx in fp32"""
+        s = self.parent
+        half = (np.array(s.mGridSize, np.float32).astype(np.float64) * 0.5).astype(np.float32)
+        return (pos - half[None, :]) * np.float32(s.getDx())
+
+    def save(self, name):
+        """Mesh::save, mesh.cpp:203-213.  `.bobj.gz` recomputes the vertex normals first, as the reference's writer does; `.obj` does not."""
+        ext = self._extension(name)
+        if ext not in (".obj", ".gz"):
+            raise RuntimeError("file '" + name + "' filetype not supported")
+        pos, normal, _ = self.nodes_numpy()
+        tris, _ = self.tris_numpy()
+        p = self._unit_cube(pos)
+        if ext == ".obj":
+            out = ["o MantaMesh\n"]
+            out += ["v %g %g %g \n" % tuple(v) for v in p.astype(np.float64)]
+            out += ["vn %g %g %g \n" % tuple(v) for v in normal.astype(np.float64)]
+            out += ["f %d %d %d \n" % tuple(t) for t in tris.astype(np.int64) + 1]
+            with open(name, "w") as f:
+                f.write("".join(out))
+            return
+        normal = _vertex_normals(pos, tris)
+        if self.nn:
+            self._set_normals(normal)
+        with gzip.open(name, "wb", compresslevel=1) as f:
+            f.write(struct.pack("<i", self.nn) + np.ascontiguousarray(p, "<f4").tobytes())
+            f.write(struct.pack("<i", self.nn) + np.ascontiguousarray(normal, "<f4").tobytes())
+            f.write(struct.pack("<i", self.nt) + np.ascontiguousarray(tris, "<i4").tobytes())
+
+    def load(self, name, append=False):
+        """Mesh::load, mesh.cpp:186-201.  A refused or unreadable file leaves the mesh as it was."""
+        ext = self._extension(name)
+        if ext == ".gz":
+            if append:
+                raise RuntimeError("readBobj: append not yet implemented!")
+            self._load_bobj(name)
+        elif ext == ".obj":
+            self._load_obj(name, bool(append))
+        else:
+            raise RuntimeError("file '" + name + "' filetype not supported")
+
+    def _load_bobj(self, name):
+        try:
+            with gzip.open(name, "rb") as f:
+                raw = f.read()
+        except OSError:
+            raise RuntimeError("readBobj: unable to open file")
+        at = [0]
+
+        def take(dtype, count):
+            a = np.frombuffer(raw, dtype, count, at[0])
+            at[0] += a.nbytes
+            return a
+        try:
+            n = int(take("<i4", 1)[0])
+            pos = take("<f4", 3 * n).reshape(n, 3)
+            m = int(take("<i4", 1)[0])
+            nrm = take("<f4", 3 * m).reshape(m, 3)
+            t = int(take("<i4", 1)[0])
+            tris = take("<i4", 3 * t).reshape(t, 3)
+        except ValueError:
+            raise RuntimeError("readBobj: file '" + name + "' is truncated")
+        s = self.parent
+        half = (np.array(s.mGridSize, np.float32).astype(np.float64) * 0.5).astype(np.float32)
+        pos = pos / np.float32(s.getDx()) + half[None, :]       # back to grid space, iomeshes.cpp:155-156
+        normal = np.zeros((n, 3), np.float32)
+        normal[:min(n, m)] = nrm[:min(n, m)]
+        self.set_numpy(pos, normal, None, tris, None)
+
+    def _load_obj(self, name, append):
+        """readObjFile, iomeshes.cpp:282-348: `v` and `f` lines; `vn` values are read into a copy of a node and so dropped -- loaded
+        nodes keep the zero normal of Node(); positions are taken as written (the reader does not undo the writer's scaling)"""
+        try:
+            with open(name) as f:
+                lines = f.read().split("\n")
+        except OSError:
+            raise RuntimeError("can't open file '" + name + "'")
+        base = self.nn if append else 0
+        verts, faces = [], []
+        for line in lines:
+            tok = line.split()
+            if not tok or tok[0][0] == "#":
+                continue
+            if tok[0] == "vn":
+                if base + len(verts) == 0:
+                    raise RuntimeError("invalid amount of nodes")
+            elif tok[0] == "v":
+                verts.append([np.float32(x) for x in (tok[1:4] + ["0", "0", "0"])[:3]])
+            elif tok[0] == "f":
+                c = []
+                for face in (tok[1:4] + ["", "", ""])[:3]:
+                    idx = _atoi(face.split("/")[0]) - 1
+                    if idx < 0:
+                        raise RuntimeError("invalid face encountered")
+                    c.append(idx + base)
+                faces.append(c)
+        verts = np.array(verts, np.float32).reshape(-1, 3)
+        faces = np.array(faces, np.int32).reshape(-1, 3)
+        if append and (self.nn or self.nt):
+            pos, normal, fl = self.nodes_numpy()
+            tris, tfl = self.tris_numpy()
+            self.set_numpy(np.concatenate([pos, verts]), np.concatenate([normal, np.zeros_like(verts)]),
+                           np.concatenate([fl, np.zeros(len(verts), np.int32)]), np.concatenate([tris, faces]),
+                           np.concatenate([tfl, np.zeros(len(faces), np.int32)]))
+        else:
+            self.set_numpy(verts, None, None, faces, None)
 
 
 class BasicParticleSystem(PbClass):
@@ -923,6 +1320,55 @@ class BasicParticleSystem(PbClass):
 
     def getPosPdata(self, target): target.data.copy_(self.pos)
     def setPosPdata(self, source): self.pos.copy_(source.data)
+
+    # .uni particle files, fileio/ioparticles.cpp:130-223: gzip stream of "PB02" + UniPartHeader + [pos.x pos.y pos.z flag] per particle
+    _UNI_PART_HEADER = "<6i256sQ"       # dim dimX dimY dimZ elementType bytesPerElement info[256] timestamp = 288 B
+
+    def save(self, name):
+        """BasicParticleSystem::save, particle.cpp:213-236: `.uni` (and `.raw`, the same format)"""
+        import time as _time
+        if "." not in name:
+            raise RuntimeError("file '" + name + "' does not have an extension")
+        if name[name.rfind("."):] not in (".uni", ".raw"):
+            raise RuntimeError("particle '" + name + "' filetype not supported for saving")
+        rec = np.zeros(self.np, np.dtype([("pos", "<f4", 3), ("flag", "<i4")]))
+        if self.np:
+            rec["pos"], rec["flag"] = self.get_positions(), self.get_flags()
+        gs = self.parent.mGridSize
+        head = struct.pack(self._UNI_PART_HEADER, self.np, gs[0], gs[1], gs[2], 0, 16, b"mantaflow_amd 0.1 64bit fp1 hip gfx950", int(_time.time() * 1000))
+        with gzip.open(name, "wb", compresslevel=1) as f:
+            f.write(b"PB02" + head + rec.tobytes())
+        return 1
+
+    def load(self, name):
+        """BasicParticleSystem::load, particle.cpp:195-211 -> readParticlesUni: every channel is resized, positions are scaled from
+        the file's solver resolution to this solver's (transformPositions: an fp32 factor per axis)"""
+        if "." not in name:
+            raise RuntimeError("file '" + name + "' does not have an extension")
+        if name[name.rfind("."):] not in (".uni", ".raw"):
+            raise RuntimeError("particle '" + name + "' filetype not supported for loading")
+        try:
+            with gzip.open(name, "rb") as f:
+                raw = f.read()
+        except OSError:
+            raise RuntimeError("can't open file " + name)
+        if raw[:4] == b"PB01":
+            raise RuntimeError("particle uni file format v01 not supported anymore")
+        if raw[:4] != b"PB02":
+            return 1
+        hs = struct.calcsize(self._UNI_PART_HEADER)
+        if len(raw) < 4 + hs:
+            raise RuntimeError("can't read file, no header present")
+        dim, dx, dy, dz, etype, bpe, info, stamp = struct.unpack(self._UNI_PART_HEADER, raw[4:4 + hs])
+        if bpe != 16 or etype != 0:
+            raise RuntimeError("particle type doesn't match")
+        if len(raw) - 4 - hs != 16 * dim:
+            raise RuntimeError("can't read uni file, stream length does not match, %d vs %d" % (16 * dim, len(raw) - 4 - hs))
+        rec = np.frombuffer(raw, np.dtype([("pos", "<f4", 3), ("flag", "<i4")]), dim, 4 + hs)
+        gs = self.parent.mGridSize
+        factor = np.array([np.float32(gs[c]) / np.float32((dx, dy, dz)[c]) for c in range(3)], np.float32)
+        self.set_positions(rec["pos"] * factor[None, :], np.array(rec["flag"]))
+        return 1
 
     def projectOutOfBnd(self, flags, bnd, plane="xXyYzZ", ptype=None, exclude=0):
         """ParticleSystem::projectOutOfBnd, particle.h:592-604"""
