@@ -19,6 +19,8 @@
 #include "../../include/manta_hip_multigrid.h"
 #include <algorithm>
 #include <chrono>
+#include <mutex>
+#include <set>
 #include <vector>
 #include <stdlib.h>
 #include <string.h>
@@ -468,9 +470,18 @@ k_mg_tail(MgView M, int first, float accuracy, int* __restrict__ info) {
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
+// the handles that mf_mg_create gave out and mf_mg_destroy has not taken back: a destroyed handle is refused without reading
+// the memory it pointed to
+std::mutex g_live_mutex;
+std::set<void*> g_live;
 Mg* as_mg(void* h) {
+	if (!h) return nullptr;
+	{
+		std::lock_guard<std::mutex> lock(g_live_mutex);
+		if (!g_live.count(h)) return nullptr;
+	}
 	Mg* m = (Mg*)h;
-	return (m && m->magic == MG_MAGIC) ? m : nullptr;
+	return m->magic == MG_MAGIC ? m : nullptr;
 }
 
 // The bucket min-heap of genCoarseGrid (NKMinHeap, multigrid.cpp:57-186): one doubly linked list per key; set_key puts an ID at
@@ -652,7 +663,7 @@ int mg_set_a(Mg* m, const float* A0, const float* Ai, const float* Aj, const flo
 }
 
 int mg_vcycle(Mg* m, float* dst, const float* rhs, hipStream_t st) {
-	if (!m->aset) return fail("GridMg::setRhs Error: A has not been set.");
+	if (!m->aset) return fail("mf_mg_vcycle: GridMg::setRhs Error: A has not been set.");
 	const MgView& V = m->v;
 	const int first = m->tail_first;
 	hipLaunchKernelGGL(k_mg_set_rhs, dim3(nblk(V.l[0].n)), dim3(BLOCK), 0, st, V.l[0], rhs);
@@ -756,6 +767,10 @@ int mf_mg_create(int sx, int sy, int sz, void** handle_out) {
 	if (const char* e = getenv("MF_MG_TAIL_VERTS")) tail_verts = atoi(e);
 	m->tail_first = V.nl - 1;
 	while (m->tail_first > 0 && V.l[m->tail_first - 1].n <= tail_verts) m->tail_first--;
+	{
+		std::lock_guard<std::mutex> lock(g_live_mutex);
+		g_live.insert(m);
+	}
 	*handle_out = m;
 	return 0;
 }
@@ -764,6 +779,10 @@ int mf_mg_destroy(void* handle) {
 	Mg* m = as_mg(handle);
 	if (!m) return fail("mf_mg_destroy: bad handle");
 	MF_HIP(hipDeviceSynchronize());
+	{
+		std::lock_guard<std::mutex> lock(g_live_mutex);
+		g_live.erase(handle);
+	}
 	free_levels(m);
 	m->magic = 0;
 	delete m;
