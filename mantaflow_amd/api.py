@@ -22,7 +22,8 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       computeVorticity, getCurl,
                       processBurn, updateFlame, calcSecDeriv2d, totalSum, normalizeSumTo, cgSolveWE, resetUvGrid, updateUvWeight,
                       getUvWeight, extrapolateSimpleFlags, initVortexVelocity,
-                      PD_fluid_guiding, releaseBlurPrecomp, lastGuidingStats, getSpiralVelocity, setGradientYWeight)
+                      PD_fluid_guiding, releaseBlurPrecomp, lastGuidingStats, getSpiralVelocity, setGradientYWeight,
+                      densityInflowMesh, densityInflowMeshNoise, lastMeshSdfStats)
 
 from .scene import (Box, Checkbox, Cylinder, Gui, NoiseField, Shape, Slider, Sphere, densityInflow, sampleFlagsWithParticles,
                     sampleLevelsetWithParticles, sampleShapeWithParticles)

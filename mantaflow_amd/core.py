@@ -932,6 +932,9 @@ class Mesh(PbClass):
         self.tri = torch.zeros(0, dtype=torch.int32, device=dev)
         self.tflag = torch.zeros(0, dtype=torch.int32, device=dev)
         self._saved_pos, self._saved_n = None, 0
+        self._sdf_cap, self._sdf_off, self._sdf_stats = 0, None, None      # the source buffers of meshSDF (_sdf_reserve)
+        self._sdf_f = torch.zeros(0, dtype=torch.float32, device=dev)
+        self._sdf_i = torch.zeros(0, dtype=torch.int32, device=dev)
 
     # --- storage ---
     def _reserve_nodes(self, n, keep=True):
@@ -1022,9 +1025,151 @@ class Mesh(PbClass):
 
     def fromShape(self, shape=None, append=False): self._not_implemented("fromShape", "no Shape::generateMesh")
     def computeVelocity(self, oldMesh=None, vel=None): self._not_implemented("computeVelocity", "no mesh velocities")
-    def computeLevelset(self, levelset=None, sigma=None, cutoff=-1.): self._not_implemented("computeLevelset", "meshSDF is not part of the mesh extension")
-    def getLevelset(self, sigma=None, cutoff=-1.): self._not_implemented("getLevelset", "meshSDF is not part of the mesh extension")
-    def applyMeshToGrid(self, grid=None, respectFlags=None, cutoff=-1., meshSigma=2.): self._not_implemented("applyMeshToGrid", "meshSDF is not part of the mesh extension")
+    # --- mesh -> level set (meshSDF, mesh.cpp:868-1005): include/open/manta_hip_meshsdf.h, DESIGN.md section 17 ---
+    def _sdf_lib(self, what):
+        """the library if Mesh::<what> can run: refused before anything is looked at (argument checks included) on a backend without the
+        extension and on a z-slab solver"""
+        s = self.parent
+        if s.lib.backend != "hip" or tuple(s._slab_window) != (0, 0):
+            self._not_implemented(what, "mesh level sets run on the HIP backend, on whole-domain solvers")
+        if not s.lib.meshsdf:
+            raise RuntimeError("Mesh::%s: %s lacks the mesh level set extension (manta_hip_meshsdf.h) -- rebuild the library" % (what, s.lib.path))
+        return s.lib
+
+    def _sdf_reserve(self, n):
+        """the source buffers: pos / normal as emitted and as binned ([3][cap] each) and four int rows of sort scratch; geometric growth"""
+        if n > self._sdf_cap:
+            cap, dev = max(n, 2 * self._sdf_cap), self.parent.device
+            self._sdf_f = torch.empty(12 * cap, dtype=torch.float32, device=dev)
+            self._sdf_i = torch.empty(4 * cap, dtype=torch.int32, device=dev)
+            self._sdf_cap = cap
+        if self._sdf_off is None or self._sdf_off.numel() < max(self.nt, 1):
+            self._sdf_off = torch.empty(max(self.tcap, 1), dtype=torch.int64, device=self.parent.device)
+        if self._sdf_stats is None:
+            self._sdf_stats = torch.zeros(4, dtype=torch.int32, device=self.parent.device)
+
+    def _mesh_sdf(self, lib, who, levelset, sigma, cutoff, flood=True):
+        """meshSDF(*this, levelset, sigma, cutoff) as plan, emit, bin, gather, flood; one 8-byte read-back sizes the sources and one int
+        per flood round ends the fill.  Scratch grids come from the level set's solver's pool."""
+        from . import plugins
+        if not isinstance(levelset, LevelsetGrid):
+            raise RuntimeError("can't convert argument to LevelsetGrid")
+        g = levelset.parent
+        if not levelset.is3D() or not self.parent.is3D():
+            raise RuntimeError("%s: 3-D grids only" % who)
+        if tuple(g._slab_window) != (0, 0):
+            raise RuntimeError("%s: not implemented on a z-slab solver" % who)
+        if g.device != self.parent.device:
+            raise RuntimeError("%s: the level set lives on another device than the mesh" % who)
+        sigma, cutoff = float(np.float32(sigma)), float(np.float32(cutoff))
+        if not sigma > 0:
+            raise RuntimeError("%s: sigma must be positive" % who)
+        mark = Mesh._sdf_mark
+        sx, sy, sz = levelset.dims
+        ms = self.parent.mGridSize
+        mult = [np.float32(a) / np.float32(b) for a, b in zip((sx, sy, sz), ms)]        # toVec3(gridRes) / toVec3(gridSize)
+        self._sdf_reserve(0)
+        st = g.stream
+        need = ctypes.c_int64(0)
+        lib.call("mf_meshsdf_tmp_bytes", self.nt, 0, levelset.n, ctypes.byref(need))
+        grids = [g._alloc("int", zero=False) for _ in range(3)]
+        ln, start, occ = grids
+        tmp = None
+        try:
+            def scratch(nbytes):
+                nonlocal tmp
+                if tmp is None or tmp.numel() * tmp.element_size() < nbytes:
+                    if nbytes <= 4 * levelset.n and len(grids) == 3:
+                        grids.append(g._alloc("int", zero=False))
+                        tmp = grids[3]
+                    else:
+                        tmp = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
+                return tmp
+            t = scratch(need.value)
+            total = ctypes.c_int64(0)
+            if mark: mark("start")
+            lib.call("mf_meshsdf_plan", self.nt, self.tcap, _ptr(self.tri), self.nn, self.ncap, _ptr(self.pos), _ptr(self._sdf_off), _ptr(t),
+                     t.numel() * t.element_size(), ctypes.byref(total), st)
+            nsrc = int(total.value)
+            self._sdf_reserve(nsrc)
+            cap = self._sdf_cap
+            f, ik = self._sdf_f, self._sdf_i
+            spos, snrm = _ptr(f), ctypes.c_void_p(f.data_ptr() + 12 * cap) if cap else None
+            bpos = ctypes.c_void_p(f.data_ptr() + 24 * cap) if cap else None
+            bnrm = ctypes.c_void_p(f.data_ptr() + 36 * cap) if cap else None
+            if not cap:
+                spos = None
+            lib.call("mf_meshsdf_emit", self.nt, self.tcap, _ptr(self.tri), self.nn, self.ncap, _ptr(self.pos), _ptr(self._sdf_off), nsrc,
+                     float(mult[0]), float(mult[1]), float(mult[2]), cap, spos, snrm, st)
+            if mark: mark("sources")
+            lib.call("mf_meshsdf_tmp_bytes", 0, nsrc, levelset.n, ctypes.byref(need))
+            t = scratch(need.value)
+            lib.call("mf_meshsdf_bin", sx, sy, sz, nsrc, cap, spos, snrm, _ptr(ik) if cap else None, bpos, bnrm, _ptr(ln), _ptr(start), _ptr(occ),
+                     _ptr(self._sdf_stats), _ptr(t), t.numel() * t.element_size(), st)
+            if mark: mark("binning")
+            lib.call("mf_meshsdf_gather", sx, sy, sz, cap, bpos, bnrm, _ptr(ln), _ptr(start), _ptr(occ), sigma, cutoff, levelset.ptr, st)
+            if mark: mark("gather")
+            out = (ctypes.c_int32 * 2)()
+            lib.call("mf_meshsdf_flood", sx, sy, sz, levelset.ptr, sigma, cutoff, 1 if flood else 0, _ptr(self._sdf_stats), out, st)
+            if mark: mark("flood")
+            plugins._mesh_sdf_stats = {"sources": nsrc, "binned": int(out[1]), "rounds": int(out[0])}
+        finally:
+            for q in grids:
+                g._release("int", q)
+
+    _sdf_mark = None      # tools/meshsdf_time.py sets a callable that is told after which stage the call is
+
+    def computeLevelset(self, levelset=None, sigma=None, cutoff=-1.):
+        """Mesh::computeLevelset, mesh.cpp:858-860"""
+        lib = self._sdf_lib("computeLevelset")
+        self._mesh_sdf(lib, "Mesh::computeLevelset", levelset, sigma, cutoff)
+
+    def getLevelset(self, sigma=None, cutoff=-1.):
+        """Mesh::getLevelset, mesh.cpp:862-866: a new level set of the mesh's solver"""
+        lib = self._sdf_lib("getLevelset")
+        if not self.parent.is3D():
+            raise RuntimeError("Mesh::getLevelset: 3-D grids only")
+        phi = LevelsetGrid(self.parent)
+        self._mesh_sdf(lib, "Mesh::getLevelset", phi, sigma, cutoff)
+        return phi
+
+    def applyMeshToGrid(self, grid=None, respectFlags=None, cutoff=-1., meshSigma=2., value=None):
+        """Mesh::applyMeshToGrid, mesh.cpp:829-856: meshSDF at the grid's size, then cells with sdf < 0 that are not obstacles of
+        respectFlags take `value` (an int, a Real or a Vec3 by the grid's type)"""
+        lib = self._sdf_lib("applyMeshToGrid")
+        who = "Mesh::applyMeshToGrid"
+        if not isinstance(grid, GridBase):
+            raise RuntimeError("can't convert argument to GridBase*")
+        if respectFlags is not None and not isinstance(respectFlags, FlagGrid):
+            raise RuntimeError("can't convert argument to FlagGrid*")
+        if not grid.is3D():
+            raise RuntimeError("%s: 3-D grids only" % who)
+        if respectFlags is not None:
+            grid._check_same(respectFlags)
+        gt = grid.getType()
+        if gt & GridBase.TypeInt:
+            kind = 0
+        elif gt & GridBase.TypeReal:
+            kind = 1
+        elif gt & GridBase.TypeVec3:
+            kind = 2
+        else:
+            raise RuntimeError("Shape::applyToGrid(): unknown grid type")
+        if value is None:
+            raise RuntimeError("Argument 'value' is not defined.")
+        iv, v = 0, (0.0, 0.0, 0.0)
+        if kind == 0:
+            iv = int(value)
+        elif kind == 1:
+            v = (float(value), 0.0, 0.0)
+        else:
+            v = tuple(float(x) for x in _to_vec3(value))
+        g = grid.parent
+        sdf = LevelsetGrid(g)
+        self._mesh_sdf(lib, who, sdf, meshSigma, cutoff)
+        lib.call("mf_meshsdf_apply", grid.sx, grid.sy, grid.sz, sdf.ptr, None if respectFlags is None else respectFlags.ptr, kind, grid.ptr, iv,
+                 v[0], v[1], v[2], g.stream)
+
     def create(self, type=None, name="", **kw): self._not_implemented("create", "no Mdata channels")
     def getNodesDataPointer(self): self._not_implemented("getNodesDataPointer", "nodes are structure-of-arrays device buffers")
     def getTrisDataPointer(self): self._not_implemented("getTrisDataPointer", "triangles are structure-of-arrays device buffers")

@@ -1868,3 +1868,44 @@ def initVortexVelocity(phiObs, vel, center, radius):
     lib.call("mf_fields_vortex_velocity", vel.sx, vel.sy, vel.sz, phi.ctypes.data_as(ctypes.c_void_p), v.ctypes.data_as(ctypes.c_void_p),
              float(_f32(c.x)), float(_f32(c.y)), float(_f32(radius)))
     vel.data.copy_(torch.from_numpy(v).to(vel.data.device))
+
+
+# ---- mesh level sets as inflow (plugin/initplugins.cpp:132-152): include/open/manta_hip_meshsdf.h -----------------------------------
+_mesh_sdf_stats = {"sources": 0, "binned": 0, "rounds": 0}
+
+
+def lastMeshSdfStats():
+    """of the most recent meshSDF (Mesh.computeLevelset / getLevelset / applyMeshToGrid, densityInflowMesh*): `sources` generated,
+    `binned` (those inside the grid) and the flood fill's `rounds` (launches; the last one changed nothing)"""
+    return dict(_mesh_sdf_stats)
+
+
+def _inflow_mesh_sdf(name, flags, density, mesh, sigma, cutoff):
+    from .core import LevelsetGrid, Mesh
+    s = density.parent
+    lib = _extension_lib(s, name, "meshsdf")
+    _chk(flags, FlagGrid, "FlagGrid")
+    if not isinstance(mesh, Mesh):
+        raise RuntimeError("can't convert argument to Mesh*")
+    if not density.is3D():
+        raise RuntimeError("%s: 3-D grids only" % name)
+    density._check_same(flags)
+    sdf = LevelsetGrid(s)
+    mesh._mesh_sdf(lib, name, sdf, sigma, cutoff)
+    return lib, sdf
+
+
+@plugin
+def densityInflowMesh(flags, density, mesh, value=1., cutoff=7., sigma=0.):
+    """initplugins.cpp:147-152: computeLevelset(sdf, 2., cutoff), then fluid cells with sdf <= sigma take `value`"""
+    lib, sdf = _inflow_mesh_sdf("densityInflowMesh", flags, density, mesh, 2., cutoff)
+    lib.call("mf_meshsdf_apply_density", flags.sx, flags.sy, flags.sz, flags.ptr, density.ptr, sdf.ptr, float(value), float(sigma),
+             density.parent.stream)
+
+
+@plugin
+def densityInflowMeshNoise(flags, density, noise, mesh, scale=1.0, sigma=0.):
+    """initplugins.cpp:139-144: computeLevelset(sdf, 1.), then KnApplyNoiseInfl as densityInflow runs it"""
+    lib, sdf = _inflow_mesh_sdf("densityInflowMeshNoise", flags, density, mesh, 1., -1.)
+    lib.call("mf_density_inflow", flags.sx, flags.sy, flags.sz, flags.ptr, density.ptr, sdf.ptr, _ptr(noise._tile), noise._params(),
+             float(scale), float(sigma), density.parent.stream)
