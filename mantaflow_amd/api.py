@@ -23,7 +23,7 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       processBurn, updateFlame, calcSecDeriv2d, totalSum, normalizeSumTo, cgSolveWE, resetUvGrid, updateUvWeight,
                       getUvWeight, extrapolateSimpleFlags, initVortexVelocity,
                       PD_fluid_guiding, releaseBlurPrecomp, lastGuidingStats, getSpiralVelocity, setGradientYWeight,
-                      densityInflowMesh, densityInflowMeshNoise, lastMeshSdfStats)
+                      densityInflowMesh, densityInflowMeshNoise, lastMeshSdfStats, lastReinitStats)
 
 from .scene import (Box, Checkbox, Cylinder, Gui, NoiseField, Shape, Slider, Sphere, densityInflow, sampleFlagsWithParticles,
                     sampleLevelsetWithParticles, sampleShapeWithParticles)

@@ -11,6 +11,7 @@ the hot path goes through the C ABI (mantaflow_amd._lib).  Grids are dense, x fa
 vectors are structure-of-arrays ([3][N]); the reference's AoS [z][y][x][3] view exists only at the numpy bridge.
 """
 import ctypes
+import os
 import ctypes.util
 import gzip
 import math
@@ -211,6 +212,7 @@ class FluidSolver(PbClass):
         self.lib = SolverLib(_lib.get(), self)
         self.device = self.lib.device
         self._pool = {}    # dtype/ncomp -> list of free tensors  (GridStorage, fluidsolver.cpp:34-50)
+        self._reinit_ctr = None    # the eight device counters of LevelsetGrid.reinitMarching
         self._live = 0
         self.timings = {}
 
@@ -672,6 +674,58 @@ class LevelsetGrid(Grid):
         finally:
             for t in (node_off, tri_off, marks) + ((tmp,) if pooled_tmp else ()):
                 s._release("int", t)
+
+    _reinit_keep = None     # tests set a list: each march appends (dir, fmFlags, keys) as numpy copies
+
+    def reinitMarching(self, flags, maxTime=4.0, velTransport=None, ignoreWalls=False, correctOuterLayer=True, obstacleType=TypeObstacle):
+        """LevelsetGrid::reinitMarching, levelset.cpp:122-228: the inward march, SetUninitialized, the outward march (which transports
+        velTransport), SetUninitialized (include/open/manta_hip_reinit.h).  A march pops its heap on the device
+        in rounds of mutually distant cells and is bit-identical to the reference's serial loop; a march that cannot prove that for its
+        input, and every march under MF_REINIT_SERIAL=1, runs the literal loop on the host.  One scalar read-back per sub-round and one
+        per march; plugins.lastReinitStats() has the counts.  Scratch comes from the solver's pool."""
+        from . import plugins
+        s = self.parent
+        lib = plugins._extension_lib(s, "LevelsetGrid::reinitMarching", "reinit")
+        if not isinstance(flags, FlagGrid):
+            raise RuntimeError("can't convert argument to FlagGrid")
+        if velTransport is not None and not isinstance(velTransport, MACGrid):
+            raise RuntimeError("can't convert argument to MACGrid*")
+        self._check_same(flags)
+        if velTransport is not None:
+            self._check_same(velTransport)
+        maxTime = float(np.float32(maxTime))
+        serial = 1 if os.environ.get("MF_REINIT_SERIAL", "0") not in ("", "0") else 0
+        ints = [s._alloc("int", zero=False) for _ in range(5)]
+        reals = [s._alloc("real", zero=False) for _ in range(2)]
+        vecs = [s._alloc("vec", zero=False)] if velTransport is not None else []
+        fm, lst, sel, epoch, snap_fm = ints
+        key, snap_phi = reals
+        if s._reinit_ctr is None:
+            s._reinit_ctr = torch.zeros(8, dtype=torch.int32, device=s.device)
+        stats = {"windows": [0, 0], "subrounds": [0, 0], "pops": [0, 0], "serial": [0, 0], "launches": [0, 0], "readbacks": [0, 0]}
+        try:
+            out = (ctypes.c_int64 * 6)()
+            for q, d in enumerate((-1, 1)):
+                lib.call("mf_reinit_march", self.sx, self.sy, self.sz, self.ptr, flags.ptr, None if velTransport is None else velTransport.ptr,
+                         _ptr(fm), _ptr(key), _ptr(lst), _ptr(sel), _ptr(epoch), _ptr(snap_phi), _ptr(snap_fm), _ptr(vecs[0]) if vecs else None,
+                         _ptr(s._reinit_ctr), maxTime, d, int(bool(ignoreWalls)), int(bool(correctOuterLayer)), int(obstacleType), serial,
+                         out, s.stream)
+                for name, v in zip(("windows", "subrounds", "pops", "serial", "launches", "readbacks"), out):
+                    stats[name][q] = int(v)
+                if LevelsetGrid._reinit_keep is not None:
+                    LevelsetGrid._reinit_keep.append((d, fm.cpu().numpy().copy(), key.cpu().numpy().copy()))
+                val = float(np.float32(-np.float64(np.float32(maxTime)) - 1.)) if d < 0 else float(np.float32(np.float64(np.float32(maxTime)) + 1.))
+                lib.call("mf_reinit_set_uninitialized", self.sx, self.sy, self.sz, self.ptr, _ptr(fm), flags.ptr, val, int(bool(ignoreWalls)),
+                         int(obstacleType), s.stream)
+            plugins._reinit_stats = {k: tuple(stats[k]) for k in ("windows", "subrounds", "pops", "serial")}
+            plugins._reinit_work = {k: tuple(stats[k]) for k in ("launches", "readbacks")}
+        finally:
+            for t in ints:
+                s._release("int", t)
+            for t in reals:
+                s._release("real", t)
+            for t in vecs:
+                s._release("vec", t)
 
 
 class FlagGrid(IntGrid):

@@ -1909,3 +1909,14 @@ def densityInflowMeshNoise(flags, density, noise, mesh, scale=1.0, sigma=0.):
     lib, sdf = _inflow_mesh_sdf("densityInflowMeshNoise", flags, density, mesh, 1., -1.)
     lib.call("mf_density_inflow", flags.sx, flags.sy, flags.sz, flags.ptr, density.ptr, sdf.ptr, _ptr(noise._tile), noise._params(),
              float(scale), float(sigma), density.parent.stream)
+
+
+# ---- level-set reinitialisation (levelset.cpp:122-228): include/open/manta_hip_reinit.h; the method is LevelsetGrid.reinitMarching ------
+_reinit_stats = {"windows": (0, 0), "subrounds": (0, 0), "pops": (0, 0), "serial": (0, 0)}
+_reinit_work = {"launches": (0, 0), "readbacks": (0, 0)}      # kernel launches and scalar read-backs of the same call (tools/reinit_time.py)
+
+
+def lastReinitStats():
+    """of the most recent LevelsetGrid.reinitMarching, each a pair (inward march, outward march): `windows` of keys, `subrounds` (a
+    selecting and a popping launch each), `pops`, and `serial` (1: the literal loop ran on the host, and windows / subrounds are 0)"""
+    return dict(_reinit_stats)
