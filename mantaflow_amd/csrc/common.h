@@ -140,6 +140,40 @@ static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 // *out = the current device's block, grown to max(2 * cap, need) bytes where need > cap (after hipDeviceSynchronize; the old
 // contents are gone, *regrown says so, also on the error return of a failed allocation, which leaves p / cap at nullptr / 0).
 int arena_reserve(Arena* per_device, size_t need, Arena** out, bool* regrown = nullptr);
+// consecutive 256-byte-aligned typed slices of one scratch block (an arena's, or a caller's tmp) of `left` bytes: the layout of a
+// block is the order of its take() calls, and a slice that would pass the end of the block is refused
+struct Cutter {
+	char* p;
+	size_t left;
+	Cutter(void* base, size_t bytes) : p((char*)base), left(bytes) {}
+	template <class T, class... More>
+	int take(size_t count, T** out, More... more) {   // one slice of count elements for each pointer
+		const size_t b = al256(sizeof(T) * count);
+		if (b > left) return fail("scratch block: a slice of %zu bytes where %zu are left", b, left);
+		*out = (T*)p;
+		p += b;
+		left -= b;
+		if constexpr (sizeof...(more) > 0) return take(count, more...);
+		return 0;
+	}
+};
+// the caller-supplied scratch of the plan entries (createMesh, meshSDF, secondary particles): a 256-byte head for the results, then
+// the scan / sort workspace of ws_bytes
+struct HeadWs {
+	int64_t* head;
+	char* ws;
+	size_t ws_bytes;
+};
+static inline int64_t head_ws_bytes(size_t ws_bytes) { return 256 + (int64_t)al256(ws_bytes); }
+static inline int head_ws_cut(const char* who, void* tmp, int64_t tmp_bytes, int64_t need, HeadWs* out) {
+	if (!tmp || tmp_bytes < need) return fail("%s: scratch of %lld bytes, %lld needed", who, (long long)tmp_bytes, (long long)need);
+	Cutter c(tmp, (size_t)need);
+	MF_TRY(c.take(32, &out->head));
+	out->ws_bytes = c.left;
+	return c.take(c.left, &out->ws);
+}
+// asynchronous copy of device memory to the given host address, then a stream synchronise (runtime.hip)
+int read_back(void* host, const void* dev, size_t bytes, hipStream_t st);
 
 // ---- wave / block reductions (wave = 64 lanes) ---------------------------------------------------------
 __device__ __forceinline__ double wave_sum(double v) {

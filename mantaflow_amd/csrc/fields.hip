@@ -135,8 +135,7 @@ int mf_fields_total_sum(int sx, int sy, int sz, const float* h, float* sum_host,
 	MF_TRY(get_workspace(&ws));
 	const hipStream_t st = (hipStream_t)stream;
 	MF_TRY(interior_sum(mkdim(sx, sy, sz), h, ws, st));
-	MF_HIP(hipMemcpyAsync(ws->host, (double*)ws->scalars + 1, sizeof(float), hipMemcpyDeviceToHost, st));
-	MF_HIP(hipStreamSynchronize(st));
+	MF_TRY(read_back(ws->host, (double*)ws->scalars + 1, sizeof(float), st));
 	memcpy(sum_host, ws->host, sizeof(float));
 	return 0;
 }
@@ -181,8 +180,7 @@ int mf_fields_get_uv_weight(const float* uv, float* w_host, void* stream) {
 	Workspace* ws;
 	MF_TRY(get_workspace(&ws));
 	const hipStream_t st = (hipStream_t)stream;
-	MF_HIP(hipMemcpyAsync(ws->host, uv, sizeof(float), hipMemcpyDeviceToHost, st));
-	MF_HIP(hipStreamSynchronize(st));
+	MF_TRY(read_back(ws->host, uv, sizeof(float), st));
 	memcpy(w_host, ws->host, sizeof(float));
 	return 0;
 }

@@ -240,8 +240,7 @@ int mf_guiding_post(int64_t n, const float* z, const float* z0, float* y, float 
 	hipLaunchKernelGGL(k_guiding_post, dim3(nb), dim3(BLOCK), 0, st, n, z, z0, y, theta, ws->fpartials);
 	hipLaunchKernelGGL(k_guiding_post_finish, dim3(1), dim3(BLOCK), 0, st, nb, ws->fpartials, (float*)ws->scalars);
 	MF_LAUNCH_CHECK();
-	MF_HIP(hipMemcpyAsync(ws->host, ws->scalars, 2 * sizeof(float), hipMemcpyDeviceToHost, st));
-	MF_HIP(hipStreamSynchronize(st));
+	MF_TRY(read_back(ws->host, ws->scalars, 2 * sizeof(float), st));
 	const float* h = (const float*)ws->host;
 	out_host[0] = sqrtf(h[0]);
 	out_host[1] = sqrtf(h[1]);

@@ -307,19 +307,21 @@ int mf_idp_mark(int sx, int sy, int sz, int32_t* flags, float* deltaX, const flo
 	const Dim d = mkdim(sx, sy, sz);
 	hipStream_t st = (hipStream_t)stream;
 	if (np < 0 || pstride < np || np >= ((int64_t)1 << 31)) return fail("markFluidAndBoundaryCells: bad particle range (np %lld, stride %lld)", (long long)np, (long long)pstride);
-	const size_t wl = al256(sizeof(int32_t) * (size_t)(np > 0 ? np : 1)), wo = al256(sizeof(int32_t) * 3 * (size_t)d.n);
+	const size_t nl = np > 0 ? np : 1, need = 256 + al256(sizeof(int32_t) * nl) + al256(sizeof(int32_t) * 3 * (size_t)d.n);
 	Arena* a;
-	MF_TRY(arena_reserve(g_arena, 256 + wl + wo, &a));
-	unsigned long long* cnt = (unsigned long long*)a->p;
-	int32_t* list = (int32_t*)(a->p + 256);
-	int32_t* owner = (int32_t*)(a->p + 256 + wl);
+	MF_TRY(arena_reserve(g_arena, need, &a));
+	Cutter c(a->p, need);
+	unsigned long long* cnt;
+	int32_t *list, *owner;
+	MF_TRY(c.take(32, &cnt));
+	MF_TRY(c.take(nl, &list));
+	MF_TRY(c.take(3 * (size_t)d.n, &owner));
 	MF_HIP(hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned long long), st));
 	MF_HIP(hipMemsetAsync(deltaX, 0, sizeof(float) * 3 * d.n, st));
 	hipLaunchKernelGGL(k_clear_fluid, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d.n, flags);
 	if (np > 0) hipLaunchKernelGGL(k_mark, dim3(nblk(np)), dim3(BLOCK), 0, st, d, flags, np, pstride, pos, pflag, ptype, exclude, list, cnt);
 	MF_LAUNCH_CHECK();
-	MF_HIP(hipMemcpyAsync(result_host, cnt, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-	MF_HIP(hipStreamSynchronize(st));
+	MF_TRY(read_back(result_host, cnt, sizeof(int64_t), st));
 	const int64_t nb = result_host[0];
 	result_host[1] = 0;
 	if (nb > 0) {
@@ -329,8 +331,7 @@ int mf_idp_mark(int sx, int sy, int sz, int32_t* flags, float* deltaX, const flo
 		hipLaunchKernelGGL((k_push<2>), g, b, 0, st, d, phiObs, nb, list, pstride, pos, deltaX, owner, cnt);
 		hipLaunchKernelGGL((k_push<3>), g, b, 0, st, d, phiObs, nb, list, pstride, pos, deltaX, owner, cnt);
 		MF_LAUNCH_CHECK();
-		MF_HIP(hipMemcpyAsync(result_host + 1, cnt + 1, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-		MF_HIP(hipStreamSynchronize(st));
+		MF_TRY(read_back(result_host + 1, cnt + 1, sizeof(int64_t), st));
 	}
 	return 0;
 }
@@ -343,9 +344,12 @@ int mf_idp_map_weights(int sx, int sy, int sz, float* density, int64_t np, int64
 	MF_HIP(hipMemsetAsync(density, 0, sizeof(float) * d.n, st));
 	if (np <= 0) return 0;
 	// the value grid of the transfer (knMapLinear's `tmp` role swapped: it receives the weighted sources) is discarded
+	const size_t need = al256(sizeof(float) * (size_t)d.n);
 	Arena* a;
-	MF_TRY(arena_reserve(g_arena, al256(sizeof(float) * (size_t)d.n), &a));
-	return p2g_ordered_cell(d, 1, (float*)a->p, density, np, pstride, pos, pflag, psrc, st);
+	MF_TRY(arena_reserve(g_arena, need, &a));
+	float* values;
+	MF_TRY(Cutter(a->p, need).take(d.n, &values));
+	return p2g_ordered_cell(d, 1, values, density, np, pstride, pos, pflag, psrc, st);
 }
 
 int mf_idp_compute_density(int sx, int sy, int sz, float* density, int32_t* flags, const float* deltaX, float dt, float mass,
@@ -353,13 +357,15 @@ int mf_idp_compute_density(int sx, int sy, int sz, float* density, int32_t* flag
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
 	hipStream_t st = (hipStream_t)stream;
-	const size_t wc = al256(sizeof(int32_t) * (size_t)d.n);
+	const size_t need = 256 + 4 * al256(sizeof(int32_t) * (size_t)d.n);
 	Arena* a;
-	MF_TRY(arena_reserve(g_arena, 256 + 4 * wc, &a));
-	unsigned long long* cnt = (unsigned long long*)a->p;
-	int32_t* f0 = (int32_t*)(a->p + 256);
-	int32_t* state = (int32_t*)(a->p + 256 + wc);
-	int32_t* cand = (int32_t*)(a->p + 256 + 2 * wc);   // 2 n words: the list, and its copy that keeps the cell of a decided slot
+	MF_TRY(arena_reserve(g_arena, need, &a));
+	Cutter c(a->p, need);
+	unsigned long long* cnt;
+	int32_t *f0, *state, *cand;
+	MF_TRY(c.take(32, &cnt));
+	MF_TRY(c.take(d.n, &f0, &state));
+	MF_TRY(c.take(2 * (size_t)d.n, &cand));   // 2 n words: the list, and its copy that keeps the cell of a decided slot
 	MF_HIP(hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned long long), st));
 	MF_HIP(hipMemcpyAsync(f0, flags, sizeof(int32_t) * d.n, hipMemcpyDeviceToDevice, st));   // FlagGrid flagsTmp(flags), :162
 	const dim3 g(nblk(d.n)), b(BLOCK);
@@ -370,9 +376,7 @@ int mf_idp_compute_density(int sx, int sy, int sz, float* density, int32_t* flag
 	}
 	hipLaunchKernelGGL(k_density_final, g, b, 0, st, d, density, f0, flags, deltaX, dt, mass, noDensityClamping, cnt);
 	MF_LAUNCH_CHECK();
-	MF_HIP(hipMemcpyAsync(result_host, cnt, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-	MF_HIP(hipStreamSynchronize(st));
-	return 0;
+	return read_back(result_host, cnt, 4 * sizeof(int64_t), st);
 }
 
 int mf_idp_compute_delta_x(int sx, int sy, int sz, const int32_t* flags, float* deltaX, float* Lambda, void* stream) {

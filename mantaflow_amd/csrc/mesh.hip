@@ -3,7 +3,7 @@
 // The per-cell bodies are in mesh_cells.h.  Reference: levelset.cpp:330-415, mesh.cpp:301-373, util/integrator.h:26-78.
 #include "mesh_cells.h"
 #include "../../include/open/manta_hip_mesh.h"
-#include <hipcub/hipcub.hpp>
+#include "scan.h"
 
 using namespace mf;
 using namespace mf::mesh;
@@ -131,8 +131,8 @@ int mf_mesh_abi_version(void) { return MF_MESH_ABI_VERSION; }
 int mf_mesh_scan_bytes(int sx, int sy, int sz, int64_t* bytes_host) {
 	MF_TRY(check_mesh_grid("createMesh", sx, sy, sz));
 	size_t b = 0;
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b, (int32_t*)nullptr, (int32_t*)nullptr, (int)((int64_t)sx * sy * sz), (hipStream_t)0));
-	*bytes_host = 256 + (int64_t)al256(b);
+	MF_TRY(exclusive_sum32_bytes((int64_t)sx * sy * sz, &b));
+	*bytes_host = head_ws_bytes(b);
 	return 0;
 }
 
@@ -140,22 +140,18 @@ int mf_mesh_create_plan(int sx, int sy, int sz, const float* phi, void* cube, vo
                         int64_t tmp_bytes, int64_t* totals_host, void* stream) {
 	int64_t need = 0;
 	MF_TRY(mf_mesh_scan_bytes(sx, sy, sz, &need));
-	if (!tmp || tmp_bytes < need) return fail("createMesh: scan scratch of %lld bytes, %lld needed", (long long)tmp_bytes, (long long)need);
 	const Dim d = mkdim(sx, sy, sz);
 	const hipStream_t st = (hipStream_t)stream;
-	int64_t* res = (int64_t*)tmp;
-	void* cub = (char*)tmp + 256;
-	size_t cub_bytes = (size_t)(need - 256);
+	HeadWs t;
+	MF_TRY(head_ws_cut("createMesh", tmp, tmp_bytes, need, &t));
 	hipLaunchKernelGGL(k_classify, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d, phi, (uint8_t*)cube);
 	hipLaunchKernelGGL(k_count, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d, (const uint8_t*)cube, (uint16_t*)mask, nodeOff, triOff);
 	MF_LAUNCH_CHECK();
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, nodeOff, nodeOff, (int)d.n, st));
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, triOff, triOff, (int)d.n, st));
-	hipLaunchKernelGGL(k_totals, dim3(1), dim3(64), 0, st, d.n, (const uint8_t*)cube, (const uint16_t*)mask, nodeOff, triOff, res);
+	MF_TRY(exclusive_sum(t.ws, t.ws_bytes, nodeOff, nodeOff, d.n, st));
+	MF_TRY(exclusive_sum(t.ws, t.ws_bytes, triOff, triOff, d.n, st));
+	hipLaunchKernelGGL(k_totals, dim3(1), dim3(64), 0, st, d.n, (const uint8_t*)cube, (const uint16_t*)mask, nodeOff, triOff, t.head);
 	MF_LAUNCH_CHECK();
-	MF_HIP(hipMemcpyAsync(totals_host, res, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-	MF_HIP(hipStreamSynchronize(st));
-	return 0;
+	return read_back(totals_host, t.head, 2 * sizeof(int64_t), st);
 }
 
 int mf_mesh_create_emit(int sx, int sy, int sz, const float* phi, const void* cube, const void* mask, const int32_t* nodeOff,

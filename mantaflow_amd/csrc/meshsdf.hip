@@ -4,7 +4,7 @@
 // launch changes nothing.  The per-item bodies are in meshsdf_cells.h.  Reference: mesh.cpp:769-1005, plugin/initplugins.cpp:132-152.
 #include "meshsdf_cells.h"
 #include "../../include/open/manta_hip_meshsdf.h"
-#include <hipcub/hipcub.hpp>
+#include "scan.h"
 
 using namespace mf;
 using namespace mf::meshsdf;
@@ -180,39 +180,15 @@ int check_mesh(const char* who, int64_t nTris, int64_t tcap, int64_t nNodes, int
 	if (nTris >= (int64_t)1 << 31) return fail("%s: too many triangles", who);
 	return 0;
 }
-int key_bits(int64_t n) {
-	int b = 1;
-	while (((int64_t)1 << b) <= n) b++;
-	return b;
-}
-size_t scan64_bytes(int64_t n) {
-	size_t b = 0;
-	(void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, (int)n, (hipStream_t)0);
-	return b;
-}
-size_t scan32_bytes(int64_t n) {
-	size_t b = 0;
-	(void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (int32_t*)nullptr, (int32_t*)nullptr, (int)n, (hipStream_t)0);
-	return b;
-}
-size_t sort_bytes(int64_t n, int bits) {
-	size_t b = 0;
-	(void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int)n, 0,
-	                                         bits, (hipStream_t)0);
-	return b;
-}
+// the largest workspace of the source-offset scan (nTris), the cell-start scan (nCells) and the source sort (nSrc), behind the head.
+// The errors of the queries (no device) are passed over: mf_meshsdf_tmp_bytes answers without a GPU, and the entries that use the
+// scratch fail at their first launch there
 int64_t tmp_need(int64_t nTris, int64_t nSrc, int64_t nCells) {
 	size_t b = 0;
-	if (nTris > 0) b = scan64_bytes(nTris);
-	if (nCells > 0) {
-		const size_t c = scan32_bytes(nCells);
-		b = c > b ? c : b;
-	}
-	if (nSrc > 0) {
-		const size_t c = sort_bytes(nSrc, key_bits(nCells));
-		b = c > b ? c : b;
-	}
-	return 256 + (int64_t)al256(b);
+	if (nTris > 0) (void)exclusive_sum64_bytes(nTris, &b);
+	if (nCells > 0) (void)exclusive_sum32_bytes(nCells, &b);
+	if (nSrc > 0) (void)sort_pairs_bytes(nSrc, key_bits(nCells), &b);
+	return head_ws_bytes(b);
 }
 
 }  // namespace
@@ -234,23 +210,21 @@ int mf_meshsdf_plan(int64_t nTris, int64_t tcap, const int32_t* tri, int64_t nNo
 	*total_host = 0;
 	if (nTris == 0) return 0;
 	const int64_t need = tmp_need(nTris, 0, 0);
-	if (!tmp || tmp_bytes < need) return fail("meshSDF: scan scratch of %lld bytes, %lld needed", (long long)tmp_bytes, (long long)need);
 	const hipStream_t st = (hipStream_t)stream;
 	// the head of tmp: res[0] the flags of k_src_count (its low int), res[1] the total, res[2] the last triangle's count
-	int64_t* res = (int64_t*)tmp;
-	void* cub = (char*)tmp + 256;
-	size_t cub_bytes = (size_t)(tmp_bytes - 256);
+	HeadWs t;
+	MF_TRY(head_ws_cut("meshSDF", tmp, tmp_bytes, need, &t));
+	int64_t* res = t.head;
 	const TriView T = {nTris, tcap, nNodes, ncap, tri, pos};
 	MF_HIP(hipMemsetAsync(res, 0, 256, st));
 	hipLaunchKernelGGL(k_src_count, dim3((unsigned)((nTris + TRIS_PER_BLOCK - 1) / TRIS_PER_BLOCK)), dim3(BLOCK), 0, st, T, off, (int32_t*)res);
 	hipLaunchKernelGGL(k_src_keep_last, dim3(1), dim3(64), 0, st, nTris, (const int64_t*)off, res + 2);
 	MF_LAUNCH_CHECK();
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, off, off, (int)nTris, st));
+	MF_TRY(exclusive_sum(t.ws, t.ws_bytes, off, off, nTris, st));
 	hipLaunchKernelGGL(k_src_total, dim3(1), dim3(64), 0, st, nTris, (const int64_t*)off, (const int64_t*)(res + 2), res);
 	MF_LAUNCH_CHECK();
 	int64_t host[2] = {0, 0};
-	MF_HIP(hipMemcpyAsync(host, res, sizeof(host), hipMemcpyDeviceToHost, st));
-	MF_HIP(hipStreamSynchronize(st));
+	MF_TRY(read_back(host, res, sizeof(host), st));
 	if (host[0] & 1) return fail("meshSDF: a triangle names a node outside the mesh's %lld nodes", (long long)nNodes);
 	if (host[0] & 2) return fail("meshSDF: a triangle edge of 43690 units or more: its sample count does not fit the reference's short");
 	if (host[1] >= (int64_t)1 << 31) return fail("meshSDF: %lld sources do not fit 32-bit source numbers", (long long)host[1]);
@@ -276,10 +250,9 @@ int mf_meshsdf_bin(int sx, int sy, int sz, int64_t nSrc, int64_t scap, const flo
 	if (nSrc < 0 || scap < nSrc || nSrc >= (int64_t)1 << 31) return fail("meshSDF: %lld sources in arrays of stride %lld", (long long)nSrc, (long long)scap);
 	const Dim d = mkdim(sx, sy, sz);
 	const int64_t need = tmp_need(0, nSrc, d.n);
-	if (!tmp || tmp_bytes < need) return fail("meshSDF: scratch of %lld bytes, %lld needed", (long long)tmp_bytes, (long long)need);
 	const hipStream_t st = (hipStream_t)stream;
-	void* cub = (char*)tmp + 256;
-	size_t cub_bytes = (size_t)(tmp_bytes - 256);
+	HeadWs t;   // the binning leaves the head alone
+	MF_TRY(head_ws_cut("meshSDF", tmp, tmp_bytes, need, &t));
 	const int64_t nocc = (int64_t)occ_dim(sx) * occ_dim(sy) * occ_dim(sz);
 	MF_HIP(hipMemsetAsync(len, 0, d.n * sizeof(int32_t), st));
 	MF_HIP(hipMemsetAsync(occ, 0, nocc * sizeof(int32_t), st));
@@ -291,12 +264,12 @@ int mf_meshsdf_bin(int sx, int sy, int sz, int64_t nSrc, int64_t scap, const flo
 		hipLaunchKernelGGL(k_bin_key, dim3(nblk(nSrc)), dim3(BLOCK), 0, st, d, nSrc, scap, spos, key, val, len, occ);
 		MF_LAUNCH_CHECK();
 	}
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, len, start, (int)d.n, st));
+	MF_TRY(exclusive_sum(t.ws, t.ws_bytes, len, start, d.n, st));
 	hipLaunchKernelGGL(k_bin_total, dim3(1), dim3(64), 0, st, d.n, (const int32_t*)len, (const int32_t*)start, stats);
 	MF_LAUNCH_CHECK();
 	if (nSrc > 0) {
 		// stable: within a cell the sources keep their order; the dropped ones (key n) come last
-		MF_HIP(hipcub::DeviceRadixSort::SortPairs(cub, cub_bytes, key, key2, val, val2, (int)nSrc, 0, key_bits(d.n), st));
+		MF_TRY(sort_pairs(t.ws, t.ws_bytes, key, key2, val, val2, nSrc, key_bits(d.n), st));
 		hipLaunchKernelGGL(k_bin_reorder, dim3(nblk(nSrc)), dim3(BLOCK), 0, st, d.n, nSrc, scap, (const uint32_t*)key2, (const int32_t*)val2, spos,
 		                   snrm, bpos, bnrm);
 		MF_LAUNCH_CHECK();
@@ -324,8 +297,7 @@ int mf_meshsdf_flood(int sx, int sy, int sz, float* phi, float sigma, float cuto
 	out_host[0] = 0;
 	int32_t host[2] = {0, 0};
 	if (!flood) {
-		MF_HIP(hipMemcpyAsync(host, stats, sizeof(host), hipMemcpyDeviceToHost, st));
-		MF_HIP(hipStreamSynchronize(st));
+		MF_TRY(read_back(host, stats, sizeof(host), st));
 		out_host[1] = host[0];
 		return 0;
 	}
@@ -337,8 +309,7 @@ int mf_meshsdf_flood(int sx, int sy, int sz, float* phi, float sigma, float cuto
 		MF_HIP(hipMemsetAsync(stats + 1, 0, sizeof(int32_t), st));
 		hipLaunchKernelGGL(k_flood_round, tiles, dim3(FLOOD_THREADS), 0, st, d, phi, c, stats + 1);
 		MF_LAUNCH_CHECK();
-		MF_HIP(hipMemcpyAsync(host, stats, sizeof(host), hipMemcpyDeviceToHost, st));
-		MF_HIP(hipStreamSynchronize(st));
+		MF_TRY(read_back(host, stats, sizeof(host), st));
 		out_host[0]++;
 		if (host[1] == 0) break;
 	}

@@ -184,8 +184,7 @@ int mf_reinit_march(int sx, int sy, int sz, float* phi, const int32_t* flags, fl
 		hipLaunchKernelGGL(k_reinit_seed, cells, blk, 0, st, m, outer, list, ctr);
 		MF_LAUNCH_CHECK();
 		launches++;
-		MF_HIP(hipMemcpyAsync(host, ctr, sizeof(host), hipMemcpyDeviceToHost, st));
-		MF_HIP(hipStreamSynchronize(st));
+		MF_TRY(read_back(host, ctr, sizeof(host), st));
 		readbacks++;
 		int64_t count = host[C_COUNT];
 		for (bool done = count == 0; !done && !flagged;) {
@@ -198,8 +197,7 @@ int mf_reinit_march(int sx, int sy, int sz, float* phi, const int32_t* flags, fl
 				hipLaunchKernelGGL(k_reinit_pop, dim3(nblk(count)), blk, 0, st, m, (int)(windows + first), list, (const int32_t*)sel, ctr);
 				MF_LAUNCH_CHECK();
 				launches += 2;
-				MF_HIP(hipMemcpyAsync(host, ctr, sizeof(host), hipMemcpyDeviceToHost, st));
-				MF_HIP(hipStreamSynchronize(st));
+				MF_TRY(read_back(host, ctr, sizeof(host), st));
 				readbacks++;
 				if (host[C_LIVE] == 0) {
 					done = true;

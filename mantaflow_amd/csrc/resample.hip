@@ -4,7 +4,7 @@
 // source/levelset.cpp.  The formulation is stated in DESIGN.md ("Particle resampling").
 #include "common.h"
 #include "../../include/manta_hip_resample.h"
-#include <hipcub/hipcub.hpp>
+#include "scan.h"
 
 using namespace mf;
 
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(BLOCK) void k_move(int64_t H, const int32_t* __rest
 static int plan_launch(Plan* plan, int64_t np, const int32_t* pflag, int32_t* A, int32_t* holes, int32_t* fillers, void* cub,
                        size_t cub_bytes, int64_t* res, int needs_hit, hipStream_t st) {
 	hipLaunchKernelGGL(k_alive, dim3(nblk(np)), dim3(BLOCK), 0, st, np, pflag, A);
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, A, A, (int)np, st));
+	MF_TRY(exclusive_sum(cub, cub_bytes, A, A, np, st));
 	hipLaunchKernelGGL(k_plan, dim3(nblk(np)), dim3(BLOCK), 0, st, np, pflag, A, holes, fillers, res, needs_hit);
 	MF_LAUNCH_CHECK();
 	plan->holes = holes;
@@ -270,12 +270,6 @@ __global__ __launch_bounds__(BLOCK) void k_pdata_init(Dim d, const float* __rest
 	}
 }
 
-static int bits_for(int64_t nc) {
-	int end_bit = 1;
-	while (end_bit < 31 && (((int64_t)1 << end_bit) <= nc)) end_bit++;
-	return end_bit;
-}
-
 }  // namespace
 
 extern "C" {
@@ -327,33 +321,27 @@ int mf_resample_round(int sx, int sy, int sz, const float* phi, int32_t* tmp, in
 		result_host[3] = 0;
 		return 0;
 	}
-	const int nc = (int)d.n, end_bit = bits_for(nc);
+	const int nc = (int)d.n, end_bit = key_bits(nc);
 	// arena: 6 arrays of np words (keys, sorted keys, vals, sorted vals, cls, kill; the prefix reuses sorted keys, the plan reuses
-	// keys / vals / sorted vals), cnt and start of nc + 1 words, the result block, the hipcub workspace
-	size_t scan_m = 0, scan_c = 0, scan_p = 0, sort_b = 0;
-	MF_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, scan_m, (int32_t*)nullptr, (int32_t*)nullptr, (int)m, st));
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_c, (int32_t*)nullptr, (int32_t*)nullptr, nc + 1, st));
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_p, (int32_t*)nullptr, (int32_t*)nullptr, (int)np, st));
-	MF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
-	                                          (int)m, 0, end_bit, st));
-	size_t cub_bytes = scan_m > scan_c ? scan_m : scan_c;
-	if (scan_p > cub_bytes) cub_bytes = scan_p;
-	if (sort_b > cub_bytes) cub_bytes = sort_b;
+	// keys / vals / sorted vals), cnt and start of nc + 1 words, the result block, the scan / sort workspace
+	size_t cub_bytes = 0;
+	MF_TRY(inclusive_sum32_bytes(m, &cub_bytes));
+	MF_TRY(exclusive_sum32_bytes(nc + 1, &cub_bytes));
+	MF_TRY(exclusive_sum32_bytes(np, &cub_bytes));
+	MF_TRY(sort_pairs_bytes(m, end_bit, &cub_bytes));
 	const size_t wp = al256(sizeof(int32_t) * (size_t)np), wc = al256(sizeof(int32_t) * ((size_t)nc + 1));
+	const size_t need = 6 * wp + 2 * wc + 256 + al256(cub_bytes);
 	Arena* a;
 	Plan* plan;
-	MF_TRY(arena(6 * wp + 2 * wc + 256 + al256(cub_bytes), &a, &plan));
-	char* b = a->p;
-	int32_t* keys = (int32_t*)b;
-	int32_t* skeys = (int32_t*)(b + wp);
-	int32_t* vals = (int32_t*)(b + 2 * wp);
-	int32_t* svals = (int32_t*)(b + 3 * wp);
-	int32_t* cls = (int32_t*)(b + 4 * wp);
-	int32_t* kill = (int32_t*)(b + 5 * wp);
-	int32_t* cnt = (int32_t*)(b + 6 * wp);
-	int32_t* start = (int32_t*)(b + 6 * wp + wc);
-	int64_t* res = (int64_t*)(b + 6 * wp + 2 * wc);
-	void* cub = b + 6 * wp + 2 * wc + 256;
+	MF_TRY(arena(need, &a, &plan));
+	Cutter c(a->p, need);
+	int32_t *keys, *skeys, *vals, *svals, *cls, *kill, *cnt, *start;
+	int64_t* res;
+	char* cub;
+	MF_TRY(c.take(np, &keys, &skeys, &vals, &svals, &cls, &kill));
+	MF_TRY(c.take(nc + 1, &cnt, &start));
+	MF_TRY(c.take(32, &res));
+	MF_TRY(c.take(cub_bytes, &cub));
 	int32_t* pre = skeys;   // free once k_decide has read the sorted keys
 
 	MF_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * ((size_t)nc + 1), st));
@@ -361,20 +349,18 @@ int mf_resample_round(int sx, int sy, int sz, const float* phi, int32_t* tmp, in
 	MF_HIP(hipMemsetAsync(res + 1, 0, 3 * sizeof(int64_t), st));
 	const dim3 gm(nblk(m)), bl(BLOCK);
 	hipLaunchKernelGGL(k_classify, gm, bl, 0, st, d, phi, m, pstride, pos, pflag, i0, narrowBand, surfaceLs, keys, vals, cls, cnt);
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, scan_c, cnt, start, nc + 1, st));
-	MF_HIP(hipcub::DeviceRadixSort::SortPairs(cub, sort_b, keys, skeys, vals, svals, (int)m, 0, end_bit, st));
+	MF_TRY(exclusive_sum(cub, cub_bytes, cnt, start, nc + 1, st));
+	MF_TRY(sort_pairs(cub, cub_bytes, (uint32_t*)keys, (uint32_t*)skeys, vals, svals, m, end_bit, st));
 	hipLaunchKernelGGL(k_decide, gm, bl, 0, st, m, nc, skeys, svals, start, tmp, maxParticles, cls, kill);
-	MF_HIP(hipcub::DeviceScan::InclusiveSum(cub, scan_m, kill, pre, (int)m, st));
+	MF_TRY(inclusive_sum(cub, cub_bytes, kill, pre, m, st));
 	hipLaunchKernelGGL(k_find, gm, bl, 0, st, m, kill, pre, mDeletes, mDeleteChunk, res);
 	hipLaunchKernelGGL(k_apply, gm, bl, 0, st, m, i0, keys, cls, kill, pre, res, pflag, tmp);
 	MF_LAUNCH_CHECK();
 	// the plan of the whole array; its kernels do nothing when the round had no hit
-	MF_TRY(plan_launch(plan, np, pflag, svals, keys, vals, cub, scan_p, res, 1, st));
+	MF_TRY(plan_launch(plan, np, pflag, svals, keys, vals, cub, cub_bytes, res, 1, st));
 	hipLaunchKernelGGL(k_round_finish, dim3(1), dim3(1), 0, st, i0, np, res);
 	MF_LAUNCH_CHECK();
-	MF_HIP(hipMemcpyAsync(result_host, res, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-	MF_HIP(hipStreamSynchronize(st));
-	return 0;
+	return read_back(result_host, res, 4 * sizeof(int64_t), st);
 }
 
 int mf_particles_compress_plan(int64_t np, const int32_t* pflag, int64_t* result_host, void* stream) {
@@ -385,18 +371,21 @@ int mf_particles_compress_plan(int64_t np, const int32_t* pflag, int64_t* result
 	}
 	if (np >= ((int64_t)1 << 31)) return fail("compress: too many particles for 32-bit indices");
 	size_t scan_p = 0;
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_p, (int32_t*)nullptr, (int32_t*)nullptr, (int)np, st));
-	const size_t wp = al256(sizeof(int32_t) * (size_t)np);
+	MF_TRY(exclusive_sum32_bytes(np, &scan_p));
+	const size_t need = 3 * al256(sizeof(int32_t) * (size_t)np) + 256 + al256(scan_p);
 	Arena* a;
 	Plan* plan;
-	MF_TRY(arena(3 * wp + 256 + al256(scan_p), &a, &plan));
-	char* b = a->p;
-	int64_t* res = (int64_t*)(b + 3 * wp);
+	MF_TRY(arena(need, &a, &plan));
+	Cutter c(a->p, need);
+	int32_t *A, *holes, *fillers;
+	int64_t* res;
+	char* cub;
+	MF_TRY(c.take(np, &A, &holes, &fillers));
+	MF_TRY(c.take(32, &res));
+	MF_TRY(c.take(scan_p, &cub));
 	MF_HIP(hipMemsetAsync(res, 0, 4 * sizeof(int64_t), st));
-	MF_TRY(plan_launch(plan, np, pflag, (int32_t*)b, (int32_t*)(b + wp), (int32_t*)(b + 2 * wp), b + 3 * wp + 256, scan_p, res, 0, st));
-	MF_HIP(hipMemcpyAsync(result_host, res + 2, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-	MF_HIP(hipStreamSynchronize(st));
-	return 0;
+	MF_TRY(plan_launch(plan, np, pflag, A, holes, fillers, cub, scan_p, res, 0, st));
+	return read_back(result_host, res + 2, 2 * sizeof(int64_t), st);
 }
 
 int mf_particles_compress_move(int64_t holes, int ncomp, int64_t pstride, void* data, void* stream) {
@@ -419,25 +408,27 @@ int mf_resample_seed_plan(int sx, int sy, int sz, const int32_t* flags, const fl
 	const Dim d = mkdim(sx, sy, sz);
 	hipStream_t st = (hipStream_t)stream;
 	size_t scan_c = 0;
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_c, (int32_t*)nullptr, (int32_t*)nullptr, (int)d.n, st));
-	const size_t wc = al256(sizeof(int32_t) * (size_t)d.n);
+	MF_TRY(exclusive_sum32_bytes(d.n, &scan_c));
+	const size_t need_bytes = al256(sizeof(int32_t) * (size_t)d.n) + 256 + al256(scan_c);
 	// a compress plan is pending only between a round and its moves; seeding comes after them and takes the arena over
 	Arena* a;
 	Plan* plan;
-	MF_TRY(arena(wc + 256 + al256(scan_c), &a, &plan));
+	MF_TRY(arena(need_bytes, &a, &plan));
 	plan->holes = plan->fillers = nullptr;
-	char* b = a->p;
-	int32_t* need = (int32_t*)b;
-	int64_t* res = (int64_t*)(b + wc);
+	Cutter c(a->p, need_bytes);
+	int32_t* need;
+	int64_t* res;
+	char* cub;
+	MF_TRY(c.take(d.n, &need));
+	MF_TRY(c.take(32, &res));
+	MF_TRY(c.take(scan_c, &cub));
 	if (np > 0) hipLaunchKernelGGL(k_clear_new, dim3(nblk(np)), dim3(BLOCK), 0, st, np, pflag);
 	hipLaunchKernelGGL(k_seed_need, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d.n, flags, phi, exclude, tmp, minParticles, narrowBand,
 	                   surfaceLs, need);
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(b + wc + 256, scan_c, need, offsets, (int)d.n, st));
+	MF_TRY(exclusive_sum(cub, scan_c, need, offsets, d.n, st));
 	hipLaunchKernelGGL(k_seed_total, dim3(1), dim3(1), 0, st, d.n, need, offsets, res);
 	MF_LAUNCH_CHECK();
-	MF_HIP(hipMemcpyAsync(total_host, res, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-	MF_HIP(hipStreamSynchronize(st));
-	return 0;
+	return read_back(total_host, res, sizeof(int64_t), st);
 }
 
 int mf_resample_seed_insert(int sx, int sy, int sz, const int32_t* offsets, const float* reals, int64_t np, int64_t total,

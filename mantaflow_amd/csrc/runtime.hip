@@ -305,9 +305,14 @@ __global__ void __launch_bounds__(BLOCK) k_maxabs_finish64(int nb, const float* 
 	}
 }
 
+int mf::read_back(void* host, const void* dev, size_t bytes, hipStream_t st) {
+	MF_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+	MF_HIP(hipStreamSynchronize(st));
+	return 0;
+}
+// the same through the pinned page
 static int read_back(Workspace* ws, const void* dev, size_t bytes, void* host_out, hipStream_t s) {
-	MF_HIP(hipMemcpyAsync(ws->host, dev, bytes, hipMemcpyDeviceToHost, s));
-	MF_HIP(hipStreamSynchronize(s));
+	MF_TRY(mf::read_back(ws->host, dev, bytes, s));
 	memcpy(host_out, ws->host, bytes);
 	return 0;
 }

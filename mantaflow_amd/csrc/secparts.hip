@@ -5,7 +5,7 @@
 // error bound of the sampled positions.
 #include "common.h"
 #include "../../include/manta_hip_secparts.h"
-#include <hipcub/hipcub.hpp>
+#include "scan.h"
 #include <limits.h>
 
 using namespace mf;
@@ -410,9 +410,7 @@ static int kills_begin(unsigned long long** cnt, hipStream_t st) {
 }
 static int kills_end(unsigned long long* cnt, int64_t* kills_host, hipStream_t st) {
 	MF_LAUNCH_CHECK();
-	MF_HIP(hipMemcpyAsync(kills_host, cnt, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-	MF_HIP(hipStreamSynchronize(st));
-	return 0;
+	return read_back(kills_host, cnt, sizeof(int64_t), st);
 }
 static int check_particles(const char* who, int64_t np, int64_t pstride) {
 	if (np < 0 || pstride < np) return fail("%s: bad particle range (np %lld, stride %lld)", who, (long long)np, (long long)pstride);
@@ -454,8 +452,8 @@ int mf_secparts_potentials(int sx, int sy, int sz, float* potTA, float* potWC, f
 int mf_secparts_scan_bytes(int64_t entries, int64_t* bytes_host) {
 	if (entries <= 0 || entries >= ((int64_t)1 << 31)) return fail("flipSampleSecondaryParticles: %lld plan entries", (long long)entries);
 	size_t b = 0;
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, (int)entries, (hipStream_t)0));
-	*bytes_host = 256 + (int64_t)((b + 255) & ~(size_t)255);
+	MF_TRY(exclusive_sum64_bytes(entries, &b));
+	*bytes_host = head_ws_bytes(b);
 	return 0;
 }
 
@@ -469,20 +467,16 @@ int mf_secparts_sample_plan(int sx, int sy, int sz, int multiple, const int32_t*
 	const int64_t entries = multiple ? 8 * d.n : d.n;
 	int64_t need = 0;
 	MF_TRY(mf_secparts_scan_bytes(entries, &need));
-	if (!tmp || tmp_bytes < need) return fail("flipSampleSecondaryParticles: scan scratch of %lld bytes, %lld needed", (long long)tmp_bytes, (long long)need);
-	int64_t* res = (int64_t*)tmp;
-	void* cub = (char*)tmp + 256;
-	size_t cub_bytes = (size_t)(need - 256);
+	HeadWs t;
+	MF_TRY(head_ws_cut("flipSampleSecondaryParticles", tmp, tmp_bytes, need, &t));
 	hipLaunchKernelGGL(k_secparts_plan, dim3(nblk(entries)), dim3(BLOCK), 0, st, d, multiple, entries, flags, potTA, potWC, potKE, k_ta,
 	                   k_wc, dt, itype, nraw, poff, roff);
 	MF_LAUNCH_CHECK();
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, poff, poff, (int)entries, st));
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(cub, cub_bytes, roff, roff, (int)entries, st));
-	hipLaunchKernelGGL(k_secparts_totals, dim3(1), dim3(1), 0, st, multiple, entries, nraw, poff, roff, res);
+	MF_TRY(exclusive_sum(t.ws, t.ws_bytes, poff, poff, entries, st));
+	MF_TRY(exclusive_sum(t.ws, t.ws_bytes, roff, roff, entries, st));
+	hipLaunchKernelGGL(k_secparts_totals, dim3(1), dim3(1), 0, st, multiple, entries, nraw, poff, roff, t.head);
 	MF_LAUNCH_CHECK();
-	MF_HIP(hipMemcpyAsync(totals_host, res, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-	MF_HIP(hipStreamSynchronize(st));
-	return 0;
+	return read_back(totals_host, t.head, 2 * sizeof(int64_t), st);
 }
 
 int mf_secparts_sample_emit(int sx, int sy, int sz, int multiple, const float* vel, const float* potTA, const float* potWC,

@@ -3,7 +3,7 @@
 // extrapolateLsSimple, setPartType, markIsolatedFluidCell, the three ptsplugins one-liners and the levelset set ops.
 // Reference: source/plugin/flip.cpp, plugin/ptsplugins.cpp, fastmarch.cpp, particle.h, grid.cpp, levelset.cpp.
 #include "common.h"
-#include <hipcub/hipcub.hpp>
+#include "scan.h"
 
 using namespace mf;
 
@@ -114,7 +114,7 @@ k_gpi_keys(Dim d, int64_t np, int64_t ps, const float* __restrict__ pos, const i
 	keys[p] = key;
 	vals[p] = (int)p;
 }
-static Arena g_sort[16];   // gridParticleIndex's hipcub workspace, per device (arena_reserve)
+static Arena g_sort[16];   // gridParticleIndex's scan / sort workspace, per device (arena_reserve)
 
 // ComputeUnionLevelsetPindex, plugin/flip.cpp:322-353 (+ setBound(0.5, 0) fused: the boundary test of knSetBoundary with w=0)
 __global__ void __launch_bounds__(BLOCK)
@@ -482,17 +482,17 @@ int mf_grid_particle_index(int sx, int sy, int sz, int64_t np, int64_t pstride, 
 		MF_LAUNCH_CHECK();
 	}
 	// index = exclusive prefix sum of the per-cell counts
-	size_t scan_bytes = 0, sort_bytes = 0;
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, counter, index, (int)d.n, st));
-	int end_bit = 1;
-	while (end_bit < 31 && (((int64_t)1 << end_bit) <= d.n)) end_bit++;
-	if (np > 0) MF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys, keys + np, vals, vals + np, (int)np, 0, end_bit, st));
+	const int end_bit = key_bits(d.n);
+	size_t ws_bytes = 0;
+	MF_TRY(exclusive_sum32_bytes(d.n, &ws_bytes));
+	if (np > 0) MF_TRY(sort_pairs_bytes(np, end_bit, &ws_bytes));
 	Arena* a;
-	MF_TRY(arena_reserve(g_sort, (scan_bytes > sort_bytes ? scan_bytes : sort_bytes) + 256, &a));
-	void* tmp = a->p;
-	MF_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, counter, index, (int)d.n, st));
+	MF_TRY(arena_reserve(g_sort, ws_bytes + 256, &a));
+	char* tmp;
+	MF_TRY(Cutter(a->p, ws_bytes + 256).take(ws_bytes, &tmp));
+	MF_TRY(exclusive_sum(tmp, ws_bytes, counter, index, d.n, st));
 	if (np > 0) {
-		MF_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, keys, keys + np, vals, vals + np, (int)np, 0, end_bit, st));
+		MF_TRY(sort_pairs(tmp, ws_bytes, (uint32_t*)keys, (uint32_t*)keys + np, vals, vals + np, np, end_bit, st));
 		// the skipped particles (key n) sort to the tail; indexSys takes the whole array, only [0, n_indexed) is meaningful
 		MF_HIP(hipMemcpyAsync(indexSys, vals + np, sizeof(int32_t) * np, hipMemcpyDeviceToDevice, st));
 	}

@@ -1,5 +1,5 @@
 """GPU: the three users of the library's growable per-device scratch blocks (arena_reserve, csrc/runtime.hip) -- gridParticleIndex
-(the hipcub workspace of surface.hip), markFluidAndBoundaryCells + mapMassToGrid (idp.hip) and adjustNumber with a compress
+(the scan / sort workspace of surface.hip), markFluidAndBoundaryCells + mapMassToGrid (idp.hip) and adjustNumber with a compress
 (resample.hip, which also keeps its compress plan inside the block) -- through one sequence of sizes in one process, so that a block
 is first allocated, regrown to a request of more than twice its size, reused by a smaller call, and regrown by doubling.  Every call
 is compared, bit for bit, with what the plugins' own GPU tests compare with: tests/partls_model.py (particle_index),
