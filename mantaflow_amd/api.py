@@ -2,7 +2,7 @@
 495-608, plus the constants of source/python/defines.py)."""
 import sys
 
-from .core import (BasicParticleSystem, FlagGrid, FluidSolver, Grid, IntGrid, LevelsetGrid, MACGrid, Mesh, ParticleIndexSystem,
+from .core import (BasicParticleSystem, FlagGrid, FluidSolver, Grid, Grid4d, Grid4dBase, Grid4Int, Grid4Real, Grid4Vec3, Grid4Vec4, IntGrid, LevelsetGrid, MACGrid, Mesh, ParticleIndexSystem,
                    PdataInt, PdataReal, PdataVec3, RealGrid, Solver, TurbulenceParticleSystem, Vec3Grid, VecGrid, resetTurbulenceParticleState,
                    vec3, vec4)
 from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, resetOutflow, apicMapPartsToMAC, apicMapMACGridToParts, extrapolateMACFromWeight, extrapolateMACSimple, markFluidCells, addBuoyancy, addGravity, addGravityNoScale, advectSemiLagrange, computePressureRhs,
@@ -23,7 +23,10 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       processBurn, updateFlame, calcSecDeriv2d, totalSum, normalizeSumTo, cgSolveWE, resetUvGrid, updateUvWeight,
                       getUvWeight, extrapolateSimpleFlags, initVortexVelocity,
                       PD_fluid_guiding, releaseBlurPrecomp, lastGuidingStats, getSpiralVelocity, setGradientYWeight,
-                      densityInflowMesh, densityInflowMeshNoise, lastMeshSdfStats, lastReinitStats)
+                      densityInflowMesh, densityInflowMeshNoise, lastMeshSdfStats, lastReinitStats,
+                      getComp4d, setComp4d, grid4dMaxDiff, grid4dMaxDiffInt, grid4dMaxDiffVec3, grid4dMaxDiffVec4, setRegion4d,
+                      setRegion4dVec4, getSliceFrom4d, getSliceFrom4dVec, interpolateGrid4d, interpolateGrid4dVec,
+                      setNoisePdata, setNoisePdataVec3, setNoisePdataInt, addTestParts, checkSymmetry, checkSymmetryVec3, testInitGridWithPos)
 
 from .scene import (Box, Checkbox, Cylinder, Gui, NoiseField, Shape, Slider, Sphere, densityInflow, sampleFlagsWithParticles,
                     sampleLevelsetWithParticles, sampleShapeWithParticles)

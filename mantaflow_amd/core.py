@@ -195,6 +195,7 @@ class FluidSolver(PbClass):
         if dim == 2 and self.mGridSize[2] != 1:
             raise RuntimeError("Trying to create 2D solver with size.z != 1")
         self.mDim = dim
+        self.mFourthDim = int(fourthDim)
         PbClass.__init__(self, self, name)
         # fluidsolver.cpp:106-109
         self.timestep = 1.0
@@ -212,6 +213,7 @@ class FluidSolver(PbClass):
         self.lib = SolverLib(_lib.get(), self)
         self.device = self.lib.device
         self._pool = {}    # dtype/ncomp -> list of free tensors  (GridStorage, fluidsolver.cpp:34-50)
+        self._pool4 = {}   # the same for the 4-D grids (mGrids4d*, fluidsolver.h): kind -> list of free tensors
         self._reinit_ctr = None    # the eight device counters of LevelsetGrid.reinitMarching
         self._live = 0
         self.timings = {}
@@ -220,6 +222,8 @@ class FluidSolver(PbClass):
     def getGridSize(self): return vec3(*self.mGridSize)
     def is2D(self): return self.mDim == 2
     def is3D(self): return self.mDim == 3
+    def supports4D(self): return self.mFourthDim > 0
+    def getFourthDim(self): return self.mFourthDim
     def getDt(self): return float(np.float32(self.timestep))
     def globalGridSize(self):
         """size of the whole domain: mGridSize, or -- for the solver of a z-slab (slab.SlabDomain) -- the undivided grid's"""
@@ -248,6 +252,24 @@ class FluidSolver(PbClass):
     def _release(self, kind, t):
         self._live -= 1
         self._pool.setdefault(kind, []).append(t)
+
+    # --- the 4-D pool (getGrid4dPointer / freeGrid4dPointer): the same stack per element type, beside the 3-D one ---
+    def _alloc4(self, kind):
+        ncomp = {"real": 1, "int": 1, "vec3": 3, "vec4": 4}[kind]
+        free = self._pool4.setdefault(kind, [])
+        if free:
+            t = free.pop()
+            t.zero_()
+        else:
+            if self._live > 200:
+                raise RuntimeError("too many temp grids used -- are they released properly ?")
+            t = torch.zeros(ncomp * self.ncells * self.mFourthDim, dtype=torch.int32 if kind == "int" else torch.float32, device=self.device)
+        self._live += 1
+        return t
+
+    def _release4(self, kind, t):
+        self._live -= 1
+        self._pool4.setdefault(kind, []).append(t)
 
     # --- time stepping, fluidsolver.cpp:143-204 ---
     def step(self, frame=-1):
@@ -808,6 +830,350 @@ RealGrid = Grid
 
 
 # ---------------------------------------------------------------------------------------------------------
+# 4-D grids, grid4d.{h,cpp}: component planes of sx*sy*sz*st words, idx = i + sx*(j + sy*(k + sz*t))
+# ---------------------------------------------------------------------------------------------------------
+def _to_vec4(v, what="Vec4"):
+    if isinstance(v, vec4):
+        return v
+    if isinstance(v, (tuple, list)) and len(v) == 4:
+        return vec4(*v)
+    raise RuntimeError("can't convert argument to %s" % what)
+
+
+def _f32_word(x):
+    """the 32-bit word of float(x), as the signed int the ABI's int32_t arguments take"""
+    return int(np.array([x], np.float32).view(np.int32)[0])
+
+
+def _c_int(x):
+    """int(Real): the C conversion truncates toward zero"""
+    return int(max(-2 ** 31, min(2 ** 31 - 1, int(np.float32(x)))))
+
+
+class Grid4dBase(PbClass):
+    TypeNone, TypeReal, TypeInt, TypeVec3, TypeVec4 = 0, 1, 2, 4, 8
+    _cname_py, _cname_cpp = "Grid4dBase", "Grid4dBase"
+    _kind, _ncomp, _gtype = None, 1, 0
+
+    def __init__(self, parent, show=True, name="", **kw):
+        PbClass.__init__(self, parent, name)
+        self.data = None
+        if not (parent.is3D() and parent.supports4D()):
+            raise RuntimeError("To use 4d grids create a 3d solver with fourthDim>0")
+        self.sx, self.sy, self.sz = parent.mGridSize
+        self.st = parent.getFourthDim()
+        self.n = self.sx * self.sy * self.sz * self.st
+        if self.n >= 2 ** 31:
+            raise RuntimeError("Grid4d: %d cells do not fit 32-bit cell indices" % self.n)
+
+    def getSizeX(self): return self.sx
+    def getSizeY(self): return self.sy
+    def getSizeZ(self): return self.sz
+    def getSizeT(self): return self.st
+    def getSize(self): return vec4(self.sx, self.sy, self.sz, self.st)
+    def getDx(self): return float(np.float32(1.0 / float(np.float32(max(self.sx, self.sy, self.sz)))))   # the 4th axis is ignored, grid4d.cpp:63-66
+    def getType(self): return self._gtype
+    def is3D(self): return True
+    def is4D(self): return True
+    @property
+    def dims(self): return (self.sx, self.sy, self.sz, self.st)
+
+
+class Grid4d(Grid4dBase):
+    """Grid4d<T>, one subclass per element type.  The flat float operators run through the core entries (every backend); the
+    broadcast forms of the vector types, the int forms, the boundaries and the vector / int reductions are kernels of
+    include/open/manta_hip_grid4d.h and are refused where that extension is not (Grid4d::<method>)."""
+    _cname_py, _cname_cpp = "Grid4d", "Grid4d"
+
+    def __init__(self, parent, show=True, name="", **kw):
+        if self._kind is None:
+            raise RuntimeError("Grid4d is a template: create a Grid4Real, Grid4Int, Grid4Vec3 or Grid4Vec4")
+        Grid4dBase.__init__(self, parent, show, name)
+        self.data = parent._alloc4(self._kind)      # zeroed: the constructor calls clear(), grid4d.cpp:68
+
+    def __del__(self):
+        try:
+            if self.data is not None:
+                self.parent._release4(self._kind, self.data)
+        except Exception:
+            pass
+
+    @property
+    def ptr(self): return _ptr(self.data)
+    def _plane(self, c): return _ptr(self.data[c * self.n:])
+    def _call(self, fn, *args): return self.parent.lib.call(fn, *args)
+    @property
+    def _N(self): return self._ncomp * self.n
+    @property
+    def _is_int(self): return self._kind == "int"
+
+    def _ext(self, what):
+        """the library if Grid4d::<what> can run: refused before anything is touched, a z-slab solver first, then a backend without
+        the extension"""
+        s, ext, who = self.parent, _lib.extension("grid4d"), "Grid4d::" + what
+        if tuple(s._slab_window) != (0, 0):
+            raise RuntimeError("%s: %s %s not run on a z-slab solver" % (who, ext.what, ext.verb))
+        if not s.lib.grid4d:
+            raise RuntimeError(ext.not_implemented(who, s.lib.backend))
+        return s.lib
+
+    def _check_same(self, a):
+        if not isinstance(a, Grid4d) or a._kind != self._kind:
+            raise RuntimeError("can't convert argument to Grid4d<%s>" % self._T)
+        if a.dims != self.dims:
+            raise RuntimeError("different Grid4d resolutions [%d,%d,%d,%d] vs [%d,%d,%d,%d]" % (a.dims + self.dims))
+
+    def _value(self, v):
+        """a T from Python: four floats (unused ones 0) or one int"""
+        if self._kind == "real":
+            return (float(v), 0., 0., 0.)
+        if self._kind == "int":
+            return int(v)
+        if self._kind == "vec3":
+            v = _to_vec3(v)
+            return (v.x, v.y, v.z, 0.)
+        return tuple(_to_vec4(v))
+
+    def clear(self):
+        if self._is_int:
+            self._call("mf_fill_i32", self._N, self.ptr, 0, self.parent.stream)
+        else:
+            self._call("mf_fill_f32", self._N, self.ptr, 0.0, self.parent.stream)
+
+    def copyFrom(self, a, copyType=True):
+        self._check_same(a)
+        self._call("mf_copy_f32", self._N, self.ptr, a.ptr, self.parent.stream)     # words are copied; copyType: the type marker is the class's
+        return self
+
+    def swap(self, other):
+        if not isinstance(other, Grid4d) or other._kind != self._kind or other.dims != self.dims:
+            raise RuntimeError("Grid4d::swap(): Grid4d dimensions mismatch.")
+        self.data, other.data = other.data, self.data
+
+    def _binary(self, what, entry, op, a, factor=0):
+        self._check_same(a)
+        if self._is_int:
+            self._ext(what)
+            self._call("mf_grid4d_int_binary", op, self.n, self.ptr, a.ptr, int(factor), self.parent.stream)
+        else:
+            self._call(entry, self._N, self.ptr, a.ptr, self.parent.stream)
+
+    def add(self, a): self._binary("add", "mf_grid_add", 0, a)
+    def sub(self, a): self._binary("sub", "mf_grid_sub", 1, a)
+    def mult(self, a): self._binary("mult", "mf_grid_mult", 2, a)
+
+    def addScaled(self, a, factor):
+        """Grid4dScaledAdd<T, T>: me += factor * other with a factor of type T, per component"""
+        self._check_same(a)
+        f = self._value(factor)
+        if self._kind == "real":
+            self._call("mf_grid_scaled_add", self.n, self.ptr, a.ptr, f[0], self.parent.stream)
+        elif self._is_int:
+            self._ext("addScaled")
+            self._call("mf_grid4d_int_binary", 3, self.n, self.ptr, a.ptr, f, self.parent.stream)
+        else:
+            self._ext("addScaled")
+            self._call("mf_grid4d_vec_scaled_add", self._ncomp, self.n, self.ptr, a.ptr, f[0], f[1], f[2], f[3], self.parent.stream)
+
+    def _const(self, what, entry, op, v):
+        v = self._value(v)
+        if self._kind == "real":
+            self._call(entry, self.n, self.ptr, v[0], self.parent.stream)
+        elif self._is_int:
+            if op == 0:
+                self._call("mf_fill_i32", self.n, self.ptr, v, self.parent.stream)
+            else:
+                self._ext(what)
+                self._call("mf_grid4d_int_const", op, self.n, self.ptr, v, self.parent.stream)
+        else:
+            self._ext(what)
+            self._call("mf_grid4d_vec_const", op, self._ncomp, self.n, self.ptr, v[0], v[1], v[2], v[3], self.parent.stream)
+
+    def setConst(self, s): self._const("setConst", "mf_fill_f32", 0, s)
+    def addConst(self, s): self._const("addConst", "mf_grid_add_const", 1, s)
+    def multConst(self, s): self._const("multConst", "mf_grid_mult_const", 2, s)
+
+    def clamp(self, min, max):
+        """kn4dClamp with T(min), T(max): every component of a vector type against the same pair; int(Real) for Grid4Int"""
+        if self._is_int:
+            self._ext("clamp")
+            self._call("mf_grid4d_int_clamp", self.n, self.ptr, _c_int(min), _c_int(max), self.parent.stream)
+        else:
+            self._call("mf_grid_clamp", self._N, self.ptr, float(min), float(max), self.parent.stream)
+
+    def _min_max(self, what):
+        """(min, max) as Reals: of the values (Real, int) or of the norms (Vec3, Vec4: sqrt of the extreme normSquare)"""
+        f32 = np.float32
+        if self._kind == "real":
+            lo, hi = ctypes.c_float(), ctypes.c_float()
+            self._call("mf_grid_min_max", self.n, self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
+            return f32(lo.value), f32(hi.value)
+        self._ext(what)
+        if self._is_int:
+            lo, hi = ctypes.c_int32(), ctypes.c_int32()
+            self._call("mf_grid4d_int_min_max", self.n, self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
+            return f32(lo.value), f32(hi.value)
+        lo, hi = ctypes.c_float(), ctypes.c_float()
+        self._call("mf_grid4d_norm_min_max", self._ncomp, self.n, self.n, self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
+        return np.sqrt(f32(lo.value)), np.sqrt(f32(hi.value))
+
+    def getMin(self): return float(self._min_max("getMin")[0])
+    def getMax(self): return float(self._min_max("getMax")[1])
+
+    def getMaxAbs(self):
+        lo, hi = self._min_max("getMaxAbs")
+        if self._ncomp > 1:
+            return float(hi)
+        return float(max(abs(lo), abs(hi)))
+
+    def setBound(self, value, boundaryWidth=1):
+        """knSetBnd4d, grid4d.cpp:299-311"""
+        v = self._value(value)
+        self._ext("setBound")
+        w = (v, 0, 0, 0) if self._is_int else tuple(_f32_word(x) for x in v)
+        self._call("mf_grid4d_set_bound", self.sx, self.sy, self.sz, self.st, self.ptr, self._ncomp, w[0], w[1], w[2], w[3],
+                   int(boundaryWidth), self.parent.stream)
+
+    def setBoundNeumann(self, boundaryWidth=1):
+        """knSetBnd4dNeumann, grid4d.cpp:313-346; every axis needs 2 * boundaryWidth + 3 cells (the entry refuses less)"""
+        self._ext("setBoundNeumann")
+        self._call("mf_grid4d_set_bound_neumann", self.sx, self.sy, self.sz, self.st, self.ptr, self._ncomp, int(boundaryWidth),
+                   self.parent.stream)
+
+    # numpy bridge: [t][z][y][x](,[c])
+    def to_numpy(self):
+        self.parent.sync()
+        a = self.data.detach().cpu().numpy()
+        if self._ncomp == 1:
+            return a.reshape(self.st, self.sz, self.sy, self.sx).copy()
+        return np.ascontiguousarray(a.reshape(self._ncomp, self.st, self.sz, self.sy, self.sx).transpose(1, 2, 3, 4, 0))
+
+    def from_numpy(self, arr):
+        arr = np.asarray(arr)
+        if self._ncomp == 1:
+            flat = np.ascontiguousarray(arr.reshape(self.n))
+        else:
+            flat = np.ascontiguousarray(arr.reshape(self.st, self.sz, self.sy, self.sx, self._ncomp).transpose(4, 0, 1, 2, 3)).reshape(self._N)
+        t = torch.from_numpy(flat.astype(np.int32 if self._is_int else np.float32, copy=False))
+        self.data.copy_(t.to(self.data.device))
+        return self
+
+    def save(self, name):
+        """Grid4d<T>::save, grid4d.cpp:120-132 (.uni, .raw)"""
+        return _grid4d_save(self, str(name))
+
+    def load(self, name):
+        """Grid4d<T>::load, grid4d.cpp:106-118"""
+        return _grid4d_load(self, str(name))
+
+    def printGrid(self, zSlice=-1, tSlice=-1, printIndex=False, bnd=0):
+        """Grid4d<T>::printGrid, grid4d.cpp:270-289 (host)"""
+        a = self.to_numpy()
+        fmt = (lambda v: "%d" % v) if self._is_int else (lambda v: "%g" % v) if self._ncomp == 1 else \
+            (lambda v: "[" + ",".join("%+4.6f" % x for x in v) + "]")
+        out = ["\n"]
+        for t in range(bnd, self.st - bnd):
+            for k in range(bnd, self.sz - bnd):
+                for j in range(bnd, self.sy - bnd):
+                    for i in range(bnd, self.sx - bnd):
+                        if (zSlice >= 0 and k != zSlice) or (tSlice >= 0 and t != tSlice):
+                            continue
+                        out.append(" ")
+                        if printIndex:
+                            out.append("  %d,%d,%d,%d:" % (i, j, k, t))
+                        out.append(fmt(a[t, k, j, i]))
+                        if i == self.sx - 1 - bnd:
+                            out.append("\n")
+                            if j == self.sy - 1 - bnd:
+                                out.append("\n")
+                                if k == self.sz - 1 - bnd:
+                                    out.append("\n")
+        out.append("\n")
+        print("Printing '%s' %s " % (self.name, "".join(out)))
+
+
+class Grid4Real(Grid4d):
+    _kind, _ncomp, _gtype, _T = "real", 1, Grid4dBase.TypeReal, "Real"
+    _cname_py = "Grid4Real"
+
+
+class Grid4Int(Grid4d):
+    _kind, _ncomp, _gtype, _T = "int", 1, Grid4dBase.TypeInt, "int"
+    _cname_py = "Grid4Int"
+
+
+class Grid4Vec3(Grid4d):
+    _kind, _ncomp, _gtype, _T = "vec3", 3, Grid4dBase.TypeVec3, "Vec3"
+    _cname_py = "Grid4Vec3"
+
+
+class Grid4Vec4(Grid4d):
+    _kind, _ncomp, _gtype, _T = "vec4", 4, Grid4dBase.TypeVec4, "Vec4"
+    _cname_py = "Grid4Vec4"
+
+
+# .uni / .raw files of 4-D grids (fileio/iogrids.cpp:624-830): "M4T3" + the UniHeader with dimT set + the elements slice by slice
+# (x fastest, the vector types with their components together)
+def _grid4d_ext(name):
+    if "." not in name:
+        raise RuntimeError("file '%s' does not have an extension" % name)
+    return name[name.rfind("."):]
+
+
+def _grid4d_save(g, name):
+    import time as _time
+    ext = _grid4d_ext(name)
+    if ext not in (".uni", ".raw"):
+        raise RuntimeError("file '%s' filetype not supported" % name)
+    raw = g.to_numpy().tobytes()
+    with gzip.open(name, "wb", compresslevel=1) as f:
+        if ext == ".uni":
+            et = 0 if (g._gtype & Grid4dBase.TypeInt) else (1 if (g._gtype & Grid4dBase.TypeReal) else 2)
+            info = b"mantaflow_amd 0.1 64bit fp1 hip gfx950"
+            f.write(b"M4T3")
+            f.write(struct.pack(_UNI_HEADER, g.sx, g.sy, g.sz, g._gtype, et, 4 * g._ncomp, info, g.st, int(_time.time() * 1000)))
+        f.write(raw)
+    return 1
+
+
+def _grid4d_load(g, name):
+    ext = _grid4d_ext(name)
+    dt = np.int32 if g._is_int else np.float32
+    nbytes = 4 * g._N
+    shape = (g.st, g.sz, g.sy, g.sx) + ((g._ncomp,) if g._ncomp > 1 else ())
+    if ext == ".raw":
+        with gzip.open(name, "rb") as f:
+            raw = f.read(nbytes)
+        if len(raw) != nbytes:
+            raise RuntimeError("can't read raw file, stream length does not match, %d vs %d" % (nbytes, len(raw)))
+    elif ext == ".uni":
+        with gzip.open(name, "rb") as f:
+            ident = f.read(4)
+            if ident != b"M4T3":              # the reference reports an unknown header at debug level 1 and leaves the grid as it is
+                print("Unknown header!")
+                return 1
+            hb = f.read(struct.calcsize(_UNI_HEADER))
+            if len(hb) != struct.calcsize(_UNI_HEADER):
+                raise RuntimeError("can't read file, no 4d header present")
+            dx, dy, dz, gtype, etype, bpe, info, dimt, stamp = struct.unpack(_UNI_HEADER, hb)
+            if bpe != 4 * g._ncomp:
+                raise RuntimeError("4d grid element size doesn't match %d vs %d" % (bpe, 4 * g._ncomp))
+            if (dx, dy, dz) != (g.sx, g.sy, g.sz):
+                raise RuntimeError("grid dim doesn't match, [%+4.2f,%+4.2f,%+4.2f] vs [%d,%d,%d,%d]" % ((dx, dy, dz) + g.dims))
+            if _unify_grid_type(gtype) != _unify_grid_type(g._gtype):
+                raise RuntimeError("grid type doesn't match %d vs %d" % (gtype, g._gtype))
+            if dimt != g.st:
+                raise RuntimeError("grid dim4 doesn't match, %d vs [%d,%d,%d,%d]" % ((dimt,) + g.dims))
+            raw = f.read(nbytes)
+            if len(raw) != nbytes:
+                raise RuntimeError("can't read file, no / not enough data")
+    else:
+        raise RuntimeError("file '%s' filetype not supported" % name)
+    g.from_numpy(np.frombuffer(raw, dtype=dt).reshape(shape).copy())
+    return 1
+
+
+# ---------------------------------------------------------------------------------------------------------
 # particles, particle.{h,cpp}: BasicParticleSystem (pos + flag; the fork's pos0 is not on the hot path)
 # ---------------------------------------------------------------------------------------------------------
 class ParticleDataImpl(PbClass):
@@ -870,6 +1236,225 @@ class ParticleDataImpl(PbClass):
         self.data.copy_(o.data)
         return self
 
+    # ---- the arithmetic of ParticleDataImpl<T>, particle.cpp:434-673, over the live slots [0, size): the flat float operators through
+    # the core entries on each component plane (every backend), the rest through include/open/manta_hip_grid4d.h (refused elsewhere)
+    @property
+    def _is_int(self): return self._dtype == torch.int32
+    def _plane(self, c): return _ptr(self.data[c * self.cap:])
+    def _call(self, fn, *args): return self.parent.lib.call(fn, *args)
+
+    def _ext(self, what):
+        """the library if ParticleDataImpl::<what> can run: refused before anything is touched, a z-slab solver first, then a
+        backend without the extension"""
+        s, ext, who = self.parent, _lib.extension("grid4d"), "ParticleDataImpl::" + what
+        if tuple(s._slab_window) != (0, 0):
+            raise RuntimeError("%s: %s %s not run on a z-slab solver" % (who, ext.what, ext.verb))
+        if not s.lib.grid4d:
+            raise RuntimeError(ext.not_implemented(who, s.lib.backend))
+        return s.lib
+
+    def _check_other(self, a):
+        if type(a) is not type(self):
+            raise RuntimeError("can't convert argument to ParticleDataImpl<%s>" % self._T)
+        if a.size() != self.size():
+            raise RuntimeError("different pdata size %d vs %d" % (a.size(), self.size()))
+
+    def _value(self, v):
+        if self._is_int:
+            return int(v)
+        if self._ncomp == 1:
+            return (float(v),)
+        v = _to_vec3(v)
+        return (v.x, v.y, v.z)
+
+    def _binary(self, what, entry, op, a, factor=0):
+        self._check_other(a)
+        if self._is_int:
+            self._ext(what)
+            if self.size():
+                self._call("mf_grid4d_int_binary", op, self.size(), self.ptr, a.ptr, int(factor), self.parent.stream)
+        elif self.size():
+            for c in range(self._ncomp):
+                self._call(entry, self.size(), self._plane(c), a._plane(c), self.parent.stream)
+
+    def add(self, a): self._binary("add", "mf_grid_add", 0, a)
+    def sub(self, a): self._binary("sub", "mf_grid_sub", 1, a)
+    def mult(self, a): self._binary("mult", "mf_grid_mult", 2, a)
+    def safeDiv(self, a): self._binary("safeDiv", "mf_grid_safe_divide", 4, a)
+
+    def addScaled(self, a, factor):
+        """knPdataScaledAdd<T, T>: me += factor * other, a factor of type T, per component"""
+        f = self._value(factor)
+        if self._is_int:
+            return self._binary("addScaled", None, 3, a, f)
+        self._check_other(a)
+        if self.size():
+            for c in range(self._ncomp):
+                self._call("mf_grid_scaled_add", self.size(), self._plane(c), a._plane(c), f[c], self.parent.stream)
+
+    def _const(self, what, entry, op, v):
+        v = self._value(v)
+        if self._is_int:
+            self._ext(what)
+            if self.size():
+                self._call("mf_grid4d_int_const", op, self.size(), self.ptr, v, self.parent.stream)
+        elif self.size():
+            for c in range(self._ncomp):
+                self._call(entry, self.size(), self._plane(c), v[c], self.parent.stream)
+
+    def addConst(self, s): self._const("addConst", "mf_grid_add_const", 1, s)
+    def multConst(self, s): self._const("multConst", "mf_grid_mult_const", 2, s)
+
+    def clamp(self, vmin, vmax):
+        """knPdataClamp with T(vmin), T(vmax): per component for Vec3, int(Real) for int"""
+        if self._is_int:
+            self._ext("clamp")
+            if self.size():
+                self._call("mf_grid4d_int_clamp", self.size(), self.ptr, _c_int(vmin), _c_int(vmax), self.parent.stream)
+        elif self.size():
+            for c in range(self._ncomp):
+                self._call("mf_grid_clamp", self.size(), self._plane(c), float(vmin), float(vmax), self.parent.stream)
+
+    def _clamp_side(self, what, side, v):
+        self._ext(what)
+        w = _c_int(v) if self._is_int else _f32_word(v)
+        self._call("mf_grid4d_pdata_clamp_side", side, int(self._is_int), self.size(), self.cap, self._ncomp, self.ptr, w, self.parent.stream)
+
+    def clampMin(self, vmin): self._clamp_side("clampMin", 0, vmin)
+    def clampMax(self, vmax): self._clamp_side("clampMax", 1, vmax)
+
+    def setConstRange(self, s, begin, end):
+        """ParticleDataImpl::setConstRange: slots [begin, end) of every component plane, as given (the reference does not clamp them;
+        past the capacity there is nothing to write)"""
+        v = self._value(s)
+        b, e = max(0, int(begin)), min(self.cap, int(end))
+        if e > b:
+            for c in range(self._ncomp):
+                self.data[c * self.cap + b:c * self.cap + e] = v if self._is_int else v[c]
+
+    def setConstIntFlag(self, s, t, flag):
+        """knPdataSetScalarIntFlag: slots with t[idx] & flag take the value"""
+        v = self._value(s)
+        if not isinstance(t, PdataInt):
+            raise RuntimeError("can't convert argument to ParticleDataImpl<int>")
+        self._ext("setConstIntFlag")
+        if t.size() != self.size():
+            raise RuntimeError("different pdata size %d vs %d" % (t.size(), self.size()))
+        w = [v, 0, 0] if self._is_int else [_f32_word(x) for x in v] + [0, 0]
+        self._call("mf_grid4d_pdata_set_flag", self.size(), self.cap, self._ncomp, self.ptr, w[0], w[1], w[2], t.ptr, int(flag), self.parent.stream)
+
+    def _min_max(self, what):
+        """(min, max) as Reals: of the values, or for Vec3 of the lengths (CompPdata_MinVec3 / MaxVec3); an empty channel gives the
+        reference's start values"""
+        f32 = np.float32
+        big = np.finfo(f32).max
+        if self._ncomp == 1 and not self._is_int:
+            if not self.size():
+                return big, -big
+            lo, hi = ctypes.c_float(), ctypes.c_float()
+            self._call("mf_grid_min_max", self.size(), self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
+            return f32(lo.value), f32(hi.value)
+        self._ext(what)
+        if not self.size():
+            if self._ncomp == 1:
+                return big, -big
+            with np.errstate(invalid="ignore"):
+                return np.sqrt(big), np.sqrt(-big)                  # sqrt(-FLT_MAX): the NaN the host's square root gives
+        if self._is_int:
+            lo, hi = ctypes.c_int32(), ctypes.c_int32()
+            self._call("mf_grid4d_int_min_max", self.size(), self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
+            return f32(lo.value), f32(hi.value)
+        lo, hi = ctypes.c_float(), ctypes.c_float()
+        self._call("mf_grid4d_norm_min_max", 3, self.size(), self.cap, self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
+        return np.sqrt(f32(lo.value)), np.sqrt(f32(hi.value))
+
+    def getMin(self): return float(self._min_max("getMin")[0])
+    def getMax(self): return float(self._min_max("getMax")[1])
+
+    def getMaxAbs(self):
+        lo, hi = self._min_max("getMaxAbs")
+        return float(hi) if self._ncomp > 1 else float(max(abs(lo), abs(hi)))
+
+    def _sum(self, what, which, t=None, itype=0):
+        if t is not None and not isinstance(t, PdataInt):
+            raise RuntimeError("can't convert argument to ParticleDataImpl<int>*")
+        self._ext(what)
+        if t is not None and t.size() != self.size():
+            raise RuntimeError("different pdata size %d vs %d" % (t.size(), self.size()))
+        r = (ctypes.c_int32 * 3)()
+        self._call("mf_grid4d_pdata_sum", which, int(self._is_int), self._ncomp, self.size(), self.cap, self.ptr, None if t is None else t.ptr,
+                   int(itype), r, self.parent.stream)
+        w = np.array(list(r), np.int32)
+        return w if (self._is_int and which == 0) else w.view(np.float32)
+
+    def sum(self, t=None, itype=0):
+        """KnPtsSum: fp64 accumulation in a fixed order, rounded once (include/open/manta_hip_grid4d.h); an int channel's is exact"""
+        r = self._sum("sum", 0, t, itype)
+        if self._is_int:
+            return int(r[0])
+        return float(r[0]) if self._ncomp == 1 else vec3(float(r[0]), float(r[1]), float(r[2]))
+
+    def sumSquare(self): return float(self._sum("sumSquare", 1)[0])
+    def sumMagnitude(self): return float(self._sum("sumMagnitude", 2)[0])
+
+    def printPdata(self, start=-1, stop=-1, printIndex=False):
+        """ParticleDataImpl::printPdata, particle.cpp:619-633 (host)"""
+        n = self.size()
+        s = min(max(start if start > 0 else 0, 0), n)
+        e = min(max(stop if stop > 0 else n, 0), n)
+        a = self.to_numpy()
+        fmt = (lambda v: "%d" % v) if self._is_int else (lambda v: "%g" % v) if self._ncomp == 1 else (lambda v: "[%+4.2f,%+4.2f,%+4.2f]" % tuple(v))
+        print("".join(("%d: " % i if printIndex else "") + fmt(a[i]) + " \n" for i in range(s, e)))
+
+    # .uni / .raw particle data files, fileio/ioparticles.cpp:225-303: gzip stream of "PD01" + UniPartHeader + the elements
+    _UNI_PART_HEADER = "<6i256sQ"       # dim dimX dimY dimZ elementType bytesPerElement info[256] timestamp
+
+    def save(self, name):
+        """ParticleDataImpl::save, particle.cpp:391-409"""
+        import time as _time
+        name = str(name)
+        if "." not in name:
+            raise RuntimeError("file '" + name + "' does not have an extension")
+        if name[name.rfind("."):] not in (".uni", ".raw"):
+            raise RuntimeError("particle data '" + name + "' filetype not supported for saving")
+        self.parent.sync()
+        gs = self.parent.mGridSize
+        head = struct.pack(self._UNI_PART_HEADER, self.size(), gs[0], gs[1], gs[2], 1, 4 * self._ncomp, b"mantaflow_amd 0.1 64bit fp1 hip gfx950",
+                           int(_time.time() * 1000))
+        with gzip.open(name, "wb", compresslevel=1) as f:
+            f.write(b"PD01" + head + np.ascontiguousarray(self.to_numpy()).tobytes())
+        return 1
+
+    def load(self, name):
+        """ParticleDataImpl::load, particle.cpp:371-389 -> readPdataUni.  The reference resizes the channel to the file's count, away
+        from its system; here a channel is as long as its system, and another count is refused with the reader's message."""
+        name = str(name)
+        if "." not in name:
+            raise RuntimeError("file '" + name + "' does not have an extension")
+        if name[name.rfind("."):] not in (".uni", ".raw"):
+            raise RuntimeError("particle data '" + name + "' filetype not supported for loading")
+        try:
+            with gzip.open(name, "rb") as f:
+                raw = f.read()
+        except OSError:
+            raise RuntimeError("can't open file " + name)
+        if raw[:4] != b"PD01":      # readPdataUni reads nothing then and still answers 1; say so, as the 4-D grid reader does
+            print("Unknown header!")
+            return 1
+        hs = struct.calcsize(self._UNI_PART_HEADER)
+        if len(raw) < 4 + hs:
+            raise RuntimeError("can't read file, no header present")
+        dim, dx, dy, dz, etype, bpe, info, stamp = struct.unpack(self._UNI_PART_HEADER, raw[4:4 + hs])
+        if dim != self.size():
+            raise RuntimeError("pdata size doesn't match")
+        if bpe != 4 * self._ncomp or etype != 1:
+            raise RuntimeError("pdata type doesn't match")
+        if len(raw) - 4 - hs != bpe * dim:
+            raise RuntimeError("can't read uni file, stream length does not match, %d vs %d" % (bpe * dim, len(raw) - 4 - hs))
+        a = np.frombuffer(raw, np.int32 if self._is_int else np.float32, dim * self._ncomp, 4 + hs)
+        self.from_numpy(a.reshape((dim, 3) if self._ncomp == 3 else (dim,)).copy())
+        return 1
+
 
 class PdataReal(ParticleDataImpl):
     _cname_py, _cname_cpp, _T = "PdataReal", "ParticleDataImpl", "Real"
@@ -885,10 +1470,6 @@ class PdataInt(ParticleDataImpl):
         raise RuntimeError("PdataInt.setSource: integer source grids are not implemented (no scene uses them)")
 
     def setConst(self, v): self.data.fill_(int(v))
-
-    def setConstRange(self, s, begin, end):
-        """ParticleDataImpl::setConstRange, particle.cpp: [begin, end)"""
-        self.data[int(begin):int(end)] = int(s)
 
 
 class PdataVec3(ParticleDataImpl):
@@ -1519,6 +2100,89 @@ class BasicParticleSystem(PbClass):
 
     def getPosPdata(self, target): target.data.copy_(self.pos)
     def setPosPdata(self, source): self.pos.copy_(source.data)
+
+    # small host-side completions of the class (particle.h:132-136, particle.cpp:142-160, 238-269)
+    def getPos(self, idx):
+        idx = int(idx)
+        if not 0 <= idx < self.np:
+            raise RuntimeError("ParticleBase::checkPartIndex: index %d out of bounds (size %d)" % (idx, self.np))
+        return vec3(*[float(self.pos[c * self.cap + idx].item()) for c in range(3)])
+
+    def setPos(self, idx, pos):
+        idx, p = int(idx), _to_vec3(pos)
+        if not 0 <= idx < self.np:
+            raise RuntimeError("ParticleBase::checkPartIndex: index %d out of bounds (size %d)" % (idx, self.np))
+        for c, x in enumerate((p.x, p.y, p.z)):
+            self.pos[c * self.cap + idx] = x
+
+    def insertBufferedParticles(self, new_pos, new_flags=None):
+        """ParticleSystem::insertBufferedParticles, particle.h:637-663: PNEW is cleared everywhere, the buffered positions are appended
+        with PNEW (| their flag), every channel grows with its setSource rule (initNewValue) or zero; the delete bookkeeping stays"""
+        new_pos = np.asarray(new_pos, np.float32).reshape(-1, 3)
+        if self.np:
+            self.flag[:self.np] &= ~PNEW
+        k = len(new_pos)
+        if k == 0:
+            return
+        old = self.np
+        self.reserve(old + k)
+        self.resizeAll(old + k, self.cap)
+        dev = self.pos.device
+        for c in range(3):
+            self.pos[c * self.cap + old:c * self.cap + old + k] = torch.from_numpy(np.ascontiguousarray(new_pos[:, c])).to(dev)
+        fl = np.full(k, PNEW, np.int32) if new_flags is None else (np.asarray(new_flags, np.int32) | PNEW)
+        self.flag[old:old + k] = torch.from_numpy(fl).to(dev)
+        # initNewValue (particle.cpp:348-369): zero, or the channel's source grid sampled at the new positions by the entries behind
+        # mapGridToParts / mapMACToParts, run on the new slots alone (the planes of positions, flags and channel from slot `old` on)
+        lib, st = self.parent.lib, self.parent.stream
+        at = lambda t: ctypes.c_void_p(t.data_ptr() + 4 * old)
+        for pd in self.pdata:
+            for c in range(pd._ncomp):
+                pd.data[c * pd.cap + old:c * pd.cap + old + k] = 0
+            g = pd.mpGridSource
+            if g is None:
+                continue
+            if pd.mGridSourceMAC:
+                lib.call("mf_map_mac_to_parts", g.sx, g.sy, g.sz, g.ptr, k, self.cap, at(self.pos), at(self.flag), at(pd.data), None, 0, st)
+            else:
+                lib.call("mf_map_grid_to_parts", g.sx, g.sy, g.sz, pd._ncomp, g.ptr, k, self.cap, at(self.pos), at(self.flag), at(pd.data), st)
+
+    def printParts(self, start=-1, stop=-1, printIndex=False):
+        """BasicParticleSystem::printParts (host)"""
+        n = self.np
+        s = min(max(start if start > 0 else 0, 0), n)
+        e = min(max(stop if stop > 0 else n, 0), n)
+        pos, fl = self.get_positions(), self.get_flags()
+        print("".join(("%d: " % i if printIndex else "") + "[%+4.2f,%+4.2f,%+4.2f] %d\n" % (tuple(pos[i]) + (fl[i],)) for i in range(s, e)))
+
+    def writeParticlesText(self, name):
+        """BasicParticleSystem::writeParticlesText: the header line, then per slot position, flag and the int, Real and Vec3 channels"""
+        ints = [p for p in self.pdata if isinstance(p, PdataInt)]
+        reals = [p for p in self.pdata if isinstance(p, PdataReal)]
+        vecs = [p for p in self.pdata if isinstance(p, PdataVec3)]
+        pos, fl = self.get_positions(), self.get_flags()
+        ch = [p.to_numpy() for p in ints + reals + vecs]
+        out = ["%d, pdata: %d (%d,%d,%d) \n" % (self.np, len(self.pdata), len(ints), len(reals), len(vecs))]
+        for i in range(self.np):
+            line = "%d: [%+4.2f,%+4.2f,%+4.2f] , %d. " % ((i,) + tuple(pos[i]) + (fl[i],))
+            for p, a in zip(ints + reals + vecs, ch):
+                line += ("%d " % a[i]) if p._is_int else ("%g " % a[i]) if p._ncomp == 1 else ("[%+4.2f,%+4.2f,%+4.2f] " % tuple(a[i]))
+            out.append(line + "\n")
+        text = "".join(out)
+        print("writeParticlesText: %s" % text, end="")
+        try:
+            with open(name, "w") as f:
+                f.write(text)
+        except OSError:
+            raise RuntimeError("can't open file!")
+
+    def readParticles(self, source):
+        """BasicParticleSystem::readParticles: positions and flags of another system, positions scaled to this solver's resolution"""
+        if not isinstance(source, BasicParticleSystem):
+            raise RuntimeError("can't convert argument to BasicParticleSystem*")
+        a, b = source.parent.mGridSize, self.parent.mGridSize
+        factor = np.array([np.float32(b[c]) / np.float32(a[c]) for c in range(3)], np.float32)
+        self.set_positions(source.get_positions() * factor[None, :] if source.np else np.zeros((0, 3), np.float32), source.get_flags())
 
     # .uni particle files, fileio/ioparticles.cpp:130-223: gzip stream of "PB02" + UniPartHeader + [pos.x pos.y pos.z flag] per particle
     _UNI_PART_HEADER = "<6i256sQ"       # dim dimX dimY dimZ elementType bytesPerElement info[256] timestamp = 288 B

@@ -3,6 +3,7 @@
 // process: MT19937 + Box-Muller in double precision, fp32 filter passes), uploaded, and evaluated on the device by
 // densityInflow (KnApplyNoiseInfl, plugin/initplugins.cpp:27-43).
 #include "common.h"
+#include "wavelet_noise_vec.h"
 #include "../../include/manta_hip_obstacles.h"
 #include <math.h>
 #include <stdlib.h>
@@ -114,61 +115,7 @@ void generate_tile(float* tile3, int seed) {
 				}
 }
 
-struct NoiseParams {
-	float gsInv[3], seedOff[3], time, posScale[3], posOffset[3], valOffset, valScale, clamp, clampNeg, clampPos;
-};
-
-// WNoise, noisefield.h:163-196: quadratic B-spline over the 27 neighbouring tile entries, x fastest
-__device__ __forceinline__ float wnoise(float p0, float p1, float p2, const float* __restrict__ data) {
-	float w[3][3];
-	int mid[3];
-	const float p[3] = {p0, p1, p2};
-#pragma unroll
-	for (int c = 0; c < 3; c++) {
-		mid[c] = (int)ceilf(p[c] - 0.5f);
-		const float t = (float)mid[c] - (p[c] - 0.5f);
-		w[c][0] = t * t * 0.5f;
-		w[c][2] = (1.f - t) * (1.f - t) * 0.5f;
-		w[c][1] = 1.f - w[c][0] - w[c][2];
-	}
-	float result = 0.f;
-#pragma unroll
-	for (int z = -1; z <= 1; z++)
-#pragma unroll
-		for (int y = -1; y <= 1; y++)
-#pragma unroll
-			for (int x = -1; x <= 1; x++) {
-				float weight = 1.0f;
-				weight *= w[0][x + 1];
-				weight *= w[1][y + 1];
-				weight *= w[2][z + 1];
-				const int xC = (mid[0] + x) & 127, yC = (mid[1] + y) & 127, zC = (mid[2] + z) & 127;
-				result += weight * data[(zC * 128 + yC) * 128 + xC];
-			}
-	return result;
-}
-// WaveletNoiseField::evaluate, noisefield.h:313-336
-__device__ __forceinline__ float noise_evaluate(const NoiseParams& P, const float* __restrict__ tile, float x, float y, float z) {
-	float pos[3] = {x, y, z};
-#pragma unroll
-	for (int c = 0; c < 3; c++) pos[c] *= P.gsInv[c];
-#pragma unroll
-	for (int c = 0; c < 3; c++) pos[c] += P.seedOff[c];
-#pragma unroll
-	for (int c = 0; c < 3; c++) pos[c] += P.time;
-#pragma unroll
-	for (int c = 0; c < 3; c++) pos[c] *= P.posScale[c];
-#pragma unroll
-	for (int c = 0; c < 3; c++) pos[c] += P.posOffset[c];
-	float v = wnoise(pos[0], pos[1], pos[2], tile);
-	v += P.valOffset;
-	v *= P.valScale;
-	if (P.clamp != 0.f) {
-		if (v < P.clampNeg) v = P.clampNeg;
-		if (v > P.clampPos) v = P.clampPos;
-	}
-	return v;
-}
+// NoiseParams, wnoise, noise_evaluate: wavelet_noise_vec.h (shared with the vector form and with the particle-data kernel of grid4d.hip)
 // KnApplyNoiseInfl, plugin/initplugins.cpp:27-36
 __global__ void __launch_bounds__(BLOCK)
 k_density_inflow(Dim d, const int32_t* __restrict__ flags, float* __restrict__ density, const float* __restrict__ sdf,
@@ -196,22 +143,7 @@ k_add_noise(Dim d, const int32_t* __restrict__ flags, float* __restrict__ densit
 	density[idx] += noise_evaluate(P, tile, (float)i, (float)j, (float)k) * scale;
 }
 
-static NoiseParams noise_params(const float* params) {
-	NoiseParams P;
-	for (int c = 0; c < 3; c++) {
-		P.gsInv[c] = params[c];
-		P.seedOff[c] = params[3 + c];
-		P.posScale[c] = params[7 + c];
-		P.posOffset[c] = params[10 + c];
-	}
-	P.time = params[6];
-	P.valOffset = params[13];
-	P.valScale = params[14];
-	P.clamp = params[15];
-	P.clampNeg = params[16];
-	P.clampPos = params[17];
-	return P;
-}
+static NoiseParams noise_params(const float* params) { return noise_params_vec(params); }
 
 }  // namespace
 

@@ -1,5 +1,6 @@
-// wavelet_noise_vec.h -- the vector evaluation of the wavelet noise field (WaveletNoiseField::evaluateVec / evaluateCurl,
-// noisefield.h:210-310, 358-394), shared by applyNoiseVec3 (turbulence.hip) and the turbulence particles (turbulence_model.hip).
+// wavelet_noise_vec.h -- the evaluation of the wavelet noise field: the scalar form (WaveletNoiseField::evaluate, noisefield.h:163-196,
+// 313-336; densityInflow and addNoise in noise.hip, setNoisePdata in grid4d.hip) and the vector form (evaluateVec / evaluateCurl,
+// noisefield.h:210-310, 358-394; applyNoiseVec3 in turbulence.hip, the turbulence particles in turbulence_model.hip, setNoisePdataVec3).
 #pragma once
 #include "common.h"
 #include <math.h>
@@ -9,6 +10,57 @@ namespace mf {
 struct NoiseParams {
 	float gsInv[3], seedOff[3], time, posScale[3], posOffset[3], valOffset, valScale, clamp, clampNeg, clampPos;
 };
+// WNoise, noisefield.h:163-196: quadratic B-spline over the 27 neighbouring tile entries, x fastest
+static __device__ __forceinline__ float wnoise(float p0, float p1, float p2, const float* __restrict__ data) {
+	float w[3][3];
+	int mid[3];
+	const float p[3] = {p0, p1, p2};
+#pragma unroll
+	for (int c = 0; c < 3; c++) {
+		mid[c] = (int)ceilf(p[c] - 0.5f);
+		const float t = (float)mid[c] - (p[c] - 0.5f);
+		w[c][0] = t * t * 0.5f;
+		w[c][2] = (1.f - t) * (1.f - t) * 0.5f;
+		w[c][1] = 1.f - w[c][0] - w[c][2];
+	}
+	float result = 0.f;
+#pragma unroll
+	for (int z = -1; z <= 1; z++)
+#pragma unroll
+		for (int y = -1; y <= 1; y++)
+#pragma unroll
+			for (int x = -1; x <= 1; x++) {
+				float weight = 1.0f;
+				weight *= w[0][x + 1];
+				weight *= w[1][y + 1];
+				weight *= w[2][z + 1];
+				const int xC = (mid[0] + x) & 127, yC = (mid[1] + y) & 127, zC = (mid[2] + z) & 127;
+				result += weight * data[(zC * 128 + yC) * 128 + xC];
+			}
+	return result;
+}
+// WaveletNoiseField::evaluate, noisefield.h:313-336
+static __device__ __forceinline__ float noise_evaluate(const NoiseParams& P, const float* __restrict__ tile, float x, float y, float z) {
+	float pos[3] = {x, y, z};
+#pragma unroll
+	for (int c = 0; c < 3; c++) pos[c] *= P.gsInv[c];
+#pragma unroll
+	for (int c = 0; c < 3; c++) pos[c] += P.seedOff[c];
+#pragma unroll
+	for (int c = 0; c < 3; c++) pos[c] += P.time;
+#pragma unroll
+	for (int c = 0; c < 3; c++) pos[c] *= P.posScale[c];
+#pragma unroll
+	for (int c = 0; c < 3; c++) pos[c] += P.posOffset[c];
+	float v = wnoise(pos[0], pos[1], pos[2], tile);
+	v += P.valOffset;
+	v *= P.valScale;
+	if (P.clamp != 0.f) {
+		if (v < P.clampNeg) v = P.clampNeg;
+		if (v > P.clampPos) v = P.clampPos;
+	}
+	return v;
+}
 // WNoiseVec, noisefield.h:210-310
 static __device__ void wnoise_vec(float p0, float p1, float p2, const float* __restrict__ data, float out[3]) {
 	const float p[3] = {p0, p1, p2};

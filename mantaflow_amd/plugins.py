@@ -1920,3 +1920,228 @@ def lastReinitStats():
     """of the most recent LevelsetGrid.reinitMarching, each a pair (inward march, outward march): `windows` of keys, `subrounds` (a
     selecting and a popping launch each), `pops`, and `serial` (1: the literal loop ran on the host, and windows / subrounds are 0)"""
     return dict(_reinit_stats)
+
+
+# =========================================================================================================
+# 4-D grids (grid4d.cpp:292-467): include/open/manta_hip_grid4d.h; the classes are core.Grid4Real / Grid4Int / Grid4Vec3 / Grid4Vec4
+# =========================================================================================================
+def _chk4(obj, cls, what):
+    if not isinstance(obj, cls):
+        raise RuntimeError("can't convert argument to Grid4d<%s>*" % what)
+    return obj
+
+
+def _same4(name, a, b):
+    if a.dims != b.dims:
+        raise RuntimeError("%s: different Grid4d resolutions [%d,%d,%d,%d] vs [%d,%d,%d,%d]" % ((name,) + a.dims + b.dims))
+
+
+def _comp4d(name, entry, real, vec, src, dst, c):
+    _chk4(real, core.Grid4Real, "Real")
+    _chk4(vec, core.Grid4Vec4, "Vec4")
+    lib = _extension_lib(real.parent, name, "grid4d")
+    _same4(name, src, dst)
+    c = int(c)
+    if not 0 <= c < 4:
+        raise RuntimeError("%s: component %d of a Vec4" % (name, c))
+    lib.call(entry, real.n, src.ptr, dst.ptr, c, real.parent.stream)
+
+
+@plugin
+def getComp4d(src, dst, c):
+    """knGetComp4d: dst = src[c]"""
+    _comp4d("getComp4d", "mf_grid4d_get_comp", dst, src, src, dst, c)
+
+
+@plugin
+def setComp4d(src, dst, c):
+    """knSetComp4d: dst[c] = src"""
+    _comp4d("setComp4d", "mf_grid4d_set_comp", src, dst, src, dst, c)
+
+
+def _max_diff4d(name, cls, what, g1, g2):
+    _chk4(g1, cls, what)
+    _chk4(g2, cls, what)
+    lib = _extension_lib(g1.parent, name, "grid4d")
+    _same4(name, g1, g2)
+    r = ctypes.c_double()
+    lib.call("mf_grid4d_max_diff", g1._ncomp, int(g1._is_int), g1.n, g1.ptr, g2.ptr, ctypes.byref(r), g1.parent.stream)
+    return float(np.float32(r.value))        # the plugin returns a Real
+
+
+@plugin
+def grid4dMaxDiff(g1, g2):
+    """the largest |g1 - g2| (grid4d.cpp:352-359)"""
+    return _max_diff4d("grid4dMaxDiff", core.Grid4Real, "Real", g1, g2)
+
+
+@plugin
+def grid4dMaxDiffInt(g1, g2):
+    return _max_diff4d("grid4dMaxDiffInt", core.Grid4Int, "int", g1, g2)
+
+
+@plugin
+def grid4dMaxDiffVec3(g1, g2):
+    """the largest per-cell sum of the component differences, formed in fp64 (grid4d.cpp:368-379)"""
+    return _max_diff4d("grid4dMaxDiffVec3", core.Grid4Vec3, "Vec3", g1, g2)
+
+
+@plugin
+def grid4dMaxDiffVec4(g1, g2):
+    return _max_diff4d("grid4dMaxDiffVec4", core.Grid4Vec4, "Vec4", g1, g2)
+
+
+def _set_region4d(name, dst, start, end, v):
+    lib = _extension_lib(dst.parent, name, "grid4d")
+    s, e = core._to_vec4(start), core._to_vec4(end)
+    lib.call("mf_grid4d_set_region", dst.sx, dst.sy, dst.sz, dst.st, dst.ptr, dst._ncomp, s.x, s.y, s.z, s.t, e.x, e.y, e.z, e.t,
+             v[0], v[1], v[2], v[3], dst.parent.stream)
+
+
+@plugin
+def setRegion4d(dst, start, end, value):
+    """knSetRegion4d<Real>: cells with start <= (i, j, k, t) <= end, compared as floats, take the value"""
+    _chk4(dst, core.Grid4Real, "Real")
+    _set_region4d("setRegion4d", dst, start, end, (float(value), 0., 0., 0.))
+
+
+@plugin
+def setRegion4dVec4(dst, start, end, value):
+    _chk4(dst, core.Grid4Vec4, "Vec4")
+    _set_region4d("setRegion4dVec4", dst, start, end, tuple(core._to_vec4(value)))
+
+
+@plugin
+def getSliceFrom4d(src, srct, dst):
+    """dst(i, j, k) = src(i, j, k, srct) where both grids have the cell; an srct outside the grid changes nothing"""
+    _chk4(src, core.Grid4Real, "Real")
+    _chk(dst, Grid, "Grid<Real>")
+    lib = _extension_lib(src.parent, "getSliceFrom4d", "grid4d")
+    _extension_lib(dst.parent, "getSliceFrom4d", "grid4d")
+    lib.call("mf_grid4d_get_slice", src.sx, src.sy, src.sz, src.st, src.ptr, 1, int(srct), dst.sx, dst.sy, dst.sz, dst.ptr, None,
+             src.parent.stream)
+
+
+@plugin
+def getSliceFrom4dVec(src, srct, dst, dstt=None):
+    """the x, y, z of the slice into a Vec3 grid, the fourth component into dstt where that is given"""
+    _chk4(src, core.Grid4Vec4, "Vec4")
+    _chk(dst, VecGrid, "Grid<Vec3>")
+    dstt = _opt(dstt, Grid, "Grid<Real>")
+    lib = _extension_lib(src.parent, "getSliceFrom4dVec", "grid4d")
+    _extension_lib(dst.parent, "getSliceFrom4dVec", "grid4d")
+    if dstt is not None:
+        dst._check_same(dstt)
+    lib.call("mf_grid4d_get_slice", src.sx, src.sy, src.sz, src.st, src.ptr, 4, int(srct), dst.sx, dst.sy, dst.sz, dst.ptr,
+             None if dstt is None else dstt.ptr, src.parent.stream)
+
+
+def grid_factor_4d(s1, s2, offset, scale, size):
+    """gridFactor4d, grid4d.cpp:440-444, in fp32 as the reference's Vec4 arithmetic: the source factor and the offset of knInterpol4d"""
+    f32 = np.float32
+    s1, s2 = np.array(s1, f32), np.array(s2, f32)
+    off, scale, size = (np.array(tuple(core._to_vec4(v)), f32) for v in (offset, scale, size))
+    s2 = np.where(size > 0., size, s2)
+    fac = (s1 / s2) / scale
+    return fac, -off * fac + fac * f32(0.5)
+
+
+def _interpolate4d(name, cls, what, target, source, offset, scale, size):
+    _chk4(target, cls, what)
+    _chk4(source, cls, what)
+    lib = _extension_lib(target.parent, name, "grid4d")
+    _extension_lib(source.parent, name, "grid4d")
+    if min(source.dims) < 2:
+        raise RuntimeError("%s: every axis of the source needs 2 cells, got [%d,%d,%d,%d]" % ((name,) + source.dims))
+    if target is source:
+        raise RuntimeError("%s: target and source are the same grid" % name)
+    with np.errstate(all="ignore"):
+        fac, off = grid_factor_4d(source.dims, target.dims, offset, scale, size)
+    lib.call("mf_grid4d_interpolate", target.sx, target.sy, target.sz, target.st, target.ptr, source.sx, source.sy, source.sz, source.st,
+             source.ptr, target._ncomp, *[float(x) for x in fac], *[float(x) for x in off], target.parent.stream)
+
+
+@plugin
+def interpolateGrid4d(target, source, offset=core.vec4(0.), scale=core.vec4(1.), size=core.vec4(-1.)):
+    """linear interpolation of a 4-D Real grid to another size (grid4d.cpp:455-460)"""
+    _interpolate4d("interpolateGrid4d", core.Grid4Real, "Real", target, source, offset, scale, size)
+
+
+@plugin
+def interpolateGrid4dVec(target, source, offset=core.vec4(0.), scale=core.vec4(1.), size=core.vec4(-1.)):
+    _interpolate4d("interpolateGrid4dVec", core.Grid4Vec4, "Vec4", target, source, offset, scale, size)
+
+
+# ---- particle-data plugins of the test harness (plugin/initplugins.cpp:53-64, 287-294) and its three grid helpers (:189-269, flip.cpp:191) ----
+def _set_noise_pdata(name, kind, cls, what, parts, pd, noise, scale):
+    if not isinstance(parts, core.BasicParticleSystem):
+        raise RuntimeError("can't convert argument to BasicParticleSystem*")
+    if not isinstance(pd, cls):
+        raise RuntimeError("can't convert argument to ParticleDataImpl<%s>*" % what)
+    s = parts.parent
+    lib = _extension_lib(s, name, "grid4d")
+    if pd.sys is not parts:
+        raise RuntimeError("%s: the channel belongs to another particle system" % name)
+    lib.call("mf_grid4d_pdata_set_noise", kind, parts.np, pd.cap, pd.ptr, parts.cap, _ptr(parts.pos), _ptr(noise._tile), noise._params(),
+             float(scale), s.stream)
+
+
+@plugin
+def setNoisePdata(parts, pd, noise, scale=1.):
+    """knSetPdataNoise<Real>: pd = noise.evaluate(pos) * scale in every slot"""
+    _set_noise_pdata("setNoisePdata", 0, core.PdataReal, "Real", parts, pd, noise, scale)
+
+
+@plugin
+def setNoisePdataVec3(parts, pd, noise, scale=1.):
+    """knSetPdataNoiseVec<Vec3>: pd = noise.evaluateVec(pos) * scale"""
+    _set_noise_pdata("setNoisePdataVec3", 2, core.PdataVec3, "Vec3", parts, pd, noise, scale)
+
+
+@plugin
+def setNoisePdataInt(parts, pd, noise, scale=1.):
+    """knSetPdataNoise<int>: the Real result converted as C does, toward zero"""
+    _set_noise_pdata("setNoisePdataInt", 1, core.PdataInt, "int", parts, pd, noise, scale)
+
+
+@plugin
+def addTestParts(parts, num):
+    """`num` buffered particles at the origin, doCompress(), insertBufferedParticles() (initplugins.cpp:287-294)"""
+    if not isinstance(parts, core.BasicParticleSystem):
+        raise RuntimeError("can't convert argument to BasicParticleSystem*")
+    parts.doCompress()
+    parts.insertBufferedParticles(np.zeros((max(int(num), 0), 3), np.float32))
+
+
+def _check_symmetry(name, a, err, symmetrize, axis, bound, disable, mac):
+    err = _opt(err, Grid, "Grid<Real>")
+    s = a.parent
+    lib = _extension_lib(s, name, "grid4d")
+    if err is not None:
+        a._check_same(err)
+    if axis not in (0, 1, 2):
+        raise RuntimeError("%s: axis %d" % (name, axis))
+    lib.call("mf_grid4d_check_symmetry", a.sx, a.sy, a.sz, a.ptr, mac, None if err is None else err.ptr, int(symmetrize), axis, bound,
+             disable, s.stream)
+
+
+@plugin
+def checkSymmetry(a, err=None, symmetrize=False, axis=0, bound=0):
+    """err = |a - mirror of a about the middle of `axis`|; with symmetrize the lower half takes the upper half's values"""
+    _chk(a, Grid, "Grid<Real>")
+    _check_symmetry("checkSymmetry", a, err, symmetrize, axis, bound, 0, 0)
+
+
+@plugin
+def checkSymmetryVec3(a, err=None, symmetrize=False, axis=0, bound=0, disable=0):
+    """the MAC form: the normal component is mirrored about size + 1 with its sign flipped, the other two like a scalar; err adds up"""
+    _chk(a, VecGrid, "Grid<Vec3>")
+    _check_symmetry("checkSymmetryVec3", a, err, symmetrize, axis, bound, disable, 1)
+
+
+@plugin
+def testInitGridWithPos(grid):
+    """grid(i, j, k) = norm(Vec3(i, j, k)) (flip.cpp:191-193)"""
+    _chk(grid, Grid, "Grid<Real>")
+    lib = _extension_lib(grid.parent, "testInitGridWithPos", "grid4d")
+    lib.call("mf_grid4d_init_grid_with_pos", grid.sx, grid.sy, grid.sz, grid.ptr, grid.parent.stream)
