@@ -52,7 +52,7 @@ MORE_EXTENSIONS = (
 )
 """The second table.  EXTENSIONS above is frozen: tests/test_extensions_api.py pins its seven names and the set of headers
 include/manta_hip_*.h, so it cannot grow.  Every later extension is a row here, with its header under include/ext/; the two tables
-are treated alike everywhere (binding, SolverLib, build()'s symbol check, the *_HEADER names, plugins._extension_lib)."""
+are treated alike everywhere (binding, SolverLib, build()'s symbol check, the *_HEADER names, core._extension_lib)."""
 OPEN_EXTENSIONS = (
     Extension("fields", "the fire, wave-equation and uv-grid plugins", "do", "open"),
     Extension("mesh", "surface meshes", "do", "open"),

@@ -24,7 +24,7 @@ import types
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, fileio
 
 # ---------------------------------------------------------------------------------------------------------
 # constants: FlagGrid::CellType (grid.h:306-320), particle status (particle.h:34-43), python/defines.py:25-60
@@ -125,6 +125,43 @@ def _method_kwargs(fn):
         kw.pop("nocheck", None)
         return fn(self, *a, **kw)
     return w
+
+
+def _extension_lib(s, name, ext):
+    """the solver's library, if plugin or method `name` of extension `ext` (a row of _lib.EXTENSIONS, by name) can run on it; refused
+    before any grid is touched: a z-slab solver first, then a backend without the extension (the CPU test backend has none)"""
+    ext = _lib.extension(ext)
+    if tuple(s._slab_window) != (0, 0):
+        raise RuntimeError("%s: %s %s not run on a z-slab solver" % (name, ext.what, ext.verb))
+    if not getattr(s.lib, ext.name):
+        raise RuntimeError(ext.not_implemented(name, s.lib.backend))
+    return s.lib
+
+
+# the numpy bridge of every container: storage is component planes ([ncomp][elements], x fastest), the arrays carry an element's
+# components together ([shape] for one component, [shape][ncomp] for more)
+def _planes_to_elements(planes, shape):
+    """a copy of `planes` ([ncomp][elements], any strides) as the bridge's array"""
+    if len(planes) == 1:
+        return planes[0].reshape(shape).copy()
+    return np.ascontiguousarray(planes.T).reshape(shape + (len(planes),))
+
+
+def _elements_to_planes(arr, shape, ncomp):
+    """the bridge's array as contiguous planes [ncomp][elements]"""
+    arr = np.asarray(arr)
+    if ncomp == 1:
+        return np.ascontiguousarray(arr.reshape(math.prod(shape)))[None]
+    return np.ascontiguousarray(arr.reshape(shape + (ncomp,)).reshape(math.prod(shape), ncomp).T)
+
+
+def _format_element(is_int, ncomp, component="%+4.2f"):
+    """how the reference's streams print one element: %d, %g, or a vector's components in brackets"""
+    if is_int:
+        return lambda v: "%d" % v
+    if ncomp == 1:
+        return lambda v: "%g" % v
+    return lambda v: "[" + ",".join(component % x for x in v) + "]"
 
 
 class PbClass(object):
@@ -410,29 +447,19 @@ class GridBase(PbClass):
 
     # numpy bridge (plugin/numpyconvert.cpp:145-223): [z][y][x](,[c]) arrays
     def to_numpy(self):
-        a = self.data.detach().cpu().numpy()
-        if self._ncomp == 1:
-            return a.reshape(self.sz, self.sy, self.sx).copy()
-        return np.ascontiguousarray(a.reshape(3, self.sz, self.sy, self.sx).transpose(1, 2, 3, 0))
+        return _planes_to_elements(self.data.detach().cpu().numpy().reshape(self._ncomp, self.n), (self.sz, self.sy, self.sx))
 
     def from_numpy(self, arr):
-        arr = np.asarray(arr)
-        if self._ncomp == 1:
-            flat = np.ascontiguousarray(arr.reshape(self.n))
-        else:
-            flat = np.ascontiguousarray(arr.reshape(self.sz, self.sy, self.sx, 3).transpose(3, 0, 1, 2)).reshape(3 * self.n)
+        flat = _elements_to_planes(arr, (self.sz, self.sy, self.sx), self._ncomp).reshape(-1)
         t = torch.from_numpy(flat.astype(np.int32 if self._kind == "int" else np.float32, copy=False))
         self.data.copy_(t.to(self.data.device))
         return self
 
 
 # ---------------------------------------------------------------------------------------------------------
-# .uni / .raw grid files (fileio/iogrids.cpp:36-44, 255-292, 386-513): gzip stream of "MNT3" + UniHeader + the raw
-# element array (x fastest; Vec3 grids as 3 floats per cell).  Data format either side of the hot path.
+# .uni / .raw grid files (fileio/iogrids.cpp:255-292, 386-513): the container is fileio's; the element array is x fastest, Vec3
+# grids as 3 floats per cell.  Data format either side of the hot path.
 # ---------------------------------------------------------------------------------------------------------
-_UNI_HEADER = "<6i252siQ"       # dimX dimY dimZ gridType elementType bytesPerElement info[252] dimT timestamp = 288 B
-
-
 def _unify_grid_type(t):
     """unifyGridType, iogrids.cpp:213-221"""
     if t & GridBase.TypeReal: t |= GridBase.TypeLevelset
@@ -442,23 +469,19 @@ def _unify_grid_type(t):
     return t
 
 
+def _grid_header(g, dimT):
+    """the UniHeader's integers of a 3-D or 4-D grid (the two classes' Type* flags agree where they are read here)"""
+    et = 0 if (g._gtype & GridBase.TypeInt) else (1 if (g._gtype & GridBase.TypeReal) else 2)
+    return (g.sx, g.sy, g.sz, g._gtype, et, 4 * g._ncomp, dimT)
+
+
 def _grid_save(g, name):
-    import gzip, struct, time as _time
-    if "." not in name:
-        raise RuntimeError("file '%s' does not have an extension" % name)
-    ext = name[name.rfind("."):]
+    ext = fileio.extension(name)
     raw = g.to_numpy().astype(np.int32 if g._kind == "int" else np.float32, copy=False).tobytes()
     if ext == ".raw":
-        with gzip.open(name, "wb", compresslevel=1) as f:
-            f.write(raw)
+        fileio.write(name, raw)
     elif ext == ".uni":
-        et = 0 if (g._gtype & GridBase.TypeInt) else (1 if (g._gtype & GridBase.TypeReal) else 2)
-        info = b"mantaflow_amd 0.1 64bit fp1 hip gfx950"
-        head = struct.pack(_UNI_HEADER, g.sx, g.sy, g.sz, g._gtype, et, 4 * g._ncomp, info, 0, int(_time.time() * 1000))
-        with gzip.open(name, "wb", compresslevel=1) as f:
-            f.write(b"MNT3")
-            f.write(head)
-            f.write(raw)
+        fileio.write(name, raw, fileio.GRID, _grid_header(g, 0))
     elif ext == ".npz":
         np.savez_compressed(name, arr_0=g.to_numpy())
     else:
@@ -467,34 +490,28 @@ def _grid_save(g, name):
 
 
 def _grid_load(g, name):
-    import gzip, struct
-    if "." not in name:
-        raise RuntimeError("file '%s' does not have an extension" % name)
-    ext = name[name.rfind("."):]
+    ext = fileio.extension(name)
     dt = np.int32 if g._kind == "int" else np.float32
     nbytes = 4 * g._ncomp * g.n
     shape = (g.sz, g.sy, g.sx) if g._ncomp == 1 else (g.sz, g.sy, g.sx, 3)
     if ext == ".raw":
-        with gzip.open(name, "rb") as f:
-            raw = f.read()
+        with fileio.Reader(name) as f:
+            raw = f.payload()
         if len(raw) != nbytes:
             raise RuntimeError("can't read raw file, stream length does not match, %d vs %d" % (nbytes, len(raw)))
     elif ext == ".uni":
-        with gzip.open(name, "rb") as f:
-            ident = f.read(4)
-            if ident != b"MNT3":
+        with fileio.Reader(name) as f:
+            ident = f.magic()
+            if ident != fileio.GRID:
                 raise RuntimeError("readGridUni: Unknown header '%s' " % ident.decode(errors="replace"))
-            hb = f.read(struct.calcsize(_UNI_HEADER))
-            if len(hb) != struct.calcsize(_UNI_HEADER):
-                raise RuntimeError("can't read file, no header present")
-            dx, dy, dz, gtype, etype, bpe, info, dimt, stamp = struct.unpack(_UNI_HEADER, hb)
+            dx, dy, dz, gtype, etype, bpe, dimt = f.header(ident, "can't read file, no header present")
             if (dx, dy, dz) != (g.sx, g.sy, g.sz):
                 raise RuntimeError("grid dim doesn't match, [%d,%d,%d] vs [%d,%d,%d]" % (dx, dy, dz, g.sx, g.sy, g.sz))
             if _unify_grid_type(gtype) != _unify_grid_type(g._gtype):
                 raise RuntimeError("grid type doesn't match %d vs %d" % (gtype, g._gtype))
             if bpe != 4 * g._ncomp:
                 raise RuntimeError("grid element size doesn't match %d vs %d" % (bpe, 4 * g._ncomp))
-            raw = f.read(nbytes)
+            raw = f.payload(nbytes)         # as much as the grid holds; a shorter stream is not told apart here
     elif ext == ".npz":
         g.from_numpy(np.load(name)["arr_0"])
         return 1
@@ -705,9 +722,8 @@ class LevelsetGrid(Grid):
         in rounds of mutually distant cells and is bit-identical to the reference's serial loop; a march that cannot prove that for its
         input, and every march under MF_REINIT_SERIAL=1, runs the literal loop on the host.  One scalar read-back per sub-round and one
         per march; plugins.lastReinitStats() has the counts.  Scratch comes from the solver's pool."""
-        from . import plugins
         s = self.parent
-        lib = plugins._extension_lib(s, "LevelsetGrid::reinitMarching", "reinit")
+        lib = _extension_lib(s, "LevelsetGrid::reinitMarching", "reinit")
         if not isinstance(flags, FlagGrid):
             raise RuntimeError("can't convert argument to FlagGrid")
         if velTransport is not None and not isinstance(velTransport, MACGrid):
@@ -739,6 +755,7 @@ class LevelsetGrid(Grid):
                 val = float(np.float32(-np.float64(np.float32(maxTime)) - 1.)) if d < 0 else float(np.float32(np.float64(np.float32(maxTime)) + 1.))
                 lib.call("mf_reinit_set_uninitialized", self.sx, self.sy, self.sz, self.ptr, _ptr(fm), flags.ptr, val, int(bool(ignoreWalls)),
                          int(obstacleType), s.stream)
+            from . import plugins
             plugins._reinit_stats = {k: tuple(stats[k]) for k in ("windows", "subrounds", "pops", "serial")}
             plugins._reinit_work = {k: tuple(stats[k]) for k in ("launches", "readbacks")}
         finally:
@@ -879,16 +896,84 @@ class Grid4dBase(PbClass):
     def dims(self): return (self.sx, self.sy, self.sz, self.st)
 
 
-class Grid4d(Grid4dBase):
+class _TypedArray(PbClass):
+    """What Grid4d<T> and ParticleDataImpl<T> share: component planes of one element type in `data`, the int forms of the operators
+    and the int and norm reductions (kernels of include/open/manta_hip_grid4d.h, refused where that extension is not), and the
+    operators that are one line over _binary / _const.  A subclass gives `_count` (the live elements), `_stride` (the words from one
+    component plane to the next), `_who` (the prefix of the refusals) and its own _binary, _const and _value: the float forms differ in
+    their launches, and the order of argument conversion, refusal and size check is each method's own."""
+    _skips_empty = False        # whether a container without elements launches nothing (after the refusals, before the arguments)
+
+    @property
+    def ptr(self): return _ptr(self.data)
+    def _plane(self, c): return _ptr(self.data[c * self._stride:])
+    def _call(self, fn, *args): return self.parent.lib.call(fn, *args)
+    @property
+    def _is_int(self): return self._T == "int"
+
+    def _ext(self, what):
+        """the library if <class>::<what> can run"""
+        return _extension_lib(self.parent, self._who + what, "grid4d")
+
+    @property
+    def _launches(self): return not self._skips_empty or self._count > 0
+
+    # the int forms: refused first, then one launch over the live elements
+    def _int_binary(self, what, op, a, factor=0):
+        self._ext(what)
+        if self._launches:
+            self._call("mf_grid4d_int_binary", op, self._count, self.ptr, a.ptr, int(factor), self.parent.stream)
+
+    def _int_const(self, what, op, v):
+        self._ext(what)
+        if self._launches:
+            self._call("mf_grid4d_int_const", op, self._count, self.ptr, v, self.parent.stream)
+
+    def _int_clamp(self, lo, hi):
+        self._ext("clamp")
+        if self._launches:
+            self._call("mf_grid4d_int_clamp", self._count, self.ptr, _c_int(lo), _c_int(hi), self.parent.stream)
+
+    def add(self, a): self._binary("add", "mf_grid_add", 0, a)
+    def sub(self, a): self._binary("sub", "mf_grid_sub", 1, a)
+    def mult(self, a): self._binary("mult", "mf_grid_mult", 2, a)
+    def addConst(self, s): self._const("addConst", "mf_grid_add_const", 1, s)
+    def multConst(self, s): self._const("multConst", "mf_grid_mult_const", 2, s)
+
+    def _min_max(self, what):
+        """(min, max) as Reals: of the values (Real, int) or of the norms (the vector types: sqrt of the extreme normSquare)"""
+        f32, scalar = np.float32, self._ncomp == 1
+        if self._is_int or not scalar:
+            self._ext(what)
+        if not self._launches:
+            return self._min_max_of_none()
+        n = self._count
+        lo, hi = (ctypes.c_int32(), ctypes.c_int32()) if self._is_int else (ctypes.c_float(), ctypes.c_float())
+        if scalar:
+            self._call("mf_grid4d_int_min_max" if self._is_int else "mf_grid_min_max", n, self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
+            return f32(lo.value), f32(hi.value)
+        self._call("mf_grid4d_norm_min_max", self._ncomp, n, self._stride, self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
+        return np.sqrt(f32(lo.value)), np.sqrt(f32(hi.value))
+
+    def getMin(self): return float(self._min_max("getMin")[0])
+    def getMax(self): return float(self._min_max("getMax")[1])
+
+    def getMaxAbs(self):
+        lo, hi = self._min_max("getMaxAbs")
+        return float(hi) if self._ncomp > 1 else float(max(abs(lo), abs(hi)))
+
+
+class Grid4d(_TypedArray, Grid4dBase):
     """Grid4d<T>, one subclass per element type.  The flat float operators run through the core entries (every backend); the
     broadcast forms of the vector types, the int forms, the boundaries and the vector / int reductions are kernels of
     include/open/manta_hip_grid4d.h and are refused where that extension is not (Grid4d::<method>)."""
-    _cname_py, _cname_cpp = "Grid4d", "Grid4d"
+    _cname_py, _cname_cpp, _who = "Grid4d", "Grid4d", "Grid4d::"
 
     def __init__(self, parent, show=True, name="", **kw):
         if self._kind is None:
             raise RuntimeError("Grid4d is a template: create a Grid4Real, Grid4Int, Grid4Vec3 or Grid4Vec4")
         Grid4dBase.__init__(self, parent, show, name)
+        self._count = self._stride = self.n
         self.data = parent._alloc4(self._kind)      # zeroed: the constructor calls clear(), grid4d.cpp:68
 
     def __del__(self):
@@ -899,23 +984,7 @@ class Grid4d(Grid4dBase):
             pass
 
     @property
-    def ptr(self): return _ptr(self.data)
-    def _plane(self, c): return _ptr(self.data[c * self.n:])
-    def _call(self, fn, *args): return self.parent.lib.call(fn, *args)
-    @property
     def _N(self): return self._ncomp * self.n
-    @property
-    def _is_int(self): return self._kind == "int"
-
-    def _ext(self, what):
-        """the library if Grid4d::<what> can run: refused before anything is touched, a z-slab solver first, then a backend without
-        the extension"""
-        s, ext, who = self.parent, _lib.extension("grid4d"), "Grid4d::" + what
-        if tuple(s._slab_window) != (0, 0):
-            raise RuntimeError("%s: %s %s not run on a z-slab solver" % (who, ext.what, ext.verb))
-        if not s.lib.grid4d:
-            raise RuntimeError(ext.not_implemented(who, s.lib.backend))
-        return s.lib
 
     def _check_same(self, a):
         if not isinstance(a, Grid4d) or a._kind != self._kind:
@@ -953,14 +1022,9 @@ class Grid4d(Grid4dBase):
     def _binary(self, what, entry, op, a, factor=0):
         self._check_same(a)
         if self._is_int:
-            self._ext(what)
-            self._call("mf_grid4d_int_binary", op, self.n, self.ptr, a.ptr, int(factor), self.parent.stream)
+            self._int_binary(what, op, a, factor)
         else:
-            self._call(entry, self._N, self.ptr, a.ptr, self.parent.stream)
-
-    def add(self, a): self._binary("add", "mf_grid_add", 0, a)
-    def sub(self, a): self._binary("sub", "mf_grid_sub", 1, a)
-    def mult(self, a): self._binary("mult", "mf_grid_mult", 2, a)
+            self._call(entry, self._N, self.ptr, a.ptr, self.parent.stream)          # one launch over every component
 
     def addScaled(self, a, factor):
         """Grid4dScaledAdd<T, T>: me += factor * other with a factor of type T, per component"""
@@ -969,8 +1033,7 @@ class Grid4d(Grid4dBase):
         if self._kind == "real":
             self._call("mf_grid_scaled_add", self.n, self.ptr, a.ptr, f[0], self.parent.stream)
         elif self._is_int:
-            self._ext("addScaled")
-            self._call("mf_grid4d_int_binary", 3, self.n, self.ptr, a.ptr, f, self.parent.stream)
+            self._int_binary("addScaled", 3, a, f)
         else:
             self._ext("addScaled")
             self._call("mf_grid4d_vec_scaled_add", self._ncomp, self.n, self.ptr, a.ptr, f[0], f[1], f[2], f[3], self.parent.stream)
@@ -983,48 +1046,19 @@ class Grid4d(Grid4dBase):
             if op == 0:
                 self._call("mf_fill_i32", self.n, self.ptr, v, self.parent.stream)
             else:
-                self._ext(what)
-                self._call("mf_grid4d_int_const", op, self.n, self.ptr, v, self.parent.stream)
+                self._int_const(what, op, v)
         else:
             self._ext(what)
             self._call("mf_grid4d_vec_const", op, self._ncomp, self.n, self.ptr, v[0], v[1], v[2], v[3], self.parent.stream)
 
     def setConst(self, s): self._const("setConst", "mf_fill_f32", 0, s)
-    def addConst(self, s): self._const("addConst", "mf_grid_add_const", 1, s)
-    def multConst(self, s): self._const("multConst", "mf_grid_mult_const", 2, s)
 
     def clamp(self, min, max):
         """kn4dClamp with T(min), T(max): every component of a vector type against the same pair; int(Real) for Grid4Int"""
         if self._is_int:
-            self._ext("clamp")
-            self._call("mf_grid4d_int_clamp", self.n, self.ptr, _c_int(min), _c_int(max), self.parent.stream)
+            self._int_clamp(min, max)
         else:
             self._call("mf_grid_clamp", self._N, self.ptr, float(min), float(max), self.parent.stream)
-
-    def _min_max(self, what):
-        """(min, max) as Reals: of the values (Real, int) or of the norms (Vec3, Vec4: sqrt of the extreme normSquare)"""
-        f32 = np.float32
-        if self._kind == "real":
-            lo, hi = ctypes.c_float(), ctypes.c_float()
-            self._call("mf_grid_min_max", self.n, self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
-            return f32(lo.value), f32(hi.value)
-        self._ext(what)
-        if self._is_int:
-            lo, hi = ctypes.c_int32(), ctypes.c_int32()
-            self._call("mf_grid4d_int_min_max", self.n, self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
-            return f32(lo.value), f32(hi.value)
-        lo, hi = ctypes.c_float(), ctypes.c_float()
-        self._call("mf_grid4d_norm_min_max", self._ncomp, self.n, self.n, self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
-        return np.sqrt(f32(lo.value)), np.sqrt(f32(hi.value))
-
-    def getMin(self): return float(self._min_max("getMin")[0])
-    def getMax(self): return float(self._min_max("getMax")[1])
-
-    def getMaxAbs(self):
-        lo, hi = self._min_max("getMaxAbs")
-        if self._ncomp > 1:
-            return float(hi)
-        return float(max(abs(lo), abs(hi)))
 
     def setBound(self, value, boundaryWidth=1):
         """knSetBnd4d, grid4d.cpp:299-311"""
@@ -1043,17 +1077,10 @@ class Grid4d(Grid4dBase):
     # numpy bridge: [t][z][y][x](,[c])
     def to_numpy(self):
         self.parent.sync()
-        a = self.data.detach().cpu().numpy()
-        if self._ncomp == 1:
-            return a.reshape(self.st, self.sz, self.sy, self.sx).copy()
-        return np.ascontiguousarray(a.reshape(self._ncomp, self.st, self.sz, self.sy, self.sx).transpose(1, 2, 3, 4, 0))
+        return _planes_to_elements(self.data.detach().cpu().numpy().reshape(self._ncomp, self.n), self.dims[::-1])
 
     def from_numpy(self, arr):
-        arr = np.asarray(arr)
-        if self._ncomp == 1:
-            flat = np.ascontiguousarray(arr.reshape(self.n))
-        else:
-            flat = np.ascontiguousarray(arr.reshape(self.st, self.sz, self.sy, self.sx, self._ncomp).transpose(4, 0, 1, 2, 3)).reshape(self._N)
+        flat = _elements_to_planes(arr, self.dims[::-1], self._ncomp).reshape(-1)
         t = torch.from_numpy(flat.astype(np.int32 if self._is_int else np.float32, copy=False))
         self.data.copy_(t.to(self.data.device))
         return self
@@ -1069,8 +1096,7 @@ class Grid4d(Grid4dBase):
     def printGrid(self, zSlice=-1, tSlice=-1, printIndex=False, bnd=0):
         """Grid4d<T>::printGrid, grid4d.cpp:270-289 (host)"""
         a = self.to_numpy()
-        fmt = (lambda v: "%d" % v) if self._is_int else (lambda v: "%g" % v) if self._ncomp == 1 else \
-            (lambda v: "[" + ",".join("%+4.6f" % x for x in v) + "]")
+        fmt = _format_element(self._is_int, self._ncomp, "%+4.6f")
         out = ["\n"]
         for t in range(bnd, self.st - bnd):
             for k in range(bnd, self.sz - bnd):
@@ -1112,50 +1138,37 @@ class Grid4Vec4(Grid4d):
     _cname_py = "Grid4Vec4"
 
 
-# .uni / .raw files of 4-D grids (fileio/iogrids.cpp:624-830): "M4T3" + the UniHeader with dimT set + the elements slice by slice
-# (x fastest, the vector types with their components together)
-def _grid4d_ext(name):
-    if "." not in name:
-        raise RuntimeError("file '%s' does not have an extension" % name)
-    return name[name.rfind("."):]
-
-
+# .uni / .raw files of 4-D grids (fileio/iogrids.cpp:624-830): the UniHeader with dimT set, then the elements slice by slice (x fastest,
+# the vector types with their components together)
 def _grid4d_save(g, name):
-    import time as _time
-    ext = _grid4d_ext(name)
+    ext = fileio.extension(name)
     if ext not in (".uni", ".raw"):
         raise RuntimeError("file '%s' filetype not supported" % name)
     raw = g.to_numpy().tobytes()
-    with gzip.open(name, "wb", compresslevel=1) as f:
-        if ext == ".uni":
-            et = 0 if (g._gtype & Grid4dBase.TypeInt) else (1 if (g._gtype & Grid4dBase.TypeReal) else 2)
-            info = b"mantaflow_amd 0.1 64bit fp1 hip gfx950"
-            f.write(b"M4T3")
-            f.write(struct.pack(_UNI_HEADER, g.sx, g.sy, g.sz, g._gtype, et, 4 * g._ncomp, info, g.st, int(_time.time() * 1000)))
-        f.write(raw)
+    if ext == ".uni":
+        fileio.write(name, raw, fileio.GRID4D, _grid_header(g, g.st))
+    else:
+        fileio.write(name, raw)
     return 1
 
 
 def _grid4d_load(g, name):
-    ext = _grid4d_ext(name)
+    ext = fileio.extension(name)
     dt = np.int32 if g._is_int else np.float32
     nbytes = 4 * g._N
     shape = (g.st, g.sz, g.sy, g.sx) + ((g._ncomp,) if g._ncomp > 1 else ())
     if ext == ".raw":
-        with gzip.open(name, "rb") as f:
-            raw = f.read(nbytes)
+        with fileio.Reader(name) as f:
+            raw = f.payload(nbytes)
         if len(raw) != nbytes:
             raise RuntimeError("can't read raw file, stream length does not match, %d vs %d" % (nbytes, len(raw)))
     elif ext == ".uni":
-        with gzip.open(name, "rb") as f:
-            ident = f.read(4)
-            if ident != b"M4T3":              # the reference reports an unknown header at debug level 1 and leaves the grid as it is
+        with fileio.Reader(name) as f:
+            ident = f.magic()
+            if ident != fileio.GRID4D:        # the reference reports an unknown header at debug level 1 and leaves the grid as it is
                 print("Unknown header!")
                 return 1
-            hb = f.read(struct.calcsize(_UNI_HEADER))
-            if len(hb) != struct.calcsize(_UNI_HEADER):
-                raise RuntimeError("can't read file, no 4d header present")
-            dx, dy, dz, gtype, etype, bpe, info, dimt, stamp = struct.unpack(_UNI_HEADER, hb)
+            dx, dy, dz, gtype, etype, bpe, dimt = f.header(ident, "can't read file, no 4d header present")
             if bpe != 4 * g._ncomp:
                 raise RuntimeError("4d grid element size doesn't match %d vs %d" % (bpe, 4 * g._ncomp))
             if (dx, dy, dz) != (g.sx, g.sy, g.sz):
@@ -1164,7 +1177,7 @@ def _grid4d_load(g, name):
                 raise RuntimeError("grid type doesn't match %d vs %d" % (gtype, g._gtype))
             if dimt != g.st:
                 raise RuntimeError("grid dim4 doesn't match, %d vs [%d,%d,%d,%d]" % ((dimt,) + g.dims))
-            raw = f.read(nbytes)
+            raw = f.payload(nbytes)
             if len(raw) != nbytes:
                 raise RuntimeError("can't read file, no / not enough data")
     else:
@@ -1176,8 +1189,9 @@ def _grid4d_load(g, name):
 # ---------------------------------------------------------------------------------------------------------
 # particles, particle.{h,cpp}: BasicParticleSystem (pos + flag; the fork's pos0 is not on the hot path)
 # ---------------------------------------------------------------------------------------------------------
-class ParticleDataImpl(PbClass):
-    _ncomp, _dtype = 1, torch.float32
+class ParticleDataImpl(_TypedArray):
+    _ncomp, _dtype, _who = 1, torch.float32, "ParticleDataImpl::"
+    _skips_empty = True
 
     def __init__(self, parent, name="", **kw):
         PbClass.__init__(self, parent, name)
@@ -1200,8 +1214,6 @@ class ParticleDataImpl(PbClass):
             self.data, self.cap = new, cap
 
     pyResize = resize
-    @property
-    def ptr(self): return _ptr(self.data)
 
     def setSource(self, grid, isMAC=False):
         """ParticleDataImpl<T>::setSource, particle.cpp:341-346: the grid new particles take their value from (adjustNumber's
@@ -1213,23 +1225,19 @@ class ParticleDataImpl(PbClass):
         self.mpGridSource, self.mGridSourceMAC = grid, bool(isMAC)
     def size(self): return self.sys.np if self.sys else 0
     def clear(self): self.data.zero_()
+    @property
+    def _count(self): return self.size()
+    @property
+    def _stride(self): return self.cap
 
     def to_numpy(self):
         n = self.size()
-        a = self.data.detach().cpu().numpy()
-        if self._ncomp == 1:
-            return a[:n].copy()
-        return np.stack([a[c * self.cap:c * self.cap + n] for c in range(3)], axis=1)
+        return _planes_to_elements(self.data.detach().cpu().numpy().reshape(self._ncomp, self.cap)[:, :n], (n,))
 
     def from_numpy(self, arr):
-        arr = np.asarray(arr)
         n = self.size()
-        if self._ncomp == 1:
-            self.data[:n] = torch.from_numpy(np.ascontiguousarray(arr.reshape(n))).to(self.data.device, self.data.dtype)
-        else:
-            arr = arr.reshape(n, 3)
-            for c in range(3):
-                self.data[c * self.cap:c * self.cap + n] = torch.from_numpy(np.ascontiguousarray(arr[:, c])).to(self.data.device, self.data.dtype)
+        for c, plane in enumerate(_elements_to_planes(arr, (n,), self._ncomp)):
+            self.data[c * self.cap:c * self.cap + n] = torch.from_numpy(plane).to(self.data.device, self.data.dtype)
         return self
 
     def copyFrom(self, o):
@@ -1237,22 +1245,8 @@ class ParticleDataImpl(PbClass):
         return self
 
     # ---- the arithmetic of ParticleDataImpl<T>, particle.cpp:434-673, over the live slots [0, size): the flat float operators through
-    # the core entries on each component plane (every backend), the rest through include/open/manta_hip_grid4d.h (refused elsewhere)
-    @property
-    def _is_int(self): return self._dtype == torch.int32
-    def _plane(self, c): return _ptr(self.data[c * self.cap:])
-    def _call(self, fn, *args): return self.parent.lib.call(fn, *args)
-
-    def _ext(self, what):
-        """the library if ParticleDataImpl::<what> can run: refused before anything is touched, a z-slab solver first, then a
-        backend without the extension"""
-        s, ext, who = self.parent, _lib.extension("grid4d"), "ParticleDataImpl::" + what
-        if tuple(s._slab_window) != (0, 0):
-            raise RuntimeError("%s: %s %s not run on a z-slab solver" % (who, ext.what, ext.verb))
-        if not s.lib.grid4d:
-            raise RuntimeError(ext.not_implemented(who, s.lib.backend))
-        return s.lib
-
+    # the core entries on each component plane (every backend), the rest through include/open/manta_hip_grid4d.h (refused elsewhere).
+    # An empty channel launches nothing, after the refusals.
     def _check_other(self, a):
         if type(a) is not type(self):
             raise RuntimeError("can't convert argument to ParticleDataImpl<%s>" % self._T)
@@ -1270,16 +1264,11 @@ class ParticleDataImpl(PbClass):
     def _binary(self, what, entry, op, a, factor=0):
         self._check_other(a)
         if self._is_int:
-            self._ext(what)
-            if self.size():
-                self._call("mf_grid4d_int_binary", op, self.size(), self.ptr, a.ptr, int(factor), self.parent.stream)
+            self._int_binary(what, op, a, factor)
         elif self.size():
-            for c in range(self._ncomp):
+            for c in range(self._ncomp):              # a launch per plane: the planes are `cap` apart, not `size`
                 self._call(entry, self.size(), self._plane(c), a._plane(c), self.parent.stream)
 
-    def add(self, a): self._binary("add", "mf_grid_add", 0, a)
-    def sub(self, a): self._binary("sub", "mf_grid_sub", 1, a)
-    def mult(self, a): self._binary("mult", "mf_grid_mult", 2, a)
     def safeDiv(self, a): self._binary("safeDiv", "mf_grid_safe_divide", 4, a)
 
     def addScaled(self, a, factor):
@@ -1295,22 +1284,15 @@ class ParticleDataImpl(PbClass):
     def _const(self, what, entry, op, v):
         v = self._value(v)
         if self._is_int:
-            self._ext(what)
-            if self.size():
-                self._call("mf_grid4d_int_const", op, self.size(), self.ptr, v, self.parent.stream)
+            self._int_const(what, op, v)
         elif self.size():
             for c in range(self._ncomp):
                 self._call(entry, self.size(), self._plane(c), v[c], self.parent.stream)
 
-    def addConst(self, s): self._const("addConst", "mf_grid_add_const", 1, s)
-    def multConst(self, s): self._const("multConst", "mf_grid_mult_const", 2, s)
-
     def clamp(self, vmin, vmax):
         """knPdataClamp with T(vmin), T(vmax): per component for Vec3, int(Real) for int"""
         if self._is_int:
-            self._ext("clamp")
-            if self.size():
-                self._call("mf_grid4d_int_clamp", self.size(), self.ptr, _c_int(vmin), _c_int(vmax), self.parent.stream)
+            self._int_clamp(vmin, vmax)
         elif self.size():
             for c in range(self._ncomp):
                 self._call("mf_grid_clamp", self.size(), self._plane(c), float(vmin), float(vmax), self.parent.stream)
@@ -1343,37 +1325,13 @@ class ParticleDataImpl(PbClass):
         w = [v, 0, 0] if self._is_int else [_f32_word(x) for x in v] + [0, 0]
         self._call("mf_grid4d_pdata_set_flag", self.size(), self.cap, self._ncomp, self.ptr, w[0], w[1], w[2], t.ptr, int(flag), self.parent.stream)
 
-    def _min_max(self, what):
-        """(min, max) as Reals: of the values, or for Vec3 of the lengths (CompPdata_MinVec3 / MaxVec3); an empty channel gives the
-        reference's start values"""
-        f32 = np.float32
-        big = np.finfo(f32).max
-        if self._ncomp == 1 and not self._is_int:
-            if not self.size():
-                return big, -big
-            lo, hi = ctypes.c_float(), ctypes.c_float()
-            self._call("mf_grid_min_max", self.size(), self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
-            return f32(lo.value), f32(hi.value)
-        self._ext(what)
-        if not self.size():
-            if self._ncomp == 1:
-                return big, -big
-            with np.errstate(invalid="ignore"):
-                return np.sqrt(big), np.sqrt(-big)                  # sqrt(-FLT_MAX): the NaN the host's square root gives
-        if self._is_int:
-            lo, hi = ctypes.c_int32(), ctypes.c_int32()
-            self._call("mf_grid4d_int_min_max", self.size(), self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
-            return f32(lo.value), f32(hi.value)
-        lo, hi = ctypes.c_float(), ctypes.c_float()
-        self._call("mf_grid4d_norm_min_max", 3, self.size(), self.cap, self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
-        return np.sqrt(f32(lo.value)), np.sqrt(f32(hi.value))
-
-    def getMin(self): return float(self._min_max("getMin")[0])
-    def getMax(self): return float(self._min_max("getMax")[1])
-
-    def getMaxAbs(self):
-        lo, hi = self._min_max("getMaxAbs")
-        return float(hi) if self._ncomp > 1 else float(max(abs(lo), abs(hi)))
+    def _min_max_of_none(self):
+        """an empty channel gives the reference's start values; for Vec3 (CompPdata_MinVec3 / MaxVec3: the lengths) their roots"""
+        big = np.finfo(np.float32).max
+        if self._ncomp == 1:
+            return big, -big
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(big), np.sqrt(-big)                  # sqrt(-FLT_MAX): the NaN the host's square root gives
 
     def _sum(self, what, which, t=None, itype=0):
         if t is not None and not isinstance(t, PdataInt):
@@ -1402,56 +1360,41 @@ class ParticleDataImpl(PbClass):
         n = self.size()
         s = min(max(start if start > 0 else 0, 0), n)
         e = min(max(stop if stop > 0 else n, 0), n)
-        a = self.to_numpy()
-        fmt = (lambda v: "%d" % v) if self._is_int else (lambda v: "%g" % v) if self._ncomp == 1 else (lambda v: "[%+4.2f,%+4.2f,%+4.2f]" % tuple(v))
+        a, fmt = self.to_numpy(), _format_element(self._is_int, self._ncomp)
         print("".join(("%d: " % i if printIndex else "") + fmt(a[i]) + " \n" for i in range(s, e)))
 
-    # .uni / .raw particle data files, fileio/ioparticles.cpp:225-303: gzip stream of "PD01" + UniPartHeader + the elements
-    _UNI_PART_HEADER = "<6i256sQ"       # dim dimX dimY dimZ elementType bytesPerElement info[256] timestamp
+    # .uni / .raw particle data files, fileio/ioparticles.cpp:225-303: the UniPartHeader + the elements; both extensions name the
+    # same format
+    def _file_name(self, name, doing):
+        name = str(name)
+        if fileio.extension(name) not in (".uni", ".raw"):
+            raise RuntimeError("particle data '" + name + "' filetype not supported for " + doing)
+        return name
 
     def save(self, name):
         """ParticleDataImpl::save, particle.cpp:391-409"""
-        import time as _time
-        name = str(name)
-        if "." not in name:
-            raise RuntimeError("file '" + name + "' does not have an extension")
-        if name[name.rfind("."):] not in (".uni", ".raw"):
-            raise RuntimeError("particle data '" + name + "' filetype not supported for saving")
+        name = self._file_name(name, "saving")
         self.parent.sync()
-        gs = self.parent.mGridSize
-        head = struct.pack(self._UNI_PART_HEADER, self.size(), gs[0], gs[1], gs[2], 1, 4 * self._ncomp, b"mantaflow_amd 0.1 64bit fp1 hip gfx950",
-                           int(_time.time() * 1000))
-        with gzip.open(name, "wb", compresslevel=1) as f:
-            f.write(b"PD01" + head + np.ascontiguousarray(self.to_numpy()).tobytes())
+        fileio.write(name, np.ascontiguousarray(self.to_numpy()).tobytes(), fileio.PDATA, (self.size(),) + self.parent.mGridSize + (1, 4 * self._ncomp))
         return 1
 
     def load(self, name):
         """ParticleDataImpl::load, particle.cpp:371-389 -> readPdataUni.  The reference resizes the channel to the file's count, away
         from its system; here a channel is as long as its system, and another count is refused with the reader's message."""
-        name = str(name)
-        if "." not in name:
-            raise RuntimeError("file '" + name + "' does not have an extension")
-        if name[name.rfind("."):] not in (".uni", ".raw"):
-            raise RuntimeError("particle data '" + name + "' filetype not supported for loading")
-        try:
-            with gzip.open(name, "rb") as f:
-                raw = f.read()
-        except OSError:
-            raise RuntimeError("can't open file " + name)
-        if raw[:4] != b"PD01":      # readPdataUni reads nothing then and still answers 1; say so, as the 4-D grid reader does
-            print("Unknown header!")
-            return 1
-        hs = struct.calcsize(self._UNI_PART_HEADER)
-        if len(raw) < 4 + hs:
-            raise RuntimeError("can't read file, no header present")
-        dim, dx, dy, dz, etype, bpe, info, stamp = struct.unpack(self._UNI_PART_HEADER, raw[4:4 + hs])
+        with fileio.Reader(self._file_name(name, "loading"), whole=True) as f:
+            ident = f.magic()
+            if ident != fileio.PDATA:      # readPdataUni reads nothing then and still answers 1; say so, as the 4-D grid reader does
+                print("Unknown header!")
+                return 1
+            dim, dx, dy, dz, etype, bpe = f.header(ident, "can't read file, no header present")
+            raw = f.payload()
         if dim != self.size():
             raise RuntimeError("pdata size doesn't match")
         if bpe != 4 * self._ncomp or etype != 1:
             raise RuntimeError("pdata type doesn't match")
-        if len(raw) - 4 - hs != bpe * dim:
-            raise RuntimeError("can't read uni file, stream length does not match, %d vs %d" % (bpe * dim, len(raw) - 4 - hs))
-        a = np.frombuffer(raw, np.int32 if self._is_int else np.float32, dim * self._ncomp, 4 + hs)
+        if len(raw) != bpe * dim:
+            raise RuntimeError("can't read uni file, stream length does not match, %d vs %d" % (bpe * dim, len(raw)))
+        a = np.frombuffer(raw, np.int32 if self._is_int else np.float32, dim * self._ncomp)
         self.from_numpy(a.reshape((dim, 3) if self._ncomp == 3 else (dim,)).copy())
         return 1
 
@@ -2152,22 +2095,19 @@ class BasicParticleSystem(PbClass):
         n = self.np
         s = min(max(start if start > 0 else 0, 0), n)
         e = min(max(stop if stop > 0 else n, 0), n)
-        pos, fl = self.get_positions(), self.get_flags()
-        print("".join(("%d: " % i if printIndex else "") + "[%+4.2f,%+4.2f,%+4.2f] %d\n" % (tuple(pos[i]) + (fl[i],)) for i in range(s, e)))
+        pos, fl, vec = self.get_positions(), self.get_flags(), _format_element(False, 3)
+        print("".join(("%d: " % i if printIndex else "") + "%s %d\n" % (vec(pos[i]), fl[i]) for i in range(s, e)))
 
     def writeParticlesText(self, name):
         """BasicParticleSystem::writeParticlesText: the header line, then per slot position, flag and the int, Real and Vec3 channels"""
         ints = [p for p in self.pdata if isinstance(p, PdataInt)]
         reals = [p for p in self.pdata if isinstance(p, PdataReal)]
         vecs = [p for p in self.pdata if isinstance(p, PdataVec3)]
-        pos, fl = self.get_positions(), self.get_flags()
-        ch = [p.to_numpy() for p in ints + reals + vecs]
+        pos, fl, vec = self.get_positions(), self.get_flags(), _format_element(False, 3)
+        ch = [(p.to_numpy(), _format_element(p._is_int, p._ncomp)) for p in ints + reals + vecs]
         out = ["%d, pdata: %d (%d,%d,%d) \n" % (self.np, len(self.pdata), len(ints), len(reals), len(vecs))]
         for i in range(self.np):
-            line = "%d: [%+4.2f,%+4.2f,%+4.2f] , %d. " % ((i,) + tuple(pos[i]) + (fl[i],))
-            for p, a in zip(ints + reals + vecs, ch):
-                line += ("%d " % a[i]) if p._is_int else ("%g " % a[i]) if p._ncomp == 1 else ("[%+4.2f,%+4.2f,%+4.2f] " % tuple(a[i]))
-            out.append(line + "\n")
+            out.append("%d: %s , %d. " % (i, vec(pos[i]), fl[i]) + "".join(fmt(a[i]) + " " for a, fmt in ch) + "\n")
         text = "".join(out)
         print("writeParticlesText: %s" % text, end="")
         try:
@@ -2184,50 +2124,37 @@ class BasicParticleSystem(PbClass):
         factor = np.array([np.float32(b[c]) / np.float32(a[c]) for c in range(3)], np.float32)
         self.set_positions(source.get_positions() * factor[None, :] if source.np else np.zeros((0, 3), np.float32), source.get_flags())
 
-    # .uni particle files, fileio/ioparticles.cpp:130-223: gzip stream of "PB02" + UniPartHeader + [pos.x pos.y pos.z flag] per particle
-    _UNI_PART_HEADER = "<6i256sQ"       # dim dimX dimY dimZ elementType bytesPerElement info[256] timestamp = 288 B
+    # .uni particle files, fileio/ioparticles.cpp:130-223: the UniPartHeader + [pos.x pos.y pos.z flag] per particle
+    _UNI_RECORD = np.dtype([("pos", "<f4", 3), ("flag", "<i4")])
 
     def save(self, name):
         """BasicParticleSystem::save, particle.cpp:213-236: `.uni` (and `.raw`, the same format)"""
-        import time as _time
-        if "." not in name:
-            raise RuntimeError("file '" + name + "' does not have an extension")
-        if name[name.rfind("."):] not in (".uni", ".raw"):
+        if fileio.extension(name) not in (".uni", ".raw"):
             raise RuntimeError("particle '" + name + "' filetype not supported for saving")
-        rec = np.zeros(self.np, np.dtype([("pos", "<f4", 3), ("flag", "<i4")]))
+        rec = np.zeros(self.np, self._UNI_RECORD)
         if self.np:
             rec["pos"], rec["flag"] = self.get_positions(), self.get_flags()
-        gs = self.parent.mGridSize
-        head = struct.pack(self._UNI_PART_HEADER, self.np, gs[0], gs[1], gs[2], 0, 16, b"mantaflow_amd 0.1 64bit fp1 hip gfx950", int(_time.time() * 1000))
-        with gzip.open(name, "wb", compresslevel=1) as f:
-            f.write(b"PB02" + head + rec.tobytes())
+        fileio.write(name, rec.tobytes(), fileio.PARTS, (self.np,) + self.parent.mGridSize + (0, 16))
         return 1
 
     def load(self, name):
         """BasicParticleSystem::load, particle.cpp:195-211 -> readParticlesUni: every channel is resized, positions are scaled from
         the file's solver resolution to this solver's (transformPositions: an fp32 factor per axis)"""
-        if "." not in name:
-            raise RuntimeError("file '" + name + "' does not have an extension")
-        if name[name.rfind("."):] not in (".uni", ".raw"):
+        if fileio.extension(name) not in (".uni", ".raw"):
             raise RuntimeError("particle '" + name + "' filetype not supported for loading")
-        try:
-            with gzip.open(name, "rb") as f:
-                raw = f.read()
-        except OSError:
-            raise RuntimeError("can't open file " + name)
-        if raw[:4] == b"PB01":
-            raise RuntimeError("particle uni file format v01 not supported anymore")
-        if raw[:4] != b"PB02":
-            return 1
-        hs = struct.calcsize(self._UNI_PART_HEADER)
-        if len(raw) < 4 + hs:
-            raise RuntimeError("can't read file, no header present")
-        dim, dx, dy, dz, etype, bpe, info, stamp = struct.unpack(self._UNI_PART_HEADER, raw[4:4 + hs])
+        with fileio.Reader(name, whole=True) as f:
+            ident = f.magic()
+            if ident == fileio.PARTS_V1:
+                raise RuntimeError("particle uni file format v01 not supported anymore")
+            if ident != fileio.PARTS:
+                return 1
+            dim, dx, dy, dz, etype, bpe = f.header(ident, "can't read file, no header present")
+            raw = f.payload()
         if bpe != 16 or etype != 0:
             raise RuntimeError("particle type doesn't match")
-        if len(raw) - 4 - hs != 16 * dim:
-            raise RuntimeError("can't read uni file, stream length does not match, %d vs %d" % (16 * dim, len(raw) - 4 - hs))
-        rec = np.frombuffer(raw, np.dtype([("pos", "<f4", 3), ("flag", "<i4")]), dim, 4 + hs)
+        if len(raw) != 16 * dim:
+            raise RuntimeError("can't read uni file, stream length does not match, %d vs %d" % (16 * dim, len(raw)))
+        rec = np.frombuffer(raw, self._UNI_RECORD, dim)
         gs = self.parent.mGridSize
         factor = np.array([np.float32(gs[c]) / np.float32((dx, dy, dz)[c]) for c in range(3)], np.float32)
         self.set_positions(rec["pos"] * factor[None, :], np.array(rec["flag"]))
@@ -2350,9 +2277,8 @@ class TurbulenceParticleSystem(BasicParticleSystem):
         self.color, self.tex0, self.tex1 = (self.create(PdataVec3) for _ in range(3))
 
     def _extension_lib(self, who):
-        """plugins._extension_lib for a method: z-slab first, then a backend without the extension"""
-        from . import plugins
-        return plugins._extension_lib(self.parent, "TurbulenceParticleSystem::" + who, "turbulence")
+        """_extension_lib for a method: z-slab first, then a backend without the extension"""
+        return _extension_lib(self.parent, "TurbulenceParticleSystem::" + who, "turbulence")
 
     def _append(self, pos, color):
         n0, m = self.np, pos.shape[0]

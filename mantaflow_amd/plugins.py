@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib, core
-from .core import (FlagGrid, Grid, GridBase, LevelsetGrid, MACGrid, VecGrid, _ptr, _to_vec3, vec3)
+from .core import (FlagGrid, Grid, GridBase, LevelsetGrid, MACGrid, VecGrid, _extension_lib, _ptr, _to_vec3, vec3)
 
 PcNone, PcMIC, PcMGDynamic, PcMGStatic = 0, 1, 2, 3
 IntEuler, IntRK2, IntRK4 = 0, 1, 2
@@ -346,17 +346,6 @@ class _MgHandle(object):
 
 
 _mg_solvers = __import__("weakref").WeakSet()    # solvers that hold a hierarchy (gMapMG, pressure.cpp:248)
-
-
-def _extension_lib(s, name, ext):
-    """the solver's library, if plugin `name` of extension `ext` (a row of _lib.EXTENSIONS, by name) can run on it; refused before
-    any grid is touched: a z-slab solver first, then a backend without the extension (the CPU test backend has none)"""
-    ext = _lib.extension(ext)
-    if tuple(s._slab_window) != (0, 0):
-        raise RuntimeError("%s: %s %s not run on a z-slab solver" % (name, ext.what, ext.verb))
-    if not getattr(s.lib, ext.name):
-        raise RuntimeError(ext.not_implemented(name, s.lib.backend))
-    return s.lib
 
 
 def _multigrid_lib(s, name):
