@@ -3,8 +3,8 @@
 import sys
 
 from .core import (BasicParticleSystem, FlagGrid, FluidSolver, Grid, Grid4d, Grid4dBase, Grid4Int, Grid4Real, Grid4Vec3, Grid4Vec4, IntGrid, LevelsetGrid, MACGrid, Mesh, ParticleIndexSystem,
-                   PdataInt, PdataReal, PdataVec3, RealGrid, Solver, TurbulenceParticleSystem, Vec3Grid, VecGrid, resetTurbulenceParticleState,
-                   vec3, vec4)
+                   PdataInt, PdataReal, PdataVec3, RealGrid, Solver, TurbulenceParticleSystem, Vec3Grid, VecGrid, VortexParticleSystem, resetTurbulenceParticleState,
+                   resetVortexSeedStream, vec3, vec4)
 from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, resetOutflow, apicMapPartsToMAC, apicMapMACGridToParts, extrapolateMACFromWeight, extrapolateMACSimple, markFluidCells, addBuoyancy, addGravity, addGravityNoScale, advectSemiLagrange, computePressureRhs,
                       correctVelocity, flipVelocityUpdate, lastCgStats, mapGridToParts, mapGridToPartsVec3, mapMACToParts,
                       mapPartsToGrid, mapPartsToGridVec3, mapPartsToMAC, setDeterministicP2G, setWallBcs, solvePressure,
@@ -26,7 +26,8 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       densityInflowMesh, densityInflowMeshNoise, lastMeshSdfStats, lastReinitStats,
                       getComp4d, setComp4d, grid4dMaxDiff, grid4dMaxDiffInt, grid4dMaxDiffVec3, grid4dMaxDiffVec4, setRegion4d,
                       setRegion4dVec4, getSliceFrom4d, getSliceFrom4dVec, interpolateGrid4d, interpolateGrid4dVec,
-                      setNoisePdata, setNoisePdataVec3, setNoisePdataInt, addTestParts, checkSymmetry, checkSymmetryVec3, testInitGridWithPos)
+                      setNoisePdata, setNoisePdataVec3, setNoisePdataInt, addTestParts, checkSymmetry, checkSymmetryVec3, testInitGridWithPos,
+                      VPseedK41, markAsFixed, densityFromLevelset)
 
 from .scene import (Box, Checkbox, Cylinder, Gui, NoiseField, Shape, Slider, Sphere, densityInflow, sampleFlagsWithParticles,
                     sampleLevelsetWithParticles, sampleShapeWithParticles)

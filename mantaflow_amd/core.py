@@ -2393,3 +2393,204 @@ def _nmod1(a):
     """nmod(a, Real(1.0)), general.h:145: fmod (exact) and one conditional add"""
     c = np.fmod(np.float32(a), np.float32(1.0))
     return np.float32(c + np.float32(1.0)) if c < 0 else np.float32(c)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# vortex particles, vortexpart.{h,cpp} (include/open/manta_hip_vortex.h)
+# ---------------------------------------------------------------------------------------------------------
+class _VortexSeedStream(object):
+    """VPseedK41's `static RandomStream rand(3489572)`, one per process (cursor: the reals drawn so far).  Reals are drawn in blocks;
+    peek() shows the next ones and advance() consumes them, so the cursor counts exactly what the reference would have drawn."""
+
+    SEED = 3489572
+
+    def __init__(self):
+        from .scene import RandomStream
+        self.rs, self.cursor, self.ahead = RandomStream(self.SEED), 0, np.zeros(0, np.float32)
+
+    def peek(self, n):
+        if self.ahead.size < n:
+            self.ahead = np.concatenate([self.ahead, self.rs.reals(max(n - self.ahead.size, 4096))])
+        return self.ahead[:n]
+
+    def advance(self, n):
+        self.ahead = self.ahead[n:]
+        self.cursor += n
+
+
+_vortex_seed_stream = _VortexSeedStream()
+
+
+def resetVortexSeedStream():
+    """restart VPseedK41's random stream, as a fresh process of the reference has it (no reference counterpart)"""
+    global _vortex_seed_stream
+    _vortex_seed_stream = _VortexSeedStream()
+
+
+def _seek_vortex_seed_stream(cursor):
+    """test hook: the process-wide stream as it is after `cursor` reals"""
+    resetVortexSeedStream()
+    _vortex_seed_stream.peek(int(cursor))
+    _vortex_seed_stream.advance(int(cursor))
+
+
+def _c_pow(name, restype):
+    global _libm
+    if _libm is None:
+        _libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+        for fn in (_libm.sinf, _libm.cosf):
+            fn.restype, fn.argtypes = ctypes.c_float, [ctypes.c_float]
+    fn = getattr(_libm, name)
+    fn.restype, fn.argtypes = restype, [restype, restype]
+    return fn
+
+
+def _seed_k41_host(lib, strength, sigma0, sigma1, N, p, dirs):
+    """the C library's half of VPseedK41 (powf, pow, normalize) for the accepted cells: the library's host entry, or libm itself where
+    the loaded library lacks the vortex extension (the CPU test backend) -> sigma[m], vorticity[m][3]"""
+    f32 = np.float32
+    m = p.shape[0]
+    sig, vort = np.zeros(m, f32), np.zeros((m, 3), f32)
+    if m == 0:
+        return sig, vort
+    p, dirs = np.ascontiguousarray(p, f32), np.ascontiguousarray(dirs, f32)
+    if lib.vortex:
+        P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        lib.call("mf_vortex_seed_k41", m, float(strength), float(sigma0), float(sigma1), float(N), P(p), P(dirs), P(sig), P(vort))
+        return sig, vort
+    powf, powd = _c_pow("powf", ctypes.c_float), _c_pow("pow", ctypes.c_double)
+    N, strength = f32(N), f32(strength)
+    e1 = float(f32(-float(N) + 1.0))
+    s0, s1 = f32(powf(float(f32(sigma0)), e1)), f32(powf(float(f32(sigma1)), e1))
+    inv = 1. / (-float(N) + 1.0)
+    ex = float(f32(-10. / 6. + float(N) / 2.0))
+    eps2 = f32(VECTOR_EPSILON) * f32(VECTOR_EPSILON)
+    for q in range(m):
+        sg = f32(powd((1.0 - float(p[q])) * float(s0) + float(f32(p[q] * s1)), inv))
+        v = dirs[q].copy()
+        l = f32(f32(v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+        if abs(float(l) - 1.) < float(eps2):
+            pass
+        elif l > eps2:
+            v = v * f32(1. / float(np.sqrt(l)))
+        else:
+            v[:] = 0
+        sig[q] = sg
+        vort[q] = (v * strength) * f32(powf(float(sg), ex))
+    return sig, vort
+
+
+class VortexParticleSystem(BasicParticleSystem):
+    """VortexParticleSystem, vortexpart.h:23-41: particles with a vorticity and a core size that move in each other's induced velocity
+    (advectSelf) and move the nodes of a Mesh (applyToMesh).  Storage is BasicParticleSystem's (SoA pos, flag) with two internal
+    channels, vorticity (Vec3) and sigma (Real), so advectInGrid and compress() apply as they are and the channels move along.  The
+    two device methods need the vortex extension and a whole-domain solver; everything else runs on every backend."""
+    _cname_py, _cname_cpp, _T = "VortexParticleSystem", "VortexParticleSystem", ""
+
+    def __init__(self, parent, name="", **kw):
+        BasicParticleSystem.__init__(self, parent, name)
+        self.mAllowCompress = True      # ParticleSystem's default; BasicParticleSystem's constructor is the one that clears it
+        self.vorticity, self.sigma = self.create(PdataVec3), self.create(PdataReal)
+        self._pos2 = None               # the second position buffer of the stages, kept from call to call
+
+    def _extension_lib(self, who):
+        return _extension_lib(self.parent, "VortexParticleSystem::" + who, "vortex")
+
+    def save(self, name):
+        raise RuntimeError("VortexParticleSystem::save: not a method of the reference's VortexParticleSystem (BasicParticleSystem only)")
+
+    def load(self, name):
+        raise RuntimeError("VortexParticleSystem::load: not a method of the reference's VortexParticleSystem (BasicParticleSystem only)")
+
+    # --- host arrays in and out (the reference has no Python way to add a vortex particle except VPseedK41) ---
+    def _write(self, n0, pos, vorticity, sigma, flag):
+        m, dev = pos.shape[0], self.pos.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        for c in range(3):
+            self.pos[c * self.cap + n0:c * self.cap + n0 + m] = up(pos[:, c])
+            self.vorticity.data[c * self.vorticity.cap + n0:c * self.vorticity.cap + n0 + m] = up(vorticity[:, c])
+        self.sigma.data[n0:n0 + m] = up(sigma)
+        self.flag[n0:n0 + m] = up(flag)
+        for pd in self.pdata:               # addEntry(): every other channel gets a zero entry
+            if pd is not self.vorticity and pd is not self.sigma:
+                for c in range(pd._ncomp):
+                    pd.data[c * pd.cap + n0:c * pd.cap + n0 + m] = 0
+
+    def set_numpy(self, pos, vorticity, sigma, flag=None):
+        """replace the particles by host arrays pos[n][3], vorticity[n][3], sigma[n], flag[n] (absent: 0)"""
+        pos = np.asarray(pos, np.float32).reshape(-1, 3)
+        n = pos.shape[0]
+        vorticity, sigma = np.asarray(vorticity, np.float32).reshape(-1, 3), np.asarray(sigma, np.float32).reshape(-1)
+        flag = np.zeros(n, np.int32) if flag is None else np.asarray(flag, np.int32).reshape(-1)
+        if vorticity.shape[0] != n or sigma.shape[0] != n or flag.shape[0] != n:
+            raise RuntimeError("VortexParticleSystem::set_numpy: array lengths do not match")
+        self.resizeAll(n)
+        if n:
+            self._write(0, pos, vorticity, sigma, flag)
+
+    def numpy(self):
+        """{pos, vorticity, sigma, flag} of the slots"""
+        self.parent.sync()
+        return dict(pos=self.get_positions().reshape(-1, 3), vorticity=self.vorticity.to_numpy().reshape(-1, 3),
+                    sigma=self.sigma.to_numpy().reshape(-1), flag=self.get_flags())
+
+    def _append(self, pos, vorticity, sigma):
+        n0, m = self.np, pos.shape[0]
+        if m:
+            self.reserve(n0 + m)
+            self.resizeAll(n0 + m, self.cap)
+            self._write(n0, pos, vorticity, sigma, np.zeros(m, np.int32))
+        self.mDeleteChunk = self.np // 20   # ParticleSystem::add, particle.h:414-420
+
+    # --- the two device methods ---
+    def _scratch(self, nfloats):
+        """(tensor, release) of at least nfloats floats: a Vec3 grid of the solver's pool where it is large enough"""
+        s = self.parent
+        if nfloats <= 3 * s.ncells:
+            t = s._alloc("vec", zero=False)
+            return t, lambda: s._release("vec", t)
+        return torch.empty(nfloats, dtype=torch.float32, device=s.device), lambda: None
+
+    def _integrate(self, lib, tpos, tflag, tmask, nT, tcap, pos2, scale, mode):
+        s = self.parent
+        need = ctypes.c_int64(0)
+        lib.call("mf_vortex_scratch_bytes", self.np, ctypes.byref(need))
+        held = [self._scratch(3 * tcap), self._scratch(3 * tcap), self._scratch((need.value + 3) // 4)]
+        try:
+            (x0, _), (ut, _), (tmp, _) = held
+            lib.call("mf_vortex_integrate", nT, tcap, _ptr(tpos), _ptr(tflag), tmask, self.np, self.cap, _ptr(self.pos),
+                     _ptr(self.flag), self.vorticity.ptr, self.sigma.ptr, float(np.float32(np.float32(scale) * np.float32(s.getDt()))), mode,
+                     _ptr(pos2), _ptr(x0), _ptr(ut), _ptr(tmp), tmp.numel() * 4, s.stream)
+        finally:
+            for _, release in held:
+                release()
+
+    def advectSelf(self, scale=1.0, integrationMode=2):
+        """vortexpart.cpp:76-79: the particles move in each other's velocity field; the sources move with the stages"""
+        lib = self._extension_lib("advectSelf")
+        mode = int(integrationMode)
+        if mode not in (0, 1, 2):
+            raise RuntimeError("unknown integration type")
+        if self.np == 0:
+            return
+        if self._pos2 is None or self._pos2.numel() != 3 * self.cap:
+            self._pos2 = torch.empty(3 * self.cap, dtype=torch.float32, device=self.parent.device)
+        self._integrate(lib, self.pos, self.flag, PDELETE, self.np, self.cap, self._pos2, scale, mode)
+
+    def applyToMesh(self, mesh, scale=1.0, integrationMode=2):
+        """vortexpart.cpp:81-84: the nodes of the mesh move in the particles' velocity field; the particles stay"""
+        lib = self._extension_lib("applyToMesh")
+        if not isinstance(mesh, Mesh):
+            raise RuntimeError("can't convert argument to Mesh*")
+        mode = int(integrationMode)
+        if mode not in (0, 1, 2):
+            raise RuntimeError("unknown integration type")
+        if mesh.parent.device != self.parent.device:
+            raise RuntimeError("VortexParticleSystem::applyToMesh: the mesh lives on another device than the particles")
+        if mesh.nn == 0:
+            return
+        pos2, release = self._scratch(3 * mesh.ncap)
+        try:
+            self._integrate(lib, mesh.pos, mesh.nflag, Mesh.NfFixed, mesh.nn, mesh.ncap, pos2, scale, mode)
+        finally:
+            release()

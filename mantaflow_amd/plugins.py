@@ -2134,3 +2134,74 @@ def testInitGridWithPos(grid):
     _chk(grid, Grid, "Grid<Real>")
     lib = _extension_lib(grid.parent, "testInitGridWithPos", "grid4d")
     lib.call("mf_grid4d_init_grid_with_pos", grid.sx, grid.sy, grid.sz, grid.ptr, grid.parent.stream)
+
+
+# =========================================================================================================
+# vortex particles (plugin/vortexplugins.cpp:29-37, 169-189, 298-310): include/open/manta_hip_vortex.h; the class is
+# core.VortexParticleSystem.  The vortex sheet half of the file (VortexSheetMesh) is not implemented.
+# =========================================================================================================
+def _chk_shape(shape):
+    if not (hasattr(shape, "_inside") and hasattr(shape, "_inside_centres")):
+        raise RuntimeError("can't convert argument to Shape*")
+    return shape
+
+
+@plugin
+def VPseedK41(system, shape, strength=0.0, sigma0=0.2, sigma1=1.0, probability=1.0, N=3.0):
+    """vortexplugins.cpp:169-189 (host, every backend): the cells of the system's solver in FOR_IJK order; one draw of the process-wide
+    stream per cell inside the shape, and seven more -- p, then the direction and the position offset, each drawn z, y, x (the
+    reference compiler's argument evaluation order) -- where the draw is below probability * dt.  powf / pow / normalize run in the C
+    library (core._seed_k41_host)."""
+    f32 = np.float32
+    if not isinstance(system, core.VortexParticleSystem):
+        raise RuntimeError("can't convert argument to VortexParticleSystem*")
+    _chk_shape(shape)
+    s = system.parent
+    sx, sy, sz = s.mGridSize
+    thr = f32(f32(probability) * f32(s.getDt()))
+    cells = np.nonzero(np.asarray(shape._inside_centres(s)).reshape(-1))[0]
+    st = core._vortex_seed_stream
+    r = st.peek(8 * cells.size)
+    hit_cell, hit_at, at = [], [], 0
+    below = (r < thr).tolist()
+    for c in cells.tolist():
+        if below[at]:
+            hit_cell.append(c)
+            hit_at.append(at + 1)
+            at += 8
+        else:
+            at += 1
+    st_r = r[:at].copy()
+    st.advance(at)
+    hit_cell, hit_at = np.array(hit_cell, np.int64), np.array(hit_at, np.int64)
+    draws = st_r[hit_at[:, None] + np.arange(7)[None, :]] if hit_at.size else np.zeros((0, 7), f32)
+    p, dirs, off = draws[:, 0], draws[:, 3:0:-1], draws[:, 6:3:-1]
+    ijk = np.stack([hit_cell % sx, (hit_cell // sx) % sy, hit_cell // (sx * sy)], 1).astype(f32)
+    sigma, vort = core._seed_k41_host(s.lib, f32(strength), f32(sigma0), f32(sigma1), f32(N), p, dirs)
+    system._append((ijk + off).astype(f32), vort, sigma)
+
+
+@plugin
+def markAsFixed(mesh, shape, exclusive=True):
+    """vortexplugins.cpp:29-37 (host): nodes inside the shape get NfFixed; with `exclusive` the others lose it"""
+    if not isinstance(mesh, core.Mesh):
+        raise RuntimeError("can't convert argument to Mesh*")
+    _chk_shape(shape)
+    if mesh.nn == 0:
+        return
+    pos, _, fl = mesh.nodes_numpy()
+    inside = np.asarray(shape._inside(pos[:, 0], pos[:, 1], pos[:, 2]))
+    fl = np.where(inside, fl | core.Mesh.NfFixed, (fl & ~core.Mesh.NfFixed) if exclusive else fl).astype(np.int32)
+    mesh.nflag[:mesh.nn] = torch.from_numpy(fl).to(mesh.nflag.device)
+
+
+@plugin
+def densityFromLevelset(phi, density, value=1.0, sigma=1.0):
+    """vortexplugins.cpp:298-310, one kernel: a linear ramp of width sigma over the interface, 0 in the two outermost layers of every
+    axis (on a 2-D solver that is every cell, as in the reference)"""
+    s = phi.parent if isinstance(phi, GridBase) else density.parent
+    lib = _extension_lib(s, "densityFromLevelset", "vortex")
+    _chk(phi, LevelsetGrid, "LevelsetGrid"); _chk(density, Grid, "Grid<Real>")
+    phi._check_same(density)
+    lib.call("mf_vortex_density_from_levelset", phi.sx, phi.sy, phi.sz, phi.ptr, density.ptr, float(np.float32(value)), float(np.float32(sigma)),
+             s.stream)
