@@ -38,6 +38,10 @@ struct Workspace {
 };
 constexpr int MAX_BLOCKS = 16384;
 constexpr int WS_PCG_FLAGS = 1024;   // byte offset in Workspace::scalars of {outside_bad, x-range lo, x-range hi} (k_cg_outside_zero, k_pack_xrange)
+// Per-device host state: every table is [MAX_DEVICES] and indexed by device_slot alone (runtime.hip), which refuses a device
+// outside the table.
+constexpr int MAX_DEVICES = 16;
+int device_slot(int* slot);
 int get_workspace(Workspace** ws);
 
 // ---- grid geometry ---------------------------------------------------------------------------------
@@ -131,12 +135,13 @@ __device__ __forceinline__ bool in_grid(const Dim& d, int i, int j, int k) {
 // blocks of BLOCK threads for n items (cells or particles), at least one: a launch of zero blocks is an invalid configuration
 static inline unsigned nblk(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK > 0 ? (n + BLOCK - 1) / BLOCK : 1); }
 
-// ---- growable per-device scratch: each user keeps its own `static Arena g_x[16]` (blocks are not shared between files) ----
+// ---- growable per-device scratch: each user keeps its own `static Arena g_x[MAX_DEVICES]` (blocks are not shared between files) ----
 struct Arena {
 	char* p;
 	size_t cap;
 };
 static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 // *out = the current device's block, grown to max(2 * cap, need) bytes where need > cap (after hipDeviceSynchronize; the old
 // contents are gone, *regrown says so, also on the error return of a failed allocation, which leaves p / cap at nullptr / 0).
 int arena_reserve(Arena* per_device, size_t need, Arena** out, bool* regrown = nullptr);

@@ -10,7 +10,7 @@ using namespace mf;
 
 namespace {
 
-Arena g_arena[16];   // this file's per-device scratch (arena_reserve): grows geometrically, never shrinks
+Arena g_arena[MAX_DEVICES];   // this file's per-device scratch (arena_reserve): grows geometrically, never shrinks
 
 // relaxed agent-scope accesses for words that one kernel writes and reads (the rounds of the density sweep)
 __device__ __forceinline__ int ld_agent(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

@@ -12,7 +12,6 @@
 
 using namespace mf;
 
-static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 // =========================================================================================================
 // MIC(0) preconditioner, conjugategrad.cpp:66-97 (init) and :135-159 (apply).
@@ -1264,27 +1263,46 @@ struct FlowState {
 	unsigned sgen = 0;
 	FlowCtl* ctl = nullptr;
 };
-static FlowState g_flow[16];
-static FlowState& flow_state() {
-	int dev = 0;
-	(void)hipGetDevice(&dev);
-	return g_flow[dev & 15];
+// device buffer growth: when *cap < bytes, allocates `bytes` bytes into a temporary and only then synchronises st (queued work may still
+// read the old buffer), frees the old buffer and sets *buf and *cap.  On failure *buf and *cap keep their old, consistent values
+template <class T>
+int grow_buffer(T** buf, size_t* cap, size_t bytes, hipStream_t st) {
+	if (bytes <= *cap) return 0;
+	T* nb = nullptr;
+	MF_HIP(hipMalloc((void**)&nb, bytes));
+	hipError_t e = *buf ? hipStreamSynchronize(st) : hipSuccess;
+	if (e == hipSuccess) e = hipFree(*buf);
+	if (e != hipSuccess) {
+		(void)hipFree(nb);
+		return fail("grow_buffer: %s", hipGetErrorString(e));
+	}
+	*buf = nb;
+	*cap = bytes;
+	return 0;
+}
+static FlowState g_flow[MAX_DEVICES];
+static int flow_state(FlowState** out) {
+	int slot;
+	MF_TRY(device_slot(&slot));
+	*out = &g_flow[slot];
+	return 0;
 }
 
 // compute units of the current device: the sweeps launch one workgroup per CU at most (round 1: 834 us per apply with 256 workgroups,
 // 1040 us with 512; round 2, with a packed-only <= 128-VGPR variant and a 32- / 48-step ring for two workgroups per CU: 445 vs 412 us,
 // 217 vs 204 us per sweep -- mid-sweep the 256 bundles already stream ~4 TB/s, the rest of the sweep is the dependency chain)
-static int cu_count() {
-	static thread_local int ncu[16] = {};
-	int dev = 0;
-	(void)hipGetDevice(&dev);
-	int& n = ncu[dev & 15];
+static int cu_count(int* out) {
+	static thread_local int ncu[MAX_DEVICES] = {};
+	int slot;
+	MF_TRY(device_slot(&slot));
+	int& n = ncu[slot];
 	if (!n) {
 		n = 256;
-		(void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+		(void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, slot);   // (the slot is the device index)
 		if (n < 1) n = 1;
 	}
-	return n;
+	*out = n;
+	return 0;
 }
 // f.nempty_host: how many bundles of the registered system sit out the sweeps, read back once per system (smoke scenes: none)
 static int count_empty_bundles(FlowState& f, hipStream_t st) {
@@ -1298,7 +1316,8 @@ static int count_empty_bundles(FlowState& f, hipStream_t st) {
 }
 
 static int rows_prepare(const Dim& d, FlowState** out, hipStream_t st, int jblock_rows, int xblock_cells) {
-	FlowState& f = flow_state();
+	FlowState* f;
+	MF_TRY(flow_state(&f));
 	const int nbj = (d.sy + 7) / 8, nbk = (d.sz + 7) / 8;
 	// x-blocks of xblock_cells cells (independent systems, the caller has cut Ai) -- or the whole row
 	const int xcells = (xblock_cells > 0 && xblock_cells < d.sx) ? xblock_cells : ((d.sx + 7) / 8) * 8;
@@ -1306,11 +1325,11 @@ static int rows_prepare(const Dim& d, FlowState** out, hipStream_t st, int jbloc
 	if (nbj > 4095 || nbk > 4095 || nxb > 127) return fail("grid too large for the MIC bundle order table");
 	int jb = jblock_rows > 0 ? jblock_rows / 8 : nbj;
 	if (jb < 1 || jb > nbj) jb = nbj;
-	if (!f.ctl) {
-		MF_HIP(hipMalloc((void**)&f.ctl, sizeof(FlowCtl)));
-		MF_HIP(hipMemset(f.ctl, 0, sizeof(FlowCtl)));
+	if (!f->ctl) {
+		MF_HIP(hipMalloc((void**)&f->ctl, sizeof(FlowCtl)));
+		MF_HIP(hipMemset(f->ctl, 0, sizeof(FlowCtl)));
 	}
-	if (f.nbj != nbj || f.nbk != nbk || f.nchunks != nchunks || f.jb != jb || f.nxb != nxb) {
+	if (f->nbj != nbj || f->nbk != nbk || f->nchunks != nchunks || f->jb != jb || f->nxb != nxb) {
 		MF_HIP(hipStreamSynchronize(st));
 		const int nb = nbj * nbk * nxb;
 		std::vector<int> h((size_t)2 * nb);
@@ -1328,32 +1347,32 @@ static int rows_prepare(const Dim& d, FlowState** out, hipStream_t st, int jbloc
 							for (int xb = 0; xb < nxb; xb++) h[rev * nb + q++] = bjl | (bk << 12) | (xb << 24);
 					}
 		}
-		if (!f.rows_xt) MF_HIP(hipMalloc((void**)&f.rows_xt, 2 * sizeof(int)));
-		MF_HIP(hipMemset(f.rows_xt, 0, 2 * sizeof(int)));
-		MF_TRY(grow_buffer(&f.border, &f.border_cap, sizeof(int) * h.size(), st));
-		MF_HIP(hipMemcpy(f.border, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice));
+		if (!f->rows_xt) MF_HIP(hipMalloc((void**)&f->rows_xt, 2 * sizeof(int)));
+		MF_HIP(hipMemset(f->rows_xt, 0, 2 * sizeof(int)));
+		MF_TRY(grow_buffer(&f->border, &f->border_cap, sizeof(int) * h.size(), st));
+		MF_HIP(hipMemcpy(f->border, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice));
 		// one granule per (bundle, x', face lane) and face
 		// (fine-grained memory, hipExtMallocWithFlags, was tried for these: 0.45 instead of 0.71 us per idle hand-off in
 		// tools/micro/pingpong_scalar.hip, but no change of the sweep time -- 575.0 vs 576.4 us per apply at 256^3; so were four
 		// scalar-path poller waves (s_load_dwordx16 glc, 0.45 us per hand-off in the micro-benchmark): bit-exact, 700+ us)
 		const size_t need = (size_t)nb * 8 * (8 * (size_t)nchunks + 2 * ROWS_PAD) * sizeof(unsigned long long);
-		size_t cap = f.sx_cap;
-		for (unsigned long long** q : {&f.sxj, &f.sxk, &f.sxj1, &f.sxk1}) {
-			cap = f.sx_cap;
+		size_t cap = f->sx_cap;
+		for (unsigned long long** q : {&f->sxj, &f->sxk, &f->sxj1, &f->sxk1}) {
+			cap = f->sx_cap;
 			MF_TRY(grow_buffer(q, &cap, need, st));
 		}
-		f.sx_cap = cap;
-		for (unsigned long long* q : {f.sxj, f.sxk, f.sxj1, f.sxk1}) MF_HIP(hipMemset(q, 0, f.sx_cap));
-		MF_HIP(hipMemset(f.ctl, 0, sizeof(FlowCtl)));
-		f.sgen = 0;
-		f.nbj = nbj;
-		f.nbk = nbk;
-		f.nblocks = nb;
-		f.nchunks = nchunks;
-		f.jb = jb;
-		f.nxb = nxb;
+		f->sx_cap = cap;
+		for (unsigned long long* q : {f->sxj, f->sxk, f->sxj1, f->sxk1}) MF_HIP(hipMemset(q, 0, f->sx_cap));
+		MF_HIP(hipMemset(f->ctl, 0, sizeof(FlowCtl)));
+		f->sgen = 0;
+		f->nbj = nbj;
+		f->nbk = nbk;
+		f->nblocks = nb;
+		f->nchunks = nchunks;
+		f->jb = jb;
+		f->nxb = nxb;
 	}
-	*out = &f;
+	*out = f;
 	return 0;
 }
 // next launch generation of the hand-off granules (tag = generation: the buffers are cleared only when the 32-bit counter wraps)
@@ -1370,7 +1389,9 @@ static int rows_next_gen(FlowState* f, hipStream_t st) {
 static int launch_rows_init(const Dim& d, FlowState* f, const int32_t* flags, float* Aprecond, const float* A0, const float* Ai,
                             const float* Aj, const float* Ak, const unsigned char* pack, hipStream_t st) {
 	MF_TRY(rows_next_gen(f, st));
-	const int ncu = cu_count(), grid = f->nblocks < ncu ? f->nblocks : ncu;
+	int ncu;
+	MF_TRY(cu_count(&ncu));
+	const int grid = f->nblocks < ncu ? f->nblocks : ncu;
 	const bool vec = (d.sx % 4 == 0) && al16(flags) && al16(Aprecond) && al16(A0) && al16(Ai) && al16(Aj) && al16(Ak);
 	auto kern = vec ? k_mic_rows_init<true> : k_mic_rows_init<false>;
 	hipLaunchKernelGGL(kern, dim3(grid), dim3(ROWS_THREADS), 0, st, d, f->nbj, f->nbk, f->jb, f->nblocks, f->nchunks, f->border, f->ctl, f->rows_xt,
@@ -1397,21 +1418,22 @@ int mf::mic_mode() { return g_mic_mode; }
 extern "C" int mf_pack_matrix(int sx, int sy, int sz, const int32_t* flags, const float* A0, const float* Ai, const float* Aj, const float* Ak, void* stream) {
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
-	FlowState& f = flow_state();
+	FlowState* f;
+	MF_TRY(flow_state(&f));
 	hipStream_t st = (hipStream_t)stream;
-	f.upack_ok_host = 0;
+	f->upack_ok_host = 0;
 	if (!d.is3d || (d.sx % 4) != 0) return 0;
-	MF_TRY(grow_buffer(&f.upack, &f.upack_cap, (size_t)d.n + 64, st));
-	if (!f.upack_ok) MF_HIP(hipMalloc((void**)&f.upack_ok, 2 * sizeof(int)));
-	MF_HIP(hipMemsetAsync(f.upack_ok, 1, 2 * sizeof(int), st));
-	hipLaunchKernelGGL(k_mic_pack, dim3((unsigned)((d.n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, d.n, flags, A0, Ai, Aj, Ak, f.upack, f.upack_ok);
+	MF_TRY(grow_buffer(&f->upack, &f->upack_cap, (size_t)d.n + 64, st));
+	if (!f->upack_ok) MF_HIP(hipMalloc((void**)&f->upack_ok, 2 * sizeof(int)));
+	MF_HIP(hipMemsetAsync(f->upack_ok, 1, 2 * sizeof(int), st));
+	hipLaunchKernelGGL(k_mic_pack, dim3((unsigned)((d.n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, d.n, flags, A0, Ai, Aj, Ak, f->upack, f->upack_ok);
 	MF_LAUNCH_CHECK();
 	int ok[2] = {0, 0};
-	MF_HIP(hipMemcpyAsync(ok, f.upack_ok, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+	MF_HIP(hipMemcpyAsync(ok, f->upack_ok, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
 	MF_HIP(hipStreamSynchronize(st));
-	f.upack_ok_host = ok[0] != 0;
-	f.up_A0 = (ok[0] && ok[1] && A0) ? A0 : nullptr;
-	f.up = FlowState::Grids{flags, Ai, Aj, Ak};
+	f->upack_ok_host = ok[0] != 0;
+	f->up_A0 = (ok[0] && ok[1] && A0) ? A0 : nullptr;
+	f->up = FlowState::Grids{flags, Ai, Aj, Ak};
 	return 0;
 }
 
@@ -1425,14 +1447,17 @@ static int launch_mic(const Dim& d, const int32_t* flags, float* dst, const floa
 	const bool vec = (d.sx % 4 == 0) && al16(flags) && al16(dst) && al16(var1) && al16(Ai) && al16(Aj) && al16(Ak) && (MODE == 0 || al16(Ap));
 	if constexpr (MODE != 0) {
 		// the system mf_mic_init registered: its mode and its preconditioner blocks; any other system: requested mode, uncut
-		const FlowState& f0 = flow_state();
-		const bool same_system = f0.reg.of(flags, Ap, Aj, Ak);
-		const int mode = same_system ? f0.mode : mic_mode();
+		FlowState* f0;
+		MF_TRY(flow_state(&f0));
+		const bool same_system = f0->reg.of(flags, Ap, Aj, Ak);
+		const int mode = same_system ? f0->mode : mic_mode();
 		if (mode == 2 && d.is3d) {
 			FlowState* f;
-			MF_TRY(rows_prepare(d, &f, st, same_system ? f0.blk_rows : 0, same_system ? f0.blk_cells : 0));
+			MF_TRY(rows_prepare(d, &f, st, same_system ? f0->blk_rows : 0, same_system ? f0->blk_cells : 0));
 			MF_TRY(rows_next_gen(f, st));
-			const int ncu = cu_count(), grid = f->nblocks < ncu ? f->nblocks : ncu;
+			int ncu;
+			MF_TRY(cu_count(&ncu));
+			const int grid = f->nblocks < ncu ? f->nblocks : ncu;
 			const int* be = (f->bempty && same_system) ? f->bempty : nullptr;
 			const bool use_pack = (d.sx % 8 == 0) && f->pack && f->pk.of(flags, Ai, Aj, Ak);
 			const unsigned char* pk = use_pack ? f->pack : nullptr;
@@ -1541,13 +1566,14 @@ int mic_pack_query(const Dim& d, const int32_t* flags, const float* A0, const fl
                    const unsigned char** pack, bool* a0_packed, hipStream_t st) {
 	*pack = nullptr;
 	*a0_packed = false;
-	const FlowState& f = flow_state();
-	if (!d.is3d || f.mode != 2 || !f.pack || !f.pack_ok || !f.pk.of(flags, Ai, Aj, Ak)) return 0;
+	FlowState* f;
+	MF_TRY(flow_state(&f));
+	if (!d.is3d || f->mode != 2 || !f->pack || !f->pack_ok || !f->pk.of(flags, Ai, Aj, Ak)) return 0;
 	int ok[2] = {0, 0};
-	MF_HIP(hipMemcpyAsync(ok, f.pack_ok, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+	MF_HIP(hipMemcpyAsync(ok, f->pack_ok, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
 	MF_HIP(hipStreamSynchronize(st));
-	if (ok[0]) *pack = f.pack;
-	*a0_packed = ok[0] && ok[1] && f.pk_A0 == A0 && A0 != nullptr;
+	if (ok[0]) *pack = f->pack;
+	*a0_packed = ok[0] && ok[1] && f->pk_A0 == A0 && A0 != nullptr;
 	return 0;
 }
 int mic_empty_map(const Dim& d, const int32_t* flags, const float* Ap, const float* Aj, const float* Ak, const int** bempty, int* nbj, bool* several,
@@ -1555,32 +1581,37 @@ int mic_empty_map(const Dim& d, const int32_t* flags, const float* Ap, const flo
 	*bempty = nullptr;
 	*nbj = 0;
 	*several = false;
-	FlowState& f = flow_state();
-	if (!d.is3d || f.mode != 2 || !f.bempty || !f.reg.of(flags, Ap, Aj, Ak)) return 0;
-	if (f.nbj != (d.sy + 7) / 8 || f.nbk != (d.sz + 7) / 8 || f.nxb != 1) return 0;
-	MF_TRY(count_empty_bundles(f, st));
-	if (f.nempty_host > 0) {
-		*bempty = f.bempty;
-		*nbj = f.nbj;
-		*several = f.nblocks > cu_count();
+	FlowState* f;
+	MF_TRY(flow_state(&f));
+	if (!d.is3d || f->mode != 2 || !f->bempty || !f->reg.of(flags, Ap, Aj, Ak)) return 0;
+	if (f->nbj != (d.sy + 7) / 8 || f->nbk != (d.sz + 7) / 8 || f->nxb != 1) return 0;
+	MF_TRY(count_empty_bundles(*f, st));
+	if (f->nempty_host > 0) {
+		*bempty = f->bempty;
+		*nbj = f->nbj;
+		int ncu;
+		MF_TRY(cu_count(&ncu));
+		*several = f->nblocks > ncu;
 	}
 	return 0;
 }
 // packed bytes built by mf_pack_matrix for exactly these grids (no synchronisation: the verdict was read when they were built)
 const unsigned char* mic_pack_user(const int32_t* flags, const float* A0, const float* Ai, const float* Aj, const float* Ak, bool* a0_packed) {
-	const FlowState& f = flow_state();
 	*a0_packed = false;
-	if (!f.upack || !f.upack_ok_host || !f.up.of(flags, Ai, Aj, Ak)) return nullptr;
-	*a0_packed = f.up_A0 != nullptr && f.up_A0 == A0;
-	return f.upack;
+	FlowState* f;
+	if (flow_state(&f)) return nullptr;      // no error channel here: "no packed bytes", and the caller's next checked call reports it
+	if (!f->upack || !f->upack_ok_host || !f->up.of(flags, Ai, Aj, Ak)) return nullptr;
+	*a0_packed = f->up_A0 != nullptr && f->up_A0 == A0;
+	return f->upack;
 }
 int mic_flow_error() {
-	FlowState& f = flow_state();
-	if (!f.ctl) return 0;
+	FlowState* f;
+	MF_TRY(flow_state(&f));
+	if (!f->ctl) return 0;
 	FlowCtl fc;
-	MF_HIP(hipMemcpy(&fc, f.ctl, sizeof fc, hipMemcpyDeviceToHost));
+	MF_HIP(hipMemcpy(&fc, f->ctl, sizeof fc, hipMemcpyDeviceToHost));
 	if (fc.err) {
-		MF_HIP(hipMemset(f.ctl, 0, sizeof(FlowCtl)));
+		MF_HIP(hipMemset(f->ctl, 0, sizeof(FlowCtl)));
 		return fail("MIC dataflow sweep: a workgroup timed out waiting for its predecessor faces");
 	}
 	return 0;
@@ -1604,7 +1635,8 @@ int mic_fused_begin(const Dim& d, hipStream_t st, unsigned char** pack, int** be
 }
 // ... and the MIC factor from those bytes (k_mic_rows_init), registered as the system of (flags, Aprecond) with no coefficient arrays
 int mic_fused_finish(const Dim& d, const int32_t* flags, float* Aprecond, hipStream_t st) {
-	FlowState* f = &flow_state();      // (mic_fused_begin prepared it for d)
+	FlowState* f;      // (mic_fused_begin prepared it for d)
+	MF_TRY(flow_state(&f));
 	MF_HIP(hipMemsetAsync(Aprecond, 0, sizeof(float) * d.n, st));
 	if (!al16(Aprecond)) return fail("mic_fused_finish: Aprecond must be 16-byte aligned");
 	MF_TRY(launch_rows_init(d, f, flags, Aprecond, nullptr, nullptr, nullptr, nullptr, f->pack, st));
@@ -1633,10 +1665,11 @@ int mf_mic_init_blocked(int sx, int sy, int sz, const int32_t* flags, float* Apr
 	if (!d.is3d) return fail("mICP only supports 3D grids so far");
 	hipStream_t st = (hipStream_t)stream;
 	MF_HIP(hipMemsetAsync(Aprecond, 0, sizeof(float) * d.n, st));
-	FlowState& f0 = flow_state();
-	f0.mode = mic_mode();
-	f0.reg = FlowState::Grids{};        // no registered system until this call has built one
-	if (f0.mode != 2) return mic_sweep(0, d, flags, Aprecond, A0, nullptr, Ai, Aj, Ak, nullptr, st);   // one launch per tile hyperplane
+	FlowState* f0;
+	MF_TRY(flow_state(&f0));
+	f0->mode = mic_mode();
+	f0->reg = FlowState::Grids{};        // no registered system until this call has built one
+	if (f0->mode != 2) return mic_sweep(0, d, flags, Aprecond, A0, nullptr, Ai, Aj, Ak, nullptr, st);   // one launch per tile hyperplane
 	// "rows": one dataflow sweep (k_mic_rows_init)
 	FlowState* f;
 	MF_TRY(rows_prepare(d, &f, st, rows_j, cells_x));

@@ -726,54 +726,51 @@ k_gather_apic(Dim d, int64_t ps, const float* __restrict__ pos, const float* __r
 	vel[node] = acc_v;
 }
 
+// one call's slices of this file's per-device block (arena_reserve), cut in the order of the members
 struct Scratch {
-	int32_t* keys = nullptr;     // [cap_p]
-	int32_t* order = nullptr;    // [cap_p]
-	int32_t* tmp = nullptr;      // [cap_p]   (rank-counting sort of a crowded cell)
-	float* pay = nullptr;        // [18 * cap_p]  rec[3] (float4), link[3] (uint2) in slot order; extra value planes of a Vec3 source alias rec[1]
-	uint32_t* spe = nullptr;     // [cap_p]
-	int32_t* counts = nullptr;   // [cap_n + 1]
-	int32_t* start = nullptr;    // [cap_n + 1]
-	int32_t* big = nullptr;      // [cap_n]
-	int32_t* sums = nullptr;     // [scan blocks of cap_n + 1]
-	int32_t* nbig = nullptr;
-	int64_t cap_p = 0, cap_n = 0;
+	int32_t* keys;      // [np]
+	int32_t* order;     // [np]
+	int32_t* tmp;       // [np]   (rank-counting sort of a crowded cell)
+	uint32_t* spe;      // [np]
+	float* pay;         // [18 * cp]  rec[3] (float4), link[3] (uint2) in slot order; extra value planes of a Vec3 source alias rec[1]
+	int64_t cp;         // the plane stride pay was cut for
+	int32_t* counts;    // [n + 1]
+	int32_t* start;     // [n + 1]
+	int32_t* big;       // [n]
+	int32_t* sums;      // [scan blocks of n + 1]
+	int32_t* nbig;
 };
-Scratch g_scratch[16];
+Arena g_arena[MAX_DEVICES];
 
-int get_scratch(int64_t np, int64_t n, Scratch** out) {
-	int dev = 0;
-	MF_HIP(hipGetDevice(&dev));
-	Scratch& s = g_scratch[dev];
-	if (np > s.cap_p || n > s.cap_n) MF_HIP(hipDeviceSynchronize());
-	if (!s.nbig) MF_HIP(hipMalloc((void**)&s.nbig, sizeof(int32_t)));
-	if (np > s.cap_p) {
-		for (void* q : {(void*)s.keys, (void*)s.order, (void*)s.tmp, (void*)s.pay, (void*)s.spe})
-			if (q) MF_HIP(hipFree(q));
-		s.cap_p = np + np / 8 + 1024;
-		MF_HIP(hipMalloc((void**)&s.keys, sizeof(int32_t) * s.cap_p));
-		MF_HIP(hipMalloc((void**)&s.order, sizeof(int32_t) * s.cap_p));
-		MF_HIP(hipMalloc((void**)&s.tmp, sizeof(int32_t) * s.cap_p));
-		MF_HIP(hipMalloc((void**)&s.pay, sizeof(float) * 18 * s.cap_p));
-		MF_HIP(hipMalloc((void**)&s.spe, sizeof(uint32_t) * s.cap_p));
-	}
-	if (n > s.cap_n) {
-		for (void* q : {(void*)s.counts, (void*)s.start, (void*)s.big, (void*)s.sums})
-			if (q) MF_HIP(hipFree(q));
-		s.cap_n = n;
-		MF_HIP(hipMalloc((void**)&s.counts, sizeof(int32_t) * (s.cap_n + 1)));
-		MF_HIP(hipMalloc((void**)&s.start, sizeof(int32_t) * (s.cap_n + 1)));
-		MF_HIP(hipMalloc((void**)&s.big, sizeof(int32_t) * s.cap_n));
-		MF_HIP(hipMalloc((void**)&s.sums, sizeof(int32_t) * ((s.cap_n + 1) / (BLOCK * SCAN_ITEMS) + 2)));
-	}
-	*out = &s;
-	return 0;
+// The plane stride of a call keeps the slack of the capacity this file used to record, so a fresh process sees the strides it always
+// saw; it is a function of this call's np alone (results do not depend on it).
+int64_t plane_stride(int64_t np) { return np + np / 8 + 1024; }
+size_t sums_len(int64_t n) { return (size_t)((n + 1) / (BLOCK * SCAN_ITEMS) + 2); }
+size_t scratch_bytes(int64_t np, int64_t n) {
+	const size_t w = sizeof(int32_t);
+	return 4 * al256(w * np) + al256(w * 18 * plane_stride(np)) + 2 * al256(w * (n + 1)) + al256(w * n) + al256(w * sums_len(n)) + 256;
+}
+// this call's slices of the current device's block
+int get_scratch(int64_t np, int64_t n, Scratch* s) {
+	const size_t need = scratch_bytes(np, n);
+	Arena* a;
+	MF_TRY(arena_reserve(g_arena, need, &a));
+	Cutter c(a->p, need);
+	s->cp = plane_stride(np);
+	MF_TRY(c.take((size_t)np, &s->keys, &s->order, &s->tmp, &s->spe));
+	MF_TRY(c.take((size_t)(18 * s->cp), &s->pay));
+	MF_TRY(c.take((size_t)n + 1, &s->counts, &s->start));
+	MF_TRY(c.take((size_t)n, &s->big));
+	MF_TRY(c.take(sums_len(n), &s->sums));
+	return c.take(1, &s->nbig);
 }
 
-// start[0..n], order[0..start[n]) : the particles of every key in increasing particle index
+// this call's slices -> *s, then start[0..n], order[0..start[n]) : the particles of every key in increasing particle index
 template <int KEYMODE>
 int bin_particles(const Dim& d, int64_t np, int64_t ps, const float* pos, const int32_t* pflag, const int32_t* ptype, int exclude, Scratch* s,
                   hipStream_t st) {
+	if (np >= ((int64_t)1 << PBITS)) return fail("ordered P2G: more than 2^%d particles; use the atomic mode (setDeterministicP2G(False))", PBITS);
+	MF_TRY(get_scratch(np, d.n, s));
 	const int64_t n1 = d.n + 1;
 	const int nsb = (int)((n1 + BLOCK * SCAN_ITEMS - 1) / (BLOCK * SCAN_ITEMS));
 	MF_HIP(hipMemsetAsync(s->counts, 0, sizeof(int32_t) * n1, st));
@@ -789,17 +786,10 @@ int bin_particles(const Dim& d, int64_t np, int64_t ps, const float* pos, const 
 	return 0;
 }
 
-int check_np(int64_t np) {
-	if (np >= ((int64_t)1 << PBITS)) return fail("ordered P2G: more than 2^%d particles; use the atomic mode (setDeterministicP2G(False))", PBITS);
-	return 0;
-}
-
 template <int COMP>
 int run_apic(const Dim& d, int64_t np, int64_t ps, const float* pos, const int32_t* pflag, const int32_t* ptype, int exclude,
              const float* pvc, const float* cp, float* vel, float* mass, hipStream_t st) {
-	MF_TRY(check_np(np));
-	Scratch* s;
-	MF_TRY(get_scratch(np, d.n, &s));
+	Scratch sc, *s = &sc;
 	MF_TRY((bin_particles<10 + COMP>(d, np, ps, pos, pflag, ptype, exclude, s, st)));
 	hipLaunchKernelGGL((k_gather_apic<COMP>), dim3(nblk(d.n)), dim3(BLOCK), 0, st, d, ps, pos, pvc, cp, s->order, s->start, vel, mass);
 	MF_LAUNCH_CHECK();
@@ -813,11 +803,9 @@ namespace mf {
 // vel / weight: SoA MAC grids (already zeroed or not: every node is written)
 int p2g_ordered_mac(const Dim& d, float* vel, float* weight, int64_t np, int64_t ps, const float* pos, const int32_t* pflag,
                     const float* pvel, const int32_t* ptype, int exclude, hipStream_t st) {
-	MF_TRY(check_np(np));
-	Scratch* s;
-	MF_TRY(get_scratch(np, d.n, &s));
+	Scratch sc, *s = &sc;
 	MF_TRY((bin_particles<3>(d, np, ps, pos, pflag, ptype, exclude, s, st)));
-	const int64_t cp = s->cap_p;
+	const int64_t cp = s->cp;
 	float4* rec = (float4*)s->pay;
 	uint32_t* link = (uint32_t*)(s->pay + 12 * cp);
 	// the number of binned particles is start[n], known on the device only: the payload kernels are launched over np slots and
@@ -841,11 +829,9 @@ int p2g_ordered_mac(const Dim& d, float* vel, float* weight, int64_t np, int64_t
 // target: ncomp planes; wsum: Real grid
 int p2g_ordered_cell(const Dim& d, int ncomp, float* target, float* wsum, int64_t np, int64_t ps, const float* pos,
                      const int32_t* pflag, const float* psrc, hipStream_t st) {
-	MF_TRY(check_np(np));
-	Scratch* s;
-	MF_TRY(get_scratch(np, d.n, &s));
+	Scratch sc, *s = &sc;
 	MF_TRY((bin_particles<3>(d, np, ps, pos, pflag, nullptr, 0, s, st)));
-	const int64_t cp = s->cap_p;
+	const int64_t cp = s->cp;
 	float4* rec = (float4*)s->pay;
 	float* sv = s->pay + 4 * cp;                 // the second and third value plane of a Vec3 source
 	uint32_t* link = (uint32_t*)(s->pay + 12 * cp);

@@ -78,23 +78,6 @@ int mic_pack_query(const Dim& d, const int32_t* flags, const float* A0, const fl
 // packed bytes built by mf_pack_matrix for exactly these grids, or nullptr (no synchronisation); *a0_packed: they carry this A0
 const unsigned char* mic_pack_user(const int32_t* flags, const float* A0, const float* Ai, const float* Aj, const float* Ak, bool* a0_packed);
 int mic_mode();          // the requested sweep mode (mf_set_mic_mode): 0 levels, 2 rows
-// device buffer growth: when *cap < bytes, allocates `bytes` bytes into a temporary and only then synchronises st (queued work may still
-// read the old buffer), frees the old buffer and sets *buf and *cap.  On failure *buf and *cap keep their old, consistent values
-template <class T>
-int grow_buffer(T** buf, size_t* cap, size_t bytes, hipStream_t st) {
-	if (bytes <= *cap) return 0;
-	T* nb = nullptr;
-	MF_HIP(hipMalloc((void**)&nb, bytes));
-	hipError_t e = *buf ? hipStreamSynchronize(st) : hipSuccess;
-	if (e == hipSuccess) e = hipFree(*buf);
-	if (e != hipSuccess) {
-		(void)hipFree(nb);
-		return fail("grow_buffer: %s", hipGetErrorString(e));
-	}
-	*buf = nb;
-	*cap = bytes;
-	return 0;
-}
 // matrix-free set-up of mf_solve_pressure_fused: buffers of the system handle (empty-bundle map preset to 1 = empty), then the MIC
 // factor from the packed bytes and the registration of (flags, Aprecond) as a system without coefficient arrays
 int mic_fused_begin(const Dim& d, hipStream_t st, unsigned char** pack, int** bempty, int* nbj);

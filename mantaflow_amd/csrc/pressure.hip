@@ -256,7 +256,6 @@ k_apply_matrix_scalar(Dim d, const int32_t* __restrict__ flags, float* __restric
 	}
 }
 
-static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 // what ApplyMatrix may use beyond the four coefficient grids (every field optional)
 struct AmOpts {
@@ -1078,10 +1077,10 @@ k_unpad(int sx, int px, int64_t n, const float* __restrict__ padded, float* __re
 	}
 }
 
-// the padded copy of mf_cg_solve's system, per device (solves on one device are ordered on one stream): 11 arrays -- flags, dst, rhs,
-// residual, search, tmp, A0, Ai, Aj, Ak, Aprecond -- of g_pad_bytes / (11 * 4) floats each, every one 256-byte aligned
-static float* g_pad_buf[16];
-static size_t g_pad_bytes[16];
+// the padded copy of mf_cg_solve's system, per device (solves on one device are ordered on one stream): 11 slices of one arena block
+// -- flags, dst, rhs, residual, search, tmp, A0, Ai, Aj, Ak, Aprecond -- of this solve's padded cell count each, cut per solve.  The
+// block follows the growth rule of every arena (arena_reserve: to max(2 * cap, need) after a device synchronise, never shrinks).
+static Arena g_pad[MAX_DEVICES];
 
 extern "C" {
 
@@ -1290,30 +1289,27 @@ int mf_cg_solve(int sx, int sy, int sz, const int32_t* flags, float* dst, const 
 		const int px = (sx + 7) & ~7;
 		const int64_t rows = (int64_t)sy * sz, np_ = (int64_t)px * rows;
 		if (np_ < ((int64_t)1 << 31)) {
-			int dev = 0;
-			MF_HIP(hipGetDevice(&dev));
-			float*& b = g_pad_buf[dev & 15];
-			size_t& bytes = g_pad_bytes[dev & 15];
-			const size_t cell = 11 * sizeof(float);
-			if ((size_t)np_ * cell <= bytes || grow_buffer(&b, &bytes, cell * (size_t)(((np_ + np_ / 8 + 63) / 64) * 64), st) == 0) {   // (1/8 to spare)
-				const int64_t cap = (int64_t)(bytes / cell);
-				float *p_flags = b, *p_dst = b + cap, *p_rhs = b + 2 * cap, *p_res = b + 3 * cap, *p_search = b + 4 * cap, *p_tmp = b + 5 * cap,
-				      *p_A0 = b + 6 * cap, *p_Ai = b + 7 * cap, *p_Aj = b + 8 * cap, *p_Ak = b + 9 * cap, *p_Ap = b + 10 * cap;
+			const size_t need = 11 * al256(sizeof(float) * (size_t)np_);
+			Arena* a;
+			int32_t* p_flags;
+			float *p_dst, *p_rhs, *p_res, *p_search, *p_tmp, *p_A0, *p_Ai, *p_Aj, *p_Ak, *p_Ap;
+			if (arena_reserve(g_pad, need, &a) == 0) {
+				Cutter c(a->p, need);
+				MF_TRY(c.take((size_t)np_, &p_flags, &p_dst, &p_rhs, &p_res, &p_search, &p_tmp, &p_A0, &p_Ai, &p_Aj, &p_Ak, &p_Ap));
 				// doInit overwrites dst, residual and search, but not the non-fluid cells of tmp: the sweeps never write them,
 				// ApplyMatrix copies search there, and the dots run over all cells -- the caller's tmp goes in with the system
-				MF_HIP(hipMemsetAsync(p_dst, 0, sizeof(float) * np_, st));
-				MF_HIP(hipMemsetAsync(p_res, 0, sizeof(float) * (cap + np_), st));      // residual, search
-				MF_HIP(hipMemsetAsync(p_Ap, 0, sizeof(float) * np_, st));
+				// (k_pad_system writes every element of the seven slices it is given)
+				for (float* q : {p_dst, p_res, p_search, p_Ap}) MF_HIP(hipMemsetAsync(q, 0, sizeof(float) * np_, st));
 				hipLaunchKernelGGL(k_pad_system, dim3(blocks_for(np_, BLOCK, 4096)), dim3(BLOCK), 0, st, sx, px, np_, flags, rhs, tmp, A0, Ai, Aj, Ak,
-				                   (int32_t*)p_flags, p_rhs, p_tmp, p_A0, p_Ai, p_Aj, p_Ak);
+				                   p_flags, p_rhs, p_tmp, p_A0, p_Ai, p_Aj, p_Ak);
 				MF_LAUNCH_CHECK();
-				MF_TRY(mf_cg_solve(px, sy, sz, (const int32_t*)p_flags, p_dst, p_rhs, p_res, p_search, p_tmp, p_A0, p_Ai, p_Aj, p_Ak, p_Ap, pc, accuracy,
+				MF_TRY(mf_cg_solve(px, sy, sz, p_flags, p_dst, p_rhs, p_res, p_search, p_tmp, p_A0, p_Ai, p_Aj, p_Ak, p_Ap, pc, accuracy,
 				                   maxIter, useL2Norm, out_host, stream));
 				hipLaunchKernelGGL(k_unpad, dim3(blocks_for(d.n, BLOCK, 4096)), dim3(BLOCK), 0, st, sx, px, d.n, p_dst, dst);
 				MF_LAUNCH_CHECK();
 				return 0;
 			}
-			(void)hipGetLastError();      // the allocation failed: clear its error, solve unpadded
+			(void)hipGetLastError();      // the reservation failed (the block is then nullptr / 0): clear its error, solve unpadded
 		}
 	}
 	return cg_solve_core(d, flags, dst, rhs, residual, search, tmp, A0, Ai, Aj, Ak, Aprecond, pc, accuracy, maxIter, useL2Norm, out_host, stream, nullptr);
@@ -1473,10 +1469,10 @@ static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const f
 	memset(&h, 0, sizeof h);
 	h.resNorm = 1e20f;
 	// one event pair per device (an event belongs to the device that was current when it was created)
-	static thread_local hipEvent_t ev_dev[16][2] = {};
-	int dev_ = 0;
-	MF_HIP(hipGetDevice(&dev_));
-	hipEvent_t* ev = ev_dev[dev_ & 15];
+	static thread_local hipEvent_t ev_dev[MAX_DEVICES][2] = {};
+	int slot_;
+	MF_TRY(device_slot(&slot_));
+	hipEvent_t* ev = ev_dev[slot_];
 	if (!ev[0]) {
 		MF_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
 		MF_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));

@@ -16,11 +16,11 @@ constexpr int C_SKIP = 0, C_KILL = 1, C_SURF = 2, C_NORM = 3;
 
 // this file's per-device scratch (arena_reserve): the working arrays of a round and the compress plan, which stays in the block
 // between a round and its moves -- no other entry may take the block over.  Grows geometrically, never shrinks.
-Arena g_arena[16];
+Arena g_arena[MAX_DEVICES];
 struct Plan {
 	int32_t *holes, *fillers;   // the current compress plan, inside the block
 };
-Plan g_plan[16];
+Plan g_plan[MAX_DEVICES];
 // the block of `need` bytes and the device's plan; the plan of a block that had to be regrown is gone with it
 static int arena(size_t need, Arena** out, Plan** plan) {
 	bool regrown = false;

@@ -15,33 +15,52 @@ int fail(const char* fmt, ...) {
 	return 1;
 }
 
-static Workspace g_ws[16];
-static bool g_ws_ok[16];
-int get_workspace(Workspace** out) {
+// The current device's index into the per-device tables.  What those tables assume: host state per device is shared by the host
+// threads of a process, and calls on one device are expected from one thread at a time (the tables are not locked).  Only the error
+// text, the slab window, the event pairs of the PCG loop and g_last_shortcut are per thread.
+int device_slot(int* slot) {
 	int dev = 0;
 	MF_HIP(hipGetDevice(&dev));
-	if (dev < 0 || dev >= 16) return fail("device index %d out of range", dev);
-	if (!g_ws_ok[dev]) {
-		Workspace& w = g_ws[dev];
-		MF_HIP(hipMalloc((void**)&w.partials, sizeof(double) * MAX_BLOCKS * 4));
-		MF_HIP(hipMalloc((void**)&w.fpartials, sizeof(float) * MAX_BLOCKS * 4));
-		MF_HIP(hipMalloc(&w.scalars, 4096));
-		MF_HIP(hipMemset(w.scalars, 0, 4096));
-		MF_HIP(hipHostMalloc(&w.host, 4096, hipHostMallocDefault));
-		MF_HIP(hipMalloc((void**)&w.tilework, 4096));
-		MF_HIP(hipMemset(w.tilework, 0, 4096));
-		g_ws_ok[dev] = true;
+	if (dev < 0 || dev >= MAX_DEVICES) return fail("device index %d out of range", dev);
+	*slot = dev;
+	return 0;
+}
+
+static Workspace g_ws[MAX_DEVICES];
+static bool g_ws_ok[MAX_DEVICES];
+// the five allocations of a device's workspace, committed to the table only when all of them stand
+static int make_workspace(Workspace* w) {
+	MF_HIP(hipMalloc((void**)&w->partials, sizeof(double) * MAX_BLOCKS * 4));
+	MF_HIP(hipMalloc((void**)&w->fpartials, sizeof(float) * MAX_BLOCKS * 4));
+	MF_HIP(hipMalloc(&w->scalars, 4096));
+	MF_HIP(hipMemset(w->scalars, 0, 4096));
+	MF_HIP(hipHostMalloc(&w->host, 4096, hipHostMallocDefault));
+	MF_HIP(hipMalloc((void**)&w->tilework, 4096));
+	MF_HIP(hipMemset(w->tilework, 0, 4096));
+	return 0;
+}
+int get_workspace(Workspace** out) {
+	int slot;
+	MF_TRY(device_slot(&slot));
+	if (!g_ws_ok[slot]) {
+		Workspace w = {};
+		if (make_workspace(&w)) {      // (what was never allocated is null, which hipFree / hipHostFree accept)
+			for (void* q : {(void*)w.partials, (void*)w.fpartials, w.scalars, (void*)w.tilework}) (void)hipFree(q);
+			(void)hipHostFree(w.host);
+			return 1;
+		}
+		g_ws[slot] = w;
+		g_ws_ok[slot] = true;
 	}
-	*out = &g_ws[dev];
+	*out = &g_ws[slot];
 	return 0;
 }
 
 int arena_reserve(Arena* per_device, size_t need, Arena** out, bool* regrown) {
 	if (regrown) *regrown = false;
-	int dev = 0;
-	MF_HIP(hipGetDevice(&dev));
-	if (dev < 0 || dev >= 16) return fail("device index %d out of range", dev);
-	Arena& a = per_device[dev];
+	int slot;
+	MF_TRY(device_slot(&slot));
+	Arena& a = per_device[slot];
 	*out = &a;
 	if (need > a.cap) {
 		const size_t cap = a.cap * 2 > need ? a.cap * 2 : need;
@@ -133,7 +152,6 @@ __global__ void __launch_bounds__(BLOCK) k_binary_scalar(int64_t n, float* a, co
 	for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
 		a[i] = op2<OP>(OP == OP_COPY ? 0.f : a[i], b[i], f);
 }
-static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 template <int OP>
 static int run_unary(int64_t n, float* a, float p, float q, void* stream) {

@@ -114,7 +114,7 @@ k_gpi_keys(Dim d, int64_t np, int64_t ps, const float* __restrict__ pos, const i
 	keys[p] = key;
 	vals[p] = (int)p;
 }
-static Arena g_sort[16];   // gridParticleIndex's scan / sort workspace, per device (arena_reserve)
+static Arena g_sort[MAX_DEVICES];   // gridParticleIndex's scan / sort workspace, per device (arena_reserve)
 
 // ComputeUnionLevelsetPindex, plugin/flip.cpp:322-353 (+ setBound(0.5, 0) fused: the boundary test of knSetBoundary with w=0)
 __global__ void __launch_bounds__(BLOCK)

@@ -233,24 +233,24 @@ def run_mac_accum(impl, inp, m=None):
     return impl.host(vel), impl.host(w)
 
 
-def run_mac(impl, inp, m=None):
-    """mf_map_parts_to_mac, atomic mode -> finished (vel, velOld, weight)"""
+def run_mac(impl, inp, m=None, deterministic=0):
+    """mf_map_parts_to_mac, atomic mode (or the ordered one: deterministic=1) -> finished (vel, velOld, weight)"""
     sx, sy, sz = inp.dims
     n3 = 3 * sx * sy * sz
     m, ps, pos, pflag, pvel, ptype = _pargs(impl, inp, m)
     vel, vo, w = _garbage(impl, n3, 1), _garbage(impl, n3, 3), _garbage(impl, n3, 2)
-    impl.call("mf_map_parts_to_mac", sx, sy, sz, vel, vo, w, m, ps, pos, pflag, pvel, ptype, EXCLUDE, 0, None)
+    impl.call("mf_map_parts_to_mac", sx, sy, sz, vel, vo, w, m, ps, pos, pflag, pvel, ptype, EXCLUDE, deterministic, None)
     impl.sync()
     return impl.host(vel), impl.host(vo), impl.host(w)
 
 
-def run_cell(impl, inp, ncomp, m=None):
-    """mf_map_parts_to_grid, atomic mode -> (divided target, raw weight sums)"""
+def run_cell(impl, inp, ncomp, m=None, deterministic=0):
+    """mf_map_parts_to_grid, atomic mode (or the ordered one: deterministic=1) -> (divided target, raw weight sums)"""
     sx, sy, sz = inp.dims
     n = sx * sy * sz
     m, ps, pos, pflag, pvel, _ = _pargs(impl, inp, m)
     tgt, w = _garbage(impl, ncomp * n, 4), _garbage(impl, n, 5)
-    impl.call("mf_map_parts_to_grid", sx, sy, sz, ncomp, tgt, w, m, ps, pos, pflag, pvel, 0, None)      # ncomp 1 reads pvel's x row
+    impl.call("mf_map_parts_to_grid", sx, sy, sz, ncomp, tgt, w, m, ps, pos, pflag, pvel, deterministic, None)      # ncomp 1 reads pvel's x row
     impl.sync()
     return impl.host(tgt), impl.host(w)
 
