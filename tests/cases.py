@@ -332,9 +332,12 @@ def advect_inputs(dims, seed, vmax=2.5, outflow=False):
     return flags, vel
 
 
-def run_advect_pkg(dims, dt, flags, vel, field, kind, **kw):
+def run_advect_pkg(dims, dt, flags, vel, field, kind, prepare=None, **kw):
+    """prepare: called with the fresh solver before any grid is created (poison_pool fills its temp-grid pool there)"""
     from mantaflow_amd import core, plugins
     s = _mk_solver(dims, dt)
+    if prepare is not None:
+        prepare(s)
     fl, v = core.FlagGrid(s), core.MACGrid(s)
     soa_to_grid(fl, flags); soa_to_grid(v, vel)
     G = {0: core.Grid, 1: core.VecGrid, 2: core.MACGrid, 3: core.LevelsetGrid}[kind]
@@ -1470,3 +1473,574 @@ def run_upres_pass_pkg(nc, vel_coarse):
         plugins.advectSemiLagrange(flags=xfl, vel=xV, grid=xD, order=2)
     xl.sync()
     return dict(energy=grid_to_soa(E), xl_weight=grid_to_soa(xW), xl_vel=grid_to_soa(xV), xl_dens=grid_to_soa(xD))
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the base kernels at the branches and launch edges that the seeded inputs above do not reach.  Each builder takes a seeded
+# input of the kind used above and plants a few dozen hand-placed particles / cells; each *_reach function counts, with plain
+# numpy on the inputs, how often every planted branch condition holds (tests/test_base_edges_inputs.py asserts the counts on
+# the CPU, tests/test_gpu_base_edges.py asserts them again and compares HIP with the oracle).
+# ---------------------------------------------------------------------------------------------------------
+EDGE_DIMS = [(12, 10, 9), SIZE_2D, (17, 11, 9)]
+PNEW, PDELETE = 1, 1 << 10
+
+
+def flag_at_model(flags, x, y, z):
+    """the rule flip.hip documents for the flag at a position: the plane is clamped into the grid, then the flat (x/y unchecked)
+    index is clamped into the array -- the flag of the nearest cell decides.  -> (flag, unclamped plane, unclamped flat index)"""
+    sz, sy, sx = flags.shape
+    k_raw = int(z)
+    k = min(max(k_raw, 0), sz - 1)
+    idx_raw = int(x) + sx * int(y) + (sx * sy if sz > 1 else 0) * k
+    idx = min(max(idx_raw, 0), flags.size - 1)
+    return int(flags.reshape(-1)[idx]), k_raw, idx_raw
+
+
+def clamp_bisect_model(flags, x0):
+    """KnClampPositions + bisectBacktracePos (particle.h:494-523) in numpy fp32 for ONE particle that did not move: it starts
+    outside the domain, so with stopInObstacle every GridAdvectKernel evaluation stops it (u = 0) in all three integration
+    modes.  -> (final position, [flag_at_model results in evaluation order])"""
+    f32 = np.float32
+    sz, sy, sx = flags.shape
+    o = [f32(v) for v in x0]
+    q = list(o)
+    i, j, k = int(q[0]), int(q[1]), int(q[2])
+    if not (0 <= i < sx and 0 <= j < sy and ((0 <= k < sz) if sz > 1 else k == 0)):
+        q = [min(max(v, f32(0)), f32(h - 1)) for v, h in zip(q, (sx, sy, sz))]
+    evals = [flag_at_model(flags, *q)]
+    if evals[0][0] & util.OBS:
+        s = f32(0)
+        for it in range(1, 5):
+            ds = f32(1.0 / (1 << it))
+            sb = f32(s + ds)
+            t = [f32(f32(float(oc) * (1.0 - float(sb))) + f32(qc * sb)) for oc, qc in zip(o, q)]
+            evals.append(flag_at_model(flags, *t))
+            if not (evals[-1][0] & util.OBS):
+                s = sb
+        q = [f32(f32(float(oc) * (1.0 - float(s))) + f32(qc * s)) for oc, qc in zip(o, q)]
+    return np.array(q, f32), evals
+
+
+def advect_parts_edge_inputs(dims, seed):
+    """advectInGrid: the particles of make_particles (some PNEW) with a ptype array for `exclude` = 2, plus particles planted
+    beside the domain (finite, within three cells of it) so that the clamp of the final position lands in an obstacle cell and the
+    bisection between the start and the clamped position evaluates the flag at positions outside the grid:
+      plane_hi_obstacle  z >= sz+1, x / y inside            plane clamp k > sz-1, nearest cell is wall
+      plane_hi_fluid     z >= sz+1, x <= -2.1               plane clamp, flat index in range: nearest cell made FLUID here
+      flat_hi_obstacle   z >= sz+1, y >= sy+1               plane clamp + flat index > n-1 -> cell n-1 (wall)
+      flat_lo_fluid      z <= -2.1, y <= -2.1               plane clamp k < 0 + flat index < 0 -> cell 0, made FLUID here
+      plane_lo_obstacle  z <= -2.1, x / y inside            plane clamp k < 0, nearest cell is wall
+    (in 2-D the same x / y at z = 0.5: only the flat-index clamps fire; a 2-D particle off its plane is left out, the reference's
+    interpolMAC reads past the velocity grid there).  `planted` marks them: the reference reads past its flag grid
+    there, so they stay out of reference runs; their outcome is checked against clamp_bisect_model instead."""
+    sx, sy, sz = dims
+    rng = np.random.default_rng(seed + 7)
+    flags = util.make_flags(sx, sy, sz, seed, empty_top=True)
+    vel = util.smooth_vel(sx, sy, sz, seed + 1, 2.0)
+    pos, pflag, _ = util.make_particles(flags, 2, seed + 2)
+    ptype = (rng.integers(0, 2, pos.shape[1]) * 2).astype(np.int32)
+    m, jrow = 12, 3
+    flags.reshape(-1)[0] = util.FLUID
+    flags[sz - 1, jrow - 1, sx - 1] = util.FLUID
+    u = lambda lo, hi: rng.uniform(lo, hi, m)
+    groups = {
+        "plane_hi_obstacle": (u(2, sx - 2), u(2, sy - 2), u(sz + 1.0, sz + 1.45)),
+        "plane_hi_fluid": (u(-2.9, -2.1), np.full(m, jrow + 0.5), u(sz + 1.0, sz + 1.45)),
+        "flat_hi_obstacle": (u(2, sx - 2), u(sy + 1.0, sy + 1.45), u(sz + 1.0, sz + 1.45)),
+        "flat_lo_fluid": (u(2, sx - 2), u(-2.9, -2.1), u(-2.9, -2.1)),
+        "plane_lo_obstacle": (u(2, sx - 2), u(2, sy - 2), u(-2.9, -2.1)),
+    }
+    if sz == 1:              # 2-D particles stay in their plane: only the groups beside the domain in x / y, only the flat-index clamps
+        del groups["plane_hi_obstacle"], groups["plane_lo_obstacle"]
+    extra = np.concatenate([np.stack(g, 0) for g in groups.values()], axis=1).astype(np.float32)
+    if sz == 1:
+        extra[2] = 0.5
+    group = np.concatenate([np.full(pos.shape[1], -1)] + [np.full(m, q) for q in range(len(groups))])
+    pos = np.ascontiguousarray(np.concatenate([pos, extra], axis=1))
+    pflag = np.concatenate([pflag, np.zeros(extra.shape[1], np.int32)])
+    ptype = np.concatenate([ptype, np.zeros(extra.shape[1], np.int32)])
+    return dict(flags=flags, vel=vel, pos=pos, pflag=pflag, ptype=ptype, exclude=2, planted=group >= 0, group=group,
+                group_names=list(groups))
+
+
+def advect_parts_edge_reach(dims, I):
+    """how often each planted branch condition holds, from the inputs alone"""
+    sx, sy, sz = dims
+    flags, pos = I["flags"], I["pos"]
+    n = flags.size
+    r = {k: 0 for k in ("plane_clamp_hi", "plane_clamp_lo", "flat_clamp_hi", "flat_clamp_lo", "nearest_obstacle", "nearest_fluid")}
+    for p in np.nonzero(I["planted"])[0]:
+        _, ev = clamp_bisect_model(flags, pos[:, p])
+        for fl, k_raw, idx_raw in ev[1:]:      # ev[0] is the clamped position itself: inside the grid
+            out = k_raw > sz - 1 or k_raw < 0 or idx_raw > n - 1 or idx_raw < 0
+            r["plane_clamp_hi"] += k_raw > sz - 1
+            r["plane_clamp_lo"] += k_raw < 0
+            r["flat_clamp_hi"] += idx_raw > n - 1
+            r["flat_clamp_lo"] += idx_raw < 0
+            r["nearest_obstacle"] += out and bool(fl & util.OBS)
+            r["nearest_fluid"] += out and bool(fl & util.FLUID)
+    alive = (I["pflag"] & PDELETE) == 0
+    r["pnew"] = int((alive & ((I["pflag"] & PNEW) != 0)).sum())
+    r["excluded"] = int((alive & ((I["ptype"] & I["exclude"]) != 0)).sum())
+    r["not_excluded"] = int((alive & ((I["ptype"] & I["exclude"]) == 0)).sum())
+    r["pnew_excluded"] = int((alive & ((I["pflag"] & PNEW) != 0) & ((I["ptype"] & I["exclude"]) != 0)).sum())
+    if sz == 1:
+        del r["plane_clamp_hi"], r["plane_clamp_lo"]
+    return {k: int(v) for k, v in r.items()}
+
+
+ADVECT_PARTS_MODES = [(mode, d, st, sk) for mode in (0, 1, 2) for d, st in ((False, True), (True, True), (False, False), (True, False))
+                      for sk in (False, True)]
+
+
+def flip_edge_inputs(dims, seed):
+    """the transfers of run_flip_pkg with particles beside the low faces: y in (-1.5, 0) and, in 3-D, z in (-1.5, 0) -- the
+    y < 0 / z < 0 clamps of build_index_shift (interpol.h:116-129)"""
+    sx, sy, sz = dims
+    rng = np.random.default_rng(seed + 5)
+    flags = util.make_flags(sx, sy, sz, seed, empty_top=True)
+    vel, velOld = util.rand_vel(sx, sy, sz, seed + 1), util.rand_vel(sx, sy, sz, seed + 2)
+    pos, pflag, pvel = util.make_particles(flags, 2, seed + 3)
+    m = 16
+    ylo = np.stack([rng.uniform(1, sx - 1, m), rng.uniform(-1.5, -0.01, m), rng.uniform(1, sz - 1, m) if sz > 1 else np.full(m, 0.5)])
+    add = [ylo]
+    if sz > 1:
+        add.append(np.stack([rng.uniform(1, sx - 1, m), rng.uniform(1, sy - 1, m), rng.uniform(-1.5, -0.01, m)]))
+        add.append(np.stack([rng.uniform(-1.5, -0.01, m), rng.uniform(-1.5, -0.01, m), rng.uniform(-1.5, -0.01, m)]))
+    add = np.concatenate(add, axis=1).astype(np.float32)
+    pos = np.ascontiguousarray(np.concatenate([pos, add], axis=1))
+    pflag = np.concatenate([pflag, np.zeros(add.shape[1], np.int32)])
+    pv = rng.normal(0, 0.5, add.shape).astype(np.float32)
+    if sz == 1:
+        pv[2] = 0
+    pvel = np.ascontiguousarray(np.concatenate([pvel, pv], axis=1))
+    ptype = rng.choice(np.array([1, 4, 1], np.int32), pos.shape[1]).astype(np.int32)
+    return dict(flags=flags, vel=vel, velOld=velOld, pos=pos, pflag=pflag, pvel=pvel, ptype=ptype)
+
+
+def flip_edge_reach(dims, I):
+    alive = ((I["pflag"] & PDELETE) == 0) & ((I["ptype"] & 4) == 0)
+    r = {"y_below_0": int((alive & (I["pos"][1] < 0)).sum())}
+    if dims[2] > 1:
+        r["z_below_0"] = int((alive & (I["pos"][2] < 0)).sum())
+    return r
+
+
+def _append_parts(I, pos, ptype, rng):
+    """append planted particles (alive, not PNEW) to the particle arrays of a surface_inputs dict"""
+    pos = np.asarray(pos, np.float32)
+    m = pos.shape[1]
+    I["pos"] = np.ascontiguousarray(np.concatenate([I["pos"], pos], axis=1))
+    I["pflag"] = np.concatenate([I["pflag"], np.zeros(m, np.int32)])
+    I["ptype"] = np.concatenate([I["ptype"], np.asarray(ptype, np.int32)])
+    pv = rng.normal(0, 0.5, (3, m)).astype(np.float32)
+    xp = (pos + rng.normal(0, 0.3, (3, m))).astype(np.float32)
+    if I["flags"].shape[0] == 1:
+        pv[2] = 0
+    I["pvel"] = np.ascontiguousarray(np.concatenate([I["pvel"], pv], axis=1))
+    I["xprev"] = np.ascontiguousarray(np.concatenate([I["xprev"], xp], axis=1))
+
+
+SURF_PATCH_ZERO, SURF_PATCH_UNIT = (3, 3, 3), (7, 3, 3)      # centre cells (i, j, k) of the two phiObs patches (k = 0 in 2-D)
+
+
+def surface_edge_inputs(dims, seed):
+    """surface_inputs plus
+      - particles exactly at cell centres (type 1 and, a few, type 4): for unionParticleLevelset the distance to their own cell
+        centre is exactly 0 (l <= eps^2) and to the six neighbouring centres exactly 1 (|l - 1| < eps^2)
+      - phiObs constant (0.1) in the 3^3 cells around SURF_PATCH_ZERO: zero gradient, normalize3 < 1e-6, pushOutofObs skips; and
+        phiObs = 0.5 * (i - 7) around SURF_PATCH_UNIT: getGradient (an undivided central difference) is exactly (1, 0, 0), the
+        |l - 1| < eps^2 arm of normalize3; particles in both centre cells
+      - 3-D: phiObs lowered by 3 in the two first and two last planes and particles in the first and the last plane: the k clamps
+        of getGradient, with phiObs below the threshold so that the gradient is evaluated
+      - particles well inside the band of projectOutOfBnd on every axis
+      - fiso: a cleared box with fluid pairs along x, y (and z): each of the cells has exactly one fluid neighbour, in one of the
+        six (four) directions; plus one fluid cell without any fluid neighbour"""
+    sx, sy, sz = dims
+    is3 = sz > 1
+    I = surface_inputs(dims, seed)
+    rng = np.random.default_rng(seed + 9)
+    kk, jj, ii = np.nonzero(I["flags"] & util.FLUID)
+    pick = rng.choice(len(ii), 14, replace=False)
+    centre = np.stack([ii[pick] + 0.5, jj[pick] + 0.5, kk[pick] + 0.5]).astype(np.float32)
+    _append_parts(I, centre, [1] * 10 + [4] * 4, rng)
+    phiObs = I["phiObs"]
+    if is3:
+        phiObs[:2] -= 3
+        phiObs[-2:] -= 3
+    for (ci, cj, ck), unit in ((SURF_PATCH_ZERO, False), (SURF_PATCH_UNIT, True)):
+        ck = ck if is3 else 0
+        ks = slice(ck - 1, ck + 2) if is3 else slice(0, 1)
+        if unit:
+            phiObs[ks, cj - 1:cj + 2, ci - 1:ci + 2] = (0.5 * (np.arange(ci - 1, ci + 2) - ci)).astype(np.float32)[None, None, :]
+        else:
+            phiObs[ks, cj - 1:cj + 2, ci - 1:ci + 2] = np.float32(0.1)
+        p = np.stack([ci + rng.uniform(0.05, 0.95, 10), cj + rng.uniform(0.05, 0.95, 10), ck + rng.uniform(0.05, 0.95, 10) if is3 else np.full(10, 0.5)])
+        _append_parts(I, p, [1] * 10, rng)
+    if is3:
+        for z0 in (0.0, sz - 1.0):
+            p = np.stack([rng.uniform(1.5, sx - 1.5, 12), rng.uniform(1.5, sy - 1.5, 12), z0 + rng.uniform(0.05, 0.95, 12)])
+            _append_parts(I, p, [1] * 12, rng)
+    p = np.stack([rng.uniform(3, sx - 3, 10), rng.uniform(3, sy - 3, 10), rng.uniform(3, sz - 3, 10) if is3 else np.full(10, 0.5)])
+    _append_parts(I, p, [1] * 10, rng)
+    p = np.stack([rng.uniform(3, sx - 3, 8), sy - rng.uniform(1.1, 2.4, 8), rng.uniform(3, sz - 3, 8) if is3 else np.full(8, 0.5)])
+    _append_parts(I, p, [1] * 8, rng)      # and a few that "Y" moves, whatever the seeded particles do
+    fiso = I["fiso"]
+    box = fiso[1:7, 1:7, 1:7] if is3 else fiso[:, 1:7, 1:7]
+    box[...] = util.EMPTY
+    kz = 2 if is3 else 0
+    for c in ((kz, 2, 2), (kz, 2, 3), (kz, 2, 5), (kz, 3, 5), (5 if is3 else 0, 5, 5)):      # x pair, y pair, the isolated cell
+        fiso[c] = util.FLUID
+    if is3:
+        fiso[2, 5, 2] = fiso[3, 5, 2] = util.FLUID                                             # z pair
+    return I
+
+
+def _cells_of(dims, pos):
+    """isInBounds(toVec3i(pos)) and the cell, in numpy (truncation towards zero)"""
+    sx, sy, sz = dims
+    c = np.trunc(pos).astype(np.int64)
+    inb = (c[0] >= 0) & (c[1] >= 0) & (c[2] >= 0) & (c[0] < sx) & (c[1] < sy) & (c[2] < sz)
+    return inb, c
+
+
+def isolated_pattern_counts(flags):
+    """fluid cells of an (sz, sy, sx) flag field by their fluid neighbours: 'none', or the one direction of the only one"""
+    f = (flags & util.FLUID) != 0
+    p = np.pad(f, 1)
+    nb = {"-x": p[1:-1, 1:-1, :-2], "+x": p[1:-1, 1:-1, 2:], "-y": p[1:-1, :-2, 1:-1], "+y": p[1:-1, 2:, 1:-1]}
+    if flags.shape[0] > 1:
+        nb.update({"-z": p[:-2, 1:-1, 1:-1], "+z": p[2:, 1:-1, 1:-1]})
+    total = sum(v.astype(np.int32) for v in nb.values())
+    r = {"none": int((f & (total == 0)).sum())}
+    for k, v in nb.items():
+        r["only" + k] = int((f & (total == 1) & v).sum())
+    return r
+
+
+def surface_edge_reach(dims, I):
+    sx, sy, sz = dims
+    is3 = sz > 1
+    pos, ptype = I["pos"], I["ptype"]
+    alive = (I["pflag"] & PDELETE) == 0
+    inb, c = _cells_of(dims, pos)
+    kept = alive & ((ptype & 4) == 0)
+    r = {}
+    at_centre = ((pos - np.trunc(pos)) == 0.5).all(0) & inb
+    interior = (c[0] >= 1) & (c[0] < sx - 1) & (c[1] >= 1) & (c[1] < sy - 1) & ((c[2] >= 1) & (c[2] < sz - 1) if is3 else True)
+    r["union_centre_dist0_and_dist1"] = int((kept & at_centre & interior).sum())
+    r["union_indexed_excluded"] = int((alive & inb & ((ptype & 4) != 0)).sum())
+    r["union_indexed_kept"] = int((kept & inb).sum())
+    for nm, (ci, cj, ck) in (("push_zero_gradient", SURF_PATCH_ZERO), ("push_unit_gradient", SURF_PATCH_UNIT)):
+        r[nm] = int((kept & inb & (c[0] == ci) & (c[1] == cj) & (c[2] == (ck if is3 else 0))).sum())
+    if is3:
+        low = I["phiObs"][:2].max() < 0.25 and I["phiObs"][-2:].max() < 0.25      # every interpolated value there is below thresh
+        r["push_first_plane"] = int((kept & inb & (c[2] == 0)).sum()) * int(low)
+        r["push_last_plane"] = int((kept & inb & (c[2] == sz - 1)).sum()) * int(low)
+    r["push_excluded"] = int((alive & ((ptype & 4) != 0)).sum())
+    b = np.float32(2.5)           # projectOutOfBnd(2.5, "xYz"), no ptype
+    r["project_x_inside"], r["project_x_moved"] = int((alive & (pos[0] > b)).sum()), int((alive & ~(pos[0] > b)).sum())
+    r["project_Y_inside"], r["project_Y_moved"] = int((alive & ~(np.float32(sy) - b < pos[1])).sum()), int((alive & (np.float32(sy) - b < pos[1])).sum())
+    if is3:
+        r["project_z_inside"], r["project_z_moved"] = int((alive & (pos[2] > b)).sum()), int((alive & ~(pos[2] > b)).sum())
+    r["project_excluded"] = int((alive & ((ptype & 4) != 0)).sum())           # projectOutOfBnd(1.25, "xXyYzZ", ptype, 4)
+    for bit in (1, 4):            # addForcePvel / eulerStep exclude 1, updateVelocityFromDeltaPos exclude 4 (no PDELETE test there)
+        r["ptype_%d_set" % bit], r["ptype_%d_clear" % bit] = int(((ptype & bit) != 0).sum()), int(((ptype & bit) == 0).sum())
+    for k, v in isolated_pattern_counts(I["fiso"]).items():
+        r["isolated_" + k] = v
+    return r
+
+
+def markfluid_edge_inputs(dims, seed):
+    """markFluidCells: flipglue_inputs with cells that are FLUID before the call and hold no particle (the empty band), particles
+    outside the grid, a ptype array for `exclude` = 4 and a random phiObs of both signs"""
+    sx, sy, sz = dims
+    fl0, pos, pflag, pvel, vel = flipglue_inputs(dims, seed)
+    rng = np.random.default_rng(seed + 6)
+    band = np.zeros(fl0.shape, bool)
+    band[:, (2 * sy) // 3:, :] = True
+    cand = np.argwhere(band & (fl0 == util.EMPTY))
+    for c in cand[rng.choice(len(cand), 30, replace=False)]:
+        fl0[tuple(c)] = util.FLUID
+    m = 12
+    out = np.stack([np.concatenate([sx + rng.uniform(0.01, 1.4, m), rng.uniform(1, sx - 1, m)]),
+                    np.concatenate([rng.uniform(1, sy - 1, m), -1 - rng.uniform(0.01, 1.4, m)]),
+                    rng.uniform(1, sz - 1, 2 * m) if sz > 1 else np.full(2 * m, 0.5)]).astype(np.float32)
+    pos = np.ascontiguousarray(np.concatenate([pos, out], axis=1))
+    pflag = np.concatenate([pflag, np.zeros(2 * m, np.int32)])
+    ptype = rng.choice(np.array([1, 4, 1, 1], np.int32), pos.shape[1]).astype(np.int32)
+    phiObs = util.rand_real((sz, sy, sx), seed + 8)
+    return dict(flags=fl0, pos=pos, pflag=pflag, ptype=ptype, exclude=4, phiObs=phiObs)
+
+
+def markfluid_edge_reach(dims, I):
+    sx, sy, sz = dims
+    fl, phi = I["flags"], I["phiObs"]
+    alive = (I["pflag"] & PDELETE) == 0
+    excl = (I["ptype"] & I["exclude"]) != 0
+    inb, c = _cells_of(dims, I["pos"])
+    r = {"excluded": int((alive & excl).sum()), "kept": int((alive & ~excl).sum()), "outside_grid": int((alive & ~excl & ~inb).sum())}
+    hit = np.zeros(fl.shape, bool)
+    sel = alive & ~excl & inb
+    hit[c[2][sel], c[1][sel], c[0][sel]] = True
+    was_fluid = (fl & util.FLUID) != 0
+    r["fluid_reset_to_empty"] = int((was_fluid & ~hit).sum())
+    now = np.where(was_fluid, (fl | util.EMPTY) & ~util.FLUID, fl)
+    now = np.where(hit & ((now & util.EMPTY) != 0), (now | util.FLUID) & ~util.EMPTY, now)
+    inner = np.zeros(fl.shape, bool)
+    inner[(slice(1, -1) if sz > 1 else slice(None), slice(1, -1), slice(1, -1))] = True
+    r["phiObs_positive"], r["phiObs_not_positive"] = int((inner & (phi > 0)).sum()), int((inner & ~(phi > 0)).sum())
+    cand = inner & ~(phi > 0) & ((now & util.EMPTY) != 0)
+    fluid = (now & util.FLUID) != 0
+    t = f = 0
+    for ax in ((2, 1, 0) if sz > 1 else (2, 1)):
+        for sgn in (1, -1):
+            nbf, opp = np.roll(fluid, sgn, axis=ax), np.roll(phi, -sgn, axis=ax)     # interior cells only: no wrap-around is read
+            t += int((cand & nbf & (opp <= 0)).sum())
+            f += int((cand & nbf & ~(opp <= 0)).sum())
+    r["fluid_neighbour_opposite_inside_obstacle"], r["fluid_neighbour_opposite_outside"] = t, f
+    return r
+
+
+def run_markfluid_pkg(dims, I):
+    from mantaflow_amd import core, plugins
+    s = _mk_solver(dims)
+    fl = soa_to_grid(core.FlagGrid(s), I["flags"])
+    pp = _mk_parts(s, I["pos"], I["pflag"])
+    pt = _pd_int(s, pp, I["ptype"])
+    plugins.markFluidCells(pp, fl, phiObs=soa_to_grid(core.Grid(s), I["phiObs"]), ptype=pt, exclude=I["exclude"])
+    out = {"flags_phi": grid_to_soa(fl)}
+    fl = soa_to_grid(core.FlagGrid(s), I["flags"])
+    plugins.markFluidCells(pp, fl, ptype=pt, exclude=I["exclude"])
+    out["flags"] = grid_to_soa(fl)
+    s.sync()
+    return out
+
+
+def run_markfluid_ref(dims, I):
+    sx, sy, sz = dims
+    n = I["pos"].shape[1]
+    out = {}
+    for nm, phi in (("flags_phi", I["phiObs"]), ("flags", None)):
+        fl = I["flags"].copy()
+        refcall("ref_mark_fluid_cells", sx, sy, sz, fl, n, n, I["pos"], I["pflag"], I["ptype"], I["exclude"], phi)
+        out[nm] = fl
+    return out
+
+
+TURB_CLAMP = (-0.05, 0.05)
+
+
+def turb_edge_inputs(dims, small_dims, seed):
+    """turb_inputs with some fluid cells turned EMPTY (their +x / +y / +z neighbours stay fluid: the `curFluid && neighbour
+    EMPTY` arm of the force application in vorticityConfinement) and a box of velocity whose curl has norm exactly 1; the noise of
+    run_turb_edge_pkg clamps to TURB_CLAMP"""
+    flags, vel, energy_in, weight_small = turb_inputs(dims, small_dims, seed)
+    rng = np.random.default_rng(seed + 4)
+    cells = np.argwhere(flags == util.FLUID)
+    for c in cells[rng.choice(len(cells), max(len(cells) // 12, 12), replace=False)]:
+        flags[tuple(c)] = util.EMPTY
+    # a box in which the velocity is (0, i, 0): the centred velocity is (0, i, 0) too and its curl exactly (0, 0, 1) -- the
+    # |l - 1| < eps^2 arm of the norm in vorticityConfinement
+    ks = slice(2, 7) if dims[2] > 1 else slice(None)
+    vel[:, ks, 2:8, 2:9] = 0
+    vel[1, ks, 2:8, 2:9] = np.arange(2, 9, dtype=np.float32)[None, None, :]
+    return dict(flags=flags, vel=vel, energy_in=energy_in, weight_small=weight_small, small_dims=small_dims)
+
+
+def turb_edge_reach(dims, I):
+    sz = dims[2]
+    fl = I["flags"]
+    inner = np.zeros(fl.shape, bool)
+    inner[(slice(1, -1) if sz > 1 else slice(None), slice(1, -1), slice(1, -1))] = True
+    cur = inner & ((fl & util.FLUID) != 0)
+    r = {}
+    for nm, ax in (("x", 2), ("y", 1)) + ((("z", 0),) if sz > 1 else ()):
+        r["fluid_with_empty_lower_" + nm] = int((cur & ((np.roll(fl, 1, axis=ax) & util.EMPTY) != 0)).sum())
+    # GetCentered + CurlOp (commonkernels.h:38-47, 126-131) on the interior, in fp32 (wrap-around of np.roll only reaches the border)
+    v = I["vel"]
+    h = np.float32(0.5)
+    c = [h * (v[0] + np.roll(v[0], -1, axis=2)), h * (v[1] + np.roll(v[1], -1, axis=1)),
+         h * (v[2] + np.roll(v[2], -1, axis=0)) if sz > 1 else np.zeros_like(v[2])]
+    dd = lambda g, ax: np.roll(g, -1, axis=ax) - np.roll(g, 1, axis=ax)
+    cz = h * (dd(c[1], 2) - dd(c[0], 1))
+    cx = h * (dd(c[2], 1) - dd(c[1], 0)) if sz > 1 else np.zeros_like(cz)
+    cy = h * (dd(c[0], 0) - dd(c[2], 2)) if sz > 1 else np.zeros_like(cz)
+    r["curl_norm_exactly_1"] = int((inner & ((cx * cx + cy * cy + cz * cz) == 1)).sum())
+    return r
+
+
+def run_turb_edge_pkg(dims, I, clamp=TURB_CLAMP, t_total=2.5):
+    """vorticityConfinement on the planted flags; applyNoiseVec3 with a clamping noise field (clamp = None: unclamped), with a
+    weight grid of the target's resolution, of another resolution, and without one"""
+    from mantaflow_amd import core, plugins, scene
+    s = _mk_solver(dims)
+    s.timeTotal = t_total
+    out = {}
+    fl = soa_to_grid(core.FlagGrid(s), I["flags"])
+    v = soa_to_grid(core.MACGrid(s), I["vel"])
+    plugins.vorticityConfinement(vel=v, flags=fl, strength=0.3)
+    out["vortconf"] = grid_to_soa(v)
+    noise = scene.NoiseField(parent=s, loadFromFile=True)
+    noise.posScale = core.vec3(int(1.0 * dims[0])) * 0.5
+    noise.timeAnim = 0.1
+    if clamp is not None:
+        noise.clamp, noise.clampNeg, noise.clampPos = True, clamp[0], clamp[1]
+    w = soa_to_grid(core.Grid(s), I["energy_in"])
+    t = soa_to_grid(core.VecGrid(s), I["vel"])
+    plugins.applyNoiseVec3(flags=fl, target=t, noise=noise, scale=0.4, weight=w)
+    out["noise_same"] = grid_to_soa(t)
+    ss = _mk_solver(I["small_dims"])
+    t = soa_to_grid(core.MACGrid(s), I["vel"])
+    plugins.applyNoiseVec3(flags=fl, target=t, noise=noise, scale=0.24, scaleSpatial=1.5, weight=soa_to_grid(core.Grid(ss), I["weight_small"]))
+    out["noise_interp"] = grid_to_soa(t)
+    t = soa_to_grid(core.VecGrid(s), I["vel"])
+    plugins.applyNoiseVec3(flags=fl, target=t, noise=noise)
+    out["noise_plain"] = grid_to_soa(t)
+    s.sync()
+    return out
+
+
+def run_turb_edge_ref(dims, I, clamp=TURB_CLAMP, t_total=2.5):
+    sx, sy, sz = dims
+    cf = ctypes.c_float
+    sd = I["small_dims"]
+    out = {}
+    v = I["vel"].copy()
+    refcall("ref_vorticity_confinement", sx, sy, sz, v, I["flags"], cf(0.3), None)
+    out["vortconf"] = v
+    ps = np.float32(int(1.0 * dims[0])) * np.float32(0.5)
+    P = np.array([ps, ps, ps, 0, 0, 0, 0.0, 1.0, 0 if clamp is None else 1, (clamp or (0, 1))[0], (clamp or (0, 1))[1], 0.1], np.float32)
+    t = I["vel"].copy()
+    refcall("ref_apply_noise_vec3", sx, sy, sz, cf(t_total), I["flags"], t, -1, P, cf(0.4), cf(1.0), I["energy_in"], sx, sy, sz, None)
+    out["noise_same"] = t
+    t = I["vel"].copy()
+    refcall("ref_apply_noise_vec3", sx, sy, sz, cf(t_total), I["flags"], t, -1, P, cf(0.24), cf(1.5), I["weight_small"], sd[0], sd[1], sd[2], None)
+    out["noise_interp"] = t
+    t = I["vel"].copy()
+    refcall("ref_apply_noise_vec3", sx, sy, sz, cf(t_total), I["flags"], t, -1, P, cf(1.0), cf(1.0), None, 0, 0, 0, None)
+    out["noise_plain"] = t
+    return out
+
+
+def turb_clamp_reach(run, dims, I):
+    """both bounds of the noise clamp bite: against the unclamped run (`run` = run_turb_edge_pkg on the oracle), how many values
+    of the plain applyNoiseVec3 change when only the lower / only the upper bound of TURB_CLAMP is on"""
+    free = run(dims, I, clamp=None)["noise_plain"]
+    lo = run(dims, I, clamp=(TURB_CLAMP[0], 1e30))["noise_plain"]
+    hi = run(dims, I, clamp=(-1e30, TURB_CLAMP[1]))["noise_plain"]
+    return {"clamp_lower_bites": int((lo != free).sum()), "clamp_upper_bites": int((hi != free).sum())}
+
+
+# ---- advectSemiLagrange with a poisoned temp-grid pool, and the depths of the z-marching semi-Lagrange kernel --------------------
+POISON = {"real": 4, "vec": 6, "int": 4}   # two "vec" more than strictly needed by a Real grid, so that all three scratch grids
+                                           # of a Vec3 / MAC MacCormack step are poisoned ones (two are used up by vel and the grid)
+
+
+def poison_pool(s):
+    """fill the solver's pool with NaN (int: 0x7f7f7f7f) tensors; -> {id(tensor)} to prove later that they were handed out"""
+    ids = set()
+    for kind, cnt in POISON.items():
+        for _ in range(cnt):
+            if kind == "int":
+                t = torch.full((s.ncells,), 0x7f7f7f7f, dtype=torch.int32, device=s.device)
+            else:
+                t = torch.full(((3 if kind == "vec" else 1) * s.ncells,), float("nan"), dtype=torch.float32, device=s.device)
+            s._pool.setdefault(kind, []).append(t)
+            ids.add(id(t))
+    return ids
+
+
+def run_advect_poisoned(dims, dt, flags, vel, field, kind, **kw):
+    """run_advect_pkg on a solver whose pool was poisoned; -> (result, poisoned tensors left in the pool, poisoned tensors put)"""
+    seen = {}
+
+    def prepare(s):
+        seen["s"], seen["ids"] = s, poison_pool(s)
+        seen["keep"] = [t for v in s._pool.values() for t in v]     # keeps the ids unique for the solver's lifetime
+
+    out = run_advect_pkg(dims, dt, flags, vel, field, kind, prepare=prepare, **kw)
+    return out, seen
+
+
+ADVECT_POISON_CASES = [(kind, order, cm, ot, os_) for kind in (0, 1, 2) for order, cm in ((1, 2), (2, 1), (2, 2)) for ot in (1, 2)
+                       for os_ in (1, 2)]
+# depths of k_semi_lagrange_zmarch (four planes per thread): one interior plane whose "next plane" is the last one (3); a second
+# group holding only the boundary plane (5); exact groups (4, 8); a plane of 5 x 4 cells and one of 33 x 5, so that one block
+# spans several groups; no interior plane at all (2).  tools/zmarch_bounds.c runs the oracle on the same list under
+# AddressSanitizer.
+ZMARCH_DIMS = [(5, 4, 3), (5, 4, 5), (9, 7, 4), (9, 7, 8), (33, 5, 6), (6, 5, 2)]
+
+
+def assert_reach(r, what):
+    """every planted branch condition holds at least 8 times (the isolated-cell patterns: at least once)"""
+    for k, v in r.items():
+        need = 1 if k.startswith("isolated_") else 8
+        assert v >= need, "%s: the input reaches '%s' %d times, fewer than %d" % (what, k, v, need)
+
+
+def run_advect_parts_edge(dims, I, mode, deleteInObstacle, stopInObstacle, skipNew):
+    return run_advect_parts_pkg(dims, 0.8, I["flags"], I["vel"], I["pos"], I["pflag"], mode, deleteInObstacle, stopInObstacle, skipNew,
+                                I["ptype"], I["exclude"])
+
+
+def check_planted_against_model(I, pos_out, pflag_out):
+    """deleteInObstacle=False, stopInObstacle=True: the planted particles end where clamp_bisect_model puts them, undeleted"""
+    for p in np.nonzero(I["planted"])[0]:
+        want, _ = clamp_bisect_model(I["flags"], I["pos"][:, p])
+        util.assert_bitexact(pos_out[:, p], want, "planted particle %d (%s) from %s" % (p, I["group_names"][I["group"][p]], I["pos"][:, p]))
+        assert pflag_out[p] == 0
+
+
+def check_poison_used(seen, kind, order):
+    """the poisoned tensors were really handed out: after the step at least the flags, the velocity, the field and the one
+    (order 1) or three (MacCormack) scratch grids no longer hold the poison -- and a float tensor that was handed out holds no NaN
+    at all any more, cleared or not: the kernels wrote every cell of the scratch grids, border included.  -> tensors used"""
+    used = 0
+    for t in seen["keep"]:
+        if t.dtype == torch.int32:
+            used += int(bool((t != 0x7f7f7f7f).any()))
+        else:
+            nan = torch.isnan(t)
+            if not bool(nan.all()):
+                used += 1
+                assert not bool(nan.any()), "a temp grid taken from the pool was left with %d unwritten cells" % int(nan.sum())
+    need = 4 if order == 1 else 6
+    assert used >= need, "only %d poisoned tensors were handed out, expected at least %d" % (used, need)
+    return used
+
+
+def run_project_pkg(dims, I, bnd=2.5, plane="XyZ"):
+    """projectOutOfBnd on the planes that run_surface_pkg's two calls ("xXyYzZ", "xYz") never leave out"""
+    s = _mk_solver(dims)
+    fl = soa_to_grid(__import__("mantaflow_amd").core.FlagGrid(s), I["flags"])
+    pp = _mk_parts(s, I["pos"], I["pflag"])
+    pp.projectOutOfBnd(fl, bnd, plane)
+    return {"project_" + plane: _ppos(pp)}
+
+
+def run_project_ref(dims, I, bnd=2.5, plane="XyZ"):
+    sx, sy, sz = dims
+    n = I["pos"].shape[1]
+    p = I["pos"].copy()
+    refcall("ref_project_out_of_bnd", sx, sy, sz, n, n, p, I["pflag"], ctypes.c_float(bnd), plane.encode(), None, 0)
+    return {"project_" + plane: p}
+
+
+OUTFLOW_DTS = (0.9, 0.2)     # 4 dt > 1: timeStep = 3.6 ; 4 dt < 1: timeStep = 1
+
+
+def outflow_edge_inputs(dims, seed):
+    """advect_inputs(outflow=True) -- outflow cells before the +x wall, fluid on their low side -- plus outflow cells behind the -x
+    wall (fluid on their high side) and a faster velocity, so that the bulk velocity of getBulkVel exceeds 1 in places"""
+    sx, sy, sz = dims
+    flags, vel = advect_inputs(dims, seed, vmax=2.5, outflow=True)
+    col = flags[:, :, 1:3]
+    col[col != util.OBS] = util.EMPTY | util.OUTFLOW
+    return flags, vel, util.rand_vel(sx, sy, sz, seed + 1, 2.0)
+
+
+def outflow_edge_reach(dims, flags):
+    out = (flags & util.OUTFLOW) != 0
+    fluid = (flags & util.FLUID) != 0
+    return {"outflow_fluid_below_x": int((out & np.roll(fluid, 1, axis=2)).sum()), "outflow_fluid_above_x": int((out & np.roll(fluid, -1, axis=2)).sum())}

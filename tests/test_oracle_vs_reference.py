@@ -464,3 +464,85 @@ def test_sample_flags_with_particles_matches_reference_stream(oracle_backend):
         util.refcall("ref_sample_flags_with_particles", dims[0], dims[1], dims[2], flags, disc, ctypes.c_float(0.2), cap, pos, ctypes.byref(cnt))
         assert cnt.value == pp.np and pp.np > 100
         assert_bitexact(pp.get_positions().T, pos[:, :cnt.value], "sampled positions")
+
+
+# ---- the edge inputs of tests/test_gpu_base_edges.py: the oracle stays pinned to the reference on them ----------------------------
+@pytest.mark.parametrize("dims", cases.EDGE_DIMS)
+def test_advect_in_grid_edge_inputs(oracle_backend, dims):
+    """PNEW + skipNew, ptype & exclude, every mode and delete / stop combination.  The particles planted beside the domain for the
+    flag clamps stay out of the reference run (the reference reads past its flag grid there); the oracle's outcome for them is
+    checked against the documented rule instead, and the others must not notice them."""
+    I = cases.advect_parts_edge_inputs(dims, 19)
+    keep = ~I["planted"]
+    pos, pflag, ptype = np.ascontiguousarray(I["pos"][:, keep]), np.ascontiguousarray(I["pflag"][keep]), np.ascontiguousarray(I["ptype"][keep])
+    for mode, dele, stop, skip in cases.ADVECT_PARTS_MODES:
+        a = cases.run_advect_parts_edge(dims, I, mode, dele, stop, skip)
+        b = cases.run_advect_parts_ref(dims, 0.8, I["flags"], I["vel"], pos, pflag, mode, dele, stop, skip, ptype, I["exclude"])
+        what = "mode %d deleteInObstacle %s stopInObstacle %s skipNew %s" % (mode, dele, stop, skip)
+        assert_bitexact(a[1][keep], b[1], what + ": particle flags")
+        assert_bitexact(a[0][:, keep], b[0], what + ": particle positions")
+        if not dele and stop:
+            cases.check_planted_against_model(I, a[0], a[1])
+
+
+@pytest.mark.parametrize("dims", cases.EDGE_DIMS)
+def test_flip_transfers_edge_inputs(oracle_backend, dims):
+    I = cases.flip_edge_inputs(dims, 14)
+    a = cases.run_flip_pkg(dims, I["flags"], I["vel"], I["velOld"], I["pos"], I["pflag"], I["pvel"], I["ptype"], 4)
+    b = cases.run_flip_ref(dims, I["flags"], I["vel"], I["velOld"], I["pos"], I["pflag"], I["pvel"], I["ptype"], 4)
+    for k in b:
+        assert_bitexact(a[k], b[k], k)
+
+
+@pytest.mark.parametrize("dims", cases.EDGE_DIMS)
+def test_surface_pieces_edge_inputs(oracle_backend, dims):
+    I = cases.surface_edge_inputs(dims, 51)
+    a = dict(cases.run_surface_pkg(dims, I), **cases.run_project_pkg(dims, I))
+    b = dict(cases.run_surface_ref(dims, I), **cases.run_project_ref(dims, I))
+    for k in b:
+        assert_bitexact(a[k], b[k], k)
+
+
+@pytest.mark.parametrize("dims", cases.EDGE_DIMS)
+def test_mark_fluid_cells_edge_inputs(oracle_backend, dims):
+    I = cases.markfluid_edge_inputs(dims, 31)
+    a = cases.run_markfluid_pkg(dims, I)
+    b = cases.run_markfluid_ref(dims, I)
+    for k in b:
+        assert_bitexact(a[k], b[k], k)
+
+
+@pytest.mark.parametrize("dims,small", [((20, 14, 12), (10, 7, 6)), (cases.SIZE_2D, (12, 9, 1)), ((17, 11, 9), (9, 6, 5))])
+def test_turbulence_edge_inputs(oracle_backend, dims, small):
+    I = cases.turb_edge_inputs(dims, small, 91)
+    for clamp in (cases.TURB_CLAMP, None):
+        a = cases.run_turb_edge_pkg(dims, I, clamp)
+        b = cases.run_turb_edge_ref(dims, I, clamp)
+        for k in b:
+            assert_bitexact(a[k], b[k], "%s clamp %s" % (k, clamp))
+
+
+@pytest.mark.parametrize("dims", [d for d in cases.ZMARCH_DIMS if d[2] != 2] + [(14, 12, 10), cases.SIZE_2D])
+def test_advect_thin_grids_and_outflow_timestep(oracle_backend, dims):
+    """the depths of tests/test_gpu_base_edges.py::test_zmarch_depths, and MAC advection with outflow cells at 4 dt > 1.
+    Depth 2 is not pinned here: a grid of two planes has no interior plane, and there the reference's KERNEL(bnd=1) loops fall into
+    their 2-D branch (they test `maxZ - bnd > 1`) and sweep plane 0 with 3-D interpolation, while the oracle and the HIP kernels
+    treat the grid as 3-D and write zeros (at (6, 5, 2), Real, order 1: 12 of 60 values differ, up to 0.82).  See DESIGN.md 6."""
+    sx, sy, sz = dims
+    for kind in (0, 1, 2):
+        flags, vel = cases.advect_inputs(dims, 9, vmax=2.5, outflow=(kind == 2))
+        field = util.rand_real((sz, sy, sx), 10) if kind == 0 else util.rand_vel(sx, sy, sz, 10)
+        for order in (1, 2):
+            a = cases.run_advect_pkg(dims, 0.9, flags, vel, field, kind, order=order, strength=0.8 if order == 2 else 1.0)
+            b = cases.run_advect_ref(dims, 0.9, flags, vel, field, kind, order=order, strength=0.8 if order == 2 else 1.0)
+            assert_bitexact(a, b, "advectSemiLagrange %s kind %d order %d" % (dims, kind, order))
+
+
+@pytest.mark.parametrize("dims", [(14, 12, 10), cases.SIZE_2D])
+def test_outflow_edge_inputs(oracle_backend, dims):
+    flags, vel, field = cases.outflow_edge_inputs(dims, 9)
+    for dt in cases.OUTFLOW_DTS:
+        for order in (1, 2):
+            a = cases.run_advect_pkg(dims, dt, flags, vel, field, 2, order=order, strength=0.8 if order == 2 else 1.0)
+            b = cases.run_advect_ref(dims, dt, flags, vel, field, 2, order=order, strength=0.8 if order == 2 else 1.0)
+            assert_bitexact(a, b, "MAC advection with outflow on both sides, dt %g order %d" % (dt, order))
