@@ -221,6 +221,212 @@ k_apply_matrix_v5(Dim d, const int32_t* __restrict__ flags, float* __restrict__ 
 	}
 }
 
+// z-march: the packed 3-D ApplyMatrix of a whole grid (no skip map, the dot over all planes).  A thread owns one x-quad of ZM_R
+// consecutive y-rows and walks a segment of ZM_L planes with them; it keeps in registers the src quads of its rows at the planes
+// k-1, k and k+1 and the Ak coefficients of plane k-1, so that per plane it loads its own rows once (of plane k+2, a whole step ahead
+// of their use), the two y-halo rows and the packed words of its rows and of row j0-1 (of plane k+1, issued before plane k is
+// computed) -- not the +-Z src rows and the k-1 packed word again, and it decodes its index once per segment, not once per tile.
+// Every load and store of a step is issued unconditionally, in straight-line code, with its address clamped into the grid and its
+// value replaced where it must not count only when it is used: behind a branch that may or may not issue a memory operation the
+// compiler has to wait for ALL outstanding ones (vmcnt(0) -- the first form of this kernel did that at every step and gained nothing
+// over v5).  For the same reason no branch per cell or row (every cell is computed, a non-fluid cell selects src), and four steps are
+// written out with the roles of the register sets rotating, so that no plane is moved from one set to the next.
+// The segments of one XCD are one contiguous z-range (xcd_swizzle); at most ZM_MAX_BLOCKS blocks, hence as many dot partials.
+// Per cell the expression of v5 (CELL5) on the same operands: flat +-X / +-Y neighbours, non-fluid cells copy src.
+#ifndef ZM_L
+#define ZM_L 16
+#endif
+#ifndef ZM_R
+#define ZM_R 2
+#endif
+constexpr int ZM_MAX_BLOCKS = 512;
+template <int R>
+struct ZmRest {      // what a thread holds of one plane besides its own src rows, as loaded (zm_fix_rest: as used)
+	float4 ym, yp;            // src of the rows j0-1 and j0+R (flat: of the neighbouring plane at the plane's edges)
+	unsigned pw[R], pwm;      // packed words of the own rows and of row j0-1
+	float sl[R], sr[R];       // the -X / +X neighbours of the quad (used by the lanes at the ends of a row or of the wave)
+	unsigned pl[R];           // ... and the packed byte of the -X neighbour
+};
+template <bool NT, int R>
+__device__ __forceinline__ void zm_load_rows(float4 (&s)[R], const Dim& d, const float* __restrict__ src, int64_t row0, int j0) {
+#pragma unroll
+	for (int r = 0; r < R; r++) {
+		const int jr = (j0 + r < d.sy) ? r : (d.sy - 1 - j0);
+		s[r] = NT ? ld_nt4(src + row0 + jr * d.Y) : *(const float4*)(src + row0 + jr * d.Y);
+	}
+}
+template <bool A0S, int R>
+__device__ __forceinline__ void zm_load_rest(ZmRest<R>& p, float4 (&a0)[R], const Dim& d, const float* __restrict__ src, const float* __restrict__ A0,
+                                             const unsigned char* __restrict__ pack, int64_t row0, int j0, int k) {
+	const int64_t Y = d.Y;
+	const int jm = (k > 0 || j0 > 0) ? -1 : 0;
+	const int jp = (j0 + R < d.sy) ? R : (d.sy - j0 - ((k < d.sz - 1) ? 0 : 1));
+	p.ym = *(const float4*)(src + row0 + jm * Y);
+	p.pwm = *(const unsigned*)(pack + row0 + jm * Y);
+	p.yp = *(const float4*)(src + row0 + jp * Y);
+#pragma unroll
+	for (int r = 0; r < R; r++) {
+		const int jr = (j0 + r < d.sy) ? r : (d.sy - 1 - j0);
+		const int64_t idx = row0 + jr * Y;
+		p.pw[r] = *(const unsigned*)(pack + idx);
+		if (A0S) a0[r] = (AM_NT >= 1) ? ld_nt4(A0 + idx) : *(const float4*)(A0 + idx);
+		const int64_t il = (idx > 0) ? idx - 1 : 0, ir = (idx + 4 < d.n) ? idx + 4 : idx;
+		p.sl[r] = src[il];
+		p.pl[r] = (unsigned)pack[il];
+		p.sr[r] = src[ir];
+	}
+}
+// the row before the grid's first and the row behind its last, the cell before the first and the cell behind the last: zero, as are
+// their couplings
+template <int R>
+__device__ __forceinline__ void zm_fix_rest(ZmRest<R>& p, const Dim& d, int64_t row0, int j0, int k) {
+	const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+	if (!(k > 0 || j0 > 0)) {
+		p.ym = z4;
+		p.pwm = 0u;
+	}
+	if (!(k < d.sz - 1 || j0 + R < d.sy)) p.yp = z4;
+#pragma unroll
+	for (int r = 0; r < R; r++) {
+		const int jr = (j0 + r < d.sy) ? r : (d.sy - 1 - j0);
+		const int64_t idx = row0 + jr * d.Y;
+		if (!(idx > 0)) {
+			p.sl[r] = 0.f;
+			p.pl[r] = 0u;
+		}
+		if (!(idx + 4 < d.n)) p.sr[r] = 0.f;
+	}
+}
+// A0S: the diagonal comes from the A0 array, not from bits 4-7 of the packed bytes (a0p bit 0 of k_apply_matrix_v5 clear); NT: its bit 1
+template <bool DOT, bool A0S, bool NT>
+__global__ void __launch_bounds__(BLOCK)
+k_apply_matrix_zmarch(Dim d, float* __restrict__ dst, const float* __restrict__ src, const float* __restrict__ A0,
+                      const unsigned char* __restrict__ pack, double* __restrict__ partials, const CgScalars* __restrict__ sc, int jgroups,
+                      int tpb) {
+	constexpr int R = ZM_R, L = ZM_L;
+	if (DOT && sc->done) return;
+	const unsigned qx = (unsigned)(d.sx >> 2);
+	const unsigned per_seg = qx * (unsigned)jgroups;
+	const unsigned nthr = per_seg * (unsigned)((d.sz + L - 1) / L);
+	const int vb0 = xcd_swizzle(blockIdx.x, gridDim.x) * tpb;
+	const int lane = threadIdx.x & 63;
+	const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+	const int64_t Y = d.Y, Z = d.Z;
+	double acc = 0.0;
+#pragma unroll 1
+	for (int t = 0; t < tpb; t++) {
+		const unsigned T0 = (unsigned)(vb0 + t) * BLOCK + threadIdx.x;
+		// (the threads behind the last leave: the lane exchange of a live lane never reads them -- the last thread ends a row, and
+		// fetches its +X neighbour -- and every memory operation below stays unconditional for the lanes that are left)
+		if (T0 >= nthr) continue;
+		const unsigned T = T0;
+		const unsigned seg = T / per_seg, in_seg = T - seg * per_seg;
+		const unsigned jg = in_seg / qx;
+		const int qi = (int)(in_seg - jg * qx), j0 = (int)jg * R;
+		const int k0 = (int)seg * L, k1 = (k0 + L < d.sz) ? k0 + L : d.sz;
+		// (the lanes this thread exchanges +-X neighbours with work on the same rows of the same planes; at the ends of a row and of
+		// the wave the neighbour is the fetched one)
+		const bool edge_l = (lane == 0) || (qi == 0), edge_r = (lane == 63) || (qi == (int)qx - 1);
+		const int64_t row00 = ((int64_t)k0 * d.sy + j0) * d.sx + 4 * qi;      // flat index of this thread's first quad in plane k0
+
+		// One plane: issue the loads of the rest of plane k + 1 (-> n, a0n) and of the own rows of plane k + 2 (-> s2), both planes
+		// clamped into the grid, then compute plane k from the rows sm / s0 / s1 of the planes k - 1 / k / k + 1, the rest c / a0c of
+		// plane k and the Ak of plane k - 1 (akm); the Ak of plane k -> ako
+		auto step = [&](int k, const float4 (&sm)[R], const float4 (&s0)[R], const float4 (&s1)[R], float4 (&s2)[R], ZmRest<R>& c,
+		                ZmRest<R>& n, const float4 (&a0c)[R], float4 (&a0n)[R], const float4 (&akm)[R], float4 (&ako)[R]) __attribute__((always_inline)) {
+			const int64_t row0 = row00 + (int64_t)(k - k0) * Z;
+			const int kn = (k + 1 < d.sz) ? k + 1 : d.sz - 1, k2 = (k + 2 < d.sz) ? k + 2 : d.sz - 1;
+			zm_load_rest<A0S, R>(n, a0n, d, src, A0, pack, row00 + (int64_t)(kn - k0) * Z, j0, kn);
+			zm_load_rows<NT, R>(s2, d, src, row00 + (int64_t)(k2 - k0) * Z, j0);
+			zm_fix_rest<R>(c, d, row0, j0, k);
+			const bool top = k == d.sz - 1;
+			float4 aj[R + 1], res[R];
+			aj[0] = unpack_coef<4u>(c.pwm);
+#pragma unroll
+			for (int r = 0; r < R; r++) {
+				const unsigned pw = c.pw[r];
+				const float4 s = s0[r], ai = unpack_coef<2u>(pw), akc = unpack_coef<8u>(pw);
+				aj[r + 1] = unpack_coef<4u>(pw);
+				ako[r] = akc;
+				float sl = wave_shr1(s.w), sr = wave_shl1(s.x);
+				float al = (__float_as_uint(wave_shr1(__uint_as_float(pw))) & 0x02000000u) ? -1.f : 0.f;
+				if (edge_l) {
+					sl = c.sl[r];
+					al = (c.pl[r] & 2u) ? -1.f : 0.f;
+				}
+				if (edge_r) sr = c.sr[r];
+				const float4 a0 = A0S ? a0c[r] : make_float4((float)((pw >> 4) & 15u), (float)((pw >> 12) & 15u), (float)((pw >> 20) & 15u), (float)((pw >> 28) & 15u));
+				const float4 sym = (r == 0) ? c.ym : s0[r > 0 ? r - 1 : 0], ajm = aj[r];
+				const float4 syp = (r + 1 < R) ? ((j0 + r < d.sy - 1) ? s0[r + 1 < R ? r + 1 : 0] : c.yp) : c.yp, ajc = aj[r + 1];
+				const float4 zm = sm[r], am = akm[r], zp = top ? z4 : s1[r];
+#define CELL5(c_, BYTE, SL, AL, SR)                                                                   \
+	{                                                                                             \
+		float v = s.c_ * a0.c_;                                                                   \
+		v = v + (SL) * (AL);                                                                      \
+		v = v + (SR) * ai.c_;                                                                     \
+		v = v + sym.c_ * ajm.c_;                                                                  \
+		v = v + syp.c_ * ajc.c_;                                                                  \
+		v = v + zm.c_ * am.c_;                                                                    \
+		v = v + zp.c_ * akc.c_;                                                                   \
+		res[r].c_ = (pw & (1u << (8 * BYTE))) ? v : s.c_;                                         \
+	}
+				CELL5(x, 0, sl, al, s.y)
+				CELL5(y, 1, s.x, ai.x, s.z)
+				CELL5(z, 2, s.y, ai.y, s.w)
+				CELL5(w, 3, s.z, ai.z, sr)
+#undef CELL5
+				if (DOT && j0 + r < d.sy) {
+					const float p0 = res[r].x * s.x, p1 = res[r].y * s.y, p2 = res[r].z * s.z, p3 = res[r].w * s.w;
+					acc += (double)p0;
+					acc += (double)p1;
+					acc += (double)p2;
+					acc += (double)p3;
+				}
+			}
+			// (a row behind the plane's last -- odd sy -- stores the thread's first row again)
+#pragma unroll
+			for (int r = 0; r < R; r++) {
+				const bool own = j0 + r < d.sy;
+				const float4 o = own ? res[r] : res[0];
+				float* const p = dst + row0 + (own ? r : 0) * Y;
+				if (AM_NT >= 2 && NT) st_nt4(p, o);
+				else *(float4*)p = o;
+			}
+		};
+
+		// ---- the state of plane k0: src rows and Ak of the plane before (zero below the grid), plane k0 whole, src rows of k0 + 1 ----
+		float4 sa[R], sb[R], sc_[R], sd[R], a0a[R], a0b[R], aka[R], akb[R];
+		ZmRest<R> ca, cb;
+#pragma unroll
+		for (int r = 0; r < R; r++) sa[r] = aka[r] = z4;
+		zm_load_rows<NT, R>(sb, d, src, row00, j0);
+		zm_load_rest<A0S, R>(ca, a0a, d, src, A0, pack, row00, j0, k0);
+		zm_load_rows<NT, R>(sc_, d, src, row00 + ((k0 + 1 < d.sz) ? Z : 0), j0);
+		if (k0 > 0) {
+			zm_load_rows<false, R>(sa, d, src, row00 - Z, j0);
+#pragma unroll
+			for (int r = 0; r < R; r++) {
+				const int jr = (j0 + r < d.sy) ? r : (d.sy - 1 - j0);
+				aka[r] = unpack_coef<8u>(*(const unsigned*)(pack + row00 - Z + jr * Y));
+			}
+		}
+#pragma unroll 1
+		for (int k = k0; k < k1; k += 4) {
+			step(k, sa, sb, sc_, sd, ca, cb, a0a, a0b, aka, akb);
+			if (k + 1 >= k1) break;
+			step(k + 1, sb, sc_, sd, sa, cb, ca, a0b, a0a, akb, aka);
+			if (k + 2 >= k1) break;
+			step(k + 2, sc_, sd, sa, sb, ca, cb, a0a, a0b, aka, akb);
+			if (k + 3 >= k1) break;
+			step(k + 3, sd, sa, sb, sc_, cb, ca, a0b, a0a, akb, aka);
+		}
+	}
+	if (DOT) {
+		acc = block_sum(acc);
+		if (threadIdx.x == 0) partials[blockIdx.x] = acc;
+	}
+}
+
 // generic fallback (sx % 4 != 0 or unaligned views): one cell per thread
 template <bool DOT>
 __global__ void __launch_bounds__(BLOCK)
@@ -279,7 +485,18 @@ static int launch_apply_matrix(const Dim& d, const int32_t* flags, float* dst, c
 	const int a0pn = (o.a0p ? 1 : 0) | ((DOT && (o.nt < 0 ? d.n > PCG_NT_CELLS : o.nt != 0)) ? 2 : 0);
 	const bool vec = (d.sx % 4 == 0) && al16(flags) && al16(dst) && al16(src) && al16(A0) && al16(Ai) && al16(Aj) && al16(Ak);
 	int nb;
-	if (vec) {
+	if (vec && d.is3d && o.pack && !o.bempty && o.dk0 <= 0 && o.dk1 >= d.sz) {
+		// whole packed 3-D grids: the z-marching kernel (the skip map of liquid scenes and the z-slab windows stay on v5)
+		const int jgroups = (d.sy + ZM_R - 1) / ZM_R;
+		const int64_t vblocks = ((int64_t)(d.sx >> 2) * jgroups * ((d.sz + ZM_L - 1) / ZM_L) + BLOCK - 1) / BLOCK;
+		const int tpb = (int)((vblocks + ZM_MAX_BLOCKS - 1) / ZM_MAX_BLOCKS);
+		nb = (int)((vblocks + tpb - 1) / tpb);
+		const bool a0s = !(a0pn & 1), nt = !DOT || (a0pn & 2);      // (outside the PCG always non-temporal, as v5)
+		auto kern = nt ? (a0s ? k_apply_matrix_zmarch<DOT, true, true> : k_apply_matrix_zmarch<DOT, false, true>)
+		               : (a0s ? k_apply_matrix_zmarch<DOT, true, !DOT> : k_apply_matrix_zmarch<DOT, false, !DOT>);
+		hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, st, d, dst, src, A0, o.pack, partials, sc, jgroups, tpb);
+		if (ranged) *ranged = true;
+	} else if (vec) {
 		constexpr int R = 2;     // y-rows per thread
 		const int jgroups = (d.sy + R - 1) / R;
 		const int64_t vblocks = ((int64_t)(d.sx >> 2) * jgroups * d.sz + BLOCK - 1) / BLOCK;
