@@ -340,6 +340,46 @@ __device__ __forceinline__ void st_nt4(float* p, float4 a) {
 	__builtin_nontemporal_store(o, (v4*)p);
 }
 
+// max(fabs(amin), fabs(amax)) of a min / max pair: the max-norm of a grid (grid.cpp:359), the PCG's residual norm
+__host__ __device__ __forceinline__ float maxabs(float lo, float hi) {
+	const float alo = fabsf(lo), ahi = fabsf(hi);
+	return alo > ahi ? alo : ahi;
+}
+
+// ---- z-slab PCG scalar steps on the gathered per-rank reductions g[world][2] = {max|residual|, dot}: rows are summed / maxed in
+// rank order, so every rank computes the same bits (conjugategrad.cpp:250-291 for the formulas)
+// alpha = sigma / dp with dp = the sum of the ranks' dots
+__device__ __forceinline__ float slab_alpha(const double* __restrict__ g, int world, float sigma) {
+	double acc = 0.0;
+	for (int r = 0; r < world; r++) acc += g[2 * r + 1];
+	const float dp = (float)acc;
+	return (fabs((double)dp) > 0.) ? sigma / dp : 0.f;
+}
+// sigmaNew = the sum of the ranks' dots, beta = sigmaNew / sigma_div, the residual norm and the stopping test on it
+struct SlabBeta {
+	float sigmaNew, beta, resNorm;
+	int stop;      // the solver's stop state: 0 go on, 1 converged, 2 diverged
+};
+__device__ __forceinline__ SlabBeta slab_beta_stop(const double* __restrict__ g, int world, float sigma_div, float accuracy) {
+	double acc = 0.0, mx = 0.0;
+	for (int r = 0; r < world; r++) {
+		acc += g[2 * r + 1];
+		mx = g[2 * r] > mx ? g[2 * r] : mx;
+	}
+	SlabBeta b;
+	b.sigmaNew = (float)acc;
+	b.resNorm = (float)mx;
+	b.beta = b.sigmaNew / sigma_div;
+	b.stop = (b.resNorm < accuracy) ? 1 : !(b.resNorm < 1e35f) ? 2 : 0;
+	return b;
+}
+
+// ---- one-block finishers of per-block partials (runtime.hip: k_sum_finish, k_maxabs_finish64), queued on st
+// *out = the sum of partials[0 .. nb) in the fixed order of strided_sum + block_sum
+int launch_sum_finish(int nb, const double* partials, double* out, hipStream_t st);
+// *out = max |.| of the nb min / max pairs in fpart; nothing when stopped (nullable) points to a non-zero word
+int launch_maxabs_finish(int nb, const float* fpart, double* out, const int* stopped, hipStream_t st);
+
 // ---- interpolation primitives, reference util/interpol.h -------------------------------------------------
 struct Bi {
 	int xi, yi, zi;

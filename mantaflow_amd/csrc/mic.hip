@@ -572,10 +572,10 @@ k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0
 						float cai, caj, cak;
 						if (packed) {
 							const unsigned bits = (unsigned)(r.W >> (8 * (REV ? 7 - a : a))) & 0xffu;
-							fl = (bits & 1u) != 0;
-							cai = (bits & 2u) ? -1.f : 0.f;
-							caj = (bits & 4u) ? -1.f : 0.f;
-							cak = (bits & 8u) ? -1.f : 0.f;
+							fl = pk_fluid(bits);
+							cai = pk_coef<PK_AI>(bits);
+							caj = pk_coef<PK_AJ>(bits);
+							cak = pk_coef<PK_AK>(bits);
 						} else {
 							fl = in && (r.F[a] & MF_FLUID);
 							cai = r.Ai[a];
@@ -761,7 +761,7 @@ k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0
 		}
 	}
 	if (MODE == 2 && !tail.sc && tail.sum_out) {
-		// z-slab solver: the one-block folds behind the sweep (k_fin_maxabs_live, k_mic_fin_sum) in the workgroup that finished last
+		// z-slab solver: the one-block folds behind the sweep (k_maxabs_finish64, k_sum_finish) in the workgroup that finished last
 		__syncthreads();
 		if (!s_lastwg) return;
 		float lo = FLT_MAX, hi = -FLT_MAX;
@@ -770,10 +770,7 @@ k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0
 		const double dd = tail_sum256<true>(dotpart, tail.nsig);
 		if (threadIdx.x == 0) {
 			tail.sum_out[0] = dd;
-			if (tail.nbr > 0 && !(tail.live && tail.live->done)) {
-				const float alo = fabsf(lo), ahi = fabsf(hi);
-				tail.maxabs_out[0] = (double)(alo > ahi ? alo : ahi);
-			}
+			if (tail.nbr > 0 && !(tail.live && tail.live->done)) tail.maxabs_out[0] = (double)maxabs(lo, hi);
 		}
 		return;
 	}
@@ -790,26 +787,7 @@ k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0
 		else tail_minmax256(tail.fpart, tail.nbr, lo, hi);
 		__syncthreads();
 		const double dd = tail_sum256<true>(dotpart, tail.nsig);
-		if (threadIdx.x == 0) {
-			float resNorm;
-			if (l2)
-				resNorm = (float)ss;
-			else {
-				const float alo = fabsf(lo), ahi = fabsf(hi);
-				resNorm = alo > ahi ? alo : ahi;
-			}
-			w->resNorm = resNorm;
-			if (resNorm < w->accuracy) {
-				w->sigma = resNorm;
-				w->done = 1;
-			} else {
-				const float sigmaNew = (float)dd;
-				w->beta = sigmaNew / w->sigma;
-				w->sigmaNew = sigmaNew;
-				w->sigma = sigmaNew;
-				if (!((double)resNorm < 1e35)) w->diverged = 1;
-			}
-		}
+		if (threadIdx.x == 0) cg_beta_step(w, l2, lo, hi, ss, dd);
 	}
 }
 
@@ -981,11 +959,11 @@ k_mic_rows_init(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, cons
 #pragma unroll
 						for (int a = 0; a < 8; a++) {
 							const unsigned bits = (unsigned)(W >> (8 * a)) & 0xffu;
-							rF[a] = (bits & 1u) ? MF_FLUID : 0;
-							r0[a] = (float)(bits >> 4);
-							ri[a] = (bits & 2u) ? -1.f : 0.f;
-							rj[a] = (bits & 4u) ? -1.f : 0.f;
-							rk[a] = (bits & 8u) ? -1.f : 0.f;
+							rF[a] = pk_fluid(bits) ? MF_FLUID : 0;
+							r0[a] = pk_a0(bits);
+							ri[a] = pk_coef<PK_AI>(bits);
+							rj[a] = pk_coef<PK_AJ>(bits);
+							rk[a] = pk_coef<PK_AK>(bits);
 						}
 					} else {
 						load_row8i<VEC, REV>(flags, rowidx, nv, rF);
@@ -1138,7 +1116,7 @@ k_mic_rows_init(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, cons
 	}
 }
 
-// one byte per cell: bit 0 fluid, bits 1..3 "Ai / Aj / Ak is -1"; ok[0] is cleared when a coefficient is neither +0 nor -1
+// one packed byte per cell (pressure.h: pk_make); ok[0] is cleared when a coefficient is neither +0 nor -1
 // (second-order boundaries, a caller's own matrix): the sweeps then read the four arrays themselves
 __global__ void __launch_bounds__(BLOCK)
 k_mic_pack(int64_t n, const int32_t* __restrict__ flags, const float* __restrict__ A0, const float* __restrict__ Ai,
@@ -1158,10 +1136,10 @@ k_mic_pack(int64_t n, const int32_t* __restrict__ flags, const float* __restrict
 	} else if (fl) {
 		const float v = A0[idx];
 		const int iv = (int)v;
-		if (__float_as_uint(v) == __float_as_uint((float)iv) && iv >= 0 && iv <= 15) a0code = (unsigned)iv;   // bit pattern: -0.0f is not the +0 the nibble rebuilds
+		if (__float_as_uint(v) == __float_as_uint((float)iv) && iv >= 0 && iv <= (int)PK_A0_MAX) a0code = (unsigned)iv;   // bit pattern: -0.0f is not the +0 the nibble rebuilds
 		else ok[1] = 0;
 	}
-	pack[idx] = (unsigned char)((fl ? 1u : 0u) | (ui == M1 ? 2u : 0u) | (uj == M1 ? 4u : 0u) | (uk == M1 ? 8u : 0u) | (a0code << 4));
+	pack[idx] = (unsigned char)pk_make(fl, ui == M1, uj == M1, uk == M1, a0code);
 }
 
 // bempty[tk * nbj + tj] = 1 when the 8x8 bundle of x-rows (tj, tk) needs no sweep: it has no fluid cell, and nothing couples
@@ -1501,30 +1479,12 @@ static int launch_mic(const Dim& d, const int32_t* flags, float* dst, const floa
 }
 
 
-// one-block sum of the per-bundle dot partials (index order) -- or, without fusion, a plain dot over the grid
-static __global__ void __launch_bounds__(BLOCK) k_mic_fin_sum(int nb, const double* __restrict__ partials, double* __restrict__ out) {
-	double acc = strided_sum(partials, nb);
-	acc = block_sum(acc);
-	if (threadIdx.x == 0) out[0] = acc;
-}
+// without fusion: a plain dot over the grid
 static __global__ void __launch_bounds__(BLOCK) k_mic_plain_dot(int64_t n, const float* __restrict__ a, const float* __restrict__ b, double* __restrict__ partials) {
 	double acc = 0.0;
 	for (int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) acc += (double)(a[i] * b[i]);
 	acc = block_sum(acc);
 	if (threadIdx.x == 0) partials[blockIdx.x] = acc;
-}
-static __global__ void __launch_bounds__(BLOCK) k_mic_fin_maxabs_live(int nb, const float* __restrict__ fpart, double* __restrict__ out, const CgScalars* __restrict__ live) {
-	if (live && live->done) return;
-	float lo = FLT_MAX, hi = -FLT_MAX;
-	for (int i = threadIdx.x; i < nb; i += blockDim.x) {
-		lo = fminf(lo, fpart[2 * i]);
-		hi = fmaxf(hi, fpart[2 * i + 1]);
-	}
-	block_minmax(lo, hi);
-	if (threadIdx.x == 0) {
-		const float alo = fabsf(lo), ahi = fabsf(hi);
-		out[0] = (double)(alo > ahi ? alo : ahi);
-	}
 }
 
 namespace mf {
@@ -1555,9 +1515,8 @@ int mic_apply_dot_fold(const Dim& d, const int32_t* flags, float* dst, const flo
 		nsig = blocks_for(d.n, BLOCK * 4, 2048);
 		hipLaunchKernelGGL(k_mic_plain_dot, dim3(nsig), dim3(BLOCK), 0, st, d.n, dst, var1, part);
 	}
-	hipLaunchKernelGGL(k_mic_fin_sum, dim3(1), dim3(BLOCK), 0, st, nsig, part, dot_dev);
-	if (nbr > 0) hipLaunchKernelGGL(k_mic_fin_maxabs_live, dim3(1), dim3(BLOCK), 0, st, nbr, fpart, maxabs_dev, live);
-	MF_LAUNCH_CHECK();
+	MF_TRY(launch_sum_finish(nsig, part, dot_dev, st));
+	if (nbr > 0) MF_TRY(launch_maxabs_finish(nbr, fpart, maxabs_dev, live ? &live->done : nullptr, st));
 	return 0;
 }
 // the packed flags/Ai/Aj/Ak bytes mf_mic_init built for exactly these grids, if every coefficient was +0 or -1 (one small

@@ -11,6 +11,14 @@
 using namespace mf;
 
 static thread_local int g_last_shortcut[3] = {0, 0, 0};      // what mf_cg_last_shortcut reports
+// maxIter <= 0: GridCg::solve (conjugategrad.cpp:302-307) never reaches iterate(), and doInit is only called from there -- pressure and
+// the work grids stay untouched; mIterations = 0, mResNorm = 1e20 (constructor, :203), sigma 0
+static int cg_no_iterations(float* out_host) {
+	out_host[0] = 0.f;
+	out_host[1] = 1e20f;
+	out_host[2] = 0.f;
+	return 0;
+}
 
 // =========================================================================================================
 // ApplyMatrix, conjugategrad.h:118-151
@@ -30,21 +38,28 @@ __device__ __forceinline__ float wave_shr1(float v) {  // lane l gets lane l-1 (
 __device__ __forceinline__ float wave_shl1(float v) {  // lane l gets lane l+1 (lane 63: unchanged)
 	return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x130, 0xf, 0xf, false));
 }
+// one fluid cell of ApplyMatrix: the left-to-right fp32 sum of the 7 products (5 in 2-D) in the reference's order -- the cell, its
+// -X / +X, -Y / +Y, -Z / +Z neighbours, each with the coefficient that couples it (that of the lower cell of the pair)
+template <bool IS3D>
+__device__ __forceinline__ float stencil_cell(float s, float a0, float sxm, float aim, float sxp, float ai, float sym, float ajm, float syp,
+                                              float aj, float szm, float akm, float szp, float ak) {
+	float v = s * a0;
+	v = v + sxm * aim;
+	v = v + sxp * ai;
+	v = v + sym * ajm;
+	v = v + syp * aj;
+	if (IS3D) {
+		v = v + szm * akm;
+		v = v + szp * ak;
+	}
+	return v;
+}
 // PACKED: flags + Ai + Aj + Ak come as one byte per cell (k_mic_pack: fluid bit, "coefficient is -1" bits; only offered by the
 // host when every coefficient is exactly +0 or -1): 5 four-byte loads per thread replace 11 sixteen-byte loads, the values
 // are rebuilt exactly and everything after the load section is shared
-__device__ __forceinline__ int4 unpack_flags(unsigned w) {
-	return make_int4((w & 0x1u) ? MF_FLUID : 0, (w & 0x100u) ? MF_FLUID : 0, (w & 0x10000u) ? MF_FLUID : 0, (w & 0x1000000u) ? MF_FLUID : 0);
-}
-template <unsigned BIT>
-__device__ __forceinline__ float4 unpack_coef(unsigned w) {
-	return make_float4((w & BIT) ? -1.f : 0.f, (w & (BIT << 8)) ? -1.f : 0.f, (w & (BIT << 16)) ? -1.f : 0.f, (w & (BIT << 24)) ? -1.f : 0.f);
-}
-// AM_NT: non-temporal accesses (common.h: ld_nt4 / st_nt4) for what ApplyMatrix touches once -- 1: A0 / Ai / flags loads, 2: the dst
-// store as well -- 91 -> 69 us at 256^3 (3: Aj / Ak too: 78 us, they are re-read as the j-1 / k-1 coefficients)
-#ifndef AM_NT
-#define AM_NT 2
-#endif
+// Non-temporal accesses (common.h: ld_nt4 / st_nt4) for what ApplyMatrix touches once -- the A0 / Ai / flags loads and the dst store:
+// 91 -> 69 us at 256^3 (Aj / Ak too: 78 us, they are re-read as the j-1 / k-1 coefficients) -- and for the thread's own src rows
+// (68.2 -> 66.2 us; the z neighbours too: 76.8 us)
 // Inside the PCG every vector stream EXCEPT the residual is non-temporal -- search and tmp in ApplyMatrix (own rows, result), tmp in the
 // residual update, search / tmp / pressure in the search update; the same in the z-slab kernels -- so that what the MIC sweeps read
 // (residual, Aprecond, packed bytes, tmp between the two sweeps) stays in L2 / the memory-side cache across the iteration: 72.3 -> 70.8 ms
@@ -52,26 +67,19 @@ __device__ __forceinline__ float4 unpack_coef(unsigned w) {
 // the vectors do not fit the caches anyway: a run-time flag of the kernels (`nt`), set for systems of more than PCG_NT_CELLS cells (10 Mi:
 // the 129-plane window of one rank of two, 8.45 M cells, is 1.2 % faster cached) that are swept whole (a liquid scene whose kernels skip
 // most bundles touches a fraction: 23.5 ms per dam-break step cached, 23.9 non-temporal).
-#ifndef PCG_NT_MI
-#define PCG_NT_MI 10
-#endif
-constexpr int64_t PCG_NT_CELLS = (int64_t)PCG_NT_MI << 20;
-// AMP_NT: 1 = the thread's own src rows non-temporal as well (68.2 -> 66.2 us; the z neighbours too: 76.8 us)
-#ifndef AMP_NT
-#define AMP_NT 1
-#endif
+constexpr int64_t PCG_NT_CELLS = (int64_t)10 << 20;
 template <bool DOT, bool IS3D, int R, bool PACKED>
 __global__ void __launch_bounds__(BLOCK)
 k_apply_matrix_v5(Dim d, const int32_t* __restrict__ flags, float* __restrict__ dst, const float* __restrict__ src,
                   const float* __restrict__ A0, const float* __restrict__ Ai, const float* __restrict__ Aj,
                   const float* __restrict__ Ak, double* __restrict__ partials, const CgScalars* __restrict__ sc, int jgroups, int tpb,
-                  const unsigned char* __restrict__ pack, int dk0, int dk1, int a0p, const int* __restrict__ bempty = nullptr, int nbj = 0,
-                  const int* __restrict__ outside_bad = nullptr, const int* __restrict__ xr = nullptr) {   // DOT covers the planes [dk0, dk1) (a z-slab's own)
-	// bempty (mf_cg_solve, liquid scenes): 8 x 8 bundles of rows without a fluid cell in which src is known to be zero (k_cg_outside_zero found
-	// rhs and the work grids zero there, and every kernel of the iteration keeps it so): dst = src = 0 is there already, nothing to do
-	// a0p bit 0 (PACKED only): bits 4-7 of the packed bytes hold the diagonal (k_mic_pack) -- A0 is not read at all, 9 instead of 13 B per cell;
-	// bit 1 (DOT, the PCG): src rows and dst non-temporal (PCG_NT_CELLS)
+                  const unsigned char* __restrict__ pack, int dk0, int dk1, bool a0_packed, bool nt, SkipMap skip) {   // DOT covers the planes [dk0, dk1) (a z-slab's own)
+	// skip (mf_cg_solve, liquid scenes): where it applies src is known to be zero (k_cg_outside_zero found rhs and the work grids zero there,
+	// and every kernel of the iteration keeps it so): dst = src = 0 is there already, nothing to do
+	// a0_packed (PACKED only): bits 4-7 of the packed bytes hold the diagonal (k_mic_pack) -- A0 is not read at all, 9 instead of 13 B per cell;
+	// nt (DOT, the PCG: only as part of the complete set, PCG_NT_CELLS; outside it always): src rows and dst non-temporal
 	if (DOT && sc->done) return;
+	const bool nts = !DOT || nt;
 	const int qx = d.sx >> 2;
 	const int64_t nthr = (int64_t)qx * jgroups * d.sz;
 	const int vb0 = xcd_swizzle(blockIdx.x, gridDim.x) * tpb;
@@ -86,15 +94,14 @@ k_apply_matrix_v5(Dim d, const int32_t* __restrict__ flags, float* __restrict__ 
 	const int j0 = (int)(rg % jgroups) * R;
 	const int k = (int)(rg / jgroups);
 	// (R divides 8: the rows of a thread lie in one bundle; the lanes this thread exchanges +-X neighbours with work on the same rows)
-	// (xr: the x-range of the system's non-zero packed bytes, k_pack_xrange -- the quads outside it are as empty as the empty bundles;
-	// the first / last quad inside fetch their outer x-neighbour themselves, the lane next to them has left)
+	// (the quads outside the x-range of the system's non-zero packed bytes are as empty as the empty bundles; the first / last quad
+	// inside fetch their outer x-neighbour themselves, the lane next to them has left)
 	int q_lo = 0, q_hi = qx;
-	if (IS3D && bempty && outside_bad[0] == 0) {
-		if (xr) {
-			q_lo = (xr[0] & ~7) >> 2;
-			q_hi = ((xr[1] + 7) & ~7) >> 2;
-		}
-		if (bempty[(k >> 3) * nbj + (j0 >> 3)] || qi < q_lo || qi >= q_hi) continue;
+	if (IS3D && skip.on() && skip.active()) {
+		const SkipMap::XRange xq = skip.range(d.sx);
+		q_lo = xq.lo >> 2;
+		q_hi = xq.hi >> 2;
+		if (skip.empty_bundle(j0, k) || qi < q_lo || qi >= q_hi) continue;
 	}
 	const int lane = threadIdx.x & 63;
 	const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -110,38 +117,38 @@ k_apply_matrix_v5(Dim d, const int32_t* __restrict__ flags, float* __restrict__ 
 	{
 		const int jm = (rg > 0) ? -1 : 0;
 		sv[0] = *(const float4*)(src + row0 + jm * Y);
-		if (PACKED) ajv[0] = unpack_coef<4u>(*(const unsigned*)(pack + row0 + jm * Y));
+		if (PACKED) ajv[0] = unpack_coef<PK_AJ>(*(const unsigned*)(pack + row0 + jm * Y));
 		else ajv[0] = *(const float4*)(Aj + row0 + jm * Y);
 	}
 #pragma unroll
 	for (int r = 0; r < R; r++) {
 		const int jr = (j0 + r < d.sy) ? r : (d.sy - 1 - j0);
 		const int64_t idx = row0 + jr * Y;
-		sv[r + 1] = ((AMP_NT & 1) && (!DOT || (a0p & 2))) ? ld_nt4(src + idx) : *(const float4*)(src + idx);      // (inside the PCG -- DOT -- only as part of the complete set)
+		sv[r + 1] = ld4(src + idx, nts);
 		unsigned pw = 0;
 		if (PACKED) pw = *(const unsigned*)(pack + idx);
-		if (PACKED && (a0p & 1)) a0[r] = make_float4((float)((pw >> 4) & 15u), (float)((pw >> 12) & 15u), (float)((pw >> 20) & 15u), (float)((pw >> 28) & 15u));
-		else a0[r] = (AM_NT >= 1) ? ld_nt4(A0 + idx) : *(const float4*)(A0 + idx);
+		if (PACKED && a0_packed) a0[r] = unpack_a0(pw);
+		else a0[r] = ld_nt4(A0 + idx);
 		if (PACKED) {
 			f[r] = unpack_flags(pw);
-			ajv[r + 1] = unpack_coef<4u>(pw);
-			ai[r] = unpack_coef<2u>(pw);
+			ajv[r + 1] = unpack_coef<PK_AJ>(pw);
+			ai[r] = unpack_coef<PK_AI>(pw);
 		} else {
-			f[r] = (AM_NT >= 1) ? ld_nt4i(flags + idx) : *(const int4*)(flags + idx);
-			ajv[r + 1] = (AM_NT >= 3) ? ld_nt4(Aj + idx) : *(const float4*)(Aj + idx);
-			ai[r] = (AM_NT >= 1) ? ld_nt4(Ai + idx) : *(const float4*)(Ai + idx);
+			f[r] = ld_nt4i(flags + idx);
+			ajv[r + 1] = *(const float4*)(Aj + idx);
+			ai[r] = ld_nt4(Ai + idx);
 		}
 		if (IS3D) {
 			const int64_t im = (k > 0) ? idx - Z : idx, ip = (k < d.sz - 1) ? idx + Z : idx;
 			if (PACKED) {
-				ak[r] = unpack_coef<8u>(pw);
-				akm[r] = unpack_coef<8u>(*(const unsigned*)(pack + im));
+				ak[r] = unpack_coef<PK_AK>(pw);
+				akm[r] = unpack_coef<PK_AK>(*(const unsigned*)(pack + im));
 			} else {
-				ak[r] = (AM_NT >= 3) ? ld_nt4(Ak + idx) : *(const float4*)(Ak + idx);
+				ak[r] = *(const float4*)(Ak + idx);
 				akm[r] = *(const float4*)(Ak + im);
 			}
-			szm[r] = (AMP_NT & 2) ? ld_nt4(src + im) : *(const float4*)(src + im);
-			szp[r] = (AMP_NT & 2) ? ld_nt4(src + ip) : *(const float4*)(src + ip);
+			szm[r] = *(const float4*)(src + im);
+			szp[r] = *(const float4*)(src + ip);
 		}
 	}
 	{
@@ -159,7 +166,7 @@ k_apply_matrix_v5(Dim d, const int32_t* __restrict__ flags, float* __restrict__ 
 		sr[r] = wave_shl1(sv[r + 1].x);
 		if (edge_l) {
 			sl[r] = (idx > 0) ? src[idx - 1] : 0.f;
-			if (PACKED) al[r] = (idx > 0 && (pack[idx - 1] & 2u)) ? -1.f : 0.f;
+			if (PACKED) al[r] = (idx > 0) ? pk_coef<PK_AI>(pack[idx - 1]) : 0.f;
 			else al[r] = (idx > 0) ? Ai[idx - 1] : 0.f;
 		}
 		if (edge_r) sr[r] = (idx + 4 < d.n) ? src[idx + 4] : 0.f;
@@ -183,19 +190,8 @@ k_apply_matrix_v5(Dim d, const int32_t* __restrict__ flags, float* __restrict__ 
 				}
 				if (k < d.sz - 1) zp = szp[r];
 			}
-#define CELL5(c, SL, AL, SR)                                                                      \
-	if (fl.c & MF_FLUID) {                                                                        \
-		float v = s.c * a0[r].c;                                                                  \
-		v = v + (SL) * (AL);                                                                      \
-		v = v + (SR) * ai[r].c;                                                                   \
-		v = v + sym.c * ajm.c;                                                                    \
-		v = v + syp.c * aj.c;                                                                     \
-		if (IS3D) {                                                                               \
-			v = v + zm.c * am.c;                                                                  \
-			v = v + zp.c * akc.c;                                                                 \
-		}                                                                                         \
-		res.c = v;                                                                                \
-	}
+#define CELL5(c, SL, AL, SR) \
+	if (fl.c & MF_FLUID) res.c = stencil_cell<IS3D>(s.c, a0[r].c, SL, AL, SR, ai[r].c, sym.c, ajm.c, syp.c, aj.c, zm.c, am.c, zp.c, akc.c);
 			CELL5(x, sl[r], al[r], s.y)
 			CELL5(y, s.x, ai[r].x, s.z)
 			CELL5(z, s.y, ai[r].y, s.w)
@@ -203,15 +199,8 @@ k_apply_matrix_v5(Dim d, const int32_t* __restrict__ flags, float* __restrict__ 
 #undef CELL5
 		}
 		if (live) {
-			if (AM_NT >= 2 && (!DOT || (a0p & 2))) st_nt4(dst + row0 + r * Y, res);
-			else *(float4*)(dst + row0 + r * Y) = res;
-			if (DOT && k >= dk0 && k < dk1) {
-				const float p0 = res.x * s.x, p1 = res.y * s.y, p2 = res.z * s.z, p3 = res.w * s.w;
-				acc += (double)p0;
-				acc += (double)p1;
-				acc += (double)p2;
-				acc += (double)p3;
-			}
+			st4(dst + row0 + r * Y, res, nts);
+			if (DOT && k >= dk0 && k < dk1) acc = dot4(acc, res, s);
 		}
 	}
 	}
@@ -232,13 +221,8 @@ k_apply_matrix_v5(Dim d, const int32_t* __restrict__ flags, float* __restrict__ 
 // over v5).  For the same reason no branch per cell or row (every cell is computed, a non-fluid cell selects src), and four steps are
 // written out with the roles of the register sets rotating, so that no plane is moved from one set to the next.
 // The segments of one XCD are one contiguous z-range (xcd_swizzle); at most ZM_MAX_BLOCKS blocks, hence as many dot partials.
-// Per cell the expression of v5 (CELL5) on the same operands: flat +-X / +-Y neighbours, non-fluid cells copy src.
-#ifndef ZM_L
-#define ZM_L 16
-#endif
-#ifndef ZM_R
-#define ZM_R 2
-#endif
+// Per cell the expression of v5 (stencil_cell) on the same operands: flat +-X / +-Y neighbours, non-fluid cells copy src.
+constexpr int ZM_L = 16, ZM_R = 2;
 constexpr int ZM_MAX_BLOCKS = 512;
 template <int R>
 struct ZmRest {      // what a thread holds of one plane besides its own src rows, as loaded (zm_fix_rest: as used)
@@ -269,7 +253,7 @@ __device__ __forceinline__ void zm_load_rest(ZmRest<R>& p, float4 (&a0)[R], cons
 		const int jr = (j0 + r < d.sy) ? r : (d.sy - 1 - j0);
 		const int64_t idx = row0 + jr * Y;
 		p.pw[r] = *(const unsigned*)(pack + idx);
-		if (A0S) a0[r] = (AM_NT >= 1) ? ld_nt4(A0 + idx) : *(const float4*)(A0 + idx);
+		if (A0S) a0[r] = ld_nt4(A0 + idx);
 		const int64_t il = (idx > 0) ? idx - 1 : 0, ir = (idx + 4 < d.n) ? idx + 4 : idx;
 		p.sl[r] = src[il];
 		p.pl[r] = (unsigned)pack[il];
@@ -297,7 +281,7 @@ __device__ __forceinline__ void zm_fix_rest(ZmRest<R>& p, const Dim& d, int64_t 
 		if (!(idx + 4 < d.n)) p.sr[r] = 0.f;
 	}
 }
-// A0S: the diagonal comes from the A0 array, not from bits 4-7 of the packed bytes (a0p bit 0 of k_apply_matrix_v5 clear); NT: its bit 1
+// A0S: the diagonal comes from the A0 array, not from bits 4-7 of the packed bytes (a0_packed of k_apply_matrix_v5 clear); NT: its nt
 template <bool DOT, bool A0S, bool NT>
 __global__ void __launch_bounds__(BLOCK)
 k_apply_matrix_zmarch(Dim d, float* __restrict__ dst, const float* __restrict__ src, const float* __restrict__ A0,
@@ -341,47 +325,37 @@ k_apply_matrix_zmarch(Dim d, float* __restrict__ dst, const float* __restrict__ 
 			zm_fix_rest<R>(c, d, row0, j0, k);
 			const bool top = k == d.sz - 1;
 			float4 aj[R + 1], res[R];
-			aj[0] = unpack_coef<4u>(c.pwm);
+			aj[0] = unpack_coef<PK_AJ>(c.pwm);
 #pragma unroll
 			for (int r = 0; r < R; r++) {
 				const unsigned pw = c.pw[r];
-				const float4 s = s0[r], ai = unpack_coef<2u>(pw), akc = unpack_coef<8u>(pw);
-				aj[r + 1] = unpack_coef<4u>(pw);
+				const float4 s = s0[r], ai = unpack_coef<PK_AI>(pw), akc = unpack_coef<PK_AK>(pw);
+				aj[r + 1] = unpack_coef<PK_AJ>(pw);
 				ako[r] = akc;
 				float sl = wave_shr1(s.w), sr = wave_shl1(s.x);
-				float al = (__float_as_uint(wave_shr1(__uint_as_float(pw))) & 0x02000000u) ? -1.f : 0.f;
+				// (the -X neighbour's "Ai is -1" bit: byte 3 of the word of the lane before)
+				float al = pk_coef<(PK_AI << 24)>(__float_as_uint(wave_shr1(__uint_as_float(pw))));
 				if (edge_l) {
 					sl = c.sl[r];
-					al = (c.pl[r] & 2u) ? -1.f : 0.f;
+					al = pk_coef<PK_AI>(c.pl[r]);
 				}
 				if (edge_r) sr = c.sr[r];
-				const float4 a0 = A0S ? a0c[r] : make_float4((float)((pw >> 4) & 15u), (float)((pw >> 12) & 15u), (float)((pw >> 20) & 15u), (float)((pw >> 28) & 15u));
+				const float4 a0 = A0S ? a0c[r] : unpack_a0(pw);
 				const float4 sym = (r == 0) ? c.ym : s0[r > 0 ? r - 1 : 0], ajm = aj[r];
 				const float4 syp = (r + 1 < R) ? ((j0 + r < d.sy - 1) ? s0[r + 1 < R ? r + 1 : 0] : c.yp) : c.yp, ajc = aj[r + 1];
 				const float4 zm = sm[r], am = akm[r], zp = top ? z4 : s1[r];
-#define CELL5(c_, BYTE, SL, AL, SR)                                                                   \
-	{                                                                                             \
-		float v = s.c_ * a0.c_;                                                                   \
-		v = v + (SL) * (AL);                                                                      \
-		v = v + (SR) * ai.c_;                                                                     \
-		v = v + sym.c_ * ajm.c_;                                                                  \
-		v = v + syp.c_ * ajc.c_;                                                                  \
-		v = v + zm.c_ * am.c_;                                                                    \
-		v = v + zp.c_ * akc.c_;                                                                   \
-		res[r].c_ = (pw & (1u << (8 * BYTE))) ? v : s.c_;                                         \
+				// (computed for every cell, then selected: no branch per cell)
+#define CELL5(c_, BYTE, SL, AL, SR)                                                                                                             \
+	{                                                                                                                                       \
+		const float v = stencil_cell<true>(s.c_, a0.c_, SL, AL, SR, ai.c_, sym.c_, ajm.c_, syp.c_, ajc.c_, zm.c_, am.c_, zp.c_, akc.c_); \
+		res[r].c_ = (pw & (PK_FLUID << (8 * BYTE))) ? v : s.c_;                                                                             \
 	}
 				CELL5(x, 0, sl, al, s.y)
 				CELL5(y, 1, s.x, ai.x, s.z)
 				CELL5(z, 2, s.y, ai.y, s.w)
 				CELL5(w, 3, s.z, ai.z, sr)
 #undef CELL5
-				if (DOT && j0 + r < d.sy) {
-					const float p0 = res[r].x * s.x, p1 = res[r].y * s.y, p2 = res[r].z * s.z, p3 = res[r].w * s.w;
-					acc += (double)p0;
-					acc += (double)p1;
-					acc += (double)p2;
-					acc += (double)p3;
-				}
+				if (DOT && j0 + r < d.sy) acc = dot4(acc, res[r], s);
 			}
 			// (a row behind the plane's last -- odd sy -- stores the thread's first row again)
 #pragma unroll
@@ -389,7 +363,7 @@ k_apply_matrix_zmarch(Dim d, float* __restrict__ dst, const float* __restrict__ 
 				const bool own = j0 + r < d.sy;
 				const float4 o = own ? res[r] : res[0];
 				float* const p = dst + row0 + (own ? r : 0) * Y;
-				if (AM_NT >= 2 && NT) st_nt4(p, o);
+				if (NT) st_nt4(p, o);
 				else *(float4*)p = o;
 			}
 		};
@@ -407,7 +381,7 @@ k_apply_matrix_zmarch(Dim d, float* __restrict__ dst, const float* __restrict__ 
 #pragma unroll
 			for (int r = 0; r < R; r++) {
 				const int jr = (j0 + r < d.sy) ? r : (d.sy - 1 - j0);
-				aka[r] = unpack_coef<8u>(*(const unsigned*)(pack + row00 - Z + jr * Y));
+				aka[r] = unpack_coef<PK_AK>(*(const unsigned*)(pack + row00 - Z + jr * Y));
 			}
 		}
 #pragma unroll 1
@@ -466,14 +440,9 @@ k_apply_matrix_scalar(Dim d, const int32_t* __restrict__ flags, float* __restric
 // what ApplyMatrix may use beyond the four coefficient grids (every field optional)
 struct AmOpts {
 	const unsigned char* pack = nullptr;     // packed bytes of these grids (k_mic_pack) instead of flags / Ai / Aj / Ak
-	bool a0p = false;                        // ... that carry A0 in bits 4-7 as well
+	bool a0_packed = false;                  // ... that carry A0 in bits 4-7 as well
 	int dk0 = 0, dk1 = 0x7fffffff;           // DOT: the planes [dk0, dk1) only (a z-slab's own)
-	// liquid scenes (mf_cg_solve): the 8 x 8 bundles of rows to skip (nbj per row of bundles), honoured while *outside_bad == 0
-	// (k_cg_outside_zero), and the x-range of the packed system (k_pack_xrange) whose outside is skipped as well
-	const int* bempty = nullptr;
-	int nbj = 0;
-	const int* outside_bad = nullptr;
-	const int* xr = nullptr;
+	SkipMap skip;                            // liquid scenes (mf_cg_solve): what to leave out
 	int nt = -1;                             // DOT: non-temporal vector streams -- 1 on, 0 off, -1 by size (PCG_NT_CELLS)
 };
 // *nblocks: the number of blocks launched (== number of partials written when DOT); *ranged: DOT honoured dk0 / dk1
@@ -482,16 +451,16 @@ static int launch_apply_matrix(const Dim& d, const int32_t* flags, float* dst, c
                                const float* Ai, const float* Aj, const float* Ak, double* partials,
                                const CgScalars* sc, hipStream_t st, const AmOpts& o = AmOpts{}, int* nblocks = nullptr, bool* ranged = nullptr) {
 	if (ranged) *ranged = false;
-	const int a0pn = (o.a0p ? 1 : 0) | ((DOT && (o.nt < 0 ? d.n > PCG_NT_CELLS : o.nt != 0)) ? 2 : 0);
+	const bool nt = !DOT || (o.nt < 0 ? d.n > PCG_NT_CELLS : o.nt != 0);      // (outside the PCG always non-temporal)
 	const bool vec = (d.sx % 4 == 0) && al16(flags) && al16(dst) && al16(src) && al16(A0) && al16(Ai) && al16(Aj) && al16(Ak);
 	int nb;
-	if (vec && d.is3d && o.pack && !o.bempty && o.dk0 <= 0 && o.dk1 >= d.sz) {
+	if (vec && d.is3d && o.pack && !o.skip.on() && o.dk0 <= 0 && o.dk1 >= d.sz) {
 		// whole packed 3-D grids: the z-marching kernel (the skip map of liquid scenes and the z-slab windows stay on v5)
 		const int jgroups = (d.sy + ZM_R - 1) / ZM_R;
 		const int64_t vblocks = ((int64_t)(d.sx >> 2) * jgroups * ((d.sz + ZM_L - 1) / ZM_L) + BLOCK - 1) / BLOCK;
 		const int tpb = (int)((vblocks + ZM_MAX_BLOCKS - 1) / ZM_MAX_BLOCKS);
 		nb = (int)((vblocks + tpb - 1) / tpb);
-		const bool a0s = !(a0pn & 1), nt = !DOT || (a0pn & 2);      // (outside the PCG always non-temporal, as v5)
+		const bool a0s = !o.a0_packed;
 		auto kern = nt ? (a0s ? k_apply_matrix_zmarch<DOT, true, true> : k_apply_matrix_zmarch<DOT, false, true>)
 		               : (a0s ? k_apply_matrix_zmarch<DOT, true, !DOT> : k_apply_matrix_zmarch<DOT, false, !DOT>);
 		hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, st, d, dst, src, A0, o.pack, partials, sc, jgroups, tpb);
@@ -503,8 +472,8 @@ static int launch_apply_matrix(const Dim& d, const int32_t* flags, float* dst, c
 		const int tpb = (int)((vblocks + MAX_BLOCKS - 1) / MAX_BLOCKS);
 		nb = (int)((vblocks + tpb - 1) / tpb);
 		auto kern = !d.is3d ? k_apply_matrix_v5<DOT, false, R, false> : o.pack ? k_apply_matrix_v5<DOT, true, R, true> : k_apply_matrix_v5<DOT, true, R, false>;
-		hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, st, d, flags, dst, src, A0, Ai, Aj, Ak, partials, sc, jgroups, tpb, o.pack, o.dk0, o.dk1, a0pn,
-		                   o.bempty, o.nbj, o.outside_bad, o.xr);
+		hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, st, d, flags, dst, src, A0, Ai, Aj, Ak, partials, sc, jgroups, tpb, o.pack, o.dk0, o.dk1, o.a0_packed,
+		                   nt, o.skip);
 		if (ranged) *ranged = true;
 	} else {
 		nb = blocks_for(d.n, BLOCK, 2048);
@@ -806,74 +775,74 @@ __global__ void __launch_bounds__(BLOCK) k_cg_alpha(CgScalars* sc, int nb, const
 		sc->xpending = 1;
 	}
 }
-// residual += (-alpha)*tmp ; [PC_NONE: tmp = residual] ; partial min/max (or sum of squares) of the new residual: k_cg_axpy2 without
-// the dst update, which mf_cg_solve leaves to k_cg_update_search_x (one pass over `search` less per iteration)
-// (Folding this pass into the loader waves of the forward MIC sweep -- they read residual and tmp anyway -- was built and measured:
-// bit-exact, the 30 us of this kernel go away and the sweep gets 21 us slower (its middle third already streams ~4 TB/s): 75.5 ms per
-// 256^3 step either way.  Not kept.)
+// ---- the two vector passes of an iteration, one body each: the kernels below differ in where their scalars come from and in the
+// template flags.  VEC: quads (16-byte aligned views) with the n & 3 cells behind the last quad done by block 0, or cell by cell.
+// what rides on the residual pass of k_cg_axpy2: dst += alpha * search (conjugategrad.cpp:254)
+struct NoRider {
+	__device__ __forceinline__ void quad(int64_t) const {}
+	__device__ __forceinline__ void cell(int64_t) const {}
+};
+struct XUpdateRider {
+	float* __restrict__ dst;
+	const float* __restrict__ search;
+	float alpha;
+	__device__ __forceinline__ void quad(int64_t q) const { ((float4*)dst)[q] = axpy4(((float4*)dst)[q], alpha, ((const float4*)search)[q]); }
+	__device__ __forceinline__ void cell(int64_t i) const { dst[i] = dst[i] + alpha * search[i]; }
+};
+// residual += nalpha * tmp (conjugategrad.cpp:265) ; COPY_TMP (PC_NONE): tmp = residual ; per block the min / max of the new residual
+// -> fpart, or (l2) its sum of squares -> dpart (:268-272).  nt: tmp is read non-temporally (alone: 64.4 vs 63.7 ms per step).
 // EDOT (liquid scenes): the MIC sweeps leave bundles of rows without fluid out, so tmp is in those cells what it is here and their share
-// of dot(M^-1 r, r) = sum tmp * r_new can be formed in this pass, which streams both anyway (bempty / nbj: mic_empty_map; sx % 4 == 0,
-// so a quad lies in one row); the shares go to epart[block] and are appended to the sweep's partials (whose entries for those bundles
-// are 0).  A kernel of its own for them cost 33 us per iteration in the 379 x 356 x 124 dam break.
-template <bool COPY_TMP, bool EDOT = false>
-__global__ void __launch_bounds__(BLOCK)
-k_cg_axpy_r(int64_t n, const CgScalars* __restrict__ sc, float* __restrict__ residual, float* __restrict__ tmp, float* __restrict__ fpart,
-            double* __restrict__ dpart, const int* __restrict__ bempty = nullptr, int nbj = 0, int sx = 0, int sy = 0,
-            double* __restrict__ epart = nullptr, const int* __restrict__ outside_bad = nullptr, const int* __restrict__ xr = nullptr, int nt = 0) {
-	if (sc->done) return;
-	// outside_bad[0] == 0 (k_cg_outside_zero): residual and tmp are zero in the bundles the sweeps leave out and stay so -- their quads
-	// are neither read nor written, they enter the min / max as the zeros they are and add nothing to the sums
-	const bool zero_outside = EDOT && outside_bad[0] == 0;
-	const int xlo = (EDOT && xr) ? (xr[0] & ~7) : 0, xhi = (EDOT && xr) ? ((xr[1] + 7) & ~7) : 0x7fffffff;
-	const float nalpha = sc->nalpha;
-	const bool l2 = sc->useL2 != 0;
+// of dot(M^-1 r, r) = sum tmp * r_new can be formed in this pass, which streams both anyway (sx % 4 == 0, so a quad lies in one row);
+// the shares go to epart[block] and are appended to the sweep's partials (whose entries for those bundles are 0) -- whether or not the
+// premise of the skip map holds.  A kernel of its own for them cost 33 us per iteration in the 379 x 356 x 124 dam break.  While the
+// premise holds (skip.active()), residual and tmp are zero in what the map leaves out and stay so: those quads are neither read nor
+// written, they enter the min / max as the zeros they are and add nothing to the sums.
+template <bool COPY_TMP, bool EDOT, bool VEC, class Rider = NoRider>
+__device__ __forceinline__ void residual_pass(int64_t n, float nalpha, bool l2, float* __restrict__ residual, float* __restrict__ tmp, bool nt,
+                                              float* __restrict__ fpart, double* __restrict__ dpart, const SkipMap& skip = SkipMap{}, int sx = 0,
+                                              int sy = 0, double* __restrict__ epart = nullptr, const Rider& rider = Rider{}) {
+	const bool zero_outside = EDOT && skip.active();
+	const SkipMap::XRange xr = EDOT ? skip.range(sx) : SkipMap::XRange{0, 0};
 	float lo = FLT_MAX, hi = -FLT_MAX;
 	double ss = 0.0, es = 0.0;
-	const int64_t n4 = n >> 2;
-	for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < n4; q += (int64_t)gridDim.x * BLOCK) {
-		bool in_empty = false;
-		if (EDOT) {
-			const int64_t row = (4 * q) / sx;
-			const int j = (int)(row % sy), k = (int)(row / sy);
-			in_empty = bempty[(k >> 3) * nbj + (j >> 3)] != 0;
-			const int x = (int)(4 * q - row * sx);
-			if (zero_outside && (in_empty || x < xlo || x >= xhi)) {
-				lo = fminf(lo, 0.f);
-				hi = fmaxf(hi, 0.f);
-				continue;
-			}
-		}
-		float4 r = ((float4*)residual)[q];
-		const float4 t = nt ? ld_nt4(tmp + 4 * q) : ((const float4*)tmp)[q];      // (non-temporal here alone: 64.4 vs 63.7 ms per step)
-		r.x = r.x + nalpha * t.x; r.y = r.y + nalpha * t.y; r.z = r.z + nalpha * t.z; r.w = r.w + nalpha * t.w;
-		((float4*)residual)[q] = r;
-		if (COPY_TMP) ((float4*)tmp)[q] = r;
-		if (EDOT) {
-			if (in_empty) {
-				es += (double)(t.x * r.x);
-				es += (double)(t.y * r.y);
-				es += (double)(t.z * r.z);
-				es += (double)(t.w * r.w);
-			}
-		}
-		if (l2) {
-			ss += (double)r.x * (double)r.x;
-			ss += (double)r.y * (double)r.y;
-			ss += (double)r.z * (double)r.z;
-			ss += (double)r.w * (double)r.w;
-		} else {
-			lo = fminf(fminf(lo, r.x), fminf(r.y, fminf(r.z, r.w)));
-			hi = fmaxf(fmaxf(hi, r.x), fmaxf(r.y, fmaxf(r.z, r.w)));
-		}
-	}
-	if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-		const int64_t i = (n4 << 2) + threadIdx.x;
+	auto cell = [&](int64_t i) {
+		rider.cell(i);
 		const float r = residual[i] + nalpha * tmp[i];
 		residual[i] = r;
 		if (COPY_TMP) tmp[i] = r;
 		if (l2) ss += (double)r * (double)r;
 		lo = fminf(lo, r);
 		hi = fmaxf(hi, r);
+	};
+	if (VEC) {
+		const int64_t n4 = n >> 2;
+		for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < n4; q += (int64_t)gridDim.x * BLOCK) {
+			bool in_empty = false;
+			if (EDOT) {
+				int j, k, x;
+				quad_cell(q, sx, sy, j, k, x);
+				in_empty = skip.empty_bundle(j, k);
+				if (zero_outside && (in_empty || xr.outside(x))) {
+					lo = fminf(lo, 0.f);
+					hi = fmaxf(hi, 0.f);
+					continue;
+				}
+			}
+			rider.quad(q);
+			const float4 r0 = ((float4*)residual)[q], t = ld4(tmp + 4 * q, nt);
+			const float4 r = axpy4(r0, nalpha, t);
+			((float4*)residual)[q] = r;
+			if (COPY_TMP) ((float4*)tmp)[q] = r;
+			if (EDOT && in_empty) es = dot4(es, t, r);
+			if (l2) ss = sumsq4(ss, r);
+			else {
+				lo = min4(lo, r);
+				hi = max4(hi, r);
+			}
+		}
+		if (blockIdx.x == 0 && threadIdx.x < (n & 3)) cell((n4 << 2) + threadIdx.x);
+	} else {
+		for (int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) cell(i);
 	}
 	if (l2) {
 		ss = block_sum(ss);
@@ -891,58 +860,58 @@ k_cg_axpy_r(int64_t n, const CgScalars* __restrict__ sc, float* __restrict__ res
 		if (threadIdx.x == 0) epart[blockIdx.x] = es;
 	}
 }
-// dst += alpha*search ; residual += (-alpha)*tmp ; [PC_NONE: tmp = residual] ; partial min/max (or sum of
-// squares) of the new residual.  conjugategrad.cpp:254-255, 265, 268-272
-template <bool COPY_TMP>
+// dst += alpha * search (conjugategrad.cpp:254) and, with upd, search = tmp + beta * search (:283) -- `search` is read once for both.
+// nt: the pressure is touched here and nowhere else in an iteration, tmp for the last time before ApplyMatrix overwrites it: non-temporal,
+// so that 128 MB per 256^3 iteration do not displace what the sweeps and the stencil re-read (63.1 vs 63.7 ms per step of tools/micro/ntv_bench.py).
+// SKIP (liquid scenes): dst, search and tmp are zero in what the map leaves out and stay zero
+template <bool SKIP, bool VEC>
+__device__ __forceinline__ void search_pass(int64_t n, float alpha, float beta, bool upd, float* __restrict__ dst, float* __restrict__ search,
+                                            const float* __restrict__ tmp, bool nt, const SkipMap& skip = SkipMap{}, int sx = 0, int sy = 0) {
+	auto cell = [&](int64_t i) {
+		const float s = search[i];
+		dst[i] = dst[i] + alpha * s;
+		if (upd) search[i] = tmp[i] + beta * s;
+	};
+	if (VEC) {
+		const SkipMap::XRange xr = SKIP ? skip.range(sx) : SkipMap::XRange{0, 0};
+		const bool zero_outside = SKIP && skip.active();
+		const int64_t n4 = n >> 2;
+		for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < n4; q += (int64_t)gridDim.x * BLOCK) {
+			if (SKIP && zero_outside) {
+				int j, k, x;
+				quad_cell(q, sx, sy, j, k, x);
+				if (skip.empty_bundle(j, k) || xr.outside(x)) continue;
+			}
+			const float4 s = ld4(search + 4 * q, nt);
+			st4(dst + 4 * q, axpy4(ld4(dst + 4 * q, nt), alpha, s), nt);
+			if (upd) st4(search + 4 * q, axpy4(ld4(tmp + 4 * q, nt), beta, s), nt);
+		}
+		if (blockIdx.x == 0 && threadIdx.x < (n & 3)) cell((n4 << 2) + threadIdx.x);
+	} else {
+		for (int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) cell(i);
+	}
+}
+
+// the residual update of mf_cg_solve: k_cg_axpy2 without the dst update, which is left to k_cg_update_search_x (one pass over `search`
+// less per iteration)
+// (Folding this pass into the loader waves of the forward MIC sweep -- they read residual and tmp anyway -- was built and measured:
+// bit-exact, the 30 us of this kernel go away and the sweep gets 21 us slower (its middle third already streams ~4 TB/s): 75.5 ms per
+// 256^3 step either way.  Not kept.)
+template <bool COPY_TMP, bool EDOT = false>
+__global__ void __launch_bounds__(BLOCK)
+k_cg_axpy_r(int64_t n, const CgScalars* __restrict__ sc, float* __restrict__ residual, float* __restrict__ tmp, float* __restrict__ fpart,
+            double* __restrict__ dpart, SkipMap skip = SkipMap{}, int sx = 0, int sy = 0, double* __restrict__ epart = nullptr, int nt = 0) {
+	if (sc->done) return;
+	residual_pass<COPY_TMP, EDOT, true>(n, sc->nalpha, sc->useL2 != 0, residual, tmp, nt != 0, fpart, dpart, skip, sx, sy, epart);
+}
+// dst += alpha*search ; residual += (-alpha)*tmp ; partial min/max (or sum of squares) of the new residual.
+// conjugategrad.cpp:254-255, 265, 268-272
 __global__ void __launch_bounds__(BLOCK)
 k_cg_axpy2(int64_t n, const CgScalars* __restrict__ sc, float* __restrict__ dst, const float* __restrict__ search,
            float* __restrict__ residual, float* __restrict__ tmp, float* __restrict__ fpart, double* __restrict__ dpart) {
 	if (sc->done) return;
-	const float alpha = sc->alpha, nalpha = sc->nalpha;
-	const bool l2 = sc->useL2 != 0;
-	float lo = FLT_MAX, hi = -FLT_MAX;
-	double ss = 0.0;
-	const int64_t n4 = n >> 2;
-	for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < n4; q += (int64_t)gridDim.x * BLOCK) {
-		float4 x = ((float4*)dst)[q];
-		const float4 s = ((const float4*)search)[q];
-		float4 r = ((float4*)residual)[q];
-		const float4 t = ((const float4*)tmp)[q];
-		x.x = x.x + alpha * s.x; x.y = x.y + alpha * s.y; x.z = x.z + alpha * s.z; x.w = x.w + alpha * s.w;
-		r.x = r.x + nalpha * t.x; r.y = r.y + nalpha * t.y; r.z = r.z + nalpha * t.z; r.w = r.w + nalpha * t.w;
-		((float4*)dst)[q] = x;
-		((float4*)residual)[q] = r;
-		if (COPY_TMP) ((float4*)tmp)[q] = r;
-		if (l2) {
-			ss += (double)r.x * (double)r.x;
-			ss += (double)r.y * (double)r.y;
-			ss += (double)r.z * (double)r.z;
-			ss += (double)r.w * (double)r.w;
-		} else {
-			lo = fminf(fminf(lo, r.x), fminf(r.y, fminf(r.z, r.w)));
-			hi = fmaxf(fmaxf(hi, r.x), fmaxf(r.y, fmaxf(r.z, r.w)));
-		}
-	}
-	if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-		const int64_t i = (n4 << 2) + threadIdx.x;
-		dst[i] = dst[i] + alpha * search[i];
-		const float r = residual[i] + nalpha * tmp[i];
-		residual[i] = r;
-		if (COPY_TMP) tmp[i] = r;
-		if (l2) ss += (double)r * (double)r;
-		lo = fminf(lo, r);
-		hi = fmaxf(hi, r);
-	}
-	if (l2) {
-		ss = block_sum(ss);
-		if (threadIdx.x == 0) dpart[blockIdx.x] = ss;
-	} else {
-		block_minmax(lo, hi);
-		if (threadIdx.x == 0) {
-			fpart[2 * blockIdx.x] = lo;
-			fpart[2 * blockIdx.x + 1] = hi;
-		}
-	}
+	residual_pass<false, false, true>(n, sc->nalpha, sc->useL2 != 0, residual, tmp, false, fpart, dpart, SkipMap{}, 0, 0, nullptr,
+	                                  XUpdateRider{dst, search, sc->alpha});
 }
 // sigmaNew partials: GridDotProduct(tmp, residual), conjugategrad.cpp:279
 __global__ void __launch_bounds__(BLOCK)
@@ -950,14 +919,8 @@ k_cg_dot(int64_t n, const CgScalars* __restrict__ sc, const float* __restrict__ 
 	if (sc->done) return;
 	double acc = 0.0;
 	const int64_t n4 = n >> 2;
-	for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < n4; q += (int64_t)gridDim.x * BLOCK) {
-		const float4 x = ((const float4*)a)[q], y = ((const float4*)b)[q];
-		const float p0 = x.x * y.x, p1 = x.y * y.y, p2 = x.z * y.z, p3 = x.w * y.w;
-		acc += (double)p0;
-		acc += (double)p1;
-		acc += (double)p2;
-		acc += (double)p3;
-	}
+	for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < n4; q += (int64_t)gridDim.x * BLOCK)
+		acc = dot4(acc, ((const float4*)a)[q], ((const float4*)b)[q]);
 	if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
 		const int64_t i = (n4 << 2) + threadIdx.x;
 		const float p = a[i] * b[i];
@@ -988,87 +951,25 @@ k_cg_beta(CgScalars* sc, int nbr, const float* __restrict__ fpart, const double*
 	ss = block_sum(ss);
 	__syncthreads();
 	dd = block_sum(dd);
-	if (threadIdx.x == 0) {
-		float resNorm;
-		if (l2)
-			resNorm = (float)ss;
-		else {
-			const float alo = fabsf(lo), ahi = fabsf(hi);
-			resNorm = alo > ahi ? alo : ahi;
-		}
-		sc->resNorm = resNorm;
-		if (resNorm < sc->accuracy) {
-			sc->sigma = resNorm;
-			sc->done = 1;
-		} else {
-			const float sigmaNew = (float)dd;
-			sc->beta = sigmaNew / sc->sigma;
-			sc->sigmaNew = sigmaNew;
-			sc->sigma = sigmaNew;
-			if (!((double)resNorm < 1e35)) {
-				sc->diverged = 1;  // the host finishes this iteration's search update, then reports
-			}
-		}
-	}
+	if (threadIdx.x == 0) cg_beta_step(sc, l2, lo, hi, ss, dd);
 }
-// dst += alpha*search (conjugategrad.cpp:254, left over from this iteration: xpending) and, unless the iteration has converged,
-// search = tmp + beta*search (:283) -- `search` is read once for both
-// SKIP (liquid scenes, see k_cg_outside_zero): dst, search and tmp are zero in the bundles without fluid and stay zero
+// the search update of mf_cg_solve: this iteration's dst += alpha*search is still to be done (xpending), the search direction is
+// renewed unless the iteration has converged
 template <bool SKIP>
 __global__ void __launch_bounds__(BLOCK)
 k_cg_update_search_x(int64_t n, const CgScalars* __restrict__ sc, float* __restrict__ dst, float* __restrict__ search, const float* __restrict__ tmp,
-                     const int* __restrict__ bempty = nullptr, int nbj = 0, int sx = 0, int sy = 0, const int* __restrict__ outside_bad = nullptr,
-                     const int* __restrict__ xr = nullptr, int nt = 0) {
+                     SkipMap skip = SkipMap{}, int sx = 0, int sy = 0, int nt = 0) {
 	if (!sc->xpending) return;
-	const bool upd = !sc->done;
-	const int xlo = (SKIP && xr) ? (xr[0] & ~7) : 0, xhi = (SKIP && xr) ? ((xr[1] + 7) & ~7) : 0x7fffffff;
-	const float alpha = sc->alpha, beta = sc->beta;
-	const int64_t n4 = n >> 2;
-	const bool zero_outside = SKIP && outside_bad[0] == 0;
-	for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < n4; q += (int64_t)gridDim.x * BLOCK) {
-		if (SKIP && zero_outside) {
-			const int64_t row = (4 * q) / sx;
-			const int j = (int)(row % sy), k = (int)(row / sy);
-			const int xc = (int)(4 * q - row * sx);
-			if (bempty[(k >> 3) * nbj + (j >> 3)] || xc < xlo || xc >= xhi) continue;
-		}
-		float4 s = nt ? ld_nt4(search + 4 * q) : ((float4*)search)[q];
-		// the pressure is touched here and nowhere else in an iteration, tmp for the last time before ApplyMatrix overwrites it: non-temporal,
-		// so that 128 MB per 256^3 iteration do not displace what the sweeps and the stencil re-read (63.1 vs 63.7 ms per step of tools/micro/ntv_bench.py)
-		float4 x = nt ? ld_nt4(dst + 4 * q) : ((float4*)dst)[q];
-		x.x = x.x + alpha * s.x; x.y = x.y + alpha * s.y; x.z = x.z + alpha * s.z; x.w = x.w + alpha * s.w;
-		if (nt) st_nt4(dst + 4 * q, x);
-		else ((float4*)dst)[q] = x;
-		if (upd) {
-			const float4 t = nt ? ld_nt4(tmp + 4 * q) : ((const float4*)tmp)[q];
-			s.x = t.x + beta * s.x; s.y = t.y + beta * s.y; s.z = t.z + beta * s.z; s.w = t.w + beta * s.w;
-			if (nt) st_nt4(search + 4 * q, s);
-			else ((float4*)search)[q] = s;
-		}
-	}
-	if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-		const int64_t i = (n4 << 2) + threadIdx.x;
-		const float s = search[i];
-		dst[i] = dst[i] + alpha * s;
-		if (upd) search[i] = tmp[i] + beta * s;
-	}
+	search_pass<SKIP, true>(n, sc->alpha, sc->beta, !sc->done, dst, search, tmp, nt != 0, skip, sx, sy);
 }
-
 // the same for views that do not start on a 16-byte boundary
 __global__ void __launch_bounds__(BLOCK)
 k_cg_update_search_x_scalar(int64_t n, const CgScalars* __restrict__ sc, float* __restrict__ dst, float* __restrict__ search, const float* __restrict__ tmp) {
 	if (!sc->xpending) return;
-	const bool upd = !sc->done;
-	const float alpha = sc->alpha, beta = sc->beta;
-	for (int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
-		const float s = search[i];
-		dst[i] = dst[i] + alpha * s;
-		if (upd) search[i] = tmp[i] + beta * s;
-	}
+	search_pass<false, false>(n, sc->alpha, sc->beta, !sc->done, dst, search, tmp, false);
 }
-// z-slab PCG scalar steps on the gathered per-rank reductions g[world][2] = {max|residual|, dot} (rows combined in rank order: the
-// same bits on every rank; conjugategrad.cpp:250-291), on a CgScalars block: `done` mirrors the stop state, `xpending` says that this
-// iteration's x += alpha * search is still to be done by the search update
+// z-slab PCG scalar steps on the gathered per-rank reductions (common.h: slab_alpha, slab_beta_stop), on a CgScalars block: `done`
+// mirrors the stop state, `xpending` says that this iteration's x += alpha * search is still to be done by the search update
 __global__ void k_slab_alpha_x(const double* __restrict__ g, int world, CgScalars* __restrict__ sc, const int32_t* __restrict__ state) {
 	if (state && state[0]) {
 		sc->alpha = 0.f;
@@ -1077,30 +978,21 @@ __global__ void k_slab_alpha_x(const double* __restrict__ g, int world, CgScalar
 		sc->done = 1;
 		return;
 	}
-	double acc = 0.0;
-	for (int r = 0; r < world; r++) acc += g[2 * r + 1];
-	const float dp = (float)acc;
-	const float a = (fabs((double)dp) > 0.) ? sc->sigma / dp : 0.f;
+	const float a = slab_alpha(g, world, sc->sigma);
 	sc->alpha = a;
 	sc->nalpha = -a;
 	sc->xpending = 1;
 	sc->done = 0;
 	sc->sigmaPrev = sc->sigma;
 }
-// k_slab_alpha_x + the residual update (k_cg_axpy_r, min / max partials) in one launch: every block forms alpha from the gathered rows
-// itself (the same bits everywhere), block 0 publishes the scalars for the kernels behind it.  Nothing this kernel writes is read by
-// another block of it (sigma and the stop state are written by the search update's kernel only).
+// k_slab_alpha_x + the residual update (min / max partials) in one launch: every block forms alpha from the gathered rows itself (the
+// same bits everywhere), block 0 publishes the scalars for the kernels behind it.  Nothing this kernel writes is read by another block
+// of it (sigma and the stop state are written by the search update's kernel only).
 __global__ void __launch_bounds__(BLOCK)
 k_slab_axpy_r(int64_t n, const double* __restrict__ g, int world, CgScalars* __restrict__ sc, const int32_t* __restrict__ state,
               float* __restrict__ residual, const float* __restrict__ tmp, float* __restrict__ fpart, int nt) {
 	const bool stopped = state[0] != 0;
-	float a = 0.f;
-	if (!stopped) {
-		double acc = 0.0;
-		for (int r = 0; r < world; r++) acc += g[2 * r + 1];
-		const float dp = (float)acc;
-		a = (fabs((double)dp) > 0.) ? sc->sigma / dp : 0.f;
-	}
+	const float a = stopped ? 0.f : slab_alpha(g, world, sc->sigma);
 	const float nalpha = -a;
 	if (blockIdx.x == 0 && threadIdx.x == 0) {
 		sc->alpha = a;
@@ -1110,139 +1002,46 @@ k_slab_axpy_r(int64_t n, const double* __restrict__ g, int world, CgScalars* __r
 		if (!stopped) sc->sigmaPrev = sc->sigma;
 	}
 	if (stopped) return;
-	float lo = FLT_MAX, hi = -FLT_MAX;
-	const int64_t n4 = n >> 2;
-	for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < n4; q += (int64_t)gridDim.x * BLOCK) {
-		float4 r = ((float4*)residual)[q];
-		const float4 t = nt ? ld_nt4(tmp + 4 * q) : ((const float4*)tmp)[q];
-		r.x = r.x + nalpha * t.x; r.y = r.y + nalpha * t.y; r.z = r.z + nalpha * t.z; r.w = r.w + nalpha * t.w;
-		((float4*)residual)[q] = r;
-		lo = fminf(fminf(lo, r.x), fminf(r.y, fminf(r.z, r.w)));
-		hi = fmaxf(fmaxf(hi, r.x), fmaxf(r.y, fmaxf(r.z, r.w)));
-	}
-	if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-		const int64_t i = (n4 << 2) + threadIdx.x;
-		const float r = residual[i] + nalpha * tmp[i];
-		residual[i] = r;
-		lo = fminf(lo, r);
-		hi = fmaxf(hi, r);
-	}
-	block_minmax(lo, hi);
-	if (threadIdx.x == 0) {
-		fpart[2 * blockIdx.x] = lo;
-		fpart[2 * blockIdx.x + 1] = hi;
-	}
+	residual_pass<false, false, true>(n, nalpha, false, residual, (float*)tmp, nt != 0, fpart, nullptr);
 }
 // the residual update for views that do not start on a 16-byte boundary, behind k_slab_alpha_x: nothing once stopped (`done`), so that the
 // residual keeps its bits -- r + (-0) * tmp would turn a -0 into +0, and into NaN where tmp has overflowed
 __global__ void __launch_bounds__(BLOCK)
 k_slab_axpy_r_scalar(int64_t n, const CgScalars* __restrict__ sc, float* __restrict__ residual, const float* __restrict__ tmp, float* __restrict__ fpart) {
 	if (sc->done) return;
-	const float nalpha = sc->nalpha;
-	float lo = FLT_MAX, hi = -FLT_MAX;
-	for (int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
-		const float r = residual[i] + nalpha * tmp[i];
-		residual[i] = r;
-		lo = fminf(lo, r);
-		hi = fmaxf(hi, r);
-	}
-	block_minmax(lo, hi);
-	if (threadIdx.x == 0) {
-		fpart[2 * blockIdx.x] = lo;
-		fpart[2 * blockIdx.x + 1] = hi;
-	}
+	residual_pass<false, false, false>(n, sc->nalpha, false, residual, (float*)tmp, false, fpart, nullptr);
 }
 __global__ void k_slab_beta_x(const double* __restrict__ g, int world, CgScalars* __restrict__ sc, float accuracy, int iter, int32_t* __restrict__ state) {
 	if (state && state[0]) return;
-	double acc = 0.0, mx = 0.0;
-	for (int r = 0; r < world; r++) {
-		acc += g[2 * r + 1];
-		mx = g[2 * r] > mx ? g[2 * r] : mx;
-	}
-	const float sigmaNew = (float)acc;
-	const float rn = (float)mx;
-	sc->resNorm = rn;
-	sc->beta = sigmaNew / sc->sigma;
-	sc->sigma = sigmaNew;
-	if (state) {
-		if (rn < accuracy) {
-			state[0] = 1;
-			state[1] = iter;
-			sc->done = 1;
-		} else if (!(rn < 1e35f)) {
-			state[0] = 2;
-			state[1] = iter;
-			sc->done = 1;
-		}
+	const SlabBeta b = slab_beta_stop(g, world, sc->sigma, accuracy);
+	sc->resNorm = b.resNorm;
+	sc->beta = b.beta;
+	sc->sigma = b.sigmaNew;
+	if (state && b.stop) {
+		state[0] = b.stop;
+		state[1] = iter;
+		sc->done = 1;
 	}
 }
-// k_slab_beta_x + k_cg_update_search_x in one launch, the same way: every block forms beta and the stopping test from the gathered rows,
+// k_slab_beta_x + the search update in one launch, the same way: every block forms beta and the stopping test from the gathered rows,
 // block 0 publishes them (sigma, the stop state) -- the other blocks read sigmaPrev / xpending / alpha, which the residual update's
 // kernel wrote
 __global__ void __launch_bounds__(BLOCK)
 k_slab_update_search_x(int64_t n, const double* __restrict__ g, int world, CgScalars* __restrict__ sc, float accuracy, int iter,
                        int32_t* __restrict__ state, float* __restrict__ dst, float* __restrict__ search, const float* __restrict__ tmp, int nt) {
 	if (!sc->xpending) return;          // stopped before this iteration
-	double acc = 0.0, mx = 0.0;
-	for (int r = 0; r < world; r++) {
-		acc += g[2 * r + 1];
-		mx = g[2 * r] > mx ? g[2 * r] : mx;
-	}
-	const float sigmaNew = (float)acc;
-	const float rn = (float)mx;
-	const float beta = sigmaNew / sc->sigmaPrev;
-	const bool converged = rn < accuracy, diverged = !converged && !(rn < 1e35f);
+	const SlabBeta b = slab_beta_stop(g, world, sc->sigmaPrev, accuracy);
 	if (blockIdx.x == 0 && threadIdx.x == 0) {
-		sc->resNorm = rn;
-		sc->beta = beta;
-		sc->sigma = sigmaNew;
-		if (converged || diverged) {
-			state[0] = converged ? 1 : 2;
+		sc->resNorm = b.resNorm;
+		sc->beta = b.beta;
+		sc->sigma = b.sigmaNew;
+		if (b.stop) {
+			state[0] = b.stop;
 			state[1] = iter;
 			sc->done = 1;
 		}
 	}
-	const bool upd = !(converged || diverged);
-	const float alpha = sc->alpha;
-	const int64_t n4 = n >> 2;
-	for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < n4; q += (int64_t)gridDim.x * BLOCK) {
-		float4 s = nt ? ld_nt4(search + 4 * q) : ((float4*)search)[q];
-		float4 x = nt ? ld_nt4(dst + 4 * q) : ((float4*)dst)[q];
-		x.x = x.x + alpha * s.x; x.y = x.y + alpha * s.y; x.z = x.z + alpha * s.z; x.w = x.w + alpha * s.w;
-		if (nt) st_nt4(dst + 4 * q, x);
-		else ((float4*)dst)[q] = x;
-		if (upd) {
-			const float4 t = nt ? ld_nt4(tmp + 4 * q) : ((const float4*)tmp)[q];
-			s.x = t.x + beta * s.x; s.y = t.y + beta * s.y; s.z = t.z + beta * s.z; s.w = t.w + beta * s.w;
-			if (nt) st_nt4(search + 4 * q, s);
-			else ((float4*)search)[q] = s;
-		}
-	}
-	if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-		const int64_t i = (n4 << 2) + threadIdx.x;
-		const float s = search[i];
-		dst[i] = dst[i] + alpha * s;
-		if (upd) search[i] = tmp[i] + beta * s;
-	}
-}
-
-// one-block finishers of the slab entry points
-__global__ void __launch_bounds__(BLOCK) k_fin_sum(int nb, const double* __restrict__ partials, double* __restrict__ out) {
-	double acc = strided_sum(partials, nb);
-	acc = block_sum(acc);
-	if (threadIdx.x == 0) out[0] = acc;
-}
-__global__ void __launch_bounds__(BLOCK) k_fin_maxabs(int nb, const float* __restrict__ fpart, double* __restrict__ out) {
-	float lo = FLT_MAX, hi = -FLT_MAX;
-	for (int i = threadIdx.x; i < nb; i += blockDim.x) {
-		lo = fminf(lo, fpart[2 * i]);
-		hi = fmaxf(hi, fpart[2 * i + 1]);
-	}
-	block_minmax(lo, hi);
-	if (threadIdx.x == 0) {
-		const float alo = fabsf(lo), ahi = fabsf(hi);
-		out[0] = (double)(alo > ahi ? alo : ahi);
-	}
+	search_pass<false, true>(n, sc->alpha, b.beta, !b.stop, dst, search, tmp, nt != 0);
 }
 
 // cgSolveDiffusion matrix set-up, conjugategrad.cpp:364-375
@@ -1262,9 +1061,6 @@ k_diffusion_matrix(int64_t n, const int32_t* __restrict__ flags, float* __restri
 	}
 }
 
-static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const float* rhs, float* residual, float* search, float* tmp,
-                         const float* A0, const float* Ai, const float* Aj, const float* Ak, float* Aprecond, int pc, float accuracy,
-                         int maxIter, int useL2Norm, float* out_host, void* stream, const unsigned char* free_pack, const PcExternal* ext = nullptr);
 // the system of mf_cg_solve with its rows padded from sx to px cells (pad cells: obstacle, zero coefficients, zero rhs), plus the caller's
 // tmp (pad cells 0), and back
 __global__ void __launch_bounds__(BLOCK)
@@ -1299,15 +1095,314 @@ k_unpad(int sx, int px, int64_t n, const float* __restrict__ padded, float* __re
 // block follows the growth rule of every arena (arena_reserve: to max(2 * cap, need) after a device synchronise, never shrinks).
 static Arena g_pad[MAX_DEVICES];
 
+// Liquid scenes: most 8 x 8 bundles of rows hold no fluid cell (benchmark_dam.py: 6 % of the cells are fluid).  MakeRhs leaves rhs zero
+// outside the fluid and the work grids are fresh zero grids, so every PCG vector is zero in those bundles and stays zero (ApplyMatrix copies
+// src, the sweeps leave them out, the vector updates combine zeros) -- the kernels of an iteration then skip them altogether.  This kernel
+// is what establishes the premise, on the device, once per solve: bad[0] counts the quads of empty bundles in which rhs or tmp is not +0.
+// x-range of the packed system (bytes of k_mic_pack / k_setup_fused; sx % 8 == 0): xr[0] = first cell with a non-zero byte, xr[1] = one
+// past the last one, plus one (a set "Ai is -1" bit couples the cell behind it).  Cells outside are non-fluid cells without couplings.
+__global__ void __launch_bounds__(BLOCK)
+k_pack_xrange(int64_t n, int sx, const unsigned char* __restrict__ pack, int* __restrict__ xr) {
+	int lo = 0x7fffffff, hi = 0;
+	const int64_t n8 = n >> 3;
+	for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < n8; q += (int64_t)gridDim.x * BLOCK) {
+		const unsigned long long w = ((const unsigned long long*)pack)[q];
+		if (w == 0ull) continue;
+		const int x0 = (int)((8 * q) % sx);
+		const int a = x0 + (__ffsll((long long)w) - 1) / 8, b = x0 + (63 - __clzll((long long)w)) / 8 + 2;
+		lo = a < lo ? a : lo;
+		hi = b > hi ? b : hi;
+	}
+#pragma unroll
+	for (int o = 32; o >= 1; o >>= 1) {
+		const int l2 = __shfl_xor(lo, o, 64), h2 = __shfl_xor(hi, o, 64);
+		lo = l2 < lo ? l2 : lo;
+		hi = h2 > hi ? h2 : hi;
+	}
+	if ((threadIdx.x & 63) == 0 && hi > 0) {
+		atomicMin(&xr[0], lo);
+		atomicMax(&xr[1], hi);
+	}
+}
+__global__ void __launch_bounds__(BLOCK)
+k_cg_outside_zero(int64_t n, int sx, int sy, SkipMap skip, const float* __restrict__ rhs, const float* __restrict__ tmp,
+                  const float* __restrict__ search, int* __restrict__ bad) {      // (bad: what skip.outside_bad points to, still to be written)
+	const int64_t n4 = n >> 2;
+	int found = 0;
+	const SkipMap::XRange xr = skip.range(sx);
+	for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < n4; q += (int64_t)gridDim.x * BLOCK) {
+		int j, k, x;
+		quad_cell(q, sx, sy, j, k, x);
+		if (!skip.empty_bundle(j, k) && !xr.outside(x)) continue;
+		const uint4 a = ((const uint4*)rhs)[q], b = ((const uint4*)tmp)[q], c = ((const uint4*)search)[q];
+		if ((a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w | c.x | c.y | c.z | c.w) != 0u) found = 1;
+	}
+	if (__any(found) && (threadIdx.x & 63) == 0) atomicAdd(bad, 1);
+}
+// ---- matrix-free set-up of a plain MakeLaplaceMatrix system (no fractions, no ghost fluid, no optional rhs terms): ONE pass over
+// flags and vel writes rhs (MakeRhs, pressure.cpp:32-84), the packed byte of every cell -- fluid bit, "Ai / Aj / Ak is -1" bits and the
+// integer diagonal in bits 4-7 (MakeLaplaceMatrix, conjugategrad.h:154-187; k_mic_pack's layout) -- and clears the empty-bundle entry
+// of every 8 x 8 bundle of rows that holds a fluid cell.  The float arrays A0 / Ai / Aj / Ak never exist.  A thread owns 4 cells.
+__global__ void __launch_bounds__(BLOCK)
+k_setup_fused(Dim d, const int32_t* __restrict__ flags, const float* __restrict__ vel, float* __restrict__ rhs, unsigned char* __restrict__ pack,
+              int* __restrict__ bempty, int nbj) {
+	const int qx = d.sx >> 2;
+	const int64_t T = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+	if (T >= (int64_t)qx * d.sy * d.sz) return;
+	const int qi = (int)(T % qx);
+	const int64_t rg = T / qx;
+	const int j = (int)(rg % d.sy), k = (int)(rg / d.sy), i0 = 4 * qi;
+	const int64_t Y = d.Y, Z = d.Z, n = d.n;
+	const int64_t idx = i0 + Y * j + Z * k;
+	const int4 f4 = *(const int4*)(flags + idx);
+	const int f[4] = {f4.x, f4.y, f4.z, f4.w};
+	float r[4] = {0.f, 0.f, 0.f, 0.f};
+	unsigned bytes = 0;
+	const bool row_in = j >= 1 && j <= d.sy - 2 && k >= 1 && k <= d.sz - 2;
+	if (row_in) {
+		const int4 ym4 = *(const int4*)(flags + idx - Y), yp4 = *(const int4*)(flags + idx + Y);
+		const int4 zm4 = *(const int4*)(flags + idx - Z), zp4 = *(const int4*)(flags + idx + Z);
+		const int ym[4] = {ym4.x, ym4.y, ym4.z, ym4.w}, yp[4] = {yp4.x, yp4.y, yp4.z, yp4.w};
+		const int zm[4] = {zm4.x, zm4.y, zm4.z, zm4.w}, zp[4] = {zp4.x, zp4.y, zp4.z, zp4.w};
+		const int fxm = i0 > 0 ? flags[idx - 1] : MF_OBSTACLE, fxp = i0 + 4 < d.sx ? flags[idx + 4] : MF_OBSTACLE;
+		const float *vx = vel, *vy = vel + n, *vz = vel + 2 * n;
+		const float4 ux4 = *(const float4*)(vx + idx), uy4 = *(const float4*)(vy + idx), uyp4 = *(const float4*)(vy + idx + Y);
+		const float4 uz4 = *(const float4*)(vz + idx), uzp4 = *(const float4*)(vz + idx + Z);
+		const float uxp = i0 + 4 < d.sx ? vx[idx + 4] : 0.f;
+		const float ux[5] = {ux4.x, ux4.y, ux4.z, ux4.w, uxp};
+		const float uy[4] = {uy4.x, uy4.y, uy4.z, uy4.w}, uyp[4] = {uyp4.x, uyp4.y, uyp4.z, uyp4.w};
+		const float uz[4] = {uz4.x, uz4.y, uz4.z, uz4.w}, uzp[4] = {uzp4.x, uzp4.y, uzp4.z, uzp4.w};
+#pragma unroll
+		for (int c = 0; c < 4; c++) {
+			const int i = i0 + c;
+			const bool fl = (f[c] & MF_FLUID) != 0;
+			unsigned b = pk_make(fl, false, false, false, 0u);
+			if (fl && i >= 1 && i <= d.sx - 2) {
+				const int xm = c > 0 ? f[c - 1] : fxm, xp = c < 3 ? f[c + 1] : fxp;
+				const unsigned a0 = (unsigned)!(xm & MF_OBSTACLE) + (unsigned)!(xp & MF_OBSTACLE) + (unsigned)!(ym[c] & MF_OBSTACLE) +
+				                    (unsigned)!(yp[c] & MF_OBSTACLE) + (unsigned)!(zm[c] & MF_OBSTACLE) + (unsigned)!(zp[c] & MF_OBSTACLE);
+				b = pk_make(true, xp & MF_FLUID, yp[c] & MF_FLUID, zp[c] & MF_FLUID, a0);
+				float set = ux[c] - ux[c + 1] + uy[c] - uyp[c];
+				set += uz[c] - uzp[c];
+				r[c] = set;
+			}
+			bytes |= b << (8 * c);
+		}
+	} else {
+#pragma unroll
+		for (int c = 0; c < 4; c++) bytes |= pk_make(f[c] & MF_FLUID, false, false, false, 0u) << (8 * c);
+	}
+	*(float4*)(rhs + idx) = make_float4(r[0], r[1], r[2], r[3]);
+	*(unsigned*)(pack + idx) = bytes;
+	if (bytes & (PK_FLUID * PK_WORD)) bempty[(k >> 3) * nbj + (j >> 3)] = 0;
+}
+
+// What the iterations of one PCG solve run, decided once before the first of them (pcg_setup); the iteration loop reads nothing else.
+// Liquid scenes: am.skip is what the kernels of an iteration leave out (pressure.h: SkipMap); where the sweep's workgroups draw several bundles each, be_map is the same map
+// for the sweep: the dot shares of its empty bundles then ride on the residual update (k_cg_axpy_r<.., EDOT>), behind its partials.
+struct PcgPlan {
+	AmOpts am;                    // ApplyMatrix: packed bytes, skip map, x-range, non-temporal policy (also that of the vector kernels)
+	const int* be_map = nullptr;
+	MicSweep sweep;               // the x-range trim of the MIC sweeps
+};
+// The set-up after doInit: packed bytes, empty-bundle maps, x-range verdict (one read-back), non-temporal policy -> *p and
+// g_last_shortcut.  free_pack (mf_solve_pressure_fused): the system exists as packed bytes only.
+static int pcg_setup(const Dim& d, const int32_t* flags, const float* rhs, const float* search, const float* tmp, const float* A0, const float* Ai,
+                     const float* Aj, const float* Ak, const float* Aprecond, int pc, const unsigned char* free_pack, Workspace* ws, hipStream_t st,
+                     PcgPlan* p) {
+	const int sx = d.sx, sy = d.sy;
+	const int64_t n = d.n;
+	const int nbs = blocks_for(n >> 2, BLOCK, 2048);
+	// ApplyMatrix reads the same packed coefficient bytes as the MIC sweeps when mf_mic_init found the matrix packable
+	if (free_pack) {
+		p->am.pack = free_pack;
+		p->am.a0_packed = true;
+	} else if (pc == MF_PC_MICP) {
+		MF_TRY(mic_pack_query(d, flags, A0, Ai, Aj, Ak, &p->am.pack, &p->am.a0_packed, st));
+	}
+	bool several = false;
+	if (pc == MF_PC_MICP && (sx % 4) == 0) MF_TRY(mic_empty_map(d, flags, Aprecond, Aj, Ak, &p->am.skip.bempty, &p->am.skip.nbj, &several, st));
+	if (several) p->be_map = p->am.skip.bempty;
+	g_last_shortcut[0] = g_last_shortcut[1] = g_last_shortcut[2] = 0;
+	p->am.nt = (!p->am.skip.on() && n > PCG_NT_CELLS) ? 1 : 0;
+	if (p->am.skip.on()) {
+		// (n % 4 == 0 here: sx % 4 == 0.)  residual = rhs and dst = 0 were set by doInit; tmp and search are the caller's
+		int* p_bad = (int*)((char*)ws->scalars + WS_PCG_FLAGS);
+		int* p_xr = p_bad + 1;
+		const bool ranged = p->am.pack != nullptr && (sx % 8) == 0;
+		p->am.skip.outside_bad = p_bad;
+		if (ranged) p->am.skip.xr = p_xr;
+		const int init3[3] = {0, 0x7fffffff, 0};
+		MF_HIP(hipMemcpyAsync(p_bad, init3, sizeof init3, hipMemcpyHostToDevice, st));
+		if (ranged) hipLaunchKernelGGL(k_pack_xrange, dim3(blocks_for(n >> 3, BLOCK, 2048)), dim3(BLOCK), 0, st, n, sx, p->am.pack, p_xr);
+		hipLaunchKernelGGL(k_cg_outside_zero, dim3(nbs), dim3(BLOCK), 0, st, n, sx, sy, p->am.skip, rhs, tmp, search, p_bad);
+		MF_LAUNCH_CHECK();
+		if (ranged) {
+			// the sweeps keep to the x-range of the fluid, if the host may know that everything outside is +0
+			int h3[3] = {1, 0, 0};
+			MF_HIP(hipMemcpyAsync(h3, p_bad, sizeof h3, hipMemcpyDeviceToHost, st));
+			MF_HIP(hipStreamSynchronize(st));
+			const SkipMap::XRange xr = SkipMap::rounded(h3[1], h3[2]);
+			int c0 = xr.lo / 8, c1 = xr.hi / 8;
+			if (c1 > sx / 8) c1 = sx / 8;
+			if (h3[0] == 0 && h3[2] > 0 && c1 > c0) {
+				p->sweep.trim_xoff = 8 * c0;
+				p->sweep.trim_chunks = c1 - c0;
+				g_last_shortcut[0] = 1;
+				if (c1 - c0 < sx / 8) {
+					g_last_shortcut[1] = 8 * c0;
+					g_last_shortcut[2] = 8 * (c1 - c0);
+				}
+			}
+		}
+	}
+	return 0;
+}
+// doInit + iterate loop of GridCg (conjugategrad.cpp:210-307).  free_pack (mf_solve_pressure_fused): the system exists as packed bytes
+// only -- A0 / Ai / Aj / Ak are null, the MIC factor is already in Aprecond and the system is registered with the sweeps
+static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const float* rhs, float* residual, float* search, float* tmp,
+                         const float* A0, const float* Ai, const float* Aj, const float* Ak, float* Aprecond, int pc, float accuracy,
+                         int maxIter, int useL2Norm, float* out_host, void* stream, const unsigned char* free_pack, const PcExternal* ext = nullptr) {
+	const int sx = d.sx, sy = d.sy, sz = d.sz;
+	const int64_t n = d.n;
+	hipStream_t st = (hipStream_t)stream;
+	Workspace* ws;
+	MF_TRY(get_workspace(&ws));
+	CgScalars* sc = (CgScalars*)ws->scalars;
+	double* p_dot = ws->partials;                   // apply-matrix / sigma dot partials
+	double* p_res = ws->partials + MAX_BLOCKS;      // sum-of-squares partials of the residual
+	double* p_sig = ws->partials + 2 * MAX_BLOCKS;  // dot(tmp, residual) partials
+	float* p_mm = ws->fpartials;
+	const int nbs = blocks_for(n >> 2, BLOCK, 2048);
+
+	// ---- doInit, conjugategrad.cpp:210-235 ----
+	MF_HIP(hipMemsetAsync(dst, 0, sizeof(float) * n, st));
+	MF_HIP(hipMemcpyAsync(residual, rhs, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
+	if (pc == MF_PC_MICP) {
+		if (!free_pack) MF_TRY(mf_mic_init(sx, sy, sz, flags, Aprecond, A0, Ai, Aj, Ak, stream));
+		MF_TRY(mf_mic_apply(sx, sy, sz, flags, tmp, residual, Aprecond, Ai, Aj, Ak, stream));
+	} else if (ext) {
+		// PC_MGP: InitPreconditionMultigrid + ApplyPreconditionMultigrid, conjugategrad.cpp:229-231
+		MF_TRY(ext->init(ext->ctx, A0, Ai, Aj, Ak, accuracy, st));
+		MF_TRY(ext->apply(ext->ctx, tmp, residual, st));
+	} else {
+		MF_HIP(hipMemcpyAsync(tmp, residual, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
+	}
+	MF_HIP(hipMemcpyAsync(search, tmp, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
+	MF_HIP(hipMemsetAsync(sc, 0, sizeof(CgScalars), st));
+	hipLaunchKernelGGL(k_cg_dot, dim3(nbs), dim3(BLOCK), 0, st, n, sc, tmp, residual, p_sig);
+	hipLaunchKernelGGL(k_cg_begin, dim3(1), dim3(BLOCK), 0, st, sc, nbs, p_sig, accuracy, useL2Norm);
+	MF_LAUNCH_CHECK();
+	PcgPlan p;
+	MF_TRY(pcg_setup(d, flags, rhs, search, tmp, A0, Ai, Aj, Ak, Aprecond, pc, free_pack, ws, st, &p));
+
+	// ---- iterate, conjugategrad.cpp:238-299; the host only polls `done`, one batch behind the batch it has just queued
+	// (every kernel of an iteration returns at once when `done` is already set, so running ahead costs a few empty
+	// launches after convergence and keeps the GPU from idling between iterations) ----
+	CgScalars h;
+	memset(&h, 0, sizeof h);
+	h.resNorm = 1e20f;
+	// one event pair per device (an event belongs to the device that was current when it was created)
+	static thread_local hipEvent_t ev_dev[MAX_DEVICES][2] = {};
+	int slot_;
+	MF_TRY(device_slot(&slot_));
+	hipEvent_t* ev = ev_dev[slot_];
+	if (!ev[0]) {
+		MF_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
+		MF_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
+	}
+	CgScalars* hslot = (CgScalars*)ws->host;   // two pinned slots
+	// (an external preconditioner -- a multigrid V-cycle -- costs far more than a round trip and its kernels do not read `done`: the
+	// host then reads the scalars of every iteration before it queues the next)
+	const int batch = ((pc == MF_PC_MICP && mic_mode() == 0) || ext) ? 1 : 4;
+	const int be_nb = ((sy + 7) / 8) * ((sz + 7) / 8);      // the sweep's partials (one per bundle) come first, the nbs of the residual update behind them
+	int issued = 0, slot = 0, pending = -1;
+	while (issued < maxIter) {
+		const int todo = (maxIter - issued < batch) ? (maxIter - issued) : batch;
+		for (int it = 0; it < todo; it++) {
+			int nba = 0, nsig = 0;
+			bool beta_done = false;
+			MF_TRY(launch_apply_matrix<true>(d, flags, tmp, search, A0, Ai, Aj, Ak, p_dot, sc, st, p.am, &nba));
+			hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(BLOCK), 0, st, sc, nba, p_dot);
+			if (pc == MF_PC_MICP) {
+				// (with the skip map but without be_map, the shares it writes behind the sweep's partials are not summed: the sweep has them)
+				auto axpy = p.am.skip.on() ? k_cg_axpy_r<false, true> : k_cg_axpy_r<false, false>;
+				hipLaunchKernelGGL(axpy, dim3(nbs), dim3(BLOCK), 0, st, n, sc, residual, tmp, p_mm, p_res, p.am.skip, sx, sy, p_sig + be_nb, p.am.nt);
+				MicSweep fwd = p.sweep;
+				MF_TRY(mic_sweep(1, d, flags, tmp, residual, Aprecond, Ai, Aj, Ak, sc, st, &fwd));
+				// sigma_new = dot(tmp, residual) comes out of the backward sweep's write-back (one partial per row bundle); the shares of
+				// the bundles the sweeps leave out: from the residual update above, behind the sweep's partials
+				// ... and the beta step is the tail of the sweep's last workgroup (one launch less per iteration)
+				MicSweep bwd = p.sweep;
+				bwd.dotpart = p_sig;
+				bwd.empty_ext = p.be_map != nullptr;
+				bwd.tail = BetaTail{sc, nbs, p_mm, p_res, p.be_map ? nbs : 0};
+				MF_TRY(mic_sweep(2, d, flags, tmp, residual, Aprecond, Ai, Aj, Ak, sc, st, &bwd));
+				nsig = bwd.ndot;
+				beta_done = bwd.tail_done;
+				if (p.be_map) {
+					if (nsig != be_nb) return fail("mf_cg_solve: the backward sweep wrote %d dot partials, %d expected", nsig, be_nb);
+					nsig += nbs;
+				}
+			} else if (ext) {
+				hipLaunchKernelGGL((k_cg_axpy_r<false>), dim3(nbs), dim3(BLOCK), 0, st, n, sc, residual, tmp, p_mm, p_res);
+				MF_TRY(ext->apply(ext->ctx, tmp, residual, st));
+			} else {
+				hipLaunchKernelGGL((k_cg_axpy_r<true>), dim3(nbs), dim3(BLOCK), 0, st, n, sc, residual, tmp, p_mm, p_res);
+			}
+			if (nsig == 0) {
+				hipLaunchKernelGGL(k_cg_dot, dim3(nbs), dim3(BLOCK), 0, st, n, sc, tmp, residual, p_sig);
+				nsig = nbs;
+			}
+			if (!beta_done) hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, st, sc, nbs, p_mm, p_res, nsig, p_sig);
+			auto update = p.am.skip.on() ? k_cg_update_search_x<true> : k_cg_update_search_x<false>;
+			hipLaunchKernelGGL(update, dim3(nbs), dim3(BLOCK), 0, st, n, sc, dst, search, tmp, p.am.skip, sx, sy, p.am.nt);
+		}
+		MF_LAUNCH_CHECK();
+		issued += todo;
+		MF_HIP(hipMemcpyAsync(&hslot[slot], sc, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
+		MF_HIP(hipEventRecord(ev[slot], st));
+		if (ext) pending = slot;
+		if (pending >= 0) {
+			MF_HIP(hipEventSynchronize(ev[pending]));
+			memcpy(&h, &hslot[pending], sizeof h);
+			if (h.done || h.diverged) break;
+		}
+		pending = slot;
+		slot ^= 1;
+	}
+	// the final state, after everything that was queued
+	MF_HIP(hipMemcpyAsync(&hslot[0], sc, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
+	MF_HIP(hipStreamSynchronize(st));
+	memcpy(&h, &hslot[0], sizeof h);
+	out_host[0] = (float)h.iterations;
+	out_host[1] = h.resNorm;
+	out_host[2] = h.sigma;
+	if (pc == MF_PC_MICP) MF_TRY(mic_flow_error());
+	if (h.diverged) return fail("GridCg::iterate: The CG solver diverged, residual norm > 1e30, stopping.");
+	return 0;
+}
+
+namespace mf {
+int cg_solve_external(const Dim& d, const int32_t* flags, float* dst, const float* rhs, float* residual, float* search, float* tmp,
+                      const float* A0, const float* Ai, const float* Aj, const float* Ak, const PcExternal* ext, float accuracy, int maxIter,
+                      int useL2Norm, float* out_host, void* stream) {
+	if (!(al16(dst) && al16(rhs) && al16(residual) && al16(search) && al16(tmp))) return fail("cg_solve_external: work grids must be 16-byte aligned");
+	if (maxIter <= 0) return cg_no_iterations(out_host);
+	return cg_solve_core(d, flags, dst, rhs, residual, search, tmp, A0, Ai, Aj, Ak, nullptr, MF_PC_MGP, accuracy, maxIter, useL2Norm, out_host, stream,
+	                     nullptr, ext);
+}
+}  // namespace mf
+
 extern "C" {
 
 int mf_apply_matrix(int sx, int sy, int sz, const int32_t* flags, float* dst, const float* src, const float* A0,
                     const float* Ai, const float* Aj, const float* Ak, void* stream) {
 	MF_TRY(check_dim(sx, sy, sz));
 	const Dim d = mkdim(sx, sy, sz);
-	bool a0p = false;
-	const unsigned char* pk = mic_pack_user(flags, A0, Ai, Aj, Ak, &a0p);
-	return launch_apply_matrix<false>(d, flags, dst, src, A0, Ai, Aj, Ak, nullptr, nullptr, (hipStream_t)stream, AmOpts{pk, a0p});
+	bool a0_packed = false;
+	const unsigned char* pk = mic_pack_user(flags, A0, Ai, Aj, Ak, &a0_packed);
+	return launch_apply_matrix<false>(d, flags, dst, src, A0, Ai, Aj, Ak, nullptr, nullptr, (hipStream_t)stream, AmOpts{pk, a0_packed});
 }
 
 static int time_apply_matrix(int sx, int sy, int sz, const int32_t* flags, float* dst, const float* src, const float* A0,
@@ -1317,7 +1412,7 @@ static int time_apply_matrix(int sx, int sy, int sz, const int32_t* flags, float
 	hipStream_t st = (hipStream_t)stream;
 	AmOpts am;
 	if (packed) {
-		MF_TRY(mic_pack_query(d, flags, A0, Ai, Aj, Ak, &am.pack, &am.a0p, st));
+		MF_TRY(mic_pack_query(d, flags, A0, Ai, Aj, Ak, &am.pack, &am.a0_packed, st));
 		if (!am.pack) return fail("mf_time_apply_matrix_packed: no packed coefficients for these grids (call mf_mic_init on them; the off-diagonals must all be +0 or -1)");
 	}
 	hipEvent_t e0, e1;
@@ -1429,7 +1524,7 @@ int mf_apply_matrix_dot_dev(int sx, int sy, int sz, const int32_t* flags, float*
 	int nb = 0;
 	bool ranged = false;
 	AmOpts am;
-	am.pack = mic_pack_user(flags, A0, Ai, Aj, Ak, &am.a0p);
+	am.pack = mic_pack_user(flags, A0, Ai, Aj, Ak, &am.a0_packed);
 	am.dk0 = k0;
 	am.dk1 = k1;
 	MF_TRY(launch_apply_matrix<true>(d, flags, dst, src, A0, Ai, Aj, Ak, ws->partials, sc, st, am, &nb, &ranged));
@@ -1439,9 +1534,7 @@ int mf_apply_matrix_dot_dev(int sx, int sy, int sz, const int32_t* flags, float*
 		nb = blocks_for(n >> 2, BLOCK, 2048);
 		hipLaunchKernelGGL(k_cg_dot, dim3(nb), dim3(BLOCK), 0, st, n, sc, dst + k0 * XY, src + k0 * XY, ws->partials);
 	}
-	hipLaunchKernelGGL(k_fin_sum, dim3(1), dim3(BLOCK), 0, st, nb, ws->partials, dot_dev);
-	MF_LAUNCH_CHECK();
-	return 0;
+	return launch_sum_finish(nb, ws->partials, dot_dev, st);
 }
 int mf_cg_slab_axpy2(int64_t n, const void* scalars, float* x, const float* search, float* residual, const float* tmp,
                      double* maxabs_dev, void* stream) {
@@ -1457,10 +1550,8 @@ int mf_cg_slab_axpy2(int64_t n, const void* scalars, float* x, const float* sear
 	Workspace* ws;
 	MF_TRY(get_workspace(&ws));
 	const int nb = blocks_for(n >> 2, BLOCK, 2048);
-	hipLaunchKernelGGL((k_cg_axpy2<false>), dim3(nb), dim3(BLOCK), 0, st, n, (const CgScalars*)scalars, x, search, residual, (float*)tmp, ws->fpartials, ws->partials + MAX_BLOCKS);
-	hipLaunchKernelGGL(k_fin_maxabs, dim3(1), dim3(BLOCK), 0, st, nb, ws->fpartials, maxabs_dev);
-	MF_LAUNCH_CHECK();
-	return 0;
+	hipLaunchKernelGGL(k_cg_axpy2, dim3(nb), dim3(BLOCK), 0, st, n, (const CgScalars*)scalars, x, search, residual, (float*)tmp, ws->fpartials, ws->partials + MAX_BLOCKS);
+	return launch_maxabs_finish(nb, ws->fpartials, maxabs_dev, nullptr, st);
 }
 
 int mf_diffusion_matrix(int sx, int sy, int sz, const int32_t* flags, float* A0, float* Ai, float* Aj, float* Ak, float alpha,
@@ -1487,14 +1578,7 @@ int mf_cg_solve(int sx, int sy, int sz, const int32_t* flags, float* dst, const 
 	if (pc != MF_PC_NONE && pc != MF_PC_MICP) return fail("GridCg<APPLYMAT>::setICPreconditioner: Invalid method specified.");
 	if (pc == MF_PC_MICP && !d.is3d) pc = MF_PC_NONE;  // conjugategrad.cpp:315-321
 	if (!(al16(dst) && al16(rhs) && al16(residual) && al16(search) && al16(tmp))) return fail("mf_cg_solve: work grids must be 16-byte aligned");
-	if (maxIter <= 0) {
-		// GridCg::solve (conjugategrad.cpp:302-307) never reaches iterate(), and doInit is only called from there: pressure
-		// and the work grids stay untouched; mIterations = 0, mResNorm = 1e20 (constructor, :203)
-		out_host[0] = 0.f;
-		out_host[1] = 1e20f;
-		out_host[2] = 0.f;
-		return 0;
-	}
+	if (maxIter <= 0) return cg_no_iterations(out_host);
 	// Row lengths that are not a multiple of 8 (benchmark_dam.py: 3.2 res + 8) would take the sweeps and ApplyMatrix off their
 	// 16-byte paths and off the packed coefficient bytes (379 x 356 x 124: 0.83 instead of ~0.5 ms per iteration).  The PCG then
 	// runs on its own copy of the system with the rows padded to the next multiple of 8: pad cells are obstacle cells with zero
@@ -1532,317 +1616,6 @@ int mf_cg_solve(int sx, int sy, int sz, const int32_t* flags, float* dst, const 
 	return cg_solve_core(d, flags, dst, rhs, residual, search, tmp, A0, Ai, Aj, Ak, Aprecond, pc, accuracy, maxIter, useL2Norm, out_host, stream, nullptr);
 }
 
-}  // extern "C"
-
-// Liquid scenes: most 8 x 8 bundles of rows hold no fluid cell (benchmark_dam.py: 6 % of the cells are fluid).  MakeRhs leaves rhs zero
-// outside the fluid and the work grids are fresh zero grids, so every PCG vector is zero in those bundles and stays zero (ApplyMatrix copies
-// src, the sweeps leave them out, the vector updates combine zeros) -- the kernels of an iteration then skip them altogether.  This kernel
-// is what establishes the premise, on the device, once per solve: bad[0] counts the quads of empty bundles in which rhs or tmp is not +0.
-// x-range of the packed system (bytes of k_mic_pack / k_setup_fused; sx % 8 == 0): xr[0] = first cell with a non-zero byte, xr[1] = one
-// past the last one, plus one (a set "Ai is -1" bit couples the cell behind it).  Cells outside are non-fluid cells without couplings.
-__global__ void __launch_bounds__(BLOCK)
-k_pack_xrange(int64_t n, int sx, const unsigned char* __restrict__ pack, int* __restrict__ xr) {
-	int lo = 0x7fffffff, hi = 0;
-	const int64_t n8 = n >> 3;
-	for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < n8; q += (int64_t)gridDim.x * BLOCK) {
-		const unsigned long long w = ((const unsigned long long*)pack)[q];
-		if (w == 0ull) continue;
-		const int x0 = (int)((8 * q) % sx);
-		const int a = x0 + (__ffsll((long long)w) - 1) / 8, b = x0 + (63 - __clzll((long long)w)) / 8 + 2;
-		lo = a < lo ? a : lo;
-		hi = b > hi ? b : hi;
-	}
-#pragma unroll
-	for (int o = 32; o >= 1; o >>= 1) {
-		const int l2 = __shfl_xor(lo, o, 64), h2 = __shfl_xor(hi, o, 64);
-		lo = l2 < lo ? l2 : lo;
-		hi = h2 > hi ? h2 : hi;
-	}
-	if ((threadIdx.x & 63) == 0 && hi > 0) {
-		atomicMin(&xr[0], lo);
-		atomicMax(&xr[1], hi);
-	}
-}
-__global__ void __launch_bounds__(BLOCK)
-k_cg_outside_zero(int64_t n, int sx, int sy, const int* __restrict__ bempty, int nbj, const float* __restrict__ rhs, const float* __restrict__ tmp,
-                  const float* __restrict__ search, int* __restrict__ bad, const int* __restrict__ xr) {
-	const int64_t n4 = n >> 2;
-	int found = 0;
-	// (xr: also the cells outside the x-range of the packed system, rounded outwards to chunks of 8 -- what the trimmed sweeps leave out)
-	const int xlo = xr ? (xr[0] & ~7) : 0, xhi = xr ? ((xr[1] + 7) & ~7) : sx;
-	for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < n4; q += (int64_t)gridDim.x * BLOCK) {
-		const int64_t row = (4 * q) / sx;
-		const int j = (int)(row % sy), k = (int)(row / sy);
-		const int x = (int)(4 * q - row * sx);
-		if (!bempty[(k >> 3) * nbj + (j >> 3)] && x >= xlo && x < xhi) continue;
-		const uint4 a = ((const uint4*)rhs)[q], b = ((const uint4*)tmp)[q], c = ((const uint4*)search)[q];
-		if ((a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w | c.x | c.y | c.z | c.w) != 0u) found = 1;
-	}
-	if (__any(found) && (threadIdx.x & 63) == 0) atomicAdd(bad, 1);
-}
-// What the iterations of one PCG solve run, decided once before the first of them (pcg_setup); the iteration loop reads nothing else.
-// Liquid scenes: am.bempty is the map of the 8 x 8 bundles of rows the vector kernels skip (every vector is +0 there, k_cg_outside_zero
-// checks it on the device, verdict in *am.outside_bad); where the sweep's workgroups draw several bundles each, be_map is the same map
-// for the sweep: the dot shares of its empty bundles then ride on the residual update (k_cg_axpy_r<.., EDOT>), behind its partials.
-struct PcgPlan {
-	AmOpts am;                    // ApplyMatrix: packed bytes, skip map, x-range, non-temporal policy (also that of the vector kernels)
-	const int* be_map = nullptr;
-	MicSweep sweep;               // the x-range trim of the MIC sweeps
-};
-// The set-up after doInit: packed bytes, empty-bundle maps, x-range verdict (one read-back), non-temporal policy -> *p and
-// g_last_shortcut.  free_pack (mf_solve_pressure_fused): the system exists as packed bytes only.
-static int pcg_setup(const Dim& d, const int32_t* flags, const float* rhs, const float* search, const float* tmp, const float* A0, const float* Ai,
-                     const float* Aj, const float* Ak, const float* Aprecond, int pc, const unsigned char* free_pack, Workspace* ws, hipStream_t st,
-                     PcgPlan* p) {
-	const int sx = d.sx, sy = d.sy;
-	const int64_t n = d.n;
-	const int nbs = blocks_for(n >> 2, BLOCK, 2048);
-	// ApplyMatrix reads the same packed coefficient bytes as the MIC sweeps when mf_mic_init found the matrix packable
-	if (free_pack) {
-		p->am.pack = free_pack;
-		p->am.a0p = true;
-	} else if (pc == MF_PC_MICP) {
-		MF_TRY(mic_pack_query(d, flags, A0, Ai, Aj, Ak, &p->am.pack, &p->am.a0p, st));
-	}
-	bool several = false;
-	if (pc == MF_PC_MICP && (sx % 4) == 0) MF_TRY(mic_empty_map(d, flags, Aprecond, Aj, Ak, &p->am.bempty, &p->am.nbj, &several, st));
-	if (several) p->be_map = p->am.bempty;
-	g_last_shortcut[0] = g_last_shortcut[1] = g_last_shortcut[2] = 0;
-	p->am.nt = (!p->am.bempty && n > PCG_NT_CELLS) ? 1 : 0;
-	if (p->am.bempty) {
-		// (n % 4 == 0 here: sx % 4 == 0.)  residual = rhs and dst = 0 were set by doInit; tmp and search are the caller's
-		int* p_bad = (int*)((char*)ws->scalars + WS_PCG_FLAGS);
-		int* p_xr = p_bad + 1;
-		const bool ranged = p->am.pack != nullptr && (sx % 8) == 0;
-		p->am.outside_bad = p_bad;
-		if (ranged) p->am.xr = p_xr;
-		const int init3[3] = {0, 0x7fffffff, 0};
-		MF_HIP(hipMemcpyAsync(p_bad, init3, sizeof init3, hipMemcpyHostToDevice, st));
-		if (ranged) hipLaunchKernelGGL(k_pack_xrange, dim3(blocks_for(n >> 3, BLOCK, 2048)), dim3(BLOCK), 0, st, n, sx, p->am.pack, p_xr);
-		hipLaunchKernelGGL(k_cg_outside_zero, dim3(nbs), dim3(BLOCK), 0, st, n, sx, sy, p->am.bempty, p->am.nbj, rhs, tmp, search, p_bad, p->am.xr);
-		MF_LAUNCH_CHECK();
-		if (ranged) {
-			// the sweeps keep to the x-range of the fluid, if the host may know that everything outside is +0
-			int h3[3] = {1, 0, 0};
-			MF_HIP(hipMemcpyAsync(h3, p_bad, sizeof h3, hipMemcpyDeviceToHost, st));
-			MF_HIP(hipStreamSynchronize(st));
-			int c0 = h3[1] >> 3, c1 = (h3[2] + 7) >> 3;
-			if (c1 > sx / 8) c1 = sx / 8;
-			if (h3[0] == 0 && h3[2] > 0 && c1 > c0) {
-				p->sweep.trim_xoff = 8 * c0;
-				p->sweep.trim_chunks = c1 - c0;
-				g_last_shortcut[0] = 1;
-				if (c1 - c0 < sx / 8) {
-					g_last_shortcut[1] = 8 * c0;
-					g_last_shortcut[2] = 8 * (c1 - c0);
-				}
-			}
-		}
-	}
-	return 0;
-}
-// doInit + iterate loop of GridCg (conjugategrad.cpp:210-307).  free_pack (mf_solve_pressure_fused): the system exists as packed bytes
-// only -- A0 / Ai / Aj / Ak are null, the MIC factor is already in Aprecond and the system is registered with the sweeps
-static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const float* rhs, float* residual, float* search, float* tmp,
-                         const float* A0, const float* Ai, const float* Aj, const float* Ak, float* Aprecond, int pc, float accuracy,
-                         int maxIter, int useL2Norm, float* out_host, void* stream, const unsigned char* free_pack, const PcExternal* ext) {
-	const int sx = d.sx, sy = d.sy, sz = d.sz;
-	const int64_t n = d.n;
-	hipStream_t st = (hipStream_t)stream;
-	Workspace* ws;
-	MF_TRY(get_workspace(&ws));
-	CgScalars* sc = (CgScalars*)ws->scalars;
-	double* p_dot = ws->partials;                   // apply-matrix / sigma dot partials
-	double* p_res = ws->partials + MAX_BLOCKS;      // sum-of-squares partials of the residual
-	double* p_sig = ws->partials + 2 * MAX_BLOCKS;  // dot(tmp, residual) partials
-	float* p_mm = ws->fpartials;
-	const int nbs = blocks_for(n >> 2, BLOCK, 2048);
-
-	// ---- doInit, conjugategrad.cpp:210-235 ----
-	MF_HIP(hipMemsetAsync(dst, 0, sizeof(float) * n, st));
-	MF_HIP(hipMemcpyAsync(residual, rhs, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
-	if (pc == MF_PC_MICP) {
-		if (!free_pack) MF_TRY(mf_mic_init(sx, sy, sz, flags, Aprecond, A0, Ai, Aj, Ak, stream));
-		MF_TRY(mf_mic_apply(sx, sy, sz, flags, tmp, residual, Aprecond, Ai, Aj, Ak, stream));
-	} else if (ext) {
-		// PC_MGP: InitPreconditionMultigrid + ApplyPreconditionMultigrid, conjugategrad.cpp:229-231
-		MF_TRY(ext->init(ext->ctx, A0, Ai, Aj, Ak, accuracy, st));
-		MF_TRY(ext->apply(ext->ctx, tmp, residual, st));
-	} else {
-		MF_HIP(hipMemcpyAsync(tmp, residual, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
-	}
-	MF_HIP(hipMemcpyAsync(search, tmp, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
-	MF_HIP(hipMemsetAsync(sc, 0, sizeof(CgScalars), st));
-	hipLaunchKernelGGL(k_cg_dot, dim3(nbs), dim3(BLOCK), 0, st, n, sc, tmp, residual, p_sig);
-	hipLaunchKernelGGL(k_cg_begin, dim3(1), dim3(BLOCK), 0, st, sc, nbs, p_sig, accuracy, useL2Norm);
-	MF_LAUNCH_CHECK();
-	PcgPlan p;
-	MF_TRY(pcg_setup(d, flags, rhs, search, tmp, A0, Ai, Aj, Ak, Aprecond, pc, free_pack, ws, st, &p));
-
-	// ---- iterate, conjugategrad.cpp:238-299; the host only polls `done`, one batch behind the batch it has just queued
-	// (every kernel of an iteration returns at once when `done` is already set, so running ahead costs a few empty
-	// launches after convergence and keeps the GPU from idling between iterations) ----
-	CgScalars h;
-	memset(&h, 0, sizeof h);
-	h.resNorm = 1e20f;
-	// one event pair per device (an event belongs to the device that was current when it was created)
-	static thread_local hipEvent_t ev_dev[MAX_DEVICES][2] = {};
-	int slot_;
-	MF_TRY(device_slot(&slot_));
-	hipEvent_t* ev = ev_dev[slot_];
-	if (!ev[0]) {
-		MF_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
-		MF_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
-	}
-	CgScalars* hslot = (CgScalars*)ws->host;   // two pinned slots
-	// (an external preconditioner -- a multigrid V-cycle -- costs far more than a round trip and its kernels do not read `done`: the
-	// host then reads the scalars of every iteration before it queues the next)
-	const int batch = ((pc == MF_PC_MICP && mic_mode() == 0) || ext) ? 1 : 4;
-	const int be_nb = ((sy + 7) / 8) * ((sz + 7) / 8);      // the sweep's partials (one per bundle) come first, the nbs of the residual update behind them
-	int issued = 0, slot = 0, pending = -1;
-	while (issued < maxIter) {
-		const int todo = (maxIter - issued < batch) ? (maxIter - issued) : batch;
-		for (int it = 0; it < todo; it++) {
-			int nba = 0, nsig = 0;
-			bool beta_done = false;
-			MF_TRY(launch_apply_matrix<true>(d, flags, tmp, search, A0, Ai, Aj, Ak, p_dot, sc, st, p.am, &nba));
-			hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(BLOCK), 0, st, sc, nba, p_dot);
-			if (pc == MF_PC_MICP) {
-				// (with the skip map but without be_map, the shares it writes behind the sweep's partials are not summed: the sweep has them)
-				auto axpy = p.am.bempty ? k_cg_axpy_r<false, true> : k_cg_axpy_r<false, false>;
-				hipLaunchKernelGGL(axpy, dim3(nbs), dim3(BLOCK), 0, st, n, sc, residual, tmp, p_mm, p_res, p.am.bempty, p.am.nbj, sx, sy, p_sig + be_nb,
-				                   p.am.outside_bad, p.am.xr, p.am.nt);
-				MicSweep fwd = p.sweep;
-				MF_TRY(mic_sweep(1, d, flags, tmp, residual, Aprecond, Ai, Aj, Ak, sc, st, &fwd));
-				// sigma_new = dot(tmp, residual) comes out of the backward sweep's write-back (one partial per row bundle); the shares of
-				// the bundles the sweeps leave out: from the residual update above, behind the sweep's partials
-				// ... and the beta step is the tail of the sweep's last workgroup (one launch less per iteration)
-				MicSweep bwd = p.sweep;
-				bwd.dotpart = p_sig;
-				bwd.empty_ext = p.be_map != nullptr;
-				bwd.tail = BetaTail{sc, nbs, p_mm, p_res, p.be_map ? nbs : 0};
-				MF_TRY(mic_sweep(2, d, flags, tmp, residual, Aprecond, Ai, Aj, Ak, sc, st, &bwd));
-				nsig = bwd.ndot;
-				beta_done = bwd.tail_done;
-				if (p.be_map) {
-					if (nsig != be_nb) return fail("mf_cg_solve: the backward sweep wrote %d dot partials, %d expected", nsig, be_nb);
-					nsig += nbs;
-				}
-			} else if (ext) {
-				hipLaunchKernelGGL((k_cg_axpy_r<false>), dim3(nbs), dim3(BLOCK), 0, st, n, sc, residual, tmp, p_mm, p_res);
-				MF_TRY(ext->apply(ext->ctx, tmp, residual, st));
-			} else {
-				hipLaunchKernelGGL((k_cg_axpy_r<true>), dim3(nbs), dim3(BLOCK), 0, st, n, sc, residual, tmp, p_mm, p_res);
-			}
-			if (nsig == 0) {
-				hipLaunchKernelGGL(k_cg_dot, dim3(nbs), dim3(BLOCK), 0, st, n, sc, tmp, residual, p_sig);
-				nsig = nbs;
-			}
-			if (!beta_done) hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(BLOCK), 0, st, sc, nbs, p_mm, p_res, nsig, p_sig);
-			auto update = p.am.bempty ? k_cg_update_search_x<true> : k_cg_update_search_x<false>;
-			hipLaunchKernelGGL(update, dim3(nbs), dim3(BLOCK), 0, st, n, sc, dst, search, tmp, p.am.bempty, p.am.nbj, sx, sy, p.am.outside_bad, p.am.xr, p.am.nt);
-		}
-		MF_LAUNCH_CHECK();
-		issued += todo;
-		MF_HIP(hipMemcpyAsync(&hslot[slot], sc, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
-		MF_HIP(hipEventRecord(ev[slot], st));
-		if (ext) pending = slot;
-		if (pending >= 0) {
-			MF_HIP(hipEventSynchronize(ev[pending]));
-			memcpy(&h, &hslot[pending], sizeof h);
-			if (h.done || h.diverged) break;
-		}
-		pending = slot;
-		slot ^= 1;
-	}
-	// the final state, after everything that was queued
-	MF_HIP(hipMemcpyAsync(&hslot[0], sc, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
-	MF_HIP(hipStreamSynchronize(st));
-	memcpy(&h, &hslot[0], sizeof h);
-	out_host[0] = (float)h.iterations;
-	out_host[1] = h.resNorm;
-	out_host[2] = h.sigma;
-	if (pc == MF_PC_MICP) MF_TRY(mic_flow_error());
-	if (h.diverged) return fail("GridCg::iterate: The CG solver diverged, residual norm > 1e30, stopping.");
-	return 0;
-}
-
-namespace mf {
-int cg_solve_external(const Dim& d, const int32_t* flags, float* dst, const float* rhs, float* residual, float* search, float* tmp,
-                      const float* A0, const float* Ai, const float* Aj, const float* Ak, const PcExternal* ext, float accuracy, int maxIter,
-                      int useL2Norm, float* out_host, void* stream) {
-	if (!(al16(dst) && al16(rhs) && al16(residual) && al16(search) && al16(tmp))) return fail("cg_solve_external: work grids must be 16-byte aligned");
-	if (maxIter <= 0) {      // as mf_cg_solve: doInit never runs
-		out_host[0] = 0.f;
-		out_host[1] = 1e20f;
-		out_host[2] = 0.f;
-		return 0;
-	}
-	return cg_solve_core(d, flags, dst, rhs, residual, search, tmp, A0, Ai, Aj, Ak, nullptr, MF_PC_MGP, accuracy, maxIter, useL2Norm, out_host, stream,
-	                     nullptr, ext);
-}
-}  // namespace mf
-
-// ---- matrix-free set-up of a plain MakeLaplaceMatrix system (no fractions, no ghost fluid, no optional rhs terms): ONE pass over
-// flags and vel writes rhs (MakeRhs, pressure.cpp:32-84), the packed byte of every cell -- fluid bit, "Ai / Aj / Ak is -1" bits and the
-// integer diagonal in bits 4-7 (MakeLaplaceMatrix, conjugategrad.h:154-187; k_mic_pack's layout) -- and clears the empty-bundle entry
-// of every 8 x 8 bundle of rows that holds a fluid cell.  The float arrays A0 / Ai / Aj / Ak never exist.  A thread owns 4 cells.
-__global__ void __launch_bounds__(BLOCK)
-k_setup_fused(Dim d, const int32_t* __restrict__ flags, const float* __restrict__ vel, float* __restrict__ rhs, unsigned char* __restrict__ pack,
-              int* __restrict__ bempty, int nbj) {
-	const int qx = d.sx >> 2;
-	const int64_t T = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
-	if (T >= (int64_t)qx * d.sy * d.sz) return;
-	const int qi = (int)(T % qx);
-	const int64_t rg = T / qx;
-	const int j = (int)(rg % d.sy), k = (int)(rg / d.sy), i0 = 4 * qi;
-	const int64_t Y = d.Y, Z = d.Z, n = d.n;
-	const int64_t idx = i0 + Y * j + Z * k;
-	const int4 f4 = *(const int4*)(flags + idx);
-	const int f[4] = {f4.x, f4.y, f4.z, f4.w};
-	float r[4] = {0.f, 0.f, 0.f, 0.f};
-	unsigned bytes = 0;
-	const bool row_in = j >= 1 && j <= d.sy - 2 && k >= 1 && k <= d.sz - 2;
-	if (row_in) {
-		const int4 ym4 = *(const int4*)(flags + idx - Y), yp4 = *(const int4*)(flags + idx + Y);
-		const int4 zm4 = *(const int4*)(flags + idx - Z), zp4 = *(const int4*)(flags + idx + Z);
-		const int ym[4] = {ym4.x, ym4.y, ym4.z, ym4.w}, yp[4] = {yp4.x, yp4.y, yp4.z, yp4.w};
-		const int zm[4] = {zm4.x, zm4.y, zm4.z, zm4.w}, zp[4] = {zp4.x, zp4.y, zp4.z, zp4.w};
-		const int fxm = i0 > 0 ? flags[idx - 1] : MF_OBSTACLE, fxp = i0 + 4 < d.sx ? flags[idx + 4] : MF_OBSTACLE;
-		const float *vx = vel, *vy = vel + n, *vz = vel + 2 * n;
-		const float4 ux4 = *(const float4*)(vx + idx), uy4 = *(const float4*)(vy + idx), uyp4 = *(const float4*)(vy + idx + Y);
-		const float4 uz4 = *(const float4*)(vz + idx), uzp4 = *(const float4*)(vz + idx + Z);
-		const float uxp = i0 + 4 < d.sx ? vx[idx + 4] : 0.f;
-		const float ux[5] = {ux4.x, ux4.y, ux4.z, ux4.w, uxp};
-		const float uy[4] = {uy4.x, uy4.y, uy4.z, uy4.w}, uyp[4] = {uyp4.x, uyp4.y, uyp4.z, uyp4.w};
-		const float uz[4] = {uz4.x, uz4.y, uz4.z, uz4.w}, uzp[4] = {uzp4.x, uzp4.y, uzp4.z, uzp4.w};
-#pragma unroll
-		for (int c = 0; c < 4; c++) {
-			const int i = i0 + c;
-			const bool fl = (f[c] & MF_FLUID) != 0;
-			unsigned b = fl ? 1u : 0u;
-			if (fl && i >= 1 && i <= d.sx - 2) {
-				const int xm = c > 0 ? f[c - 1] : fxm, xp = c < 3 ? f[c + 1] : fxp;
-				const unsigned a0 = (unsigned)!(xm & MF_OBSTACLE) + (unsigned)!(xp & MF_OBSTACLE) + (unsigned)!(ym[c] & MF_OBSTACLE) +
-				                    (unsigned)!(yp[c] & MF_OBSTACLE) + (unsigned)!(zm[c] & MF_OBSTACLE) + (unsigned)!(zp[c] & MF_OBSTACLE);
-				b |= ((xp & MF_FLUID) ? 2u : 0u) | ((yp[c] & MF_FLUID) ? 4u : 0u) | ((zp[c] & MF_FLUID) ? 8u : 0u) | (a0 << 4);
-				float set = ux[c] - ux[c + 1] + uy[c] - uyp[c];
-				set += uz[c] - uzp[c];
-				r[c] = set;
-			}
-			bytes |= b << (8 * c);
-		}
-	} else {
-#pragma unroll
-		for (int c = 0; c < 4; c++) bytes |= ((f[c] & MF_FLUID) ? 1u : 0u) << (8 * c);
-	}
-	*(float4*)(rhs + idx) = make_float4(r[0], r[1], r[2], r[3]);
-	*(unsigned*)(pack + idx) = bytes;
-	if (bytes & 0x01010101u) bempty[(k >> 3) * nbj + (j >> 3)] = 0;
-}
-
-extern "C" {
-
 int mf_solve_pressure_fused(int sx, int sy, int sz, const int32_t* flags, const float* vel, float* pressure, float* rhs, float* residual,
                             float* search, float* tmp, float* Aprecond, float accuracy, int maxIter, int useL2Norm, float* out_host,
                             void* stream) {
@@ -1860,12 +1633,7 @@ int mf_solve_pressure_fused(int sx, int sy, int sz, const int32_t* flags, const 
 	hipLaunchKernelGGL(k_setup_fused, dim3((unsigned)((nthr + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, d, flags, vel, rhs, pack, bempty, nbj);
 	MF_LAUNCH_CHECK();
 	MF_TRY(mic_fused_finish(d, flags, Aprecond, st));
-	if (maxIter <= 0) {
-		out_host[0] = 0.f;
-		out_host[1] = 1e20f;
-		out_host[2] = 0.f;
-		return 0;
-	}
+	if (maxIter <= 0) return cg_no_iterations(out_host);
 	// the sweeps never write a non-fluid cell of tmp: it has to start from zeros (a fresh temp grid in the reference)
 	MF_HIP(hipMemsetAsync(tmp, 0, sizeof(float) * d.n, st));
 	return cg_solve_core(d, flags, pressure, rhs, residual, search, tmp, nullptr, nullptr, nullptr, nullptr, Aprecond, MF_PC_MICP, accuracy, maxIter,
@@ -1904,8 +1672,7 @@ int mf_cg_slab_after_dp(const double* gathered, int world, void* scalars, const 
 			MF_TRY(get_workspace(&ws));
 			const int nb = blocks_for(n_own, BLOCK, 2048);
 			hipLaunchKernelGGL(k_slab_axpy_r_scalar, dim3(nb), dim3(BLOCK), 0, st, n_own, sc, r, t, ws->fpartials);
-			hipLaunchKernelGGL(k_fin_maxabs, dim3(1), dim3(BLOCK), 0, st, nb, ws->fpartials, maxabs_dev);
-			MF_LAUNCH_CHECK();
+			MF_TRY(launch_maxabs_finish(nb, ws->fpartials, maxabs_dev, nullptr, st));
 		}
 	}
 	return mf_mic_apply_dot_dev(sx, sy, sz, flags, tmp, residual, Aprecond, Ai, Aj, Ak, dot_dev, stream);

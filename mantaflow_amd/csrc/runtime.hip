@@ -263,15 +263,10 @@ __global__ void __launch_bounds__(BLOCK) k_maxabs_finish(int nb, const float* __
 		hi = fmaxf(hi, partials[2 * i + 1]);
 	}
 	block_minmax(lo, hi);
-	if (threadIdx.x == 0) {
-		lo = fabsf(lo);
-		hi = fabsf(hi);
-		out[0] = lo > hi ? lo : hi;   // max(fabs(amin), fabs(amax)), grid.cpp:359
-	}
+	if (threadIdx.x == 0) out[0] = maxabs(lo, hi);
 }
 
-// z-slab PCG scalar steps on gathered per-rank reductions g[world][2] = {max|residual|, dot}: rows are summed / maxed in
-// rank order, so every rank computes the same bits (conjugategrad.cpp:250-291 for the formulas)
+// z-slab PCG scalar steps (common.h: slab_alpha, slab_beta_stop) on loose device scalars
 __global__ void k_slab_alpha(const double* __restrict__ g, int world, const float* __restrict__ sigma, float* __restrict__ alpha,
                              const int32_t* __restrict__ state) {
 	if (state && state[0]) {
@@ -279,48 +274,43 @@ __global__ void k_slab_alpha(const double* __restrict__ g, int world, const floa
 		alpha[1] = -0.f;
 		return;
 	}
-	double acc = 0.0;
-	for (int r = 0; r < world; r++) acc += g[2 * r + 1];
-	const float dp = (float)acc;
-	const float a = (fabs((double)dp) > 0.) ? sigma[0] / dp : 0.f;
+	const float a = slab_alpha(g, world, sigma[0]);
 	alpha[0] = a;
 	alpha[1] = -a;      // nalpha of the CgScalars layout (mf_cg_slab_axpy2)
 }
 __global__ void k_slab_beta(const double* __restrict__ g, int world, float* __restrict__ sigma, float* __restrict__ beta, float* __restrict__ res,
                             float accuracy, int iter, int32_t* __restrict__ state) {
 	if (state && state[0]) return;
-	double acc = 0.0, mx = 0.0;
-	for (int r = 0; r < world; r++) {
-		acc += g[2 * r + 1];
-		mx = g[2 * r] > mx ? g[2 * r] : mx;
-	}
-	const float sigmaNew = (float)acc;
-	const float rn = (float)mx;
-	res[0] = rn;
-	beta[0] = sigmaNew / sigma[0];
-	sigma[0] = sigmaNew;
-	if (state) {
-		if (rn < accuracy) {
-			state[0] = 1;
-			state[1] = iter;
-		} else if (!(rn < 1e35f)) {
-			state[0] = 2;
-			state[1] = iter;
-		}
+	const SlabBeta b = slab_beta_stop(g, world, sigma[0], accuracy);
+	res[0] = b.resNorm;
+	beta[0] = b.beta;
+	sigma[0] = b.sigmaNew;
+	if (state && b.stop) {
+		state[0] = b.stop;
+		state[1] = iter;
 	}
 }
-__global__ void __launch_bounds__(BLOCK) k_maxabs_finish64(int nb, const float* __restrict__ partials, double* __restrict__ out) {
+// stopped (nullable; the z-slab solver's iterations queued past the stop): *out keeps the value of the stopping iteration
+__global__ void __launch_bounds__(BLOCK) k_maxabs_finish64(int nb, const float* __restrict__ partials, double* __restrict__ out,
+                                                           const int* __restrict__ stopped) {
+	if (stopped && stopped[0]) return;
 	float lo = FLT_MAX, hi = -FLT_MAX;
 	for (int i = threadIdx.x; i < nb; i += blockDim.x) {
 		lo = fminf(lo, partials[2 * i]);
 		hi = fmaxf(hi, partials[2 * i + 1]);
 	}
 	block_minmax(lo, hi);
-	if (threadIdx.x == 0) {
-		lo = fabsf(lo);
-		hi = fabsf(hi);
-		out[0] = (double)(lo > hi ? lo : hi);
-	}
+	if (threadIdx.x == 0) out[0] = (double)maxabs(lo, hi);
+}
+int mf::launch_sum_finish(int nb, const double* partials, double* out, hipStream_t st) {
+	hipLaunchKernelGGL(k_sum_finish, dim3(1), dim3(BLOCK), 0, st, nb, partials, out);
+	MF_LAUNCH_CHECK();
+	return 0;
+}
+int mf::launch_maxabs_finish(int nb, const float* fpart, double* out, const int* stopped, hipStream_t st) {
+	hipLaunchKernelGGL(k_maxabs_finish64, dim3(1), dim3(BLOCK), 0, st, nb, fpart, out, stopped);
+	MF_LAUNCH_CHECK();
+	return 0;
 }
 
 int mf::read_back(void* host, const void* dev, size_t bytes, hipStream_t st) {
@@ -380,8 +370,7 @@ int mf_grid_dot(int64_t n, const float* a, const float* b, double* r, void* s) {
 	MF_TRY(get_workspace(&ws));
 	const int nb = blocks_for(n, BLOCK * 8, 1024);
 	hipLaunchKernelGGL(k_dot_partials<0>, dim3(nb), dim3(BLOCK), 0, (hipStream_t)s, n, a, b, ws->partials);
-	hipLaunchKernelGGL(k_sum_finish, dim3(1), dim3(BLOCK), 0, (hipStream_t)s, nb, ws->partials, (double*)ws->scalars);
-	MF_LAUNCH_CHECK();
+	MF_TRY(launch_sum_finish(nb, ws->partials, (double*)ws->scalars, (hipStream_t)s));
 	return read_back(ws, ws->scalars, sizeof(double), r, (hipStream_t)s);
 }
 int mf_grid_dot_dev(int64_t n, const float* a, const float* b, double* out_dev, void* s) {
@@ -389,8 +378,7 @@ int mf_grid_dot_dev(int64_t n, const float* a, const float* b, double* out_dev, 
 	MF_TRY(get_workspace(&ws));
 	const int nb = blocks_for(n, BLOCK * 8, 1024);
 	hipLaunchKernelGGL(k_dot_partials<0>, dim3(nb), dim3(BLOCK), 0, (hipStream_t)s, n, a, b, ws->partials);
-	hipLaunchKernelGGL(k_sum_finish, dim3(1), dim3(BLOCK), 0, (hipStream_t)s, nb, ws->partials, out_dev);
-	MF_LAUNCH_CHECK();
+	MF_TRY(launch_sum_finish(nb, ws->partials, out_dev, (hipStream_t)s));
 	return 0;
 }
 int mf_grid_max_abs_dev(int64_t n, const float* a, float* out_dev, void* s) {
@@ -407,8 +395,7 @@ int mf_grid_max_abs_dev_f64(int64_t n, const float* a, double* out_dev, void* s)
 	MF_TRY(get_workspace(&ws));
 	const int nb = blocks_for(n, BLOCK * 8, 1024);
 	hipLaunchKernelGGL(k_minmax_partials, dim3(nb), dim3(BLOCK), 0, (hipStream_t)s, n, a, ws->fpartials);
-	hipLaunchKernelGGL(k_maxabs_finish64, dim3(1), dim3(BLOCK), 0, (hipStream_t)s, nb, ws->fpartials, out_dev);
-	MF_LAUNCH_CHECK();
+	MF_TRY(launch_maxabs_finish(nb, ws->fpartials, out_dev, nullptr, (hipStream_t)s));
 	return 0;
 }
 int mf_cg_slab_alpha(const double* gathered, int world, const float* sigma_dev, float* alpha_dev, const int32_t* state_dev, void* s) {
@@ -439,8 +426,7 @@ int mf_grid_sum_sqr(int64_t n, const float* a, double* r, void* s) {
 	MF_TRY(get_workspace(&ws));
 	const int nb = blocks_for(n, BLOCK * 8, 1024);
 	hipLaunchKernelGGL(k_dot_partials<1>, dim3(nb), dim3(BLOCK), 0, (hipStream_t)s, n, a, a, ws->partials);
-	hipLaunchKernelGGL(k_sum_finish, dim3(1), dim3(BLOCK), 0, (hipStream_t)s, nb, ws->partials, (double*)ws->scalars);
-	MF_LAUNCH_CHECK();
+	MF_TRY(launch_sum_finish(nb, ws->partials, (double*)ws->scalars, (hipStream_t)s));
 	return read_back(ws, ws->scalars, sizeof(double), r, (hipStream_t)s);
 }
 int mf_grid_min_max(int64_t n, const float* a, float* mn, float* mx, void* s) {
@@ -459,9 +445,7 @@ int mf_grid_min_max(int64_t n, const float* a, float* mn, float* mx, void* s) {
 int mf_grid_max_abs(int64_t n, const float* a, float* r, void* s) {
 	float lo, hi;
 	MF_TRY(mf_grid_min_max(n, a, &lo, &hi, s));
-	lo = fabsf(lo);
-	hi = fabsf(hi);
-	*r = lo > hi ? lo : hi;  // max(fabs(amin), fabs(amax)), grid.cpp:359
+	*r = maxabs(lo, hi);
 	return 0;
 }
 int mf_grid_max_abs_vec3(int64_t n, const float* a, float* r, void* s) {
@@ -481,8 +465,7 @@ int mf_count_empty_cells(int64_t n, const int32_t* flags, int32_t* r, void* s) {
 	MF_TRY(get_workspace(&ws));
 	const int nb = blocks_for(n, BLOCK * 8, 1024);
 	hipLaunchKernelGGL(k_count_flag_partials, dim3(nb), dim3(BLOCK), 0, (hipStream_t)s, n, flags, (int)MF_EMPTY, ws->partials);
-	hipLaunchKernelGGL(k_sum_finish, dim3(1), dim3(BLOCK), 0, (hipStream_t)s, nb, ws->partials, (double*)ws->scalars);
-	MF_LAUNCH_CHECK();
+	MF_TRY(launch_sum_finish(nb, ws->partials, (double*)ws->scalars, (hipStream_t)s));
 	double d;
 	MF_TRY(read_back(ws, ws->scalars, sizeof(double), &d, (hipStream_t)s));
 	*r = (int32_t)d;
