@@ -30,6 +30,7 @@ constexpr unsigned PMASK = (1u << PBITS) - 1u;
 constexpr int SMALL_RUN = 32;                      // longest run the per-cell insertion sort takes
 constexpr int BIG_LDS = 4096;                      // longest run the workgroup sort takes in LDS
 constexpr int SCAN_ITEMS = 16;                     // per thread and scan block
+constexpr int BIG_BLOCKS = 256;                    // workgroups of the workgroup sort; each loops over the crowded cells
 
 struct Corner {
 	int bx, by, bz;
@@ -781,7 +782,7 @@ int bin_particles(const Dim& d, int64_t np, int64_t ps, const float* pos, const 
 	hipLaunchKernelGGL(k_scan_blocks, dim3(nsb), dim3(BLOCK), 0, st, n1, s->counts, s->sums, s->start);
 	hipLaunchKernelGGL(k_bin_place, dim3(nblk(np)), dim3(BLOCK), 0, st, d.n, np, s->keys, s->start, s->counts, s->order);
 	hipLaunchKernelGGL(k_bin_sort_cells, dim3(nblk(d.n)), dim3(BLOCK), 0, st, d.n, s->start, s->order, s->nbig, s->big);
-	hipLaunchKernelGGL(k_bin_sort_big, dim3(256), dim3(BLOCK), 0, st, s->start, s->order, s->nbig, s->big, s->tmp);
+	hipLaunchKernelGGL(k_bin_sort_big, dim3(BIG_BLOCKS), dim3(BLOCK), 0, st, s->start, s->order, s->nbig, s->big, s->tmp);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
