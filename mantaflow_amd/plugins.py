@@ -30,6 +30,10 @@ PYTHON() declarations; orchestration mirrors the reference function by function,
   extrapolateSimpleFlags                      source/plugin/waveletturbulence.cpp:239-307
   initVortexVelocity                          source/plugin/initplugins.cpp:478-503
                                              (include/open/manta_hip_fields.h; not on z-slab solvers)
+  copyArrayToGrid* / copyGridToArray* / copyArrayToPdata* / copyPdataToArray*   source/plugin/numpyconvert.cpp:145-223
+  simpleNumpyTest / extractFeatureVel / extractFeaturePhi / extractFeatureGeo / getRegions / getRegionalCounts / extendRegion /
+  markSmallRegions                            source/plugin/tfplugins.cpp
+                                             (include/open/manta_hip_mlflip.h; not on z-slab solvers)
 """
 import ctypes
 import functools
@@ -2205,3 +2209,353 @@ def densityFromLevelset(phi, density, value=1.0, sigma=1.0):
     phi._check_same(density)
     lib.call("mf_vortex_density_from_levelset", phi.sx, phi.sy, phi.sz, phi.ptr, density.ptr, float(np.float32(value)), float(np.float32(sigma)),
              s.stream)
+
+
+# =========================================================================================================
+# the array bridge and the MLFLIP data plugins (plugin/numpyconvert.cpp:29-223, plugin/tfplugins.cpp:22-220):
+# include/open/manta_hip_mlflip.h.  An array is a numpy ndarray, a CPU tensor or a tensor on the solver's device; a device tensor
+# is read or written where it is, on the solver's stream, a host array goes through one device staging tensor.  Every plugin is
+# refused first (z-slab solver, backend without the extension), validates second and touches memory third.  DESIGN.md section 22.
+# =========================================================================================================
+_NP_TYPES = {np.dtype(np.int32): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
+_TORCH_TYPES = {torch.int32: 0, torch.float32: 1, torch.float64: 2}
+_TYPE_NAMES = ("int32", "float32", "float64")
+_TORCH_OF = (torch.int32, torch.float32, torch.float64)
+
+
+def _mlflip_lib(name, *objs):
+    """the library for plugin `name`, found through the first argument that has a solver; the refusals come before every other check"""
+    for o in objs:
+        if isinstance(o, core.PbClass):
+            return o.parent, _extension_lib(o.parent, name, "mlflip")
+    raise RuntimeError("%s: can't convert argument to a grid or particle object" % name)
+
+
+def _solver_device(s):
+    d = torch.device(s.device)
+    if d.type == "cuda" and d.index is None:
+        d = torch.device("cuda", torch.cuda.current_device())
+    return d
+
+
+class _Array(object):
+    """one validated array argument: `code` (0 int32, 1 float32, 2 float64), `size` and `dims` as the reference's PyArrayContainer
+    has them.  stage() gives the device tensor the kernel reads or writes, finish() brings a host target home."""
+
+    def __init__(self, who, s, obj, target, host, code):
+        self.who, self.s, self.obj, self.target, self.host, self.code = who, s, obj, target, host, code
+        self.dims = tuple(int(v) for v in obj.shape)
+        self.size = int(obj.size) if isinstance(obj, np.ndarray) else int(obj.numel())
+        self.dev = None
+
+    def stage(self, keep=False):
+        """keep: a target the kernel writes only partly starts from the caller's values"""
+        dev = _solver_device(self.s)
+        if not self.host:
+            self.dev = self.obj if self.target else self.obj.contiguous()
+        elif self.target and not keep:
+            self.dev = torch.empty(self.size, dtype=_TORCH_OF[self.code], device=dev)
+        else:
+            if isinstance(self.obj, np.ndarray):
+                h = np.ascontiguousarray(self.obj)       # as PyArray_CheckFromAny does in the reference
+                h = torch.from_numpy(h if h.flags["WRITEABLE"] else h.copy())
+            else:
+                h = self.obj.contiguous()
+            self.dev = h.reshape(-1).to(dev)
+        return _ptr(self.dev)
+
+    def finish(self):
+        if self.target and self.host:
+            h = torch.from_numpy(self.obj) if isinstance(self.obj, np.ndarray) else self.obj
+            h.view(-1).copy_(self.dev.view(-1))      # a blocking download on the solver's stream
+
+
+def _array_arg(who, s, obj, target, need=None):
+    """Validate the array argument of plugin `who` on solver `s` and return its _Array; nothing is copied or staged here.
+    target: the plugin writes it (it must then be C-contiguous and writable); need: the one element type the plugin takes, where the
+    reference reinterprets the memory blindly."""
+    if isinstance(obj, np.ndarray):
+        code, host = _NP_TYPES.get(obj.dtype), True
+        contiguous, found = obj.flags["C_CONTIGUOUS"], str(obj.dtype)
+        if target and not obj.flags["WRITEABLE"]:
+            raise RuntimeError("%s: target array is read-only" % who)
+    elif isinstance(obj, torch.Tensor):
+        code, host = _TORCH_TYPES.get(obj.dtype), obj.device.type == "cpu"
+        contiguous, found = obj.is_contiguous(), str(obj.dtype).replace("torch.", "")
+        if not host and obj.device != _solver_device(s):
+            raise RuntimeError("%s: the tensor lives on %s, the solver on %s" % (who, obj.device, _solver_device(s)))
+    else:
+        raise RuntimeError("%s: can't convert argument to a numpy array or a torch tensor" % who)
+    if need is not None and code != need:
+        raise RuntimeError("%s: array of type %s where %s is needed" % (who, found, _TYPE_NAMES[need]))
+    if code is None:
+        raise RuntimeError("%s: unknown type of Numpy array" % who)      # numpyWrap.cpp:74-88
+    if target and not contiguous:
+        raise RuntimeError("%s: target array must be C-contiguous" % who)
+    return _Array(who, s, obj, target, host, code)
+
+
+def _check_grid_array(who, a, g, to_grid):
+    """the two assertions of copyArrayToGrid* / copyGridToArray* (numpyconvert.cpp:38-39, 64-65, 94-95, 121-122), with the array's
+    element type checked first: the reference would zero the target grid and then fail"""
+    vec = g._ncomp == 3
+    if vec and a.code == 0:
+        raise RuntimeError("%s: unknown/unsupported type of Vec3 Numpy array" % who)
+    if a.size != g._ncomp * g.n:
+        if vec:
+            raise RuntimeError("%s: The size of the numpy array doesn't match the size of the grid!" % who)
+        if to_grid:
+            raise RuntimeError("%s: The size of the numpy array doesn't match the size of the Grid!" % who)
+        raise RuntimeError("%s: The size of the numpy array %d doesn't match the size of the grid!" % (who, a.size))
+    if a.dims[:3] != (g.sz, g.sy, g.sx):
+        d = a.dims + (0, 0, 0)
+        arr, grd = "(%d, %d, %d)" % (d[2], d[1], d[0]), "(%d, %d, %d)" % (g.sx, g.sy, g.sz)
+        if to_grid:
+            raise RuntimeError("%s: The dimensions of source numpy array %s and target grid %s do not match!" % (who, arr, grd))
+        raise RuntimeError("%s: The dimensions of source grid %s and target numpy array %s do not match!" % (who, grd, arr))
+
+
+def _array_to_grid(who, source, target, cls, cname):
+    s, lib = _mlflip_lib(who, target)
+    _chk(target, cls, cname)
+    a = _array_arg(who, s, source, False)
+    _check_grid_array(who, a, target, True)
+    if target._ncomp == 3:
+        lib.call("mf_mlflip_elements_to_planes", target.n, target.n, a.stage(), a.code, target.ptr, s.stream)
+    else:
+        lib.call("mf_mlflip_convert", target.n, a.stage(), a.code, target.ptr, 0 if target._kind == "int" else 1, s.stream)
+
+
+def _grid_to_array(who, source, target, cls, cname):
+    s, lib = _mlflip_lib(who, source)
+    _chk(source, cls, cname)
+    a = _array_arg(who, s, target, True)
+    _check_grid_array(who, a, source, False)
+    if source._ncomp == 3:
+        lib.call("mf_mlflip_planes_to_elements", source.n, source.n, source.ptr, a.stage(), a.code, s.stream)
+    else:
+        lib.call("mf_mlflip_convert", source.n, source.ptr, 0 if source._kind == "int" else 1, a.stage(), a.code, s.stream)
+    a.finish()
+
+
+@plugin
+def copyArrayToGridReal(source, target):
+    """numpyconvert.cpp:145-147: int32 / float32 / float64 [z][y][x] (or [z][y][x][1]) into a real grid, converted as C does"""
+    _array_to_grid("copyArrayToGridReal", source, target, Grid, "Grid<Real>")
+
+
+@plugin
+def copyGridToArrayReal(source, target):
+    _grid_to_array("copyGridToArrayReal", source, target, Grid, "Grid<Real>")
+
+
+@plugin
+def copyArrayToGridFlag(source, target):
+    """a float array truncates towards zero"""
+    _array_to_grid("copyArrayToGridFlag", source, target, FlagGrid, "FlagGrid")
+
+
+@plugin
+def copyGridToArrayFlag(source, target):
+    _grid_to_array("copyGridToArrayFlag", source, target, FlagGrid, "FlagGrid")
+
+
+@plugin
+def copyArrayToGridLevelset(source, target):
+    _array_to_grid("copyArrayToGridLevelset", source, target, LevelsetGrid, "LevelsetGrid")
+
+
+@plugin
+def copyGridToArrayLevelset(source, target):
+    _grid_to_array("copyGridToArrayLevelset", source, target, LevelsetGrid, "LevelsetGrid")
+
+
+@plugin
+def copyArrayToGridVec3(source, target):
+    """float32 / float64 [z][y][x][3] into the three component planes: one transposing kernel"""
+    _array_to_grid("copyArrayToGridVec3", source, target, VecGrid, "Grid<Vec3>")
+
+
+@plugin
+def copyGridToArrayVec3(source, target):
+    _grid_to_array("copyGridToArrayVec3", source, target, VecGrid, "Grid<Vec3>")
+
+
+@plugin
+def copyArrayToGridMAC(source, target):
+    _array_to_grid("copyArrayToGridMAC", source, target, MACGrid, "MACGrid")
+
+
+@plugin
+def copyGridToArrayMAC(source, target):
+    _grid_to_array("copyGridToArrayMAC", source, target, MACGrid, "MACGrid")
+
+
+def _pdata_copy(who, arr, pd, cls, cname, to_pdata):
+    """numpyconvert.cpp:189-223: the words of the live slots, no conversion -- so the element type is required (the reference
+    reinterprets whatever it is given)"""
+    s, lib = _mlflip_lib(who, pd)
+    _chk(pd, cls, cname)
+    a = _array_arg(who, s, arr, not to_pdata, 0 if pd._dtype == torch.int32 else 1)
+    n = pd.size()
+    if a.size != n * pd._ncomp:
+        raise RuntimeError("%s: The size of the numpy array doesn't match the size of the pdata field!" % who)
+    if n == 0:
+        return
+    if pd._ncomp == 3:
+        if to_pdata:
+            lib.call("mf_mlflip_elements_to_planes", n, pd.cap, a.stage(), 1, pd.ptr, s.stream)
+        else:
+            lib.call("mf_mlflip_planes_to_elements", n, pd.cap, pd.ptr, a.stage(), 1, s.stream)
+    elif to_pdata:
+        lib.call("mf_mlflip_convert", n, a.stage(), a.code, pd.ptr, a.code, s.stream)
+    else:
+        lib.call("mf_mlflip_convert", n, pd.ptr, a.code, a.stage(), a.code, s.stream)
+    a.finish()
+
+
+@plugin
+def copyArrayToPdataInt(source, target):
+    _pdata_copy("copyArrayToPdataInt", source, target, core.PdataInt, "ParticleDataImpl<int>", True)
+
+
+@plugin
+def copyPdataToArrayInt(source, target):
+    _pdata_copy("copyPdataToArrayInt", target, source, core.PdataInt, "ParticleDataImpl<int>", False)
+
+
+@plugin
+def copyArrayToPdataReal(source, target):
+    _pdata_copy("copyArrayToPdataReal", source, target, core.PdataReal, "ParticleDataImpl<Real>", True)
+
+
+@plugin
+def copyPdataToArrayReal(source, target):
+    _pdata_copy("copyPdataToArrayReal", target, source, core.PdataReal, "ParticleDataImpl<Real>", False)
+
+
+@plugin
+def copyArrayToPdataVec3(source, target):
+    _pdata_copy("copyArrayToPdataVec3", source, target, core.PdataVec3, "ParticleDataImpl<Vec3>", True)
+
+
+@plugin
+def copyPdataToArrayVec3(source, target):
+    _pdata_copy("copyPdataToArrayVec3", target, source, core.PdataVec3, "ParticleDataImpl<Vec3>", False)
+
+
+def _feature_layout(who, np_, is3d, kind, N_row, off_begin, window, fv_size):
+    """the checks of a feature call -> (stencil points, values per point)"""
+    if window < 0:
+        raise RuntimeError("%s: window %d" % (who, window))
+    w = 2 * window + 1
+    nst, D = w * w * (w if is3d else 1), ((3 if is3d else 2) if kind == 0 else 1)
+    if off_begin < 0 or off_begin + nst * D > N_row:
+        raise RuntimeError("%s: %d stencil points of %d values from column %d do not fit a row of %d" % (who, nst, D, off_begin, N_row))
+    if fv_size < np_ * N_row:
+        raise RuntimeError("%s: the feature array holds %d values, %d rows of %d need %d" % (who, fv_size, np_, N_row, np_ * N_row))
+    return nst, D
+
+
+def _extract_feature(who, kind, fv, N_row, off_begin, p, grid, cls, cname, scale, ptype, exclude, window):
+    s, lib = _mlflip_lib(who, p, grid)
+    if not isinstance(p, core.BasicParticleSystem):
+        raise RuntimeError("can't convert argument to BasicParticleSystem*")
+    _chk(grid, cls, cname)
+    ptype = _opt(ptype, core.PdataInt, "ParticleDataImpl<int>")
+    N_row, off_begin = int(N_row), int(off_begin)
+    a = _array_arg(who, s, fv, True, 1)
+    _feature_layout(who, p.np, grid.is3D(), kind, N_row, off_begin, window, a.size)
+    if ptype is not None and ptype.size() != p.np:
+        raise RuntimeError("%s: ptype has %d entries, the system %d particles" % (who, ptype.size(), p.np))
+    if p.np == 0:
+        return
+    (np_, cap, pos, pfl), pt = _pargs(p, ptype)
+    if ptype is not None and ptype.cap != cap:
+        raise RuntimeError("%s: ptype is not a channel of the particle system" % who)
+    lib.call("mf_mlflip_extract_feature", kind, grid.sx, grid.sy, grid.sz, grid.ptr, np_, cap, pos, pfl, pt, int(exclude), int(window),
+             float(np.float32(scale)), a.stage(keep=True), a.size, N_row, off_begin, s.stream)
+    a.finish()
+
+
+@plugin
+def extractFeatureVel(fv, N_row, off_begin, p, vel, scale=1.0, ptype=None, exclude=0, window=1):
+    """tfplugins.cpp:38-66, 122-130: interpolMAC(pos + (i, j, k)) * scale for the (2 window + 1)^dim stencil points, i outer, k inner,
+    into fv[idx * N_row + off_begin + stencil * D + c]; rows of deleted or excluded slots and the rest of a row are not written"""
+    _extract_feature("extractFeatureVel", 0, fv, N_row, off_begin, p, vel, MACGrid, "MACGrid", scale, ptype, exclude, window)
+
+
+@plugin
+def extractFeaturePhi(fv, N_row, off_begin, p, phi, scale=1.0, ptype=None, exclude=0, window=1):
+    """tfplugins.cpp:68-93, 131-139: interpol(pos + (i, j, k)) * scale, one value per stencil point"""
+    _extract_feature("extractFeaturePhi", 1, fv, N_row, off_begin, p, phi, Grid, "Grid<Real>", scale, ptype, exclude, window)
+
+
+@plugin
+def extractFeatureGeo(fv, N_row, off_begin, p, flag, scale=1.0, ptype=None, exclude=0, window=1):
+    """tfplugins.cpp:95-120, 140-148: float(flags at the cell pos + (i, j, k) truncates to) * scale.  Precondition: that cell is inside
+    the grid (the reference indexes unchecked; the kernel clamps the cell index)"""
+    _extract_feature("extractFeatureGeo", 2, fv, N_row, off_begin, p, flag, FlagGrid, "FlagGrid", scale, ptype, exclude, window)
+
+
+def _regions(who, r, flags, ctype, counts):
+    s, lib = _mlflip_lib(who, r, flags)
+    _chk(r, core.IntGrid, "Grid<int>"); _chk(flags, FlagGrid, "FlagGrid")
+    flags._check_same(r)
+    if r is flags:
+        raise RuntimeError("%s: r and flags are the same grid" % who)
+    n = ctypes.c_int32(0)
+    lib.call("mf_mlflip_regions", flags.sx, flags.sy, flags.sz, flags.ptr, _c_int32(ctype), counts, r.ptr, ctypes.byref(n), s.stream)
+    return int(n.value)
+
+
+def _c_int32(v):
+    """an int parameter as the C int it is in the reference (flag masks may have the sign bit)"""
+    return ctypes.c_int32(int(v) & 0xffffffff).value
+
+
+@plugin
+def getRegions(r, flags, ctype):
+    """tfplugins.cpp:155-176: r = the number (from 1, in the order of their lowest flat index) of the face-connected component of
+    flags & ctype cells a cell belongs to, 0 outside; returns the number of components.  Precondition: no ctype cell in the outermost
+    layer of the grid (there the reference's flood fill reads across row ends); a neighbour outside the grid is not connected here"""
+    return _regions("getRegions", r, flags, ctype, 0)
+
+
+@plugin
+def getRegionalCounts(r, flags, ctype):
+    """tfplugins.cpp:178-188: r = the number of cells of the cell's component, 0 outside"""
+    _regions("getRegionalCounts", r, flags, ctype, 1)
+
+
+@plugin
+def extendRegion(flags, region, exclude, depth):
+    """tfplugins.cpp:190-207: `depth` rounds; a cell without flags & exclude beside a cell with flags & region becomes `region`"""
+    s, lib = _mlflip_lib("extendRegion", flags)
+    _chk(flags, FlagGrid, "FlagGrid")
+    depth = _coerce(depth, 0)
+    if depth <= 0:
+        return
+    tmp = _scratch_grid(s, core.IntGrid)
+    lib.call("mf_mlflip_extend_region", flags.sx, flags.sy, flags.sz, flags.ptr, tmp.ptr, _c_int32(region), _c_int32(exclude), depth, s.stream)
+
+
+@plugin
+def markSmallRegions(flags, rcnt, mark, exclude, th=1):
+    """tfplugins.cpp:209-220: flags = mark where !(flags & exclude) and rcnt <= th"""
+    s, lib = _mlflip_lib("markSmallRegions", flags, rcnt)
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(rcnt, core.IntGrid, "Grid<int>")
+    flags._check_same(rcnt)
+    lib.call("mf_mlflip_mark_small_regions", flags.sx, flags.sy, flags.sz, flags.ptr, rcnt.ptr, _c_int32(mark), _c_int32(exclude), int(th), s.stream)
+
+
+@plugin
+def simpleNumpyTest(grid, npAr, scale):
+    """tfplugins.cpp:22-33: grid(i, j, k) += scale * npAr[j * sx + i]; the array is float32 and holds at least sx * sy values (the
+    reference checks neither)"""
+    s, lib = _mlflip_lib("simpleNumpyTest", grid)
+    _chk(grid, Grid, "Grid<Real>")
+    a = _array_arg("simpleNumpyTest", s, npAr, False, 1)
+    if a.size < grid.sx * grid.sy:
+        raise RuntimeError("simpleNumpyTest: the array holds %d values, a plane of the grid has %d" % (a.size, grid.sx * grid.sy))
+    lib.call("mf_mlflip_simple_array_add", grid.sx, grid.sy, grid.sz, grid.ptr, a.stage(), a.size, float(np.float32(scale)), s.stream)
