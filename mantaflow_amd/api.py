@@ -32,7 +32,8 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       copyGridToArrayLevelset, copyArrayToGridVec3, copyGridToArrayVec3, copyArrayToGridMAC, copyGridToArrayMAC,
                       copyArrayToPdataInt, copyPdataToArrayInt, copyArrayToPdataReal, copyPdataToArrayReal, copyArrayToPdataVec3,
                       copyPdataToArrayVec3, extractFeatureVel, extractFeaturePhi, extractFeatureGeo, getRegions, getRegionalCounts,
-                      extendRegion, markSmallRegions, simpleNumpyTest)
+                      extendRegion, markSmallRegions, simpleNumpyTest,
+                      blurMacGrid, blurRealGrid, calcCenterOfMass, projectImage, projectPpmFull, getLaplacian, getCurvature)
 
 from .scene import (Box, Checkbox, Cylinder, Gui, NoiseField, Shape, Slider, Sphere, densityInflow, sampleFlagsWithParticles,
                     sampleLevelsetWithParticles, sampleShapeWithParticles)

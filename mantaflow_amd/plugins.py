@@ -34,6 +34,9 @@ PYTHON() declarations; orchestration mirrors the reference function by function,
   simpleNumpyTest / extractFeatureVel / extractFeaturePhi / extractFeatureGeo / getRegions / getRegionalCounts / extendRegion /
   markSmallRegions                            source/plugin/tfplugins.cpp
                                              (include/open/manta_hip_mlflip.h; not on z-slab solvers)
+  blurMacGrid / blurRealGrid / calcCenterOfMass / projectPpmFull (+ projectImage)   source/plugin/initplugins.cpp:273-282, 337-348, 510-655
+  getLaplacian / getCurvature                 source/plugin/flip.cpp:779-785
+                                             (include/open/manta_hip_datagen.h; not on z-slab solvers)
 """
 import ctypes
 import functools
@@ -2559,3 +2562,124 @@ def simpleNumpyTest(grid, npAr, scale):
     if a.size < grid.sx * grid.sy:
         raise RuntimeError("simpleNumpyTest: the array holds %d values, a plane of the grid has %d" % (a.size, grid.sx * grid.sy))
     lib.call("mf_mlflip_simple_array_add", grid.sx, grid.sy, grid.sz, grid.ptr, a.stage(), a.size, float(np.float32(scale)), s.stream)
+
+
+# =========================================================================================================
+# the smoke data-generation plugins: the Gaussian grid blurs, calcCenterOfMass and projectPpmFull of source/plugin/initplugins.cpp
+# (:273-282, :337-348, :510-655; util/simpleimage.cpp) and getLaplacian / getCurvature of source/plugin/flip.cpp:779-785:
+# include/open/manta_hip_datagen.h, whole-domain solvers only.  Every plugin is refused first (z-slab solver, backend without the
+# extension), validates second and touches memory third.  DESIGN.md section 23.
+# =========================================================================================================
+def _datagen_lib(name, *objs):
+    """the solver and its library for plugin `name`, found through the first argument that is a grid"""
+    for o in objs:
+        if isinstance(o, core.PbClass):
+            return o.parent, _extension_lib(o.parent, name, "datagen")
+    raise RuntimeError("%s: can't convert argument to a grid" % name)
+
+
+def _blur(name, cls, cname, kind, ncomp, oG, tG, si):
+    s, lib = _datagen_lib(name, oG, tG)
+    _chk(oG, cls, cname); _chk(tG, cls, cname)
+    oG._check_same(tG)
+    sigma = np.float32(si)
+    if not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError("%s: sigma must be positive" % name)
+    # oG -> A -> tG, on a 3-D grid oG -> A -> B -> tG: oG is only read, so `oG is tG` needs no copy
+    tmp = [s._alloc(kind, zero=False) for _ in range(2 if oG.sz > 1 else 1)]
+    try:
+        mdim = ctypes.c_int(0)
+        lib.call("mf_datagen_blur", oG.sx, oG.sy, oG.sz, ncomp, oG.ptr, tG.ptr, _ptr(tmp[0]), _ptr(tmp[1]) if len(tmp) > 1 else None,
+                 float(sigma), ctypes.byref(mdim), s.stream)
+    finally:
+        for t in reversed(tmp):
+            s._release(kind, t)
+    return int(mdim.value)
+
+
+@plugin
+def blurMacGrid(oG, tG, si):
+    """initplugins.cpp:616-651: the separable Gaussian blur of sigma si (weights not normalised, taps clamped into the grid) of every
+    component at the cell's own index; returns the kernel's length.  Stricter than the reference: si <= 0 or not finite is a
+    ValueError (the reference fills the grid with NaN)."""
+    return _blur("blurMacGrid", MACGrid, "MACGrid", "vec", 3, oG, tG, si)
+
+
+@plugin
+def blurRealGrid(oG, tG, si):
+    """initplugins.cpp:602-613, 653-655: the same blur of a Grid<Real>"""
+    return _blur("blurRealGrid", Grid, "Grid<Real>", "real", 1, oG, tG, si)
+
+
+@plugin
+def calcCenterOfMass(density):
+    """initplugins.cpp:337-348: sum(density * cell centre) / sum(density), undivided where the fp32 sum of density is <= 1e-6.  The
+    terms are the reference's fp32 products; the sums are fp64 in a fixed order (the reference's serial fp32 sum has no parallel
+    form) and each quotient is rounded once.  One read-back of three floats."""
+    s, lib = _datagen_lib("calcCenterOfMass", density)
+    _chk(density, Grid, "Grid<Real>")
+    out = (ctypes.c_float * 3)()
+    lib.call("mf_datagen_center_of_mass", density.sx, density.sy, density.sz, density.ptr, out, s.stream)
+    return vec3(float(out[0]), float(out[1]), float(out[2]))
+
+
+def _project(name, val, shadeMode, scale, views=7):
+    s, lib = _datagen_lib(name, val)
+    _chk(val, Grid, "Grid<Real>")
+    w = val.sx + val.sz + val.sx if val.sz > 1 else val.sx
+    h = max(val.sx, val.sy, val.sz)
+    img = torch.empty(h * w * 3, dtype=torch.uint8, device=s.device)
+    light = s._alloc("real", zero=False) if shadeMode == 1 else None       # the reference's grid L, which only surface mode reads
+    try:
+        lib.call("mf_datagen_project", val.sx, val.sy, val.sz, val.ptr, _ptr(light), int(shadeMode), float(np.float32(scale)), int(views), _ptr(img),
+                 s.stream)
+    finally:
+        if light is not None:
+            s._release("real", light)
+    return img.cpu().numpy().reshape(h, w, 3)
+
+
+@plugin
+def projectImage(val, shadeMode=0, scale=1.):
+    """what projectPpmFull writes, as the (h, w, 3) uint8 array in file row order (top row first): the view along z and, on a 3-D
+    grid, the views along x and y beside it; shadeMode 1 composites lit surfaces, every other value accumulates smoke.  One thread
+    per pixel marches in the reference's order, so the bytes are the reference's.  One read-back of the image."""
+    return _project("projectImage", val, shadeMode, scale)
+
+
+@plugin
+def projectPpmFull(val, name, shadeMode=0, scale=1.):
+    """initplugins.cpp:273-282: projectImage written as a binary .ppm"""
+    img = _project("projectPpmFull", val, shadeMode, scale)
+    try:
+        f = open(name, "wb")
+    except OSError as e:
+        raise RuntimeError("projectPpmFull: unable to open '%s' for writing (%s)" % (name, e.strerror))
+    with f:
+        f.write(b"P6\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
+        f.write(img.tobytes())
+
+
+def _stencil(name, out, grid):
+    s, lib = _datagen_lib(name, out, grid)
+    _chk(out, Grid, "Grid<Real>"); _chk(grid, Grid, "Grid<Real>")
+    out._check_same(grid)
+    if out is grid or out.data.data_ptr() == grid.data.data_ptr():
+        raise ValueError("%s: the output grid must not be the input grid" % name)
+    return s, lib
+
+
+@plugin
+def getLaplacian(laplacian, grid):
+    """flip.cpp:779-781, LaplaceOp on the interior; the border of `laplacian` keeps its values.  Stricter than the reference: the
+    output may not be the input (the reference's result would depend on its thread schedule)."""
+    s, lib = _stencil("getLaplacian", laplacian, grid)
+    lib.call("mf_datagen_laplacian", grid.sx, grid.sy, grid.sz, grid.ptr, laplacian.ptr, s.stream)
+
+
+@plugin
+def getCurvature(curv, grid, h=1.0):
+    """flip.cpp:783-785, CurvatureOp on the interior: the mean curvature of the level set `grid` with cell size h; the border of
+    `curv` keeps its values.  The output may not be the input."""
+    s, lib = _stencil("getCurvature", curv, grid)
+    lib.call("mf_datagen_curvature", grid.sx, grid.sy, grid.sz, grid.ptr, curv.ptr, float(np.float32(h)), s.stream)
