@@ -3,7 +3,7 @@
 import sys
 
 from .core import (BasicParticleSystem, FlagGrid, FluidSolver, Grid, Grid4d, Grid4dBase, Grid4Int, Grid4Real, Grid4Vec3, Grid4Vec4, IntGrid, LevelsetGrid, MACGrid, Mesh, ParticleIndexSystem,
-                   PdataInt, PdataReal, PdataVec3, RealGrid, Solver, TurbulenceParticleSystem, Vec3Grid, VecGrid, VortexParticleSystem, resetTurbulenceParticleState,
+                   PdataInt, PdataReal, PdataVec3, RealGrid, Solver, TurbulenceParticleSystem, Vec3Grid, VecGrid, VortexParticleSystem, resetMovingObstacleState, resetTurbulenceParticleState,
                    resetVortexSeedStream, vec3, vec4)
 from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, resetOutflow, apicMapPartsToMAC, apicMapMACGridToParts, extrapolateMACFromWeight, extrapolateMACSimple, markFluidCells, addBuoyancy, addGravity, addGravityNoScale, advectSemiLagrange, computePressureRhs,
                       correctVelocity, flipVelocityUpdate, lastCgStats, mapGridToParts, mapGridToPartsVec3, mapMACToParts,
@@ -33,9 +33,10 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       copyArrayToPdataInt, copyPdataToArrayInt, copyArrayToPdataReal, copyPdataToArrayReal, copyArrayToPdataVec3,
                       copyPdataToArrayVec3, extractFeatureVel, extractFeaturePhi, extractFeatureGeo, getRegions, getRegionalCounts,
                       extendRegion, markSmallRegions, simpleNumpyTest,
-                      blurMacGrid, blurRealGrid, calcCenterOfMass, projectImage, projectPpmFull, getLaplacian, getCurvature)
+                      blurMacGrid, blurRealGrid, calcCenterOfMass, projectImage, projectPpmFull, getLaplacian, getCurvature,
+                      set_wall_bcs2, resetPhiInObs)
 
-from .scene import (Box, Checkbox, Cylinder, Gui, NoiseField, Shape, Slider, Sphere, densityInflow, sampleFlagsWithParticles,
+from .scene import (Box, Checkbox, Cylinder, Gui, MovingObstacle, NoiseField, Shape, Slider, Sphere, densityInflow, sampleFlagsWithParticles,
                     sampleLevelsetWithParticles, sampleShapeWithParticles)
 
 # module constants, registry.cpp:390-421

@@ -537,6 +537,12 @@ class Grid(GridBase):
     def safeDivide(self, a): self._check_same(a); self._call("mf_grid_safe_divide", self.n, self.ptr, a.ptr, self.parent.stream)
     def stomp(self, th): self._call("mf_grid_stomp", self.n, self.ptr, float(th), self.parent.stream)
 
+    def clamp_norm(self, val):
+        """Grid<Real>::clamp_norm -> knGridClampNorm, grid.cpp:306-317: where sqrt(v * v) > val, v *= val / sqrt(v * v) in fp32
+        (include/open/manta_hip_movingobs.h)"""
+        lib = _extension_lib(self.parent, "Grid::clamp_norm", "movingobs")
+        lib.call("mf_movingobs_clamp_norm", self.n, 1, self.ptr, float(np.float32(val)), self.parent.stream)
+
     def setBound(self, value, boundaryWidth=1):
         """Grid::setBound -> knSetBoundary, grid.cpp:629-637"""
         self._call("mf_grid_set_bound", self.sx, self.sy, self.sz, self.ptr, float(value), int(boundaryWidth), self.parent.stream)
@@ -618,6 +624,12 @@ class VecGrid(GridBase):
 
     getMax = getMaxAbs
 
+    def clamp_norm(self, val):
+        """Grid<Vec3>::clamp_norm -> knGridClampNorm, grid.cpp:306-317: where the fp32 norm n exceeds val, every component is
+        multiplied by the one quotient val / n (include/open/manta_hip_movingobs.h)"""
+        lib = _extension_lib(self.parent, "%s::clamp_norm" % type(self)._cname_py, "movingobs")
+        lib.call("mf_movingobs_clamp_norm", self.n, 3, self.ptr, float(np.float32(val)), self.parent.stream)
+
     def getMin(self):
         """sqrt(CompMinVec), grid.cpp:364-366: smallest normSquare (x*x + y*y + z*z in fp32)"""
         self.parent.sync()
@@ -637,6 +649,21 @@ Vec3Grid = VecGrid
 class MACGrid(VecGrid):
     _gtype = GridBase.TypeMAC | GridBase.TypeVec3
     _cname_py, _cname_cpp, _T = "MACGrid", "MACGrid", ""
+
+    def _set_bound_mac(self, name, value, boundaryWidth, rule):
+        lib = _extension_lib(self.parent, name, "movingobs")
+        v = _to_vec3(value)
+        lib.call("mf_movingobs_set_bound_mac", self.sx, self.sy, self.sz, self.ptr, float(np.float32(v.x)), float(np.float32(v.y)),
+                 float(np.float32(v.z)), int(boundaryWidth), rule, self.parent.stream)
+
+    def setBoundMAC(self, value, boundaryWidth, normalOnly=False):
+        """MACGrid::setBoundMAC, grid.cpp:672-692: knSetBoundaryMAC, or with normalOnly knSetBoundaryMACNorm; every component has its
+        own band (include/open/manta_hip_movingobs.h)"""
+        self._set_bound_mac("MACGrid::setBoundMAC", value, boundaryWidth, 1 if normalOnly else 0)
+
+    def set_bound_MAC2(self, value, boundaryWidth):
+        """MACGrid::set_bound_MAC2 -> kn_set_bound_MAC2, grid.cpp:695-715: the walls of the boundary cells"""
+        self._set_bound_mac("MACGrid::set_bound_MAC2", value, boundaryWidth, 2)
 
 
 class LevelsetGrid(Grid):
@@ -835,6 +862,17 @@ class FlagGrid(IntGrid):
         upd = ((d & (TypeObstacle | TypeOutflow)) == 0) & (phi > LevelsetGrid.invalidTimeValue())
         newv = (d & ~(TypeEmpty | TypeFluid)) | torch.where(phi <= 0, TypeFluid, TypeEmpty).to(torch.int32)
         d.copy_(torch.where(upd, newv, d))
+
+    def mark_surface(self):
+        """FlagGrid::mark_surface, grid.cpp:930-972: TypeSurface is cleared everywhere, then set in the fluid cells that touch
+        (26 neighbours, 8 in 2-D) the outside of the grid or a non-fluid cell off the outermost layer.  Prints nothing."""
+        lib = _extension_lib(self.parent, "FlagGrid::mark_surface", "movingobs")
+        lib.call("mf_movingobs_mark_surface", self.sx, self.sy, self.sz, self.ptr, self.parent.stream)
+
+    def clear_obstacle(self, include_boundary=False):
+        """FlagGrid::clear_obstacle, grid.cpp:974-984: obstacle cells become TypeEmpty; the outermost layer only with include_boundary"""
+        lib = _extension_lib(self.parent, "FlagGrid::clear_obstacle", "movingobs")
+        lib.call("mf_movingobs_clear_obstacle", self.sx, self.sy, self.sz, self.ptr, int(bool(include_boundary)), self.parent.stream)
 
     def countCells(self, flag, bnd=0, mask=None):
         v = self._view()
@@ -2176,6 +2214,28 @@ class BasicParticleSystem(PbClass):
         self.set_positions(np.concatenate([old, np.array([[p.x, p.y, p.z]], np.float32)]), np.concatenate([fl, [0]]))
         self.mDeleteChunk = self.np // 20     # ParticleSystem::add, particle.h:414-420
 
+    def projectOutside(self, gradient):
+        """ParticleSystem::projectOutside -> KnProjectParticles, particle.h:551-578: every active particle inside the grid moves along
+        the level-set gradient by -|grad| + 0.1 (1 + r), then every active particle is clamped to [1 + jitter, size - 1 - jitter].
+        The reference's serial loop draws from one process-wide stream; here a kernel counts each particle's draws, a scan gives its
+        place in the stream, the host draws exactly the total (the one read-back) and a second kernel applies them."""
+        s = self.parent
+        lib = _extension_lib(s, "BasicParticleSystem::projectOutside", "movingobs")
+        if not isinstance(gradient, VecGrid):
+            raise RuntimeError("can't convert argument to Grid<Vec3>")
+        if self.np == 0:
+            return
+        need = ctypes.c_int64(0)
+        lib.call("mf_movingobs_project_scratch", self.np, ctypes.byref(need))
+        offsets = torch.empty(self.np + 1, dtype=torch.int32, device=s.device)
+        tmp = torch.empty(int(need.value), dtype=torch.uint8, device=s.device)
+        total = ctypes.c_int64(0)
+        lib.call("mf_movingobs_project_count", gradient.sx, gradient.sy, gradient.sz, self.np, self.cap, _ptr(self.pos), _ptr(self.flag),
+                 _ptr(offsets), _ptr(tmp), int(need.value), ctypes.byref(total), s.stream)
+        reals = torch.from_numpy(_movingobs().rs.reals(int(total.value)) if total.value else np.zeros(1, np.float32)).to(s.device)
+        lib.call("mf_movingobs_project_apply", gradient.sx, gradient.sy, gradient.sz, self.np, self.cap, _ptr(self.pos), _ptr(self.flag),
+                 gradient.ptr, _ptr(offsets), _ptr(reals), s.stream)
+
     def advectInGrid(self, flags, vel, integrationMode, deleteInObstacle=True, stopInObstacle=True, skipNew=False,
                      ptype=None, exclude=0):
         """ParticleSystem::advectInGrid, particle.h:526-550"""
@@ -2189,6 +2249,38 @@ class BasicParticleSystem(PbClass):
                    _ptr(self.pos), _ptr(self.flag), s.getDt(), int(integrationMode), int(bool(deleteInObstacle)),
                    int(bool(stopInObstacle)), int(bool(skipNew)), None if ptype is None else ptype.ptr, int(exclude),
                    _ptr(scratch), s.stream)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# moving obstacles, movingobs.{h,cpp} (include/open/manta_hip_movingobs.h): the process-wide state
+# ---------------------------------------------------------------------------------------------------------
+class _MovingObstacleState(object):
+    """what the reference keeps per process: MovingObstacle::sIDcnt (movingobs.cpp:24) and KnProjectParticles' `static RandomStream
+    rand(3123984)` (particle.h:555) of the BasicParticleSystem instance, which is never reseeded"""
+
+    SEED = 3123984
+
+    def __init__(self):
+        from .scene import RandomStream
+        self.id_count = 10
+        self.rs = RandomStream(self.SEED)
+
+
+_movingobs_state = None
+
+
+def _movingobs():
+    global _movingobs_state
+    if _movingobs_state is None:
+        _movingobs_state = _MovingObstacleState()
+    return _movingobs_state
+
+
+def resetMovingObstacleState():
+    """put MovingObstacle's ID counter back to 10 and projectOutside's random stream back to its seed, as a fresh process of the
+    reference has them (no reference counterpart)"""
+    global _movingobs_state
+    _movingobs_state = _MovingObstacleState()
 
 
 # ---------------------------------------------------------------------------------------------------------

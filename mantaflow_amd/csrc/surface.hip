@@ -4,6 +4,7 @@
 // Reference: source/plugin/flip.cpp, plugin/ptsplugins.cpp, fastmarch.cpp, particle.h, grid.cpp, levelset.cpp.
 #include "common.h"
 #include "scan.h"
+#include "shape_inside.h"
 
 using namespace mf;
 
@@ -224,27 +225,7 @@ static HD float shape_sdf_cylinder(const float* q, float x, float y, float z) {
 #undef FMIN
 #undef SQRT
 #undef FABS
-#define HD __device__ __forceinline__
-#define FABS(a) fabsf(a)
-
-/* Box::isInside :151-154 (z is tested in 2-D as well), Sphere::isInside :240-242, Cylinder::isInside :324-329 (r^2 < R^2, no root) */
-static HD int shape_inside(int kind, const float* q, float x, float y, float z) {
-	if (kind == 0) return x >= q[0] && y >= q[1] && z >= q[2] && x <= q[3] && y <= q[4] && z <= q[5];
-	if (kind == 1) {
-		const float a = (x - q[0]) / q[4], b = (y - q[1]) / q[5], c = (z - q[2]) / q[6];
-		return (a * a + b * b + c * c) <= q[3] * q[3];
-	}
-	const float px = x - q[0], py = y - q[1], pz = z - q[2];
-	const float zz = px * q[4] + py * q[5] + pz * q[6];
-	if (FABS(zz) > q[7]) return 0;
-	const float r2 = (px * px + py * py + pz * pz) - zz * zz;
-	return r2 < q[3] * q[3];
-}
-#undef HD
-#undef FABS
-struct ShapeParams {
-	float q[12];
-};
+// Shape::isInside and the parameter record: shape_inside.h
 __global__ void __launch_bounds__(BLOCK) k_shape_levelset(Dim d, int kind, ShapeParams P, float* __restrict__ phi) {
 	CELL_IJK(d)
 	const float x = (float)i + 0.5f, y = (float)j + 0.5f, z = (float)(k + d.zoff) + 0.5f;

@@ -37,6 +37,8 @@ PYTHON() declarations; orchestration mirrors the reference function by function,
   blurMacGrid / blurRealGrid / calcCenterOfMass / projectPpmFull (+ projectImage)   source/plugin/initplugins.cpp:273-282, 337-348, 510-655
   getLaplacian / getCurvature                 source/plugin/flip.cpp:779-785
                                              (include/open/manta_hip_datagen.h; not on z-slab solvers)
+  set_wall_bcs2 / resetPhiInObs / extrapolateMACSimple(phiObs=)   source/plugin/extforces.cpp:337-373, advection.cpp:397-402,
+                                             fastmarch.cpp:303-375 (include/open/manta_hip_movingobs.h; not on z-slab solvers)
 """
 import ctypes
 import functools
@@ -634,9 +636,16 @@ def mapGridToPartsVec3(source, parts, target):
 def extrapolateMACSimple(flags, vel, distance=4, phiObs=None, intoObs=False):
     """fastmarch.cpp:337-376"""
     _chk(flags, FlagGrid, "FlagGrid"); _chk(vel, MACGrid, "MACGrid")
-    if phiObs is not None and not (isinstance(phiObs, int) and phiObs == 0):
-        raise RuntimeError("extrapolateMACSimple: the phiObs variant (knUnprojectNormalComp) is outside the hot path")
     s = flags.parent
+    if phiObs is not None and not (isinstance(phiObs, int) and phiObs == 0):
+        # knUnprojectNormalComp between the component passes and the into-boundary copy (include/open/manta_hip_movingobs.h)
+        lib = _extension_lib(s, "extrapolateMACSimple", "movingobs")
+        _chk(phiObs, LevelsetGrid, "LevelsetGrid")
+        flags._check_same(phiObs)
+        tmp, velTmp = core.IntGrid(s), MACGrid(s)
+        lib.call("mf_movingobs_extrapolate_mac_simple", flags.sx, flags.sy, flags.sz, flags.ptr, vel.ptr, int(distance), int(bool(intoObs)),
+                 phiObs.ptr, tmp.ptr, velTmp.ptr, s.stream)
+        return
     tmp, velTmp = core.IntGrid(s), MACGrid(s)
     s.lib.call("mf_extrapolate_mac_simple", flags.sx, flags.sy, flags.sz, flags.ptr, vel.ptr, int(distance), int(bool(intoObs)),
                tmp.ptr, velTmp.ptr, s.stream)
@@ -2683,3 +2692,27 @@ def getCurvature(curv, grid, h=1.0):
     `curv` keeps its values.  The output may not be the input."""
     s, lib = _stencil("getCurvature", curv, grid)
     lib.call("mf_datagen_curvature", grid.sx, grid.sy, grid.sz, grid.ptr, curv.ptr, float(np.float32(h)), s.stream)
+
+
+# =========================================================================================================
+# obstacle coupling of the moving-obstacle scenes (include/open/manta_hip_movingobs.h)
+# =========================================================================================================
+@plugin
+def set_wall_bcs2(flags, vel, obvel):
+    """extforces.cpp:337-373: on every face between a fluid cell and an obstacle cell the normal velocity becomes the obstacle's (obvel
+    at the same face); on a 2-D grid vel.z = 0 in every cell"""
+    s = flags.parent if isinstance(flags, FlagGrid) else vel.parent
+    lib = _extension_lib(s, "set_wall_bcs2", "movingobs")
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(vel, MACGrid, "MACGrid"); _chk(obvel, MACGrid, "MACGrid")
+    flags._check_same(vel); flags._check_same(obvel)
+    lib.call("mf_movingobs_set_wall_bcs2", flags.sx, flags.sy, flags.sz, flags.ptr, vel.ptr, obvel.ptr, s.stream)
+
+
+@plugin
+def resetPhiInObs(flags, sdf):
+    """advection.cpp:397-402: sdf = 0.1 in obstacle cells where it is negative, so that the surface does not stick inside obstacles"""
+    s = flags.parent if isinstance(flags, FlagGrid) else sdf.parent
+    lib = _extension_lib(s, "resetPhiInObs", "movingobs")
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(sdf, Grid, "Grid<Real>")
+    flags._check_same(sdf)
+    lib.call("mf_movingobs_reset_phi_in_obs", flags.n, flags.ptr, sdf.ptr, s.stream)
