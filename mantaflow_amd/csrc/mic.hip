@@ -286,19 +286,23 @@ __device__ __forceinline__ void granule_store(unsigned long long* p, float v, un
 constexpr int FLOW_SPIN_LIMIT = 1 << 21;
 
 // ---------------------------------------------------------------------------------------------------------
-// MIC apply, row-streaming form ("rows"): a workgroup of TWO waves owns an 8x8 bundle of x-rows (tj,tk) and streams
+// MIC apply, row-streaming form ("rows"): a workgroup of SEVEN waves owns an 8x8 bundle of x-rows (tj,tk) and streams
 // along the whole x extent.
-//   compute wave: lane (b,c) works on cell x' = h - b - c at step h.  The i-dependency never leaves the lane's
+//   compute wave (0): lane (b,c) works on cell x' = h - b - c at step h.  The i-dependency never leaves the lane's
 //     registers (no i-faces, no 14-step fill/drain per 8 cells), the j/k dependencies inside the bundle move by DPP /
 //     ds_bpermute as in the tile kernel, and only the two outer faces of the bundle cross workgroups -- as tagged
-//     8-byte sc1 granules, one per (x', face lane), polled 8 steps at a time in a lane-relative window (a consumer
-//     bundle runs 15 steps behind its producer).  Its only vector-memory traffic is those granules: vmcnt is in-order,
-//     so a polling load must never queue behind an HBM fetch.
-//   memory wave: fetches the operands of the bundle's rows in 8-cell chunks, three chunks ahead, commits them to a
-//     32-step LDS ring and writes finished chunks back to dst.  The ring is indexed by the STEP at which a lane
-//     consumes the cell ((h+2) & 31), i.e. the skew b+c is applied when the memory wave stores, and every lane of the
-//     compute wave reads the same ring row at a given step: immediate LDS offsets, no per-lane address arithmetic.
-//   The two waves meet only through two LDS counters (chunks committed / blocks finished).
+//     8-byte sc1 granules, one per (x', face lane).  The wave touches LDS only: operands in, results out.
+//   loader waves (1-3): fetch the operands of the bundle's rows in 8-cell chunks (chunk n -> wave 1 + n % 3) and commit
+//     them to an LDS ring of ROWS_RING steps (8 chunks; the loaders run up to 7 chunks ahead of the write-back).  The ring
+//     is indexed by the STEP at which a lane consumes the cell ((h+2) & (ROWS_RING-1)), i.e. the skew b+c is applied when a
+//     loader stores, and every lane of the compute wave reads the same ring row at a given step: immediate LDS offsets, no
+//     per-lane address arithmetic.  On packed operands a cell is ONE 16-byte slot (see the ring's declaration below).
+//   write-back wave (4): stores finished chunks to dst and, in the backward sweep, sums the fused dot(dst, var1).
+//   poller wave (5): the only wave that loads granules -- a half window (4 steps) of both incoming faces per instruction; a
+//     consumer bundle runs 11 steps behind its producer.  vmcnt is in-order, so a polling load never shares a wave with an
+//     HBM fetch.
+//   publisher wave (6): turns the outer rows / columns of every finished half block into the outgoing granules.
+//   The waves meet only through LDS counters (chunks committed, half blocks finished / published, chunks written back).
 // Bundles are ticketed in anti-diagonal order (tj+tk): a workgroup only ever waits for bundles drawn before its own.
 // 256^3: 1024 bundles, 62 bundle hops per sweep.  Per-cell arithmetic = k_mic_tiles = the reference's.
 // ---------------------------------------------------------------------------------------------------------
@@ -317,6 +321,23 @@ constexpr int ROWS_THREADS = 448;
 #ifndef ROWS_NAP
 #define ROWS_NAP 1
 #endif
+// the same for the 16-byte slots of k_mic_rows' packed operands (128 steps, loaders up to 15 chunks ahead, measured no faster:
+// DESIGN.md section 6)
+#ifndef ROWS_RING_PK
+#define ROWS_RING_PK 64
+#endif
+// The packed byte of a cell as a slot of that ring carries it: one byte per field -- fluid as 0 / 1, "Ai / Aj / Ak is -1" as 0 / 0xff.
+// The compute wave turns a field into its coefficient (+0.0f or -1.0f) with one sign-extending byte conversion instead of a mask, a
+// compare and a select on the wave's condition registers; the loaders, which have the time, spread the bits.
+__device__ __forceinline__ unsigned slot_spread(unsigned b) {
+	return (b & PK_FLUID) | ((b & PK_AI) ? 0xff00u : 0u) | ((b & PK_AJ) ? 0xff0000u : 0u) | ((b & PK_AK) ? 0xff000000u : 0u);
+}
+__device__ __forceinline__ bool slot_fluid(unsigned w) { return (w & 0xffu) != 0; }
+template <unsigned BIT>      // PK_AI, PK_AJ or PK_AK
+__device__ __forceinline__ float slot_coef(unsigned w) {
+	constexpr int sh = BIT == PK_AI ? 8 : (BIT == PK_AJ ? 16 : 24);
+	return (float)(int)(signed char)(w >> sh);
+}
 template <int MODE, bool VEC>
 __global__ void __launch_bounds__(ROWS_THREADS)
 k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0, const int* __restrict__ order, FlowCtl* ctl, int* xt,
@@ -347,9 +368,27 @@ k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0
 	// the compute wave is the critical path: everything else yields to it
 	if (wave == 0) __builtin_amdgcn_s_setprio(3);
 	else __builtin_amdgcn_s_setprio(0);
-	__shared__ float4 sA[ROWS_RING * 64];   // {fluid ? rhs : dst  (-> result), Ai, Aj, Ak}     index = ((h + 2) & (ROWS_RING - 1)) * 64 + lane
-	__shared__ float2 sB[ROWS_RING * 64];   // {Aprecond, fluid}
-	__shared__ float sR[MODE == 2 ? ROWS_RING * 64 : 1];   // with_dot: var1 of the cell
+	// The operand ring, index = ((h + 2) & (ring - 1)) * 64 + lane, in one of two layouts that share one static block (`packed` is a
+	// device-side verdict on some routes, so both live in this kernel):
+	//   packed operands: ONE 16-byte slot per cell, {fluid ? rhs : dst  (-> result), Aprecond, packed byte of the cell, var1 (with_dot)}.
+	//     A loader writes a cell with one ds_write_b128, the compute wave reads one ds_read_b128 per step and rebuilds fluid and the
+	//     three A * Aprecond products from the byte (the LDS serves a wave's requests in order: its k-neighbour permute, which is on
+	//     the dependency chain, queues behind its own operand reads and behind the loaders' store bursts)
+	//   coefficient arrays: sA {value, Ai, Aj, Ak}, sB {Aprecond, fluid}, sR var1 -- 24 resp. 28 bytes per cell
+	struct RowsRingArrays {
+		float4 A[ROWS_RING * 64];
+		float2 B[ROWS_RING * 64];
+		float R[MODE == 2 ? ROWS_RING * 64 : 1];
+	};
+	union RowsRingBlock {
+		RowsRingArrays u;
+		float4 S[ROWS_RING_PK * 64];
+	};
+	__shared__ RowsRingBlock ring;
+	float4* const sS = ring.S;
+	float4* const sA = ring.u.A;
+	float2* const sB = ring.u.B;
+	float* const sR = ring.u.R;
 	__shared__ __attribute__((aligned(16))) float sFj[2][8][8];
 	__shared__ __attribute__((aligned(16))) float sFk[2][8][8];   // face values of a block [block parity][face lane][step]
 	// s_flags = {chunks committed by loader wave 1, 2, 3, face blocks published}: one 16-byte LDS word, so that the compute wave
@@ -447,13 +486,18 @@ k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0
 				const int h2 = 4 * n + st;                                  // ring row (= step + 2) of this lane's granule
 				const int xg = h2 - 2 - skewL;                              // its cell
 				if (live && (unsigned)xg < (unsigned)X8) {
-					const int slot = (h2 & (ROWS_RING - 1)) * 64 + L;
-					const float4 cA = sA[slot];
-					float fv = cA.x;
-					if (MODE == 1) {
-						const float p = sB[slot].x;
-						const float t = cA.x * (fsel == 0 ? cA.z : cA.w);
-						fv = packed ? t : t * p;
+					float fv;
+					if (packed) {
+						// val * (A * Aprecond): the products of the compute wave's packed block, in its order
+						const float4 cS = sS[(h2 & (ROWS_RING_PK - 1)) * 64 + L];
+						const unsigned bits = __float_as_uint(cS.z);
+						fv = cS.x;
+						if (MODE == 1) fv = cS.x * ((fsel == 0 ? slot_coef<PK_AJ>(bits) : slot_coef<PK_AK>(bits)) * cS.y);
+					} else {
+						const int slot = (h2 & (ROWS_RING - 1)) * 64 + L;
+						const float4 cA = sA[slot];
+						fv = cA.x;
+						if (MODE == 1) fv = (cA.x * (fsel == 0 ? cA.z : cA.w)) * sB[slot].x;
 					}
 					granule_store(outp + (int64_t)h2 * 8, fv, gen);
 				}
@@ -565,33 +609,23 @@ k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0
 					int nv;
 					chunk_geom(m, rowidx, nv);
 					const int p0 = 8 * m + skew + 2;
+					if (packed) {
+						// one 16-byte store per cell; a row outside the grid has a zero word (non-fluid, no couplings) and zero operands
+#pragma unroll
+						for (int a = 0; a < 8; a++) {
+							const unsigned bits = (unsigned)(r.W >> (8 * (REV ? 7 - a : a))) & 0xffu;
+							const int idx = ((p0 + a) & (ROWS_RING_PK - 1)) * 64 + lane;
+							sS[idx] = make_float4((MODE == 1 && pk_fluid(bits)) ? r.V[a] : r.D[a], r.P[a], __uint_as_float(slot_spread(bits)),
+							                      (MODE == 2 && with_dot) ? r.V[a] : 0.f);
+						}
+						return;
+					}
 #pragma unroll
 					for (int a = 0; a < 8; a++) {
 						const bool in = ((REV ? 7 - a : a) < nv);
-						bool fl;
-						float cai, caj, cak;
-						if (packed) {
-							const unsigned bits = (unsigned)(r.W >> (8 * (REV ? 7 - a : a))) & 0xffu;
-							fl = pk_fluid(bits);
-							cai = pk_coef<PK_AI>(bits);
-							caj = pk_coef<PK_AJ>(bits);
-							cak = pk_coef<PK_AK>(bits);
-						} else {
-							fl = in && (r.F[a] & MF_FLUID);
-							cai = r.Ai[a];
-							caj = r.Aj[a];
-							cak = r.Ak[a];
-						}
+						const bool fl = in && (r.F[a] & MF_FLUID);
 						const int idx = ((p0 + a) & (ROWS_RING - 1)) * 64 + lane;
-						// packed operands: the ring holds A * Aprecond instead of A.  For A in {+0, -1} (what the packed bytes certify)
-						// (x * A) * p == x * (A * p) bit for bit, for every x and p (signed zeros, infinities and NaNs included): the
-						// compute wave saves a multiplication per neighbour and per step, on its dependency chain
-						if (packed) {
-							cai = cai * r.P[a];
-							caj = caj * r.P[a];
-							cak = cak * r.P[a];
-						}
-						sA[idx] = make_float4((MODE == 1 && fl) ? r.V[a] : r.D[a], cai, caj, cak);
+						sA[idx] = make_float4((MODE == 1 && fl) ? r.V[a] : r.D[a], r.Ai[a], r.Aj[a], r.Ak[a]);
 						sB[idx] = make_float2(r.P[a], fl ? 1.f : 0.f);
 						if (MODE == 2 && with_dot) sR[idx] = r.V[a];     // 0 outside the grid (load_row8)
 					}
@@ -600,13 +634,14 @@ k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0
 				// committed (three blocks before the compute wave needs them), then the wave waits for the ring rows
 				RowsChunk R;
 				const int w = wave - 1;
+				const int rchunks = (packed ? ROWS_RING_PK : ROWS_RING) / 8;     // chunks the ring holds
 #pragma unroll 1
 				for (int n = w; n < nchunks; n += 3) {
 					issue(R, n);
-					// the ring rows of chunk n were last used by chunk n - ROWS_RING / 8: it must have been written back
-					if (n >= ROWS_RING / 8) wait_for(&s_flushed, n - ROWS_RING / 8 + 1);
+					// the ring rows of chunk n were last used by chunk n - rchunks: it must have been written back
+					if (n >= rchunks) wait_for(&s_flushed, n - rchunks + 1);
 					// ... and its outer rows / columns (finished with block n-2) must have been published
-					if (n >= ROWS_RING / 8) wait_for(&s_pub, 2 * (n - ROWS_RING / 8 + 2) + 2);
+					if (n >= rchunks) wait_for(&s_pub, 2 * (n - rchunks + 2) + 2);
 					commit(R, n);
 					__hip_atomic_store(&s_ready[w], n + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 				}
@@ -622,10 +657,18 @@ k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0
 					float w[8];
 #pragma unroll
 					for (int e = 0; e < 8; e++) {
-						const int slot = ((p0 + e) & (ROWS_RING - 1)) * 64 + lane;
-						const float res = sA[slot].x;
+						float res, v1 = 0.f;
+						if (packed) {
+							const float4 cS = sS[((p0 + e) & (ROWS_RING_PK - 1)) * 64 + lane];     // result and var1 in one read
+							res = cS.x;
+							v1 = cS.w;
+						} else {
+							const int slot = ((p0 + e) & (ROWS_RING - 1)) * 64 + lane;
+							res = sA[slot].x;
+							if (MODE == 2 && with_dot) v1 = sR[slot];
+						}
 						w[REV ? 7 - e : e] = res;
-						if (MODE == 2 && with_dot) dacc += (double)(res * sR[slot]);
+						if (MODE == 2 && with_dot) dacc += (double)(res * v1);
 					}
 					__hip_atomic_store(&s_flushed, q + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 					// (non-temporal loads of Aprecond / var1 / dst or stores of dst make the sweeps slower -- 66.9-68.4 vs 63.7 ms per step: their
@@ -649,11 +692,13 @@ k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0
 		} else {
 			// ================= compute wave: LDS in, LDS out (wave 6 publishes the faces) =================
 			float oi0 = 0.f, oj0 = 0.f, ok0 = 0.f;
-			float4 nA = sA[lane];                  // ring row of h = -2 (never valid)
-			float2 nB = sB[lane];
+			// operands of the next step, fetched one step ahead; the ring row of h = -2 comes first (never valid)
+			float4 nA = packed ? sS[lane] : sA[lane];     // packed operands: the whole slot
+			float2 nB = packed ? make_float2(0.f, 0.f) : sB[lane];
 			auto block = [&](int m, auto edge_tag, auto pre_tag) {
 				constexpr bool EDGE = decltype(edge_tag)::value;
-				constexpr bool PRE = decltype(pre_tag)::value;      // the ring holds A * Aprecond (packed operands)
+				constexpr bool PRE = decltype(pre_tag)::value;      // packed operands: 16-byte slots, products A * Aprecond
+				constexpr int RING = PRE ? ROWS_RING_PK : ROWS_RING;
 				const int xq = 8 * m - 2 - skew;                       // this lane's x' at the first step of the block
 				// flags and face values in one batch of LDS reads: the LDS serves a wave's requests in order, and the poller
 				// publishes the values before the flag -- a flag read that shows block m is followed by reads that see its values
@@ -680,7 +725,7 @@ k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0
 				float gj[8], gk[8];
 				gj[0] = j0.x; gj[1] = j0.y; gj[2] = j0.z; gj[3] = j0.w; gj[4] = j1.x; gj[5] = j1.y; gj[6] = j1.z; gj[7] = j1.w;
 				gk[0] = k0.x; gk[1] = k0.y; gk[2] = k0.z; gk[3] = k0.w; gk[4] = k1.x; gk[5] = k1.y; gk[6] = k1.z; gk[7] = k1.w;
-				const int base = (8 * m) & (ROWS_RING - 1);
+				const int base = (8 * m) & (RING - 1);
 #pragma unroll
 				for (int s = 0; s < 8; s++) {
 					if (s == 4 && !have2) {
@@ -696,22 +741,41 @@ k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0
 						gj[4] = j1.x; gj[5] = j1.y; gj[6] = j1.z; gj[7] = j1.w;
 						gk[4] = k1.x; gk[5] = k1.y; gk[6] = k1.z; gk[7] = k1.w;
 					}
-					const float4 cA = nA;
-					const float2 cB = nB;
 					// base is a multiple of 8: the rows of a block never wrap inside it (immediate LDS offsets from one address)
 					const int row = (base + s) * 64 + lane;
-					const int nrow = (s < 7) ? (base + s + 1) * 64 + lane : ((base + 8) & (ROWS_RING - 1)) * 64 + lane;
-					nA = sA[nrow];
-					nB = sB[nrow];
+					const int nrow = (s < 7) ? (base + s + 1) * 64 + lane : ((base + 8) & (RING - 1)) * 64 + lane;
+					float ai, aj, ak, p, val;
+					bool fl;
+					if constexpr (!PRE) {
+						ai = nA.y; aj = nA.z; ak = nA.w; p = nB.x; val = nA.x;
+						fl = nB.y != 0.f;
+						nA = sA[nrow];
+						nB = sB[nrow];
+					}
 					const float dj = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(oj0), 0x111, 0xf, 0xf, true));   // row_shr:1; lanes b == 0 take the face value
 					const float sk = __shfl_up(ok0, 8, 64);
+					if constexpr (PRE) {
+						// The slot fetched one step ahead gives fluid and the products A * Aprecond.  For A in {+0, -1} (what the packed bytes
+						// certify) (x * A) * p == x * (A * p) bit for bit, for every x and p (signed zeros, infinities and NaNs included), and
+						// the multiplication by +0 / -1 stays a multiplication for that reason.  The products are formed behind the permute of
+						// the k-neighbour and in front of the next slot's read -- while the wave would wait for the permute anyway, off the
+						// dependency chain (the scheduling barriers keep the compiler from sinking them to their use behind the new value)
+						__builtin_amdgcn_sched_barrier(0);
+						const unsigned bits = __float_as_uint(nA.z);
+						val = nA.x;
+						p = nA.y;
+						fl = slot_fluid(bits);
+						ai = slot_coef<PK_AI>(bits) * p;
+						aj = slot_coef<PK_AJ>(bits) * p;
+						ak = slot_coef<PK_AK>(bits) * p;
+						asm volatile("" : "+v"(ai), "+v"(aj), "+v"(ak));
+						nA = sS[nrow];
+						__builtin_amdgcn_sched_barrier(0);
+					}
 					const float ij0 = (b == 0) ? gj[s] : dj;
 					const float ik0 = (c == 0) ? gk[s] : sk;
 					const float ii0 = oi0;
 					const bool valid = !EDGE || ((unsigned)(xq + s) < (unsigned)X8);
-					const float ai = cA.y, aj = cA.z, ak = cA.w, p = cB.x;
-					const bool fl = cB.y != 0.f;
-					float val = cA.x;
 					if (MODE == 1) {
 						const float nv = p * (val - ii0 - ij0 - ik0);
 						val = fl ? nv : val;
@@ -723,7 +787,7 @@ k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0
 						val = fl ? nv : val;
 						oi0 = oj0 = ok0 = valid ? val : 0.f;
 					}
-					if (valid) sA[row].x = val;
+					if (valid) (PRE ? sS : sA)[row].x = val;
 					if (s == 3) {
 						// first half of the block is in the ring (the LDS serves this wave's writes in order: no wait needed)
 						asm volatile("" ::: "memory");
