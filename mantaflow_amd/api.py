@@ -34,10 +34,17 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       copyPdataToArrayVec3, extractFeatureVel, extractFeaturePhi, extractFeatureGeo, getRegions, getRegionalCounts,
                       extendRegion, markSmallRegions, simpleNumpyTest,
                       blurMacGrid, blurRealGrid, calcCenterOfMass, projectImage, projectPpmFull, getLaplacian, getCurvature,
-                      set_wall_bcs2, resetPhiInObs)
+                      set_wall_bcs2, resetPhiInObs,
+                      addForceField, setForceField, setInitialVelocity, extrapolateVec3Simple, applyEmission, resetInObstacle, copyMACData,
+                      copyRealToVec3, copyVec3ToReal, resampleMacToVec3, swapComponents, getGridAvg, debugIntToReal,
+                      applySimpleNoiseReal, applySimpleNoiseVec3,
+                      flipComputePotentialTrappedAir, flipComputePotentialKineticEnergy, flipComputePotentialWaveCrest,
+                      flipComputeSurfaceNormals, flipUpdateNeighborRatio)
 
 from .scene import (Box, Checkbox, Cylinder, Gui, MovingObstacle, NoiseField, Shape, Slider, Sphere, densityInflow, sampleFlagsWithParticles,
                     sampleLevelsetWithParticles, sampleShapeWithParticles)
+
+WaveletNoiseField = NoiseField     # the class's C++ name; Python scenes of the reference use either (noisefield.h)
 
 # module constants, registry.cpp:390-421
 GUI = False
@@ -83,6 +90,43 @@ def getUniFileSize(name):
     if ident not in (b"MNT2", b"M4T2", fileio.GRID, fileio.GRID4D) or len(head) != 12:
         return vec3(0, 0, 0)
     return vec3(*[float(v) for v in struct.unpack("<3i", head)])
+
+
+def printUniFileInfoString(name):
+    """fileio/iogrids.cpp:374-380: prints "File '<name>' info: x,y,z" with ",t" appended for a 4-D grid file; a file that cannot be read
+    prints 0,0,0.  (A legacy M4T2 file prints without its fourth dimension here.)"""
+    from . import fileio
+    size = getUniFileSize(name)
+    info = "%d,%d,%d" % (size.x, size.y, size.z)
+    try:
+        with fileio.Reader(name) as f:
+            ident = f.magic()
+            if ident in (fileio.GRID, fileio.GRID4D):
+                dimt = f.header(ident, "can't read file, no header present")[6]
+                if dimt > 0:
+                    info += ",%d" % dimt
+    except (OSError, RuntimeError):
+        pass
+    mantaMsg("File '%s' info: %s" % (name, info), 1)
+
+
+def getNpzFileSize(name):
+    """fileio/iogrids.cpp:952-975: the grid size in a .npz grid file, (x, y, z) = (shape[2], shape[1], shape[0]) of its arr_0.  That
+    is what the function is written to return and does return in a build without zlib; in a build WITH zlib its guard is inverted
+    (`#if NO_ZLIB != 1` prints "file format not supported without zlib" and returns), so the recorded reference gives (0, 0, 0) for
+    every file (tests/golden/gridops.npz, npzsize/file).  Here the size is returned.  A file that cannot be opened raises, as
+    cnpy::npz_load does; a file without a 3-D arr_0 raises where the reference reads outside the shape."""
+    import numpy as np
+    try:
+        with np.load(name) as z:
+            if "arr_0" not in z.files:
+                raise RuntimeError("getNpzFileSize: '%s' holds no arr_0" % name)
+            shape = z["arr_0"].shape
+    except (OSError, ValueError) as e:
+        raise RuntimeError("npz_load: Error! Unable to open file %s! (%s)" % (name, e))
+    if len(shape) < 3:
+        raise RuntimeError("getNpzFileSize: arr_0 of '%s' has %d dimensions, a grid has at least 3" % (name, len(shape)))
+    return vec3(float(shape[2]), float(shape[1]), float(shape[0]))
 
 
 def printBuildInfo():

@@ -437,6 +437,168 @@ class GridBase(PbClass):
             v = v.index_select(1, src(self.sz))
         self.data.copy_(v.index_select(2, src(self.sy)).index_select(3, src(self.sx)).reshape(-1))
 
+    # host-only accessors (grid.h:34-35, 83-84; Grid<T>::get / set): no kernel, every backend
+    def get_name(self): return self.getName()
+    def set_name(self, s): self.setName(s)
+    def getSizeT(self): return 1
+    def getStrideT(self): return 0
+
+    def _checked_index(self, what, i, j, k):
+        """the linear index of cell (i, j, k), refused outside the grid (GridBase::checkIndex, grid.h:56)"""
+        i, j, k = int(i), int(j), int(k)
+        if not (0 <= i < self.sx and 0 <= j < self.sy and 0 <= k < self.sz):
+            raise RuntimeError("Grid::%s: index %d,%d,%d out of bound [%d,%d,%d]" % (what, i, j, k, self.sx, self.sy, self.sz))
+        return i + self.sx * (j + self.sy * k)
+
+    def _words(self, idx):
+        """the element at a linear index, read back: one value per component plane"""
+        self.parent.sync()
+        return [self.data[c * self.n + idx].item() for c in range(self._ncomp)]
+
+    def get(self, i, j, k):
+        """Grid<T>::get(i, j, k): one element read back to the host (an int, a float or a vec3)"""
+        w = self._words(self._checked_index("get", i, j, k))
+        return vec3(*w) if self._ncomp == 3 else w[0]
+
+    def set(self, i, j, k, val):
+        """Grid<T>::set(i, j, k, val): one element written from the host"""
+        idx = self._checked_index("set", i, j, k)
+        if self._ncomp == 3:
+            v = _to_vec3(val)
+            for c, x in enumerate((v.x, v.y, v.z)):
+                self.data[c * self.n + idx] = float(np.float32(x))
+        else:
+            self.data[idx] = int(val) if self._kind == "int" else float(np.float32(val))
+
+    @staticmethod
+    def _interpol_axis(p, size, clamp_on_index, cut_upper=True):
+        """one axis of BUILD_INDEX (p = pos - 0.5, util/interpol.h:52-67) or of its shifted half (p = pos, :116-129): the base index
+        and the fp32 weights (w0, w1); `1. - w1` is a double difference rounded once.  The upper clamp tests p itself in BUILD_INDEX
+        and the truncated index in the shifted half; a 2-D grid's z axis has no upper clamp."""
+        f32 = np.float32
+        p = f32(p)
+        if not np.isfinite(p) or abs(float(p)) >= 2.0 ** 31:
+            raise RuntimeError("Grid::getInterpolated: position %r cannot be truncated to a cell" % float(p))
+        i = int(p)                                          # (int): toward zero
+        w1 = f32(p - f32(i))
+        w0 = f32(1. - float(w1))
+        if p < 0:
+            i, w0, w1 = 0, f32(1), f32(0)
+        if cut_upper and ((i >= size - 1) if clamp_on_index else (p >= f32(size - 1))):
+            i, w0, w1 = size - 2, f32(0), f32(1)
+        return i, w0, w1
+
+    def _interpolated(self, pos, mac):
+        """interpol<T> (util/interpol.h:71-82) per component, or interpolMAC (:131-164): eight elements per component read back, the
+        reference's association order in fp32.  Where the reference's base index leaves the array (interpolMAC on a 2-D grid with a
+        large z: it multiplies the z index by size.y, not by the z stride) the call is refused."""
+        f32 = np.float32
+        p = _to_vec3(pos)
+        sx, sy, sz = self.dims
+        z3 = self.is3D()
+        Z = sx * sy if z3 else 0                             # mStrideZ
+        ax = [self._interpol_axis(f32(q) - f32(0.5), n, False, c < 2 or sz > 1) for c, (q, n) in enumerate(zip((p.x, p.y, p.z), self.dims))]
+        sh = [self._interpol_axis(q, n, True, c < 2 or sz > 1) for c, (q, n) in enumerate(zip((p.x, p.y, p.z), self.dims))] if mac else ax
+        self.parent.sync()
+        out = []
+        for c in range(self._ncomp):
+            # the axis that takes the shifted index and weights: component c of a MAC grid, none otherwise
+            (xi, s0, s1), (yi, t0, t1), (zi, f0, f1) = [(sh if (mac and a == c) else ax)[a] for a in range(3)]
+            base = (zi * sy + yi) * sx + xi if mac else xi + sx * yi + Z * zi
+            if base < 0 or base + 1 + sx + Z > self.n - 1:
+                raise RuntimeError("Grid::getInterpolated: position [%g,%g,%g] out of bound [%d,%d,%d]" % (p.x, p.y, p.z, sx, sy, sz))
+            d = self.data[c * self.n:(c + 1) * self.n]
+            r = lambda o: f32(d[base + o].item())
+            a = f32(f32(f32(r(0) * t0) + f32(r(sx) * t1)) * s0) + f32(f32(f32(r(1) * t0) + f32(r(1 + sx) * t1)) * s1)
+            b = f32(f32(f32(r(Z) * t0) + f32(r(sx + Z) * t1)) * s0) + f32(f32(f32(r(1 + Z) * t0) + f32(r(1 + sx + Z) * t1)) * s1)
+            out.append(float(f32(f32(f32(a) * f0) + f32(f32(b) * f1))))
+        return out
+
+    # the grid operations of include/open/manta_hip_gridops.h: Real, int and Vec3 / MAC grids alike
+    _GRIDOPS_KIND = {"real": 0, "int": 1, "vec": 2}
+
+    def _gridops_lib(self, what):
+        """_extension_lib for a grid method: z-slab first, then a backend without the extension"""
+        return _extension_lib(self.parent, "Grid::" + what, "gridops")
+
+    @staticmethod
+    def _permutation(axis0, axis1, axis2):
+        """the three axes, or None where the reference returns without doing anything (grid.cpp:323, 332)"""
+        ax = (int(axis0), int(axis1), int(axis2))
+        return ax if sorted(ax) == [0, 1, 2] else None
+
+    def permuteAxes(self, axis0, axis1, axis2):
+        """Grid<T>::permuteAxes, grid.cpp:322-330: target(s[axis0], s[axis1], s[axis2]) = self(s) into a pool scratch grid that then
+        swaps storage with this grid; an invalid or repeated axis returns silently.  The grid must be cubic (square in 2-D); on a 2-D
+        grid axis 2 must stay, because the reference's z stride of 0 folds every other permutation onto one row."""
+        lib = self._gridops_lib("permuteAxes")
+        ax = self._permutation(axis0, axis1, axis2)
+        if ax is None:
+            return
+        s = self.parent
+        if not (self.sx == self.sy and (s.is2D() or self.sy == self.sz)):
+            raise RuntimeError("Grid must be cubic!")
+        if s.is2D() and ax[2] != 2:
+            raise RuntimeError("permuteAxes: (%d, %d, %d) moves axis 2 of a 2-D grid" % ax)
+        tmp = s._alloc(self._kind, zero=False)
+        try:
+            lib.call("mf_gridops_permute", self.sx, self.sy, self.sz, ax[0], ax[1], ax[2], self._ncomp, self.ptr, _ptr(tmp), s.stream)
+            self.data, tmp = tmp, self.data
+        finally:
+            s._release(self._kind, tmp)
+
+    def permuteAxesCopyToGrid(self, axis0, axis1, axis2, out):
+        """Grid<T>::permuteAxesCopyToGrid, grid.cpp:331-339, with the reference's two asserts.  Its kernel writes outside `out` for the
+        two 3-cycles on a non-cubic grid (the assert asks sizeTarget[axisN] == size[N], the kernel needs sizeTarget[N] == size[axisN])
+        and wherever axis 2 moves on a 2-D grid: those are refused here."""
+        lib = self._gridops_lib("permuteAxesCopyToGrid")
+        ax = self._permutation(axis0, axis1, axis2)
+        if ax is None:
+            return
+        if not isinstance(out, GridBase):
+            raise RuntimeError("can't convert argument to Grid*")
+        if self.getGridType() != out.getGridType():
+            raise RuntimeError("Grids must have same data type!")
+        size, target = self.dims, out.dims
+        if any(target[ax[q]] != size[q] for q in range(3)):
+            raise RuntimeError("Permuted grids must have the same dimensions!")
+        if (self.parent.is2D() or out.parent.is2D()) and ax[2] != 2:
+            raise RuntimeError("permuteAxesCopyToGrid: (%d, %d, %d) moves axis 2 of a 2-D grid: the reference writes outside the target" % ax)
+        if any(target[q] != size[ax[q]] for q in range(3)):
+            raise RuntimeError("permuteAxesCopyToGrid: a cyclic permutation (%d, %d, %d) of a non-cubic grid [%d,%d,%d]: the reference "
+                               "writes outside the target" % (ax + size))
+        _extension_lib(out.parent, "Grid::permuteAxesCopyToGrid", "gridops")     # out's solver may be another one: no z-slab either
+        if out.data.data_ptr() == self.data.data_ptr():
+            raise RuntimeError("permuteAxesCopyToGrid: out must not be the grid itself")
+        lib.call("mf_gridops_permute", self.sx, self.sy, self.sz, ax[0], ax[1], ax[2], self._ncomp, self.ptr, out.ptr, self.parent.stream)
+
+    def _norm(self, what, l2, bnd):
+        lib = self._gridops_lib(what)
+        if int(bnd) < 0:
+            raise RuntimeError("%s: bnd %d is negative: the reference reads outside the grid" % (what, int(bnd)))
+        r = ctypes.c_float()
+        lib.call("mf_gridops_norm", self._GRIDOPS_KIND[self._kind], l2, self.sx, self.sy, self.sz, int(bnd), self.ptr, ctypes.byref(r),
+                 self.parent.stream)
+        return r.value
+
+    def getL1(self, bnd=0):
+        """Grid<T>::getL1, grid.cpp:390-396, 412-414: the fp64 sum of norm(x) over the cells at least bnd from every side, as fp32; the
+        sum is the device's fixed-order reduction (DESIGN.md section 25 has the bound against the reference's serial loop)"""
+        return self._norm("getL1", 0, bnd)
+
+    def getL2(self, bnd=0):
+        """Grid<T>::getL2, grid.cpp:401-409, 416-418: sqrt of the fp64 sum of normSquare(x), as fp32"""
+        return self._norm("getL2", 1, bnd)
+
+    def join(self, a, keepMax=True):
+        """Grid<T>::join, grid.cpp:258-268, 340-348: the larger (keepMax) or smaller of the two values per cell; for Vec3 grids every
+        component becomes the larger / smaller normSquare"""
+        lib = self._gridops_lib("join")
+        if not isinstance(a, GridBase) or a._kind != self._kind:
+            raise RuntimeError("can't convert argument to Grid*")
+        self._check_same(a)
+        lib.call("mf_gridops_join", self._GRIDOPS_KIND[self._kind], self.n, self.ptr, a.ptr, int(bool(keepMax)), self.parent.stream)
+
     def save(self, name):
         """Grid<T>::save, grid.cpp:157-179 (.uni, .raw, .npz)"""
         return _grid_save(self, str(name))
@@ -552,6 +714,11 @@ class Grid(GridBase):
         self._call("mf_grid_max_abs", self.n, self.ptr, ctypes.byref(r), self.parent.stream)
         return r.value
 
+    def getInterpolated(self, pos):
+        """Grid<Real>::getInterpolated -> interpol<Real>, grid.h:150, util/interpol.h:71-82: trilinear (2-D: bilinear) at a position in
+        grid coordinates, clamped to the border.  Host-only: eight elements are read back."""
+        return self._interpolated(pos, False)[0]
+
     def _minmax(self):
         lo, hi = ctypes.c_float(), ctypes.c_float()
         self._call("mf_grid_min_max", self.n, self.ptr, ctypes.byref(lo), ctypes.byref(hi), self.parent.stream)
@@ -624,6 +791,11 @@ class VecGrid(GridBase):
 
     getMax = getMaxAbs
 
+    def getInterpolated(self, pos):
+        """Grid<Vec3>::getInterpolated -> interpol<Vec3>, grid.h:150, util/interpol.h:71-82: every component like a Real grid's.
+        Host-only: 24 elements are read back."""
+        return vec3(*self._interpolated(pos, False))
+
     def clamp_norm(self, val):
         """Grid<Vec3>::clamp_norm -> knGridClampNorm, grid.cpp:306-317: where the fp32 norm n exceeds val, every component is
         multiplied by the one quotient val / n (include/open/manta_hip_movingobs.h)"""
@@ -664,6 +836,57 @@ class MACGrid(VecGrid):
     def set_bound_MAC2(self, value, boundaryWidth):
         """MACGrid::set_bound_MAC2 -> kn_set_bound_MAC2, grid.cpp:695-715: the walls of the boundary cells"""
         self._set_bound_mac("MACGrid::set_bound_MAC2", value, boundaryWidth, 2)
+
+    # host-only samplers, grid.h:264-267, 460-506: a few elements read back, the reference's expression in fp32 (0.5 * and 0.25 * of an
+    # fp32 sum are exact halvings, so the double literals round to the same fp32).  Every element of the stencil must lie in the grid.
+    def _stencil(self, what, i, j, k, reach):
+        """plane(c, di, dj, dk) -> the fp32 value of component c at (i + di, j + dj, k + dk); reach: the offsets the sampler reads"""
+        i, j, k = int(i), int(j), int(k)
+        z3 = self.is3D()
+        for di, dj, dk in [(0, 0, 0)] + reach:
+            if dk and not z3:
+                continue
+            self._checked_index(what, i + di, j + dj, k + dk)
+        self.parent.sync()
+        base = i + self.sx * (j + self.sy * k)
+
+        def plane(c, di=0, dj=0, dk=0):
+            return np.float32(self.data[c * self.n + base + di + self.sx * (dj + self.sy * dk)].item())
+        return plane, z3
+
+    def getInterpolated(self, pos):
+        """MACGrid::getInterpolated -> interpolMAC, grid.h:269, util/interpol.h:116-164: each component is sampled on its own faces
+        (the index and the weights of its own axis come from pos, the others from pos - 0.5)"""
+        return vec3(*self._interpolated(pos, True))
+
+    def getCentered(self, pos):
+        """MACGrid::getCentered(Vec3i), grid.h:460-471: the face values averaged to the cell centre"""
+        p = _to_vec3(pos, "Vec3i")
+        f, z3 = self._stencil("getCentered", p.x, p.y, p.z, [(1, 0, 0), (0, 1, 0), (0, 0, 1)])
+        h = np.float32(0.5)
+        return vec3(float(h * (f(0) + f(0, 1))), float(h * (f(1) + f(1, 0, 1))), float(h * (f(2) + f(2, 0, 0, 1))) if z3 else 0.0)
+
+    def getAtMACX(self, i, j, k):
+        """MACGrid::getAtMACX, grid.h:473-484: the velocity at the x face of the cell"""
+        f, z3 = self._stencil("getAtMACX", i, j, k, [(-1, 0, 0), (0, 1, 0), (-1, 1, 0), (0, 0, 1), (-1, 0, 1)])
+        q = np.float32(0.25)
+        return vec3(float(f(0)), float(q * (f(1) + f(1, -1) + f(1, 0, 1) + f(1, -1, 1))),
+                    float(q * (f(2) + f(2, -1) + f(2, 0, 0, 1) + f(2, -1, 0, 1))) if z3 else 0.0)
+
+    def getAtMACY(self, i, j, k):
+        """MACGrid::getAtMACY, grid.h:486-496"""
+        f, z3 = self._stencil("getAtMACY", i, j, k, [(0, -1, 0), (1, 0, 0), (1, -1, 0), (0, 0, 1), (0, -1, 1)])
+        q = np.float32(0.25)
+        return vec3(float(q * (f(0) + f(0, 0, -1) + f(0, 1) + f(0, 1, -1))), float(f(1)),
+                    float(q * (f(2) + f(2, 0, -1) + f(2, 0, 0, 1) + f(2, 0, -1, 1))) if z3 else 0.0)
+
+    def getAtMACZ(self, i, j, k):
+        """MACGrid::getAtMACZ, grid.h:498-506; on a 2-D grid the reference's z stride is 0, so the "k - 1" elements are the cell's own"""
+        z3 = self.is3D()
+        f, _ = self._stencil("getAtMACZ", i, j, k, [(1, 0, 0), (0, 1, 0)] + ([(0, 0, -1), (1, 0, -1), (0, 1, -1)] if z3 else []))
+        q, dk = np.float32(0.25), (-1 if z3 else 0)
+        return vec3(float(q * (f(0) + f(0, 0, 0, dk) + f(0, 1) + f(0, 1, 0, dk))), float(q * (f(1) + f(1, 0, 0, dk) + f(1, 0, 1) + f(1, 0, 1, dk))),
+                    float(f(2)))
 
 
 class LevelsetGrid(Grid):
@@ -2161,6 +2384,16 @@ class BasicParticleSystem(PbClass):
         a, b = source.parent.mGridSize, self.parent.mGridSize
         factor = np.array([np.float32(b[c]) / np.float32(a[c]) for c in range(3)], np.float32)
         self.set_positions(source.get_positions() * factor[None, :] if source.np else np.zeros((0, 3), np.float32), source.get_flags())
+
+    def transformPositions(self, dimOld, dimNew):
+        """ParticleSystem::transformPositions, particle.h:449-455: every position times calcGridSizeFactor(dimNew, dimOld), the fp32
+        quotient per axis that load and readParticles apply; flags and channels stay.  Host-only: no kernel of ours."""
+        a, b = _to_vec3(dimOld, "Vec3i"), _to_vec3(dimNew, "Vec3i")
+        if not all(int(o) > 0 for o in (a.x, a.y, a.z)):
+            raise RuntimeError("transformPositions: dimOld [%d,%d,%d] has a side that is not positive" % (int(a.x), int(a.y), int(a.z)))
+        for c, (o, n) in enumerate(((a.x, b.x), (a.y, b.y), (a.z, b.z))):
+            if self.np:
+                self.pos[c * self.cap:c * self.cap + self.np] *= float(np.float32(int(n)) / np.float32(int(o)))
 
     # .uni particle files, fileio/ioparticles.cpp:130-223: the UniPartHeader + [pos.x pos.y pos.z flag] per particle
     _UNI_RECORD = np.dtype([("pos", "<f4", 3), ("flag", "<i4")])

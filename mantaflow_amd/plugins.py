@@ -39,6 +39,15 @@ PYTHON() declarations; orchestration mirrors the reference function by function,
                                              (include/open/manta_hip_datagen.h; not on z-slab solvers)
   set_wall_bcs2 / resetPhiInObs / extrapolateMACSimple(phiObs=)   source/plugin/extforces.cpp:337-373, advection.cpp:397-402,
                                              fastmarch.cpp:303-375 (include/open/manta_hip_movingobs.h; not on z-slab solvers)
+  addForceField / setForceField / setInitialVelocity   source/plugin/extforces.cpp:24-43, 376-407, 430-436
+  extrapolateVec3Simple                       source/fastmarch.cpp:525-557
+  applyEmission / resetInObstacle             source/plugin/initplugins.cpp:110-128, 154-183
+  copyMACData / copyRealToVec3 / copyVec3ToReal / resampleMacToVec3 / swapComponents / getGridAvg / debugIntToReal
+                                             source/grid.cpp:496-536, 564-571, 717-739, 1013-1033, plugin/flip.cpp:266-269
+  applySimpleNoiseReal / applySimpleNoiseVec3 source/plugin/waveletturbulence.cpp:85-116
+  flipComputePotentialTrappedAir / flipComputePotentialKineticEnergy / flipComputePotentialWaveCrest / flipComputeSurfaceNormals /
+  flipUpdateNeighborRatio                     source/plugin/secondaryparticles.cpp:549-706
+                                             (include/open/manta_hip_gridops.h; not on z-slab solvers)
 """
 import ctypes
 import functools
@@ -83,7 +92,8 @@ def plugin(fn):
     rules (typed by the parameter's default value)."""
     import inspect
     params = list(inspect.signature(fn).parameters.values())
-    typed = {p.name: p.default for p in params if isinstance(p.default, (bool, int)) and p.default is not None}
+    typed = {p.name: p.default for p in params if isinstance(p.default, (bool, int)) and p.default is not None
+             and p.name not in getattr(fn, "_real_parameters", ())}
     pos_typed = [(i, p.default) for i, p in enumerate(params) if p.name in typed]
 
     @functools.wraps(fn)
@@ -114,6 +124,15 @@ def plugin(fn):
             rec[1] += time.time() - t0
         return r
     return w
+
+
+def real_parameters(*names):
+    """for a plugin whose reference signature spells a Real default as an int literal (`Real resetValue=0`): those parameters are not
+    typed by their default, so they take any number.  Goes below @plugin."""
+    def mark(fn):
+        fn._real_parameters = names
+        return fn
+    return mark
 
 
 class Timings(object):
@@ -2716,3 +2735,264 @@ def resetPhiInObs(flags, sdf):
     _chk(flags, FlagGrid, "FlagGrid"); _chk(sdf, Grid, "Grid<Real>")
     flags._check_same(sdf)
     lib.call("mf_movingobs_reset_phi_in_obs", flags.n, flags.ptr, sdf.ptr, s.stream)
+
+
+# =========================================================================================================
+# the remaining grid plugins (include/open/manta_hip_gridops.h)
+# =========================================================================================================
+def _gridops(name, *objs):
+    """the solver of the first grid among objs and its library, refused by `name` on a z-slab solver or a backend without the extension
+    before any argument is looked at"""
+    s = next((o.parent for o in objs if isinstance(o, GridBase)), None)
+    if s is None:
+        raise RuntimeError("%s: can't convert argument to Grid*" % name)
+    return s, _extension_lib(s, name, "gridops")
+
+
+def _force_field(name, flags, vel, force, region, additive, isMAC):
+    s, lib = _gridops(name, flags, vel, force)
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(vel, MACGrid, "MACGrid"); _chk(force, VecGrid, "Grid<Vec3>")
+    region = _opt(region, Grid, "Grid<Real>")
+    flags._check_same(vel); flags._check_same(force)
+    if region is not None:
+        flags._check_same(region)
+    lib.call("mf_gridops_force_field", flags.sx, flags.sy, flags.sz, flags.ptr, vel.ptr, force.ptr, None if region is None else region.ptr,
+             additive, int(isMAC), s.stream)
+
+
+@plugin
+def addForceField(flags, vel, force, region=None, isMAC=False):
+    """extforces.cpp:430-432 -> KnApplyForceField: vel += the force at the face (force itself with isMAC, else the mean of the two cells)
+    on the faces between fluid / fluid and fluid / empty cells of the interior; cells where region > 0 are left out"""
+    _force_field("addForceField", flags, vel, force, region, 1, isMAC)
+
+
+@plugin
+def setForceField(flags, vel, force, region=None, isMAC=False):
+    """extforces.cpp:434-436 -> KnApplyForceField: like addForceField, but vel = the force at the face"""
+    _force_field("setForceField", flags, vel, force, region, 0, isMAC)
+
+
+@plugin
+def setInitialVelocity(flags, vel, invel):
+    """extforces.cpp:405-407 -> KnAddForceIfLower: vel + f on the same faces, clamped so that it does not pass the larger (f > 0) or the
+    smaller of vel and f"""
+    s, lib = _gridops("setInitialVelocity", flags, vel, invel)
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(vel, MACGrid, "MACGrid"); _chk(invel, VecGrid, "Grid<Vec3>")
+    flags._check_same(vel); flags._check_same(invel)
+    lib.call("mf_gridops_add_force_if_lower", flags.sx, flags.sy, flags.sz, flags.ptr, vel.ptr, invel.ptr, s.stream)
+
+
+@plugin
+def extrapolateVec3Simple(vel, phi, distance=4, inside=False):
+    """fastmarch.cpp:525-557: cell-centred Vec3 values are carried `distance` layers outwards from the cells with phi < 0 (inside: phi > 0),
+    each new cell the per-component mean of its neighbours of the previous layer; every interior cell that is not reached becomes 0"""
+    s, lib = _gridops("extrapolateVec3Simple", vel, phi)
+    _chk(vel, VecGrid, "Grid<Vec3>"); _chk(phi, Grid, "Grid<Real>")
+    vel._check_same(phi)
+    tmp = s._alloc("int", zero=False)
+    try:
+        lib.call("mf_gridops_extrapolate_vec3_simple", vel.sx, vel.sy, vel.sz, vel.ptr, phi.ptr, int(distance), int(inside), _ptr(tmp), s.stream)
+    finally:
+        s._release("int", tmp)
+
+
+@plugin
+def applyEmission(flags, target, source, emissionTexture=None, isAbsolute=True, type=0):
+    """initplugins.cpp:126-128 -> KnApplyEmission: target = source (isAbsolute) or target += source; a cell is skipped only where its
+    flag does not match a given type AND the given emissionTexture is 0 there"""
+    s, lib = _gridops("applyEmission", flags, target, source)
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(target, Grid, "Grid<Real>"); _chk(source, Grid, "Grid<Real>")
+    tex = _opt(emissionTexture, Grid, "Grid<Real>")
+    for g in (target, source) + (() if tex is None else (tex,)):
+        flags._check_same(g)
+    lib.call("mf_gridops_apply_emission", flags.n, flags.ptr, target.ptr, source.ptr, None if tex is None else tex.ptr, int(isAbsolute),
+             int(type), s.stream)
+
+
+@plugin
+@real_parameters("resetValue")
+def resetInObstacle(flags, vel, density, heat=None, fuel=None, flame=None, red=None, green=None, blue=None, resetValue=0):
+    """initplugins.cpp:179-183 -> KnResetInObstacle: vel and every given grid = resetValue in the obstacle cells; flame goes with fuel,
+    green and blue go with red.  resetValue is a Real whose default the reference spells 0."""
+    s, lib = _gridops("resetInObstacle", flags, vel)
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(vel, MACGrid, "MACGrid")
+    g = [_opt(x, Grid, "Grid<Real>") for x in (density, heat, fuel, flame, red, green, blue)]
+    if g[2] is not None and g[3] is None:
+        raise RuntimeError("resetInObstacle: fuel is given without flame")
+    if g[4] is not None and (g[5] is None or g[6] is None):
+        raise RuntimeError("resetInObstacle: red is given without green and blue")
+    flags._check_same(vel)
+    for x in g:
+        if x is not None:
+            flags._check_same(x)
+    lib.call("mf_gridops_reset_in_obstacle", flags.n, flags.ptr, vel.ptr, *([None if x is None else x.ptr for x in g] +
+             [float(np.float32(resetValue)), s.stream]))
+
+
+@plugin
+def copyMACData(source, target, flags, flag, bnd):
+    """grid.cpp:1013-1033: target = source in the cells at least bnd from every side whose flags have a bit of `flag`"""
+    s, lib = _gridops("copyMACData", source, target, flags)
+    _chk(source, MACGrid, "MACGrid"); _chk(target, MACGrid, "MACGrid"); _chk(flags, FlagGrid, "FlagGrid")
+    if source.dims != target.dims:
+        raise RuntimeError("different grid resolutions [%d,%d,%d] vs [%d,%d,%d]" % (source.dims + target.dims))
+    target._check_same(flags)
+    if int(bnd) < 0:
+        raise RuntimeError("copyMACData: bnd %d is negative: the reference reads outside the grid" % int(bnd))
+    lib.call("mf_gridops_copy_mac_data", target.sx, target.sy, target.sz, source.ptr, target.ptr, flags.ptr, int(flag), int(bnd), s.stream)
+
+
+@plugin
+def copyRealToVec3(sourceX, sourceY, sourceZ, target):
+    """grid.cpp:527-536: the three Real grids become the components of target"""
+    s, lib = _gridops("copyRealToVec3", sourceX, sourceY, sourceZ, target)
+    for g in (sourceX, sourceY, sourceZ):
+        _chk(g, Grid, "Grid<Real>")
+    _chk(target, VecGrid, "Grid<Vec3>")
+    for g in (sourceX, sourceY, sourceZ):
+        target._check_same(g)
+    n = target.n
+    lib.call("mf_gridops_copy_planes", n, sourceX.ptr, sourceY.ptr, sourceZ.ptr, target.ptr, _ptr(target.data[n:]), _ptr(target.data[2 * n:]),
+             s.stream)
+
+
+@plugin
+def copyVec3ToReal(source, targetX, targetY, targetZ):
+    """grid.cpp:516-525: the components of source go to the three Real grids"""
+    s, lib = _gridops("copyVec3ToReal", source, targetX, targetY, targetZ)
+    _chk(source, VecGrid, "Grid<Vec3>")
+    for g in (targetX, targetY, targetZ):
+        _chk(g, Grid, "Grid<Real>")
+        source._check_same(g)
+    n = source.n
+    lib.call("mf_gridops_copy_planes", n, source.ptr, _ptr(source.data[n:]), _ptr(source.data[2 * n:]), targetX.ptr, targetY.ptr, targetZ.ptr,
+             s.stream)
+
+
+@plugin
+def resampleMacToVec3(source, target):
+    """grid.cpp:496-505: target = source.getCentered(i, j, k) on the interior; the border of target keeps its values"""
+    s, lib = _gridops("resampleMacToVec3", source, target)
+    _chk(source, MACGrid, "MACGrid"); _chk(target, VecGrid, "Grid<Vec3>")
+    source._check_same(target)
+    if source.data.data_ptr() == target.data.data_ptr():
+        raise RuntimeError("resampleMacToVec3: target must not be source")
+    lib.call("mf_gridops_resample_mac_to_vec3", source.sx, source.sy, source.sz, source.ptr, target.ptr, s.stream)
+
+
+@plugin
+def swapComponents(vel, c1=0, c2=1, c3=2):
+    """grid.cpp:564-571: (x, y, z) = (v[c1], v[c2], v[c3]) of the old value in every cell"""
+    s, lib = _gridops("swapComponents", vel)
+    _chk(vel, VecGrid, "Grid<Vec3>")
+    if not all(0 <= c <= 2 for c in (c1, c2, c3)):
+        raise RuntimeError("swapComponents: component (%d, %d, %d) outside 0..2: the reference reads outside the vector" % (c1, c2, c3))
+    lib.call("mf_gridops_swap_components", vel.n, vel.ptr, c1, c2, c3, s.stream)
+
+
+@plugin
+def getGridAvg(source, flags=None):
+    """grid.cpp:728-739: the mean of source over every cell, or over the fluid cells of flags; an fp64 sum (the device's fixed-order
+    reduction) times 1 / count, as fp32; -1 where there is no such cell"""
+    s, lib = _gridops("getGridAvg", source, flags)
+    _chk(source, Grid, "Grid<Real>")
+    flags = _opt(flags, FlagGrid, "FlagGrid")
+    if flags is not None:
+        source._check_same(flags)
+    r = ctypes.c_float()
+    lib.call("mf_gridops_grid_avg", source.n, source.ptr, None if flags is None else flags.ptr, ctypes.byref(r), s.stream)
+    return r.value
+
+
+def _simple_noise(name, is_vec, flags, target, noise, scale, weight):
+    s, lib = _gridops(name, flags, target)
+    _chk(flags, FlagGrid, "FlagGrid")
+    _chk(target, VecGrid, "Grid<Vec3>") if is_vec else _chk(target, Grid, "Grid<Real>")
+    if not hasattr(noise, "_tile") or not hasattr(noise, "_params"):
+        raise RuntimeError("can't convert argument to WaveletNoiseField*")
+    weight = _opt(weight, Grid, "Grid<Real>")
+    flags._check_same(target)
+    if weight is not None:
+        flags._check_same(weight)
+    lib.call("mf_gridops_simple_noise", int(is_vec), flags.sx, flags.sy, flags.sz, flags.ptr, target.ptr, _ptr(noise._tile), noise._params(),
+             float(np.float32(scale)), None if weight is None else weight.ptr, s.stream)
+
+
+@plugin
+def applySimpleNoiseVec3(flags, target, noise, scale=1.0, weight=None):
+    """waveletturbulence.cpp:94-99 -> knApplySimpleNoiseVec3: target += noise.evaluateCurl(cell centre) * scale * weight on fluid cells; no
+    position scaling, no uv grid"""
+    _simple_noise("applySimpleNoiseVec3", True, flags, target, noise, scale, weight)
+
+
+@plugin
+def applySimpleNoiseReal(flags, target, noise, scale=1.0, weight=None):
+    """waveletturbulence.cpp:112-116 -> knApplySimpleNoiseReal: target += noise.evaluate(cell centre) * scale * weight on fluid cells"""
+    _simple_noise("applySimpleNoiseReal", False, flags, target, noise, scale, weight)
+
+
+def _legacy_potential(name, which, pot, flags, v, radius, normal, tauMin, tauMax, scaleFromManta, itype, jtype):
+    s, lib = _gridops(name, pot, flags, v)
+    _chk(pot, Grid, "Grid<Real>"); _chk(flags, FlagGrid, "FlagGrid"); _chk(v, MACGrid, "MACGrid")
+    if which == 1:
+        _chk(normal, VecGrid, "Grid<Vec3>")
+        pot._check_same(normal)
+    pot._check_same(flags); pot._check_same(v)
+    if not 0 <= int(radius) <= 16:
+        raise RuntimeError("%s: radius %d outside 0..16" % (name, int(radius)))
+    lib.call("mf_gridops_legacy_potential", which, pot.sx, pot.sy, pot.sz, pot.ptr, flags.ptr, v.ptr, None if normal is None else normal.ptr,
+             int(radius), float(np.float32(tauMin)), float(np.float32(tauMax)), float(np.float32(scaleFromManta)), int(itype), int(jtype), s.stream)
+
+
+@plugin
+def flipComputePotentialTrappedAir(pot, flags, v, radius, tauMin, tauMax, scaleFromManta, itype=1, jtype=1):
+    """secondaryparticles.cpp:579-587 (legacy; flipComputeSecondaryParticlePotentials is the combined form): the trapped-air potential
+    of the interior cells with flags & itype from their neighbours with flags & jtype; pot is cleared first.  Every itype cell must be
+    `radius` cells from each side and no neighbour may lie on the upper outermost layer: the reference reads outside the grid otherwise,
+    and here such a neighbour is skipped where its words leave the array."""
+    _legacy_potential("flipComputePotentialTrappedAir", 0, pot, flags, v, radius, None, tauMin, tauMax, scaleFromManta, itype, jtype)
+
+
+@plugin
+def flipComputePotentialKineticEnergy(pot, flags, v, tauMin, tauMax, scaleFromManta, itype=1):
+    """secondaryparticles.cpp:604-611 (legacy): 0.5 * 125 * |v|^2 of every cell with flags & itype, clamped between the thresholds"""
+    _legacy_potential("flipComputePotentialKineticEnergy", 2, pot, flags, v, 0, None, tauMin, tauMax, scaleFromManta, itype, 0)
+
+
+@plugin
+def flipComputePotentialWaveCrest(pot, flags, v, radius, normal, tauMin, tauMax, scaleFromManta, itype=1, jtype=1):
+    """secondaryparticles.cpp:650-658 (legacy): the wave-crest potential from the surface normals of flipComputeSurfaceNormals; the same
+    preconditions as flipComputePotentialTrappedAir"""
+    _legacy_potential("flipComputePotentialWaveCrest", 1, pot, flags, v, radius, normal, tauMin, tauMax, scaleFromManta, itype, jtype)
+
+
+@plugin
+def flipComputeSurfaceNormals(normal, phi):
+    """secondaryparticles.cpp:666-670 (legacy): normal = the central-difference gradient of phi on the interior, then normalised in
+    every cell (the border's own values included)"""
+    s, lib = _gridops("flipComputeSurfaceNormals", normal, phi)
+    _chk(normal, VecGrid, "Grid<Vec3>"); _chk(phi, Grid, "Grid<Real>")
+    normal._check_same(phi)
+    lib.call("mf_gridops_surface_normals", normal.sx, normal.sy, normal.sz, normal.ptr, phi.ptr, s.stream)
+
+
+@plugin
+def flipUpdateNeighborRatio(flags, neighborRatio, radius, itype=1, jtype=2):
+    """secondaryparticles.cpp:699-706 (legacy): the itype neighbours within radius over the neighbours that are not jtype (jtype means
+    "skip" here, default obstacle); NaN where there is no countable neighbour.  Every itype cell must be `radius` cells from each side."""
+    s, lib = _gridops("flipUpdateNeighborRatio", flags, neighborRatio)
+    _chk(flags, FlagGrid, "FlagGrid"); _chk(neighborRatio, Grid, "Grid<Real>")
+    flags._check_same(neighborRatio)
+    if not 0 <= int(radius) <= 16:
+        raise RuntimeError("flipUpdateNeighborRatio: radius %d outside 0..16" % int(radius))
+    lib.call("mf_gridops_neighbor_ratio", flags.sx, flags.sy, flags.sz, flags.ptr, neighborRatio.ptr, int(radius), int(itype), int(jtype), s.stream)
+
+
+@plugin
+def debugIntToReal(source, dest, factor=1.):
+    """flip.cpp:266-269: dest = Real(source) * factor"""
+    s, lib = _gridops("debugIntToReal", source, dest)
+    _chk(source, core.IntGrid, "Grid<int>"); _chk(dest, Grid, "Grid<Real>")
+    source._check_same(dest)
+    lib.call("mf_gridops_int_to_real", source.n, source.ptr, dest.ptr, float(np.float32(factor)), s.stream)
