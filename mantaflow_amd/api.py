@@ -27,7 +27,7 @@ from .plugins import (Timings, cgSolveDiffusion, getComponent, setComponent, res
                       getComp4d, setComp4d, grid4dMaxDiff, grid4dMaxDiffInt, grid4dMaxDiffVec3, grid4dMaxDiffVec4, setRegion4d,
                       setRegion4dVec4, getSliceFrom4d, getSliceFrom4dVec, interpolateGrid4d, interpolateGrid4dVec,
                       setNoisePdata, setNoisePdataVec3, setNoisePdataInt, addTestParts, checkSymmetry, checkSymmetryVec3, testInitGridWithPos,
-                      VPseedK41, markAsFixed, densityFromLevelset,
+                      VPseedK41, markAsFixed, densityFromLevelset, smoothMesh, killSmallComponents, lastMeshOpsStats,
                       copyArrayToGridReal, copyGridToArrayReal, copyArrayToGridFlag, copyGridToArrayFlag, copyArrayToGridLevelset,
                       copyGridToArrayLevelset, copyArrayToGridVec3, copyGridToArrayVec3, copyArrayToGridMAC, copyGridToArrayMAC,
                       copyArrayToPdataInt, copyPdataToArrayInt, copyArrayToPdataReal, copyPdataToArrayReal, copyArrayToPdataVec3,

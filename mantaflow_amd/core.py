@@ -1755,7 +1755,8 @@ class Mesh(PbClass):
     """Mesh, mesh.{h,cpp}: a triangle mesh resident on the solver's device.  Nodes are structure-of-arrays -- pos[3][ncap],
     normal[3][ncap], flags[ncap] -- and triangles c[3][tcap] (int32 node numbers) with flags[tcap]; the buffers grow geometrically and
     are reused from call to call.  createMesh (LevelsetGrid), advectInGrid and the node transforms are kernels of
-    include/open/manta_hip_mesh.h; save / load are host code.  No Mdata channels, corner tables or 1-ring lookups."""
+    include/open/manta_hip_mesh.h; save / load are host code.  The corner table and the 1-ring lookup are device tables of
+    include/open/manta_hip_meshops.h, cached until the triangle list changes (corners_numpy, ring_numpy).  No Mdata channels."""
     _cname_py, _cname_cpp, _T = "Mesh", "Mesh", ""
     NfNone, NfFixed, NfMarked, NfKillme, NfCollide = 0, 1, 2, 4, 8
     FfNone, FfDoubled, FfMarked = 0, 1, 2
@@ -1774,6 +1775,7 @@ class Mesh(PbClass):
         self._sdf_cap, self._sdf_off, self._sdf_stats = 0, None, None      # the source buffers of meshSDF (_sdf_reserve)
         self._sdf_f = torch.zeros(0, dtype=torch.float32, device=dev)
         self._sdf_i = torch.zeros(0, dtype=torch.int32, device=dev)
+        self._topo_gen, self._conn, self._conn_gen = 0, None, -1          # the connectivity tables and the generation they are of
 
     # --- storage ---
     def _reserve_nodes(self, n, keep=True):
@@ -1838,6 +1840,7 @@ class Mesh(PbClass):
         if normal.shape[0] != n or flags.shape[0] != n or triFlags.shape[0] != t:
             raise RuntimeError("Mesh::set_numpy: array lengths do not match")
         self.nn = self.nt = 0
+        self._topo_gen += 1
         self._reserve_nodes(n, keep=False)
         self._reserve_tris(t, keep=False)
         dev = self.parent.device
@@ -1858,6 +1861,7 @@ class Mesh(PbClass):
     def clear(self):
         """Mesh::clear, mesh.cpp:143-160 (the buffers stay)"""
         self.nn = self.nt = 0
+        self._topo_gen += 1
 
     def _not_implemented(self, what, why):
         raise RuntimeError("Mesh::%s: not implemented in mantaflow_amd (%s)" % (what, why))
@@ -2008,6 +2012,66 @@ class Mesh(PbClass):
         self._mesh_sdf(lib, who, sdf, meshSigma, cutoff)
         lib.call("mf_meshsdf_apply", grid.sx, grid.sy, grid.sz, sdf.ptr, None if respectFlags is None else respectFlags.ptr, kind, grid.ptr, iv,
                  v[0], v[1], v[2], g.stream)
+
+    # --- connectivity (mesh.cpp:238-292): include/open/manta_hip_meshops.h, DESIGN.md section 26 ---
+    def _meshops_scratch(self, nbytes):
+        """-> (tensor of at least nbytes, release): a grid of the solver's pool where one is large enough"""
+        s = self.parent
+        for kind, size in (("int", 4 * s.ncells), ("vec", 12 * s.ncells)):
+            if nbytes <= size:
+                t = s._alloc(kind, zero=False)
+                return t, lambda: s._release(kind, t)
+        return torch.empty(nbytes, dtype=torch.uint8, device=s.device), lambda: None
+
+    def _connectivity(self, lib, who):
+        """the corner table and the 1-ring lookup of the triangle list as device tensors, rebuilt only when the topology generation has
+        moved (clear, set_numpy, load, createMesh, killSmallComponents).  Refusals -- a triangle with a repeated node, a corner without
+        an opposite -- are raised before the cache is touched."""
+        from . import plugins
+        if self._conn is not None and self._conn_gen == self._topo_gen:
+            plugins._meshops_stats.update(singletons=0, multi=self._conn["multi"], rebuilt=False)
+            return self._conn
+        s, dev = self.parent, self.parent.device
+        nt, nn = self.nt, self.nn
+        conn = {"opposite": torch.empty(max(3 * nt, 1), dtype=torch.int32, device=dev),
+                "nodeOff": torch.empty(nn + 1, dtype=torch.int32, device=dev), "nodes": torch.empty(max(6 * nt, 1), dtype=torch.int32, device=dev),
+                "triOff": torch.empty(nn + 1, dtype=torch.int32, device=dev), "tris": torch.empty(max(3 * nt, 1), dtype=torch.int32, device=dev)}
+        need = ctypes.c_int64(0)
+        lib.call("mf_meshops_tmp_bytes", nt, nn, ctypes.byref(need))
+        tmp, release = self._meshops_scratch(need.value)
+        try:
+            out = (ctypes.c_int32 * 4)()
+            lib.call("mf_meshops_build", nt, self.tcap, _ptr(self.tri), nn, _ptr(conn["opposite"]), _ptr(conn["nodeOff"]), _ptr(conn["nodes"]),
+                     _ptr(conn["triOff"]), _ptr(conn["tris"]), _ptr(tmp), tmp.numel() * tmp.element_size(), out, s.stream)
+        finally:
+            release()
+        if out[3] >= 0:
+            raise RuntimeError("%s: triangle %d names a node outside the mesh's %d nodes" % (who, out[3], nn))
+        if out[2] >= 0:
+            raise RuntimeError("%s: triangle %d has a repeated node" % (who, out[2]))
+        plugins._meshops_stats.update(singletons=int(out[0]), multi=int(out[1]), rebuilt=True)
+        if out[0]:
+            raise RuntimeError("can't rebuild corners, index without an opposite")
+        conn["multi"] = int(out[1])
+        self._conn, self._conn_gen = conn, self._topo_gen
+        return conn
+
+    def corners_numpy(self):
+        """-> opposite[3 * numTris] int32, the corner table of Mesh::rebuildCorners (corner 3t + c is node c of triangle t)"""
+        from . import plugins
+        lib = plugins._extension_lib(self.parent, "Mesh::corners_numpy", "meshops")
+        conn = self._connectivity(lib, "Mesh::corners_numpy")
+        self.parent.sync()
+        return conn["opposite"][:3 * self.nt].cpu().numpy().copy()
+
+    def ring_numpy(self):
+        """-> (nodeOff[n + 1], nodes, triOff[n + 1], tris): the 1-ring lookup of Mesh::rebuildLookup as two CSR tables, ascending per node"""
+        from . import plugins
+        lib = plugins._extension_lib(self.parent, "Mesh::ring_numpy", "meshops")
+        conn = self._connectivity(lib, "Mesh::ring_numpy")
+        self.parent.sync()
+        node_off, tri_off = conn["nodeOff"].cpu().numpy().copy(), conn["triOff"].cpu().numpy().copy()
+        return node_off, conn["nodes"][:int(node_off[-1])].cpu().numpy().copy(), tri_off, conn["tris"][:int(tri_off[-1])].cpu().numpy().copy()
 
     def create(self, type=None, name="", **kw): self._not_implemented("create", "no Mdata channels")
     def getNodesDataPointer(self): self._not_implemented("getNodesDataPointer", "nodes are structure-of-arrays device buffers")

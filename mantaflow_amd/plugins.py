@@ -48,6 +48,8 @@ PYTHON() declarations; orchestration mirrors the reference function by function,
   flipComputePotentialTrappedAir / flipComputePotentialKineticEnergy / flipComputePotentialWaveCrest / flipComputeSurfaceNormals /
   flipUpdateNeighborRatio                     source/plugin/secondaryparticles.cpp:549-706
                                              (include/open/manta_hip_gridops.h; not on z-slab solvers)
+  smoothMesh / killSmallComponents            source/plugin/meshplugins.cpp:36-104, 563-619
+                                             (include/open/manta_hip_meshops.h; not on z-slab solvers)
 """
 import ctypes
 import functools
@@ -2228,6 +2230,101 @@ def markAsFixed(mesh, shape, exclusive=True):
     inside = np.asarray(shape._inside(pos[:, 0], pos[:, 1], pos[:, 2]))
     fl = np.where(inside, fl | core.Mesh.NfFixed, (fl & ~core.Mesh.NfFixed) if exclusive else fl).astype(np.int32)
     mesh.nflag[:mesh.nn] = torch.from_numpy(fl).to(mesh.nflag.device)
+
+
+# =========================================================================================================
+# mesh smoothing and component removal (plugin/meshplugins.cpp:36-104, 563-619): include/open/manta_hip_meshops.h, DESIGN.md section 26.
+# Both rest on the connectivity tables of core.Mesh._connectivity.  subdivideMesh is not implemented.
+# =========================================================================================================
+_meshops_stats = {}
+
+
+def lastMeshOpsStats():
+    """of the most recent connectivity build, smoothMesh or killSmallComponents: `singletons` / `multi` (edge groups of one corner / of
+    three or more), `rebuilt` (False: the cached tables were reused); after killSmallComponents `rounds` of labelling, `components`,
+    `nodes` and `tris` deleted; after smoothMesh `sums`, the 2 x 4 fp64 sums of computeCenterOfMass before and after the steps"""
+    return dict(_meshops_stats)
+
+
+def _real_arg(v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise RuntimeError("argument is not a float")
+    return float(np.float32(v))
+
+
+def _meshops_args(name, mesh):
+    if not isinstance(mesh, core.Mesh):
+        raise RuntimeError("can't convert argument to Mesh*")
+    return _extension_lib(mesh.parent, name, "meshops")
+
+
+@plugin
+def smoothMesh(mesh, strength, steps=1, minLength=1e-5):
+    """meshplugins.cpp:36-104: `steps` Jacobi sweeps over the 1-rings (one lane per node, ring walked ascending), then the rescale about
+    the centre of mass that restores the volume; the two centres of mass are fixed-tree fp64 sums read back as 2 x 32 bytes"""
+    lib = _meshops_args("smoothMesh", mesh)
+    strength, minLength = _real_arg(strength), _real_arg(minLength)
+    s = mesh.parent
+    str_ = float(min(np.float32(np.float32(s.getDt()) * np.float32(strength)), np.float32(1)))
+    conn = mesh._connectivity(lib, "smoothMesh")
+    _meshops_stats.pop("rounds", None)
+    need = ctypes.c_int64(0)
+    lib.call("mf_meshops_tmp_bytes", mesh.nt, mesh.nn, ctypes.byref(need))
+    tmp, release = mesh._meshops_scratch(need.value)
+    temp, release_temp = mesh._meshops_scratch(12 * max(mesh.nn, 1))
+    try:
+        def sums():
+            out = (ctypes.c_double * 4)()
+            lib.call("mf_meshops_volume_sums", mesh.nt, mesh.tcap, _ptr(mesh.tri), mesh.nn, mesh.ncap, _ptr(mesh.pos), _ptr(tmp),
+                     tmp.numel() * tmp.element_size(), out, s.stream)
+            return out
+        s0 = sums()
+        for _ in range(steps):
+            lib.call("mf_meshops_smooth_step", mesh.nn, mesh.ncap, _ptr(mesh.pos), _ptr(mesh.nflag), _ptr(conn["nodeOff"]), _ptr(conn["nodes"]),
+                     _ptr(conn["triOff"]), str_, minLength, _ptr(temp), s.stream)
+        s1 = sums()
+        sc = (ctypes.c_float * 7)()
+        lib.call("mf_meshops_rescale_scalars", s0, s1, sc)
+        lib.call("mf_meshops_rescale", mesh.nn, mesh.ncap, _ptr(mesh.pos), _ptr(mesh.nflag), sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], s.stream)
+        _meshops_stats["sums"] = (tuple(s0), tuple(s1))
+    finally:
+        release_temp()
+        release()
+
+
+@plugin
+def killSmallComponents(mesh, elements=10):
+    """meshplugins.cpp:563-619: the components of the triangle graph with fewer than `elements` triangles are removed with their nodes,
+    in the reference's order (removeTri over the tainted triangles descending, removeNodes over the nodes in order of first appearance).
+    Two refusals leave the mesh untouched where the reference does not: an edge with three or more triangles, and a node that a
+    killed and a kept component share."""
+    lib = _meshops_args("killSmallComponents", mesh)
+    s = mesh.parent
+    conn = mesh._connectivity(lib, "killSmallComponents")
+    if conn["multi"]:
+        raise RuntimeError("killSmallComponents: non-manifold edge")
+    need = ctypes.c_int64(0)
+    lib.call("mf_meshops_tmp_bytes", mesh.nt, mesh.nn, ctypes.byref(need))
+    tmp, release = mesh._meshops_scratch(need.value)
+    try:
+        out = (ctypes.c_int32 * 5)()
+        nbytes = tmp.numel() * tmp.element_size()
+        lib.call("mf_meshops_kill_plan", mesh.nt, mesh.tcap, _ptr(mesh.tri), mesh.nn, _ptr(conn["opposite"]), elements, _ptr(tmp), nbytes, out, s.stream)
+        rounds, comps, ktris, knodes, shared = (int(x) for x in out)
+        if shared >= 0:
+            raise RuntimeError("killSmallComponents: node %d is shared with a kept component" % shared)
+        _meshops_stats.pop("sums", None)
+        _meshops_stats.update(rounds=rounds, components=comps, tris=ktris, nodes=knodes)
+        if ktris == 0:
+            return
+        lib.call("mf_meshops_kill_apply", mesh.nt, mesh.tcap, _ptr(mesh.tri), _ptr(mesh.tflag), mesh.nn, mesh.ncap, _ptr(mesh.pos), _ptr(mesh.normal),
+                 _ptr(mesh.nflag), ktris, knodes, _ptr(tmp), nbytes, s.stream)
+        mesh.nt, mesh.nn = mesh.nt - ktris, mesh.nn - knodes
+        mesh._topo_gen += 1
+    finally:
+        release()
+    from . import api
+    api.mantaMsg("Killed small components : %d nodes, %d tris deleted." % (knodes, ktris), 0)      # the reference writes to cout: every debug level
 
 
 @plugin
