@@ -117,13 +117,21 @@ __device__ __forceinline__ int xcd_swizzle(int b, int nb) {
 // idx of block `blk` and its cell coordinates, with 32-bit unsigned divisions: exact because check_dim keeps n below 2^31 and
 // idx < n after the guard (64-bit divisions dominated the cheap sweeps).  Every entry that launches such a kernel has passed
 // check_dim.
+__device__ __forceinline__ void cell_ijk(const Dim& d, int64_t idx, int& i, int& j, int& k) {
+	const unsigned t = (unsigned)idx / (unsigned)d.sx;
+	i = (int)((unsigned)idx - t * (unsigned)d.sx);
+	j = (int)(t % (unsigned)d.sy);
+	k = (int)(t / (unsigned)d.sy);
+}
+// one thread per item of a flat range (cells of any layout, particles, points)
+#define ITEM_IDX(n)                                                   \
+	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x;    \
+	if (idx >= (n)) return;
 #define CELL_IJK_BLOCK(d, blk)                                          \
 	const int64_t idx = (blk) * (int64_t)BLOCK + threadIdx.x;           \
 	if (idx >= (d).n) return;                                           \
-	const unsigned t_ = (unsigned)idx / (unsigned)(d).sx;               \
-	const int i = (int)((unsigned)idx - t_ * (unsigned)(d).sx);         \
-	const int j = (int)(t_ % (unsigned)(d).sy);                         \
-	const int k = (int)(t_ / (unsigned)(d).sy);                         \
+	int i, j, k;                                                        \
+	cell_ijk(d, idx, i, j, k);                                          \
 	(void)i; (void)j; (void)k;
 #define CELL_IJK(d) CELL_IJK_BLOCK(d, blockIdx.x)
 // the cells of KERNEL(bnd = b); the complement of INTERIOR is the set of setBound(value, 0)
@@ -179,6 +187,8 @@ static inline int head_ws_cut(const char* who, void* tmp, int64_t tmp_bytes, int
 }
 // asynchronous copy of device memory to the given host address, then a stream synchronise (runtime.hip)
 int read_back(void* host, const void* dev, size_t bytes, hipStream_t st);
+// the same through the workspace's pinned page (bytes <= 4096), then on to host_out
+int read_scalars(Workspace* ws, const void* dev, size_t bytes, void* host_out, hipStream_t st);
 
 // ---- wave / block reductions (wave = 64 lanes) ---------------------------------------------------------
 __device__ __forceinline__ double wave_sum(double v) {
@@ -201,40 +211,7 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 	for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
 	return v;
 }
-// block-wide sum for blockDim.x == BLOCK (4 waves); result valid in thread 0
-__device__ __forceinline__ double block_sum(double v) {
-	__shared__ double sh[BLOCK / 64];
-	v = wave_sum(v);
-	const int w = threadIdx.x >> 6;
-	__syncthreads();
-	if ((threadIdx.x & 63) == 0) sh[w] = v;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		v = sh[0];
-		for (int i = 1; i < (int)(blockDim.x >> 6); i++) v += sh[i];
-	}
-	return v;
-}
-__device__ __forceinline__ void block_minmax(float& lo, float& hi) {
-	__shared__ float shl[BLOCK / 64], shh[BLOCK / 64];
-	lo = wave_min(lo);
-	hi = wave_max(hi);
-	const int w = threadIdx.x >> 6;
-	__syncthreads();
-	if ((threadIdx.x & 63) == 0) {
-		shl[w] = lo;
-		shh[w] = hi;
-	}
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		lo = shl[0];
-		hi = shh[0];
-		for (int i = 1; i < (int)(blockDim.x >> 6); i++) {
-			lo = fminf(lo, shl[i]);
-			hi = fmaxf(hi, shh[i]);
-		}
-	}
-}
+// (the block-wide folds of these, block_sum and block_minmax, are in reduce.h)
 
 // ---- partials that another workgroup of the SAME launch folds (the beta step as the tail of the backward MIC sweep): written with
 // one agent-scope (sc1, write-through) store whose completion the writer waits for before its workgroup reports in, read with
@@ -305,21 +282,6 @@ __device__ __forceinline__ void tail_minmax256(const float* fpart, int nb, float
 	}
 }
 
-// per-thread strided sum over per-block partials with 8 loads in flight (a plain loop serialises one
-// memory round trip per element); fixed order -> deterministic
-__device__ __forceinline__ double strided_sum(const double* __restrict__ p, int nb) {
-	double acc = 0.0;
-	int i = threadIdx.x;
-	const int S = blockDim.x;
-	for (; i + 7 * S < nb; i += 8 * S) {
-		const double v0 = p[i], v1 = p[i + S], v2 = p[i + 2 * S], v3 = p[i + 3 * S];
-		const double v4 = p[i + 4 * S], v5 = p[i + 5 * S], v6 = p[i + 6 * S], v7 = p[i + 7 * S];
-		acc += v0; acc += v1; acc += v2; acc += v3; acc += v4; acc += v5; acc += v6; acc += v7;
-	}
-	for (; i < nb; i += S) acc += p[i];
-	return acc;
-}
-
 // Non-temporal 16-byte accesses for data a kernel touches exactly once (streams that nothing re-reads from the caches): on gfx950 they
 // leave L2 / MALL to the operands that are re-read (stencil neighbours) -- ApplyMatrix 91 -> 69 us at 256^3 with A0 / Ai / flags loaded
 // and dst stored this way.
@@ -374,7 +336,7 @@ __device__ __forceinline__ SlabBeta slab_beta_stop(const double* __restrict__ g,
 	return b;
 }
 
-// ---- one-block finishers of per-block partials (runtime.hip: k_sum_finish, k_maxabs_finish64), queued on st
+// ---- one-block finishers of per-block partials (runtime.hip: instances of reduce.h's finisher), queued on st
 // *out = the sum of partials[0 .. nb) in the fixed order of strided_sum + block_sum
 int launch_sum_finish(int nb, const double* partials, double* out, hipStream_t st);
 // *out = max |.| of the nb min / max pairs in fpart; nothing when stopped (nullable) points to a non-zero word

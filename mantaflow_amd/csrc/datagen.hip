@@ -3,7 +3,7 @@
 // (source/util/simpleimage.cpp:20-67, 206-281), LaplaceOp and CurvatureOp (source/commonkernels.h:75-101).  DESIGN.md section 23 has
 // the rounding points.  The reference's Real is float; a literal such as 2.0, 0.5 or 1. makes its expression double until the next
 // store into a Real, which is what the casts below say.
-#include "common.h"
+#include "reduce.h"
 #include "../../include/open/manta_hip_datagen.h"
 #include <math.h>
 
@@ -80,15 +80,13 @@ int make_taps(const char* who, float sigma, int cap, Taps* t) {
 }
 
 // ---- centre of mass ---------------------------------------------------------------------------------------------------------------
-// per-workgroup partials of the four sums, partials[q * gridDim.x + block]; each term is the reference's fp32 product, the sums are
-// fp64 in the fixed order thread (strided over the grid) -> wavefront shuffles -> workgroup
-__global__ void __launch_bounds__(BLOCK) k_datagen_com(Dim d, const float* __restrict__ density, double* __restrict__ partials) {
-	double s[4] = {0.0, 0.0, 0.0, 0.0};
-	for (int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x; idx < d.n; idx += (int64_t)gridDim.x * BLOCK) {
-		const unsigned t_ = (unsigned)idx / (unsigned)d.sx;
-		const int i = (int)((unsigned)idx - t_ * (unsigned)d.sx);
-		const int j = (int)(t_ % (unsigned)d.sy);
-		const int k = (int)(t_ / (unsigned)d.sy);
+// the four sums: each term is the reference's fp32 product, the sums are fp64 in the fixed order of reduce.h
+struct ComTerm {
+	Dim d;
+	const float* density;
+	__device__ __forceinline__ void operator()(int64_t idx, double (&s)[4]) const {
+		int i, j, k;
+		cell_ijk(d, idx, i, j, k);
 		const float v = density[idx];
 		const float tx = v * ((float)i + 0.5f), ty = v * ((float)j + 0.5f), tz = v * ((float)k + 0.5f);
 		s[0] += (double)tx;
@@ -96,23 +94,15 @@ __global__ void __launch_bounds__(BLOCK) k_datagen_com(Dim d, const float* __res
 		s[2] += (double)tz;
 		s[3] += (double)v;
 	}
-#pragma unroll
-	for (int q = 0; q < 4; q++) {
-		const double r = block_sum(s[q]);
-		if (threadIdx.x == 0) partials[q * gridDim.x + blockIdx.x] = r;
-	}
-}
-
-// one workgroup: the four sums of the partials (strided_sum + block_sum), the `w > 1e-6f` test on the rounded weight, the quotients
-__global__ void __launch_bounds__(BLOCK) k_datagen_com_finish(int nb, const double* __restrict__ partials, float* __restrict__ out) {
-	double s[4];
-#pragma unroll
-	for (int q = 0; q < 4; q++) s[q] = block_sum(strided_sum(partials + (int64_t)q * nb, nb));
-	if (threadIdx.x == 0) {
+};
+// the `w > 1e-6f` test on the rounded weight, the quotients
+struct ComQuotients {
+	float* out;
+	__device__ __forceinline__ void operator()(const double (&s)[4]) const {
 		const bool divide = (float)s[3] > 1e-6f;
 		for (int q = 0; q < 3; q++) out[q] = divide ? (float)(s[q] / s[3]) : (float)s[q];
 	}
-}
+};
 
 // ---- projection -------------------------------------------------------------------------------------------------------------------
 // gridPrecompLight (simpleimage.cpp:206-215) for one cell: n = getGradient * -1. (grid.h:556-573; an exact negation), normalize
@@ -321,13 +311,9 @@ int mf_datagen_center_of_mass(int sx, int sy, int sz, const float* density, floa
 	Workspace* ws;
 	MF_TRY(get_workspace(&ws));
 	hipStream_t st = (hipStream_t)stream;
-	const int nb = blocks_for(d.n, BLOCK * 4, 2048);
-	hipLaunchKernelGGL(k_datagen_com, dim3(nb), dim3(BLOCK), 0, st, d, density, ws->partials);
-	hipLaunchKernelGGL(k_datagen_com_finish, dim3(1), dim3(BLOCK), 0, st, nb, ws->partials, (float*)ws->scalars);
-	MF_LAUNCH_CHECK();
-	MF_TRY(read_back(ws->host, ws->scalars, 3 * sizeof(float), st));
-	memcpy(out_host, ws->host, 3 * sizeof(float));
-	return 0;
+	const dim3 grid(blocks_for(d.n, BLOCK * 4, 2048));
+	MF_TRY((reduce<SumF64, 4>(d.n, grid, ComTerm{d, density}, ws->partials, ComQuotients{(float*)ws->scalars}, st)));
+	return read_scalars(ws, ws->scalars, 3 * sizeof(float), out_host, st);
 }
 
 int mf_datagen_project(int sx, int sy, int sz, const float* val, float* light, int shadeMode, float scale, int views, uint8_t* img,

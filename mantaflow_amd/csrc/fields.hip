@@ -2,6 +2,7 @@
 // with lanes along x; the per-cell bodies are in fields_cells.h.
 // Reference: plugin/fire.cpp, plugin/waves.cpp, grid.cpp:573-627, plugin/waveletturbulence.cpp:239-307, plugin/initplugins.cpp:478-503.
 #include "fields_cells.h"
+#include "reduce.h"
 #include "../../include/open/manta_hip_fields.h"
 
 using namespace mf;
@@ -28,26 +29,24 @@ __global__ void __launch_bounds__(BLOCK) k_sec_deriv_2d(Dim d, const float* __re
 	ret[idx] = (float)five_point(d, v, idx);
 }
 
-// knTotalSum, waves.cpp:46-47: per-block partials of the interior cells in a fixed order, folded by runtime.hip's scheme (block_sum,
-// then one finishing block) -- deterministic run to run
-__global__ void __launch_bounds__(BLOCK) k_interior_sum_partials(Dim d, const float* __restrict__ h, double* __restrict__ partials) {
-	double acc = 0.0;
-	for (int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x; idx < d.n; idx += (int64_t)gridDim.x * BLOCK) {
-		const unsigned t_ = (unsigned)idx / (unsigned)d.sx;
-		const int i = (int)((unsigned)idx - t_ * (unsigned)d.sx), j = (int)(t_ % (unsigned)d.sy), k = (int)(t_ / (unsigned)d.sy);
-		if (INTERIOR(d)) acc += (double)h[idx];
+// knTotalSum, waves.cpp:46-47: the fp64 sum of the interior cells in the fixed order of reduce.h; the epilogue leaves the sum as a
+// double and, one double further, rounded to Real
+struct InteriorTerm {
+	Dim d;
+	const float* h;
+	__device__ __forceinline__ void operator()(int64_t idx, double (&acc)[1]) const {
+		int i, j, k;
+		cell_ijk(d, idx, i, j, k);
+		if (INTERIOR(d)) acc[0] += (double)h[idx];
 	}
-	acc = block_sum(acc);
-	if (threadIdx.x == 0) partials[blockIdx.x] = acc;
-}
-__global__ void __launch_bounds__(BLOCK) k_interior_sum_finish(int nb, const double* __restrict__ partials, double* __restrict__ sum, float* __restrict__ sum32) {
-	double acc = strided_sum(partials, nb);
-	acc = block_sum(acc);
-	if (threadIdx.x == 0) {
-		*sum = acc;
-		*sum32 = (float)acc;
+};
+struct StoreSum32 {
+	double* sum;
+	__device__ __forceinline__ void operator()(const double (&acc)[1]) const {
+		sum[0] = acc[0];
+		*(float*)(sum + 1) = (float)acc[0];
 	}
-}
+};
 // `Real factor = target / ts.sum; height.multConst(factor)`, waves.cpp:58-59: a double quotient rounded once, from the device scalar
 __global__ void __launch_bounds__(BLOCK) k_scale_to(int64_t n, float* __restrict__ h, float target, const double* __restrict__ sum) {
 	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
@@ -87,12 +86,7 @@ __global__ void __launch_bounds__(BLOCK) k_extrapolate_pass(Dim d, const int32_t
 }
 
 int interior_sum(const Dim& d, const float* h, Workspace* ws, hipStream_t st) {
-	const int nb = blocks_for(d.n, BLOCK * 8, 1024);
-	double* sum = (double*)ws->scalars;
-	hipLaunchKernelGGL(k_interior_sum_partials, dim3(nb), dim3(BLOCK), 0, st, d, h, ws->partials);
-	hipLaunchKernelGGL(k_interior_sum_finish, dim3(1), dim3(BLOCK), 0, st, nb, ws->partials, sum, (float*)(sum + 1));
-	MF_LAUNCH_CHECK();
-	return 0;
+	return reduce<SumF64, 1>(d.n, dim3(blocks_for(d.n, BLOCK * 8, 1024)), InteriorTerm{d, h}, ws->partials, StoreSum32{(double*)ws->scalars}, st);
 }
 
 }  // namespace
@@ -135,9 +129,7 @@ int mf_fields_total_sum(int sx, int sy, int sz, const float* h, float* sum_host,
 	MF_TRY(get_workspace(&ws));
 	const hipStream_t st = (hipStream_t)stream;
 	MF_TRY(interior_sum(mkdim(sx, sy, sz), h, ws, st));
-	MF_TRY(read_back(ws->host, (double*)ws->scalars + 1, sizeof(float), st));
-	memcpy(sum_host, ws->host, sizeof(float));
-	return 0;
+	return read_scalars(ws, (double*)ws->scalars + 1, sizeof(float), sum_host, st);
 }
 
 int mf_fields_normalize_sum(int sx, int sy, int sz, float* h, float target, void* stream) {
@@ -179,10 +171,7 @@ int mf_fields_set_uv_weight(int64_t n, float* uv, float w, void* stream) {
 int mf_fields_get_uv_weight(const float* uv, float* w_host, void* stream) {
 	Workspace* ws;
 	MF_TRY(get_workspace(&ws));
-	const hipStream_t st = (hipStream_t)stream;
-	MF_TRY(read_back(ws->host, uv, sizeof(float), st));
-	memcpy(w_host, ws->host, sizeof(float));
-	return 0;
+	return read_scalars(ws, uv, sizeof(float), w_host, (hipStream_t)stream);
 }
 
 int mf_fields_extrapolate_mark(int64_t n, const int32_t* flags, int32_t* tmp, int flagFrom, void* stream) {

@@ -2,6 +2,8 @@
 // along blockIdx.y; the per-cell bodies are in grid4d_cells.h.
 // Reference: grid4d.h, grid4d.cpp, util/vector4d.h:393-442.
 #include "grid4d_cells.h"
+#include "reduce.h"
+#include <type_traits>
 #include "wavelet_noise_vec.h"
 #include "../../include/open/manta_hip_grid4d.h"
 
@@ -17,12 +19,8 @@ struct I4 {
 	int32_t v[4];
 };
 
-#define FLAT_IDX(n)                                                   \
-	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x;    \
-	if (idx >= (n)) return;
-
 __global__ void __launch_bounds__(BLOCK) k_vec_const(int op, int64_t n, float* __restrict__ me, F4 v) {
-	FLAT_IDX(n)
+	ITEM_IDX(n)
 	const int c = blockIdx.y;
 	float* p = me + c * n + idx;
 	if (op == 0) *p = v.v[c];
@@ -32,140 +30,69 @@ __global__ void __launch_bounds__(BLOCK) k_vec_const(int op, int64_t n, float* _
 
 // me may be other (a.addScaled(a, f)): no __restrict__
 __global__ void __launch_bounds__(BLOCK) k_vec_scaled_add(int64_t n, float* me, const float* other, F4 f) {
-	FLAT_IDX(n)
+	ITEM_IDX(n)
 	const int c = blockIdx.y;
 	me[c * n + idx] += f.v[c] * other[c * n + idx];
 }
 
 __global__ void __launch_bounds__(BLOCK) k_int_const(int op, int64_t n, int32_t* __restrict__ me, int32_t v) {
-	FLAT_IDX(n)
+	ITEM_IDX(n)
 	me[idx] = op == 1 ? add_i(me[idx], v) : mul_i(me[idx], v);
 }
 
 // me may be other (a.add(a)): no __restrict__
 __global__ void __launch_bounds__(BLOCK) k_int_binary(int op, int64_t n, int32_t* me, const int32_t* other, int32_t factor) {
-	FLAT_IDX(n)
+	ITEM_IDX(n)
 	const int32_t a = me[idx], b = other[idx];
 	me[idx] = op == 0 ? add_i(a, b) : op == 1 ? sub_i(a, b) : op == 2 ? mul_i(a, b) : op == 3 ? add_i(a, mul_i(factor, b)) : safe_div_i(a, b);
 }
 
 __global__ void __launch_bounds__(BLOCK) k_int_clamp(int64_t n, int32_t* __restrict__ me, int32_t lo, int32_t hi) {
-	FLAT_IDX(n)
+	ITEM_IDX(n)
 	me[idx] = clamp_i(me[idx], lo, hi);
 }
 
-// ---- reductions: per-block partials over a grid-stride loop, then one finishing block; min / max are order-free ----
-__device__ __forceinline__ void block_minmax_i(int& lo, int& hi) {
-	__shared__ int shl[BLOCK / 64], shh[BLOCK / 64];
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) {
-		lo = min(lo, __shfl_down(lo, o, 64));
-		hi = max(hi, __shfl_down(hi, o, 64));
-	}
-	const int w = threadIdx.x >> 6;
-	__syncthreads();
-	if ((threadIdx.x & 63) == 0) {
-		shl[w] = lo;
-		shh[w] = hi;
-	}
-	__syncthreads();
-	if (threadIdx.x == 0)
-		for (int q = 0; q < BLOCK / 64; q++) {
-			lo = min(lo, shl[q]);
-			hi = max(hi, shh[q]);
-		}
-}
-__device__ __forceinline__ double block_max_d(double v) {
-	__shared__ double sh[BLOCK / 64];
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-	const int w = threadIdx.x >> 6;
-	__syncthreads();
-	if ((threadIdx.x & 63) == 0) sh[w] = v;
-	__syncthreads();
-	if (threadIdx.x == 0)
-		for (int q = 0; q < BLOCK / 64; q++) v = fmax(v, sh[q]);
-	return v;
-}
-
-// pass 0: a is the grid (n cells); pass 1: a is the nb pairs of partials
-__global__ void __launch_bounds__(BLOCK) k_int_min_max(int pass, int64_t n, const int32_t* __restrict__ a, int32_t* __restrict__ out) {
-	int lo = INT32_MAX, hi = INT32_MIN;
-	for (int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * BLOCK) {
-		lo = min(lo, pass ? a[2 * idx] : a[idx]);
-		hi = max(hi, pass ? a[2 * idx + 1] : a[idx]);
-	}
-	block_minmax_i(lo, hi);
-	if (threadIdx.x == 0) {
-		out[2 * blockIdx.x] = lo;
-		out[2 * blockIdx.x + 1] = hi;
-	}
-}
-
-__global__ void __launch_bounds__(BLOCK) k_norm_min_max(int ncomp, int64_t n, int64_t stride, const float* __restrict__ a, float* __restrict__ out) {
-	float lo = FLT_MAX, hi = -FLT_MAX;
-	for (int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * BLOCK) {
-		const float s = norm_square(a, stride, idx, ncomp);
-		lo = fminf(lo, s);
-		hi = fmaxf(hi, s);
-	}
-	block_minmax(lo, hi);
-	if (threadIdx.x == 0) {
-		out[2 * blockIdx.x] = lo;
-		out[2 * blockIdx.x + 1] = hi;
-	}
-}
-__global__ void __launch_bounds__(BLOCK) k_min_max_finish(int nb, const float* __restrict__ part, float* __restrict__ out) {
-	float lo = FLT_MAX, hi = -FLT_MAX;
-	for (int q = threadIdx.x; q < nb; q += BLOCK) {
-		lo = fminf(lo, part[2 * q]);
-		hi = fmaxf(hi, part[2 * q + 1]);
-	}
-	block_minmax(lo, hi);
-	if (threadIdx.x == 0) {
-		out[0] = lo;
-		out[1] = hi;
-	}
-}
-
-__global__ void __launch_bounds__(BLOCK) k_max_diff(int ncomp, int isInt, int64_t n, const void* __restrict__ a, const void* __restrict__ b,
-                                                    double* __restrict__ out) {
-	double m = 0.;
-	for (int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * BLOCK)
-		m = fmax(m, cell_diff(a, b, n, idx, ncomp, isInt));
-	m = block_max_d(m);
-	if (threadIdx.x == 0) out[blockIdx.x] = m;
-}
-__global__ void __launch_bounds__(BLOCK) k_max_finish(int nb, const double* __restrict__ part, double* __restrict__ out) {
-	double m = 0.;
-	for (int q = threadIdx.x; q < nb; q += BLOCK) m = fmax(m, part[q]);
-	m = block_max_d(m);
-	if (threadIdx.x == 0) *out = m;
-}
+// ---- the terms of the reductions (reduce.h) ----
+struct IntMinMaxTerm {
+	const int32_t* a;
+	__device__ __forceinline__ void operator()(int64_t idx, Pair<int32_t> (&acc)[1]) const { MinMaxI32::fold(acc[0], a[idx]); }
+};
+struct NormMinMaxTerm {
+	int ncomp;
+	int64_t stride;
+	const float* a;
+	__device__ __forceinline__ void operator()(int64_t idx, Pair<float> (&acc)[1]) const { MinMaxF32::fold(acc[0], norm_square(a, stride, idx, ncomp)); }
+};
+struct MaxDiffTerm {
+	int ncomp, isInt;
+	int64_t n;
+	const void *a, *b;
+	__device__ __forceinline__ void operator()(int64_t idx, double (&acc)[1]) const { MaxF64::fold(acc[0], cell_diff(a, b, n, idx, ncomp, isInt)); }
+};
 
 // ---- boundaries, region, slices, components ----
 __global__ void __launch_bounds__(BLOCK) k_set_bound(Dim4 d, int32_t* __restrict__ grid, I4 v, int w) {
-	FLAT_IDX(d.n)
+	ITEM_IDX(d.n)
 	if (is_bound(d, cell_of(d, idx), w)) grid[blockIdx.y * d.n + idx] = v.v[blockIdx.y];
 }
 // in place: the source of a boundary cell is no boundary cell (the entry refuses axes below 2w+3), so nothing read here is written here
 __global__ void __launch_bounds__(BLOCK) k_set_bound_neumann(Dim4 d, int32_t* grid, int w) {
-	FLAT_IDX(d.n)
+	ITEM_IDX(d.n)
 	const int64_t src = neumann_source(d, cell_of(d, idx), w);
 	if (src >= 0) grid[blockIdx.y * d.n + idx] = grid[blockIdx.y * d.n + src];
 }
 __global__ void __launch_bounds__(BLOCK) k_set_region(Dim4 d, float* __restrict__ grid, F4 start, F4 end, F4 v) {
-	FLAT_IDX(d.n)
+	ITEM_IDX(d.n)
 	if (in_region(cell_of(d, idx), start.v, end.v)) grid[blockIdx.y * d.n + idx] = v.v[blockIdx.y];
 }
 __global__ void __launch_bounds__(BLOCK) k_copy_plane(int64_t n, const float* __restrict__ src, float* __restrict__ dst) {
-	FLAT_IDX(n)
+	ITEM_IDX(n)
 	dst[idx] = src[idx];
 }
 // one thread per cell (i, j, k) of the source's 3-D slab; blockIdx.y is the component of the Vec4 form
 __global__ void __launch_bounds__(BLOCK)
 k_get_slice(Dim4 d, const float* __restrict__ src, int srct, int dx, int dy, int dz, float* __restrict__ dst, float* __restrict__ dstt) {
-	FLAT_IDX(d.T)
+	ITEM_IDX(d.T)
 	const int64_t di = slice_target(cell_of(d, idx), dx, dy, dz);
 	if (di < 0) return;
 	const int comp = blockIdx.y;
@@ -176,7 +103,7 @@ k_get_slice(Dim4 d, const float* __restrict__ src, int srct, int dx, int dy, int
 }
 
 __global__ void __launch_bounds__(BLOCK) k_interpolate(Dim4 td, float* __restrict__ target, Dim4 sd, const float* __restrict__ source, F4 fac, F4 off) {
-	FLAT_IDX(td.n)
+	ITEM_IDX(td.n)
 	target[blockIdx.y * td.n + idx] = interpolate_cell(sd, source + blockIdx.y * sd.n, cell_of(td, idx), fac.v, off.v);
 }
 
@@ -185,59 +112,39 @@ struct I3 {
 	int32_t v[3];
 };
 __global__ void __launch_bounds__(BLOCK) k_pdata_set_flag(int64_t n, int64_t stride, int32_t* __restrict__ me, I3 w, const int32_t* __restrict__ t, int itype) {
-	FLAT_IDX(n)
+	ITEM_IDX(n)
 	if (t[idx] & itype) me[blockIdx.y * stride + idx] = w.v[blockIdx.y];
 }
 __global__ void __launch_bounds__(BLOCK) k_pdata_clamp_side(int side, int isInt, int64_t n, int64_t stride, int32_t* __restrict__ me, int32_t v) {
-	FLAT_IDX(n)
+	ITEM_IDX(n)
 	int32_t* p = me + blockIdx.y * stride + idx;
 	if (isInt) *p = clamp_side<int32_t>(side, v, *p);
 	else *(float*)p = clamp_side<float>(side, __int_as_float(v), *(float*)p);
 }
-// per-block partials of component blockIdx.y at part[blockIdx.y * gridDim.x + blockIdx.x]; int sums are exact in 64 bits
-__global__ void __launch_bounds__(BLOCK)
-k_pdata_sum(int what, int isInt, int ncomp, int64_t n, int64_t stride, const void* __restrict__ a, const int32_t* __restrict__ t, int itype,
-            double* __restrict__ part) {
-	const int c = blockIdx.y;
-	const bool exact = isInt && what == 0;
-	double acc = 0.0;
-	long long iacc = 0;
-	for (int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * BLOCK) {
-		if (what == 0 && t && !(t[idx] & itype)) continue;
-		if (exact) iacc += ((const int32_t*)a)[idx];
-		else acc += sum_term(what, isInt, ncomp, c, a, stride, idx);
+// one term of component blockIdx.y; EXACT: the int sum (what == 0 of an int array), folded as 64-bit integers, which is exact whatever
+// the order (as doubles the two halves of a large sum would lose bits)
+template <bool EXACT>
+struct PdataSumTerm {
+	int what, isInt, ncomp;
+	int64_t stride;
+	const void* a;
+	const int32_t* t;
+	int itype;
+	__device__ __forceinline__ void operator()(int64_t idx, std::conditional_t<EXACT, long long, double> (&acc)[1]) const {
+		if (what == 0 && t && !(t[idx] & itype)) return;
+		if (EXACT) acc[0] += ((const int32_t*)a)[idx];
+		else acc[0] += sum_term(what, isInt, ncomp, blockIdx.y, a, stride, idx);
 	}
-	if (exact) {
-		// 64-bit integer sums are exact whatever the order: fold the two halves as doubles would lose bits, so fold as integers
-		__shared__ long long shi[BLOCK / 64];
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) iacc += __shfl_down(iacc, o, 64);
-		if ((threadIdx.x & 63) == 0) shi[threadIdx.x >> 6] = iacc;
-		__syncthreads();
-		if (threadIdx.x == 0) {
-			for (int q = 1; q < BLOCK / 64; q++) iacc += shi[q];
-			((long long*)part)[c * gridDim.x + blockIdx.x] = iacc;
-		}
-	} else {
-		acc = block_sum(acc);
-		if (threadIdx.x == 0) part[c * gridDim.x + blockIdx.x] = acc;
-	}
-}
-// one block per component: out[c] = the fp32 (or, exact, the wrapped int32) of the folded partials
-__global__ void __launch_bounds__(BLOCK) k_pdata_sum_finish(int exact, int nb, const double* __restrict__ part, int32_t* __restrict__ out) {
-	const int c = blockIdx.x;
-	if (exact) {
-		if (threadIdx.x == 0) {
-			long long s = 0;
-			for (int q = 0; q < nb; q++) s += ((const long long*)part)[c * nb + q];
-			out[c] = (int32_t)(uint32_t)(unsigned long long)s;
-		}
-		return;
-	}
-	double acc = strided_sum(part + c * nb, nb);
-	acc = block_sum(acc);
-	if (threadIdx.x == 0) out[c] = __float_as_int((float)acc);
-}
+};
+// out[c] = the fp32 of the folded partials of component c, or the wrapped int32 of the exact sum
+struct StorePdataSum {
+	int32_t* out;
+	__device__ __forceinline__ void operator()(const double (&acc)[1]) const { out[blockIdx.x] = __float_as_int((float)acc[0]); }
+	__device__ __forceinline__ void operator()(const long long (&acc)[1]) const { out[blockIdx.x] = (int32_t)(uint32_t)(unsigned long long)acc[0]; }
+};
+
+// the grid of the reductions over n items
+dim3 grid_for(int64_t n) { return dim3(blocks_for(n, BLOCK * 8, 1024)); }
 
 int check_pdata(const char* who, int64_t n, int64_t stride, int ncomp) {
 	if (n < 0 || n >= (int64_t)1 << 31 || stride < n) return fail("%s: invalid size %lld / stride %lld", who, (long long)n, (long long)stride);
@@ -249,7 +156,7 @@ int check_pdata(const char* who, int64_t n, int64_t stride, int ncomp) {
 __global__ void __launch_bounds__(BLOCK)
 k_pdata_set_noise(int kind, int64_t n, int64_t stride, void* __restrict__ pd, int64_t pstride, const float* __restrict__ pos,
                   const float* __restrict__ tile, NoiseParams P, float scale) {
-	FLAT_IDX(n)
+	ITEM_IDX(n)
 	const float x = pos[idx], y = pos[pstride + idx], z = pos[2 * pstride + idx];
 	if (kind == 2) {
 		float v[3];
@@ -338,14 +245,11 @@ int mf_grid4d_int_min_max(int64_t n, const int32_t* a, int32_t* min_host, int32_
 	Workspace* ws;
 	MF_TRY(get_workspace(&ws));
 	const hipStream_t st = (hipStream_t)stream;
-	const int nb = blocks_for(n, BLOCK * 8, 1024);
-	int32_t* part = (int32_t*)ws->fpartials;
-	hipLaunchKernelGGL(k_int_min_max, dim3(nb), dim3(BLOCK), 0, st, 0, n, a, part);
-	hipLaunchKernelGGL(k_int_min_max, dim3(1), dim3(BLOCK), 0, st, 1, (int64_t)nb, part, (int32_t*)ws->scalars);
-	MF_LAUNCH_CHECK();
-	MF_TRY(read_back(ws->host, ws->scalars, 2 * sizeof(int32_t), st));
-	memcpy(min_host, ws->host, sizeof(int32_t));
-	memcpy(max_host, (char*)ws->host + sizeof(int32_t), sizeof(int32_t));
+	Pair<int32_t>*part = (Pair<int32_t>*)ws->fpartials, *out = (Pair<int32_t>*)ws->scalars, r;
+	MF_TRY((reduce<MinMaxI32, 1>(n, grid_for(n), IntMinMaxTerm{a}, part, Store<Pair<int32_t>>{out}, st)));
+	MF_TRY(read_scalars(ws, out, sizeof(r), &r, st));
+	*min_host = r.lo;
+	*max_host = r.hi;
 	return 0;
 }
 
@@ -356,13 +260,11 @@ int mf_grid4d_norm_min_max(int ncomp, int64_t n, int64_t stride, const float* a,
 	Workspace* ws;
 	MF_TRY(get_workspace(&ws));
 	const hipStream_t st = (hipStream_t)stream;
-	const int nb = blocks_for(n, BLOCK * 8, 1024);
-	hipLaunchKernelGGL(k_norm_min_max, dim3(nb), dim3(BLOCK), 0, st, ncomp, n, stride, a, ws->fpartials);
-	hipLaunchKernelGGL(k_min_max_finish, dim3(1), dim3(BLOCK), 0, st, nb, ws->fpartials, (float*)ws->scalars);
-	MF_LAUNCH_CHECK();
-	MF_TRY(read_back(ws->host, ws->scalars, 2 * sizeof(float), st));
-	memcpy(min_host, ws->host, sizeof(float));
-	memcpy(max_host, (char*)ws->host + sizeof(float), sizeof(float));
+	Pair<float>*part = (Pair<float>*)ws->fpartials, *out = (Pair<float>*)ws->scalars, r;
+	MF_TRY((reduce<MinMaxF32, 1>(n, grid_for(n), NormMinMaxTerm{ncomp, stride, a}, part, Store<Pair<float>>{out}, st)));
+	MF_TRY(read_scalars(ws, out, sizeof(r), &r, st));
+	*min_host = r.lo;
+	*max_host = r.hi;
 	return 0;
 }
 
@@ -373,13 +275,8 @@ int mf_grid4d_max_diff(int ncomp, int isInt, int64_t n, const void* a, const voi
 	Workspace* ws;
 	MF_TRY(get_workspace(&ws));
 	const hipStream_t st = (hipStream_t)stream;
-	const int nb = blocks_for(n, BLOCK * 8, 1024);
-	hipLaunchKernelGGL(k_max_diff, dim3(nb), dim3(BLOCK), 0, st, ncomp, isInt, n, a, b, ws->partials);
-	hipLaunchKernelGGL(k_max_finish, dim3(1), dim3(BLOCK), 0, st, nb, ws->partials, (double*)ws->scalars);
-	MF_LAUNCH_CHECK();
-	MF_TRY(read_back(ws->host, ws->scalars, sizeof(double), st));
-	memcpy(result_host, ws->host, sizeof(double));
-	return 0;
+	MF_TRY((reduce<MaxF64, 1>(n, grid_for(n), MaxDiffTerm{ncomp, isInt, n, a, b}, ws->partials, Store<double>{(double*)ws->scalars}, st)));
+	return read_scalars(ws, ws->scalars, sizeof(double), result_host, st);
 }
 
 int mf_grid4d_set_bound(int sx, int sy, int sz, int st, void* grid, int ncomp, int32_t v0, int32_t v1, int32_t v2, int32_t v3, int w,
@@ -489,13 +386,13 @@ int mf_grid4d_pdata_sum(int what, int isInt, int ncomp, int64_t n, int64_t strid
 	Workspace* ws;
 	MF_TRY(get_workspace(&ws));
 	const hipStream_t st = (hipStream_t)stream;
-	const int nb = blocks_for(n, BLOCK * 8, 1024);
-	hipLaunchKernelGGL(k_pdata_sum, dim3(nb, nres), dim3(BLOCK), 0, st, what, isInt, ncomp, n, stride, a, t, itype, ws->partials);
-	hipLaunchKernelGGL(k_pdata_sum_finish, dim3(nres), dim3(BLOCK), 0, st, (int)(isInt && what == 0), nb, ws->partials, (int32_t*)ws->scalars);
-	MF_LAUNCH_CHECK();
-	MF_TRY(read_back(ws->host, ws->scalars, 4 * nres, st));
-	memcpy(result_host, ws->host, 4 * nres);
-	return 0;
+	const dim3 grid(grid_for(n).x, nres);
+	const StorePdataSum out = {(int32_t*)ws->scalars};
+	if (isInt && what == 0)
+		MF_TRY((reduce<SumI64, 1>(n, grid, PdataSumTerm<true>{what, isInt, ncomp, stride, a, t, itype}, (long long*)ws->partials, out, st)));
+	else
+		MF_TRY((reduce<SumF64, 1>(n, grid, PdataSumTerm<false>{what, isInt, ncomp, stride, a, t, itype}, ws->partials, out, st)));
+	return read_scalars(ws, ws->scalars, 4 * nres, result_host, st);
 }
 
 int mf_grid4d_pdata_set_noise(int kind, int64_t n, int64_t stride, void* pd, int64_t pstride, const float* pos, const float* tile,

@@ -2,7 +2,7 @@
 // reductions in the project's fixed order, and bandwidth-bound element-wise / stencil kernels, one thread per cell (lanes along x).
 // Reference: grid.cpp:251-268, 322-348, 387-418, 496-536, 564-571, 717-739, 1013-1033, plugin/extforces.cpp:24-43, 376-407,
 // fastmarch.cpp:434-468, 525-557, plugin/initplugins.cpp:110-128, 154-183, plugin/flip.cpp:266-269.
-#include "common.h"
+#include "reduce.h"
 #include "vec3_math.h"
 #include "wavelet_noise_vec.h"
 #include "../../include/open/manta_hip_gridops.h"
@@ -85,9 +85,11 @@ __device__ __forceinline__ float norm3(float x, float y, float z) {
 
 // ---- loop_calcL1Grid / loop_calcL2Grid, grid.cpp:390-409: the terms; the sum is fp64 ----
 template <int KIND, int L2>
-__global__ void __launch_bounds__(BLOCK) k_norm_partial(Dim d, Range r, const void* __restrict__ a, double* __restrict__ partials) {
-	double acc = 0.0;
-	for (int64_t q = blockIdx.x * (int64_t)BLOCK + threadIdx.x; q < r.m; q += (int64_t)gridDim.x * BLOCK) {
+struct NormTerm {
+	Dim d;
+	Range r;
+	const void* a;
+	__device__ __forceinline__ void operator()(int64_t q, double (&acc)[1]) const {
 		const int64_t idx = range_cell(d, r, q);
 		float term;
 		if (KIND == 0) {
@@ -103,28 +105,20 @@ __global__ void __launch_bounds__(BLOCK) k_norm_partial(Dim d, Range r, const vo
 			const float x = f[idx], y = f[d.n + idx], z = f[2 * d.n + idx];
 			term = L2 ? x * x + y * y + z * z : norm3(x, y, z);
 		}
-		acc += (double)term;
+		acc[0] += (double)term;
 	}
-	acc = block_sum(acc);
-	if (threadIdx.x == 0) partials[blockIdx.x] = acc;
-}
+};
 
-// ---- knGridTotalSum + knCountFluidCells, grid.cpp:718-725: partials[b] the sum, partials[nb + b] the count (exact in fp64) ----
-__global__ void __launch_bounds__(BLOCK)
-k_avg_partial(int64_t n, const float* __restrict__ a, const int32_t* __restrict__ flags, double* __restrict__ partials) {
-	double acc = 0.0, cnt = 0.0;
-	for (int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * BLOCK) {
-		if (flags && !(flags[idx] & MF_FLUID)) continue;
-		acc += (double)a[idx];
-		cnt += 1.0;
+// ---- knGridTotalSum + knCountFluidCells, grid.cpp:718-725: the sum and the count (exact in fp64) ----
+struct AvgTerm {
+	const float* a;
+	const int32_t* flags;
+	__device__ __forceinline__ void operator()(int64_t idx, double (&acc)[2]) const {
+		if (flags && !(flags[idx] & MF_FLUID)) return;
+		acc[0] += (double)a[idx];
+		acc[1] += 1.0;
 	}
-	acc = block_sum(acc);
-	cnt = block_sum(cnt);
-	if (threadIdx.x == 0) {
-		partials[blockIdx.x] = acc;
-		partials[gridDim.x + blockIdx.x] = cnt;
-	}
-}
+};
 
 // ---- knJoinReal / knJoinInt / knJoinVec, grid.cpp:258-268: std::max(a, b) is (a < b) ? b : a, std::min(a, b) is (b < a) ? b : a ----
 template <class T>
@@ -470,9 +464,11 @@ int check_n(const char* who, int64_t n) {
 }
 
 template <int KIND>
-void launch_norm(int l2, int nb, hipStream_t st, const Dim& d, const Range& r, const void* a, double* partials) {
-	if (l2) hipLaunchKernelGGL((k_norm_partial<KIND, 1>), dim3(nb), dim3(BLOCK), 0, st, d, r, a, partials);
-	else hipLaunchKernelGGL((k_norm_partial<KIND, 0>), dim3(nb), dim3(BLOCK), 0, st, d, r, a, partials);
+int reduce_norm(int l2, const Dim& d, const Range& r, const void* a, Workspace* ws, hipStream_t st) {
+	const dim3 grid(blocks_for(r.m, BLOCK * 8, 1024));
+	const Store<double> out = {(double*)ws->scalars};
+	if (l2) return reduce<SumF64, 1>(r.m, grid, NormTerm<KIND, 1>{d, r, a}, ws->partials, out, st);
+	return reduce<SumF64, 1>(r.m, grid, NormTerm<KIND, 0>{d, r, a}, ws->partials, out, st);
 }
 
 }  // namespace
@@ -529,15 +525,9 @@ int mf_gridops_norm(int kind, int l2, int sx, int sy, int sz, int bnd, const voi
 	Workspace* ws;
 	MF_TRY(get_workspace(&ws));
 	const hipStream_t st = (hipStream_t)stream;
-	const int nb = blocks_for(r.m, BLOCK * 8, 1024);
-	if (kind == 0) launch_norm<0>(l2, nb, st, d, r, a, ws->partials);
-	else if (kind == 1) launch_norm<1>(l2, nb, st, d, r, a, ws->partials);
-	else launch_norm<2>(l2, nb, st, d, r, a, ws->partials);
-	MF_LAUNCH_CHECK();
-	MF_TRY(launch_sum_finish(nb, ws->partials, (double*)ws->scalars, st));
-	MF_TRY(read_back(ws->host, ws->scalars, sizeof(double), st));
+	MF_TRY(kind == 0 ? reduce_norm<0>(l2, d, r, a, ws, st) : kind == 1 ? reduce_norm<1>(l2, d, r, a, ws, st) : reduce_norm<2>(l2, d, r, a, ws, st));
 	double acc;
-	memcpy(&acc, ws->host, sizeof(double));
+	MF_TRY(read_scalars(ws, ws->scalars, sizeof(double), &acc, st));
 	*result_host = l2 ? (float)sqrt(acc) : (float)acc;
 	return 0;
 }
@@ -655,14 +645,9 @@ int mf_gridops_grid_avg(int64_t n, const float* source, const int32_t* flags, fl
 	Workspace* ws;
 	MF_TRY(get_workspace(&ws));
 	const hipStream_t st = (hipStream_t)stream;
-	const int nb = blocks_for(n, BLOCK * 8, 1024);
-	hipLaunchKernelGGL(k_avg_partial, dim3(nb), dim3(BLOCK), 0, st, n, source, flags, ws->partials);
-	MF_LAUNCH_CHECK();
-	MF_TRY(launch_sum_finish(nb, ws->partials, (double*)ws->scalars, st));
-	MF_TRY(launch_sum_finish(nb, ws->partials + nb, (double*)ws->scalars + 1, st));
-	MF_TRY(read_back(ws->host, ws->scalars, 2 * sizeof(double), st));
 	double r[2];
-	memcpy(r, ws->host, sizeof(r));
+	MF_TRY((reduce<SumF64, 2>(n, dim3(blocks_for(n, BLOCK * 8, 1024)), AvgTerm{source, flags}, ws->partials, Store<double, 2>{(double*)ws->scalars}, st)));
+	MF_TRY(read_scalars(ws, ws->scalars, sizeof(r), r, st));
 	// getGridAvg, grid.cpp:736-738: `sum *= 1. / cells`, returned as Real
 	*result_host = r[1] > 0. ? (float)(r[0] * (1. / r[1])) : -1.f;
 	return 0;

@@ -2,7 +2,7 @@
 // (:31-45, host), the separable blur with its obstacle restore (:49-136), precomputeInvA (:254-263) and the element-wise chains of
 // one primal-dual iteration (:229-239, :266-271, :323-344) in three kernels.  DESIGN.md, "Primal-dual fluid guiding", has the
 // rounding points and the forms of the blur that were considered.
-#include "common.h"
+#include "reduce.h"
 #include "../../include/manta_hip_guiding.h"
 #include <math.h>
 
@@ -112,7 +112,7 @@ k_guiding_mid(int64_t n, float* __restrict__ x, const float* __restrict__ y, con
 
 // y = ((z - z0) * theta) + z, and per block the largest normSquare of z - z0 and of z (vectorbase.h:392-395: x*x + y*y + z*z)
 __global__ void __launch_bounds__(BLOCK)
-k_guiding_post(int64_t n, const float* __restrict__ z, const float* __restrict__ z0, float* __restrict__ y, float theta, float* __restrict__ partials) {
+k_guiding_post(int64_t n, const float* __restrict__ z, const float* __restrict__ z0, float* __restrict__ y, float theta, Pair<float>* __restrict__ partials) {
 	float mr = -FLT_MAX, mz = -FLT_MAX;
 	for (int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * BLOCK) {
 		float r[3], zz[3];
@@ -127,29 +127,19 @@ k_guiding_post(int64_t n, const float* __restrict__ z, const float* __restrict__
 		mr = fmaxf(mr, r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
 		mz = fmaxf(mz, zz[0] * zz[0] + zz[1] * zz[1] + zz[2] * zz[2]);
 	}
-	// block_minmax folds a minimum and a maximum: hand it the negated first maximum (negation is exact)
-	float lo = -mr, hi = mz;
-	block_minmax(lo, hi);
-	if (threadIdx.x == 0) {
-		partials[2 * blockIdx.x] = -lo;
-		partials[2 * blockIdx.x + 1] = hi;
-	}
+	// the loop writes y, so the kernel is its own; its two maxima ride the shared min / max fold in one pass, the first one negated as the
+	// minimum (negation is exact, and fminf(-a, -b) is -fmaxf(a, b)): a max / max pair policy for this one caller would be more code than
+	// the two negations, here and in the finisher's epilogue
+	const Pair<float> r = block_fold<MinMaxF32>({-mr, mz});
+	if (threadIdx.x == 0) partials[blockIdx.x] = r;
 }
-
-__global__ void __launch_bounds__(BLOCK) k_guiding_post_finish(int nb, const float* __restrict__ partials, float* __restrict__ out) {
-	float lo = FLT_MAX, hi = -FLT_MAX;
-	for (int b = threadIdx.x; b < nb; b += BLOCK) {
-		lo = fminf(lo, -partials[2 * b]);
-		hi = fmaxf(hi, partials[2 * b + 1]);
+struct StoreNegLo {
+	float* out;
+	__device__ __forceinline__ void operator()(const Pair<float> (&acc)[1]) const {
+		out[0] = -acc[0].lo;
+		out[1] = acc[0].hi;
 	}
-	block_minmax(lo, hi);
-	if (threadIdx.x == 0) {
-		out[0] = -lo;
-		out[1] = hi;
-	}
-}
-
-inline dim3 cells(int64_t n) { return dim3((unsigned)((n + BLOCK - 1) / BLOCK)); }
+};
 
 int check_n(const char* who, int64_t n) {
 	if (n < 1 || 3 * n >= (int64_t)1 << 31) return fail("%s: invalid cell count %lld", who, (long long)n);
@@ -210,7 +200,7 @@ int mf_guiding_blur(int sx, int sy, int sz, const int32_t* flags, float* grid, f
 
 int mf_guiding_inv_a(int64_t n, const float* weight, float sigma, float* invA, void* stream) {
 	MF_TRY(check_n("mf_guiding_inv_a", n));
-	hipLaunchKernelGGL(k_guiding_inv_a, cells(n), dim3(BLOCK), 0, (hipStream_t)stream, n, weight, sigma, invA);
+	hipLaunchKernelGGL(k_guiding_inv_a, dim3(nblk(n)), dim3(BLOCK), 0, (hipStream_t)stream, n, weight, sigma, invA);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -218,7 +208,7 @@ int mf_guiding_inv_a(int64_t n, const float* weight, float sigma, float* invA, v
 int mf_guiding_pre(int64_t n, const float* x, const float* y, const float* Q, const float* invA, float* xv, float* vn, float inv_sigma,
                    float sigma, void* stream) {
 	MF_TRY(check_n("mf_guiding_pre", n));
-	hipLaunchKernelGGL(k_guiding_pre, cells(n), dim3(BLOCK), 0, (hipStream_t)stream, n, x, y, Q, invA, xv, vn, inv_sigma, sigma);
+	hipLaunchKernelGGL(k_guiding_pre, dim3(nblk(n)), dim3(BLOCK), 0, (hipStream_t)stream, n, x, y, Q, invA, xv, vn, inv_sigma, sigma);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -226,7 +216,7 @@ int mf_guiding_pre(int64_t n, const float* x, const float* y, const float* Q, co
 int mf_guiding_mid(int64_t n, float* x, const float* y, const float* xv, const float* vn, const float* invA, const float* velC,
                    const float* z, float* zn, float sigma, float tau, void* stream) {
 	MF_TRY(check_n("mf_guiding_mid", n));
-	hipLaunchKernelGGL(k_guiding_mid, cells(n), dim3(BLOCK), 0, (hipStream_t)stream, n, x, y, xv, vn, invA, velC, z, zn, sigma, tau);
+	hipLaunchKernelGGL(k_guiding_mid, dim3(nblk(n)), dim3(BLOCK), 0, (hipStream_t)stream, n, x, y, xv, vn, invA, velC, z, zn, sigma, tau);
 	MF_LAUNCH_CHECK();
 	return 0;
 }
@@ -237,11 +227,11 @@ int mf_guiding_post(int64_t n, const float* z, const float* z0, float* y, float 
 	MF_TRY(get_workspace(&ws));
 	hipStream_t st = (hipStream_t)stream;
 	const int nb = blocks_for(n, BLOCK * 4, 2048);
-	hipLaunchKernelGGL(k_guiding_post, dim3(nb), dim3(BLOCK), 0, st, n, z, z0, y, theta, ws->fpartials);
-	hipLaunchKernelGGL(k_guiding_post_finish, dim3(1), dim3(BLOCK), 0, st, nb, ws->fpartials, (float*)ws->scalars);
-	MF_LAUNCH_CHECK();
-	MF_TRY(read_back(ws->host, ws->scalars, 2 * sizeof(float), st));
-	const float* h = (const float*)ws->host;
+	Pair<float>* part = (Pair<float>*)ws->fpartials;
+	hipLaunchKernelGGL(k_guiding_post, dim3(nb), dim3(BLOCK), 0, st, n, z, z0, y, theta, part);
+	MF_TRY((reduce_finish<MinMaxF32, 1>(nb, 1, part, StoreNegLo{(float*)ws->scalars}, st)));
+	float h[2];
+	MF_TRY(read_scalars(ws, ws->scalars, sizeof(h), h, st));
 	out_host[0] = sqrtf(h[0]);
 	out_host[1] = sqrtf(h[1]);
 	return 0;

@@ -3,6 +3,7 @@
 // and computeCenterOfMass as per-triangle fp64 terms summed in a fixed tree.  The per-element bodies are in meshops_cells.h.
 // Reference: mesh.cpp:123-141, 238-292, plugin/meshplugins.cpp:36-104.
 #include "meshops_cells.h"
+#include "reduce.h"
 #include "../../include/open/manta_hip_meshops.h"
 #include "scan.h"
 #include <limits.h>
@@ -111,25 +112,17 @@ __global__ void __launch_bounds__(BLOCK) k_volume_terms(Tris T, int64_t ncap, co
 	volume_terms(T, ncap, pos, t, v);
 	for (int q = 0; q < 4; q++) terms[q * T.nTris + t] = v[q];
 }
-// the fixed tree: a block sums its 256 triangles (block_sum), ...
-__global__ void __launch_bounds__(BLOCK) k_volume_partials(Tris T, int64_t ncap, const float* __restrict__ pos, double* __restrict__ part) {
-	const int64_t t = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
-	double v[4] = {0., 0., 0., 0.};
-	if (t < T.nTris) volume_terms(T, ncap, pos, t, v);
-	for (int q = 0; q < 4; q++) {
-		const double s = block_sum(v[q]);
-		if (threadIdx.x == 0) part[q * (int64_t)gridDim.x + blockIdx.x] = s;
+// the four sums of the triangles' terms, one triangle per thread, in the fixed tree of reduce.h
+struct VolumeTerm {
+	Tris T;
+	int64_t ncap;
+	const float* pos;
+	__device__ __forceinline__ void operator()(int64_t t, double (&acc)[4]) const {
+		double v[4];
+		volume_terms(T, ncap, pos, t, v);
+		for (int q = 0; q < 4; q++) acc[q] += v[q];
 	}
-}
-// ... and one block sums the partials: lane i adds partials i, i + 256, ... in that order, then block_sum
-__global__ void __launch_bounds__(BLOCK) k_volume_total(int64_t nb, const double* __restrict__ part, double* __restrict__ sums) {
-	for (int q = 0; q < 4; q++) {
-		double a = 0.;
-		for (int64_t b = threadIdx.x; b < nb; b += BLOCK) a += part[q * nb + b];
-		const double s = block_sum(a);
-		if (threadIdx.x == 0) sums[q] = s;
-	}
-}
+};
 
 __global__ void __launch_bounds__(BLOCK)
 k_rescale(int64_t n, int64_t ncap, float* __restrict__ pos, const int32_t* __restrict__ flags, float ox, float oy, float oz, float nx, float ny, float nz,
@@ -425,9 +418,7 @@ int mf_meshops_volume_sums(int64_t nTris, int64_t tcap, const int32_t* tri, int6
 	double* part;
 	MF_TRY(cut.take((size_t)(4 * nb), &part));
 	const Tris T = {nTris, tcap, nNodes, tri};
-	hipLaunchKernelGGL(k_volume_partials, dim3((unsigned)nb), dim3(BLOCK), 0, st, T, ncap, pos, part);
-	hipLaunchKernelGGL(k_volume_total, dim3(1), dim3(BLOCK), 0, st, nb, (const double*)part, (double*)t.head);
-	MF_LAUNCH_CHECK();
+	MF_TRY((reduce<SumF64, 4>(nTris, dim3((unsigned)nb), VolumeTerm{T, ncap, pos}, part, Store<double, 4>{(double*)t.head}, st)));
 	return read_back(sums_host, t.head, 4 * sizeof(double), st);
 }
 

@@ -2,7 +2,7 @@
 // substitution sweeps of ApplyPreconditionModifiedIncompCholesky2 (source/conjugategrad.cpp:66-97, 135-159), which the
 // reference runs as single-threaded lexicographic sweeps.  Two parallelisations with identical results: "rows" (k_mic_rows /
 // k_mic_rows_init, one dataflow launch per sweep, the default) and "levels" (k_mic_tiles, one launch per tile hyperplane).
-#include "common.h"
+#include "reduce.h"
 #include "pressure.h"
 #include <float.h>
 #include <stdlib.h>
@@ -825,7 +825,7 @@ k_mic_rows(Dim d, int nbj, int nbk, int jb, int nstreams, int nchunks, int xoff0
 		}
 	}
 	if (MODE == 2 && !tail.sc && tail.sum_out) {
-		// z-slab solver: the one-block folds behind the sweep (k_maxabs_finish64, k_sum_finish) in the workgroup that finished last
+		// z-slab solver: the one-block folds behind the sweep (launch_maxabs_finish, launch_sum_finish) in the workgroup that finished last
 		__syncthreads();
 		if (!s_lastwg) return;
 		float lo = FLT_MAX, hi = -FLT_MAX;
@@ -1543,14 +1543,6 @@ static int launch_mic(const Dim& d, const int32_t* flags, float* dst, const floa
 }
 
 
-// without fusion: a plain dot over the grid
-static __global__ void __launch_bounds__(BLOCK) k_mic_plain_dot(int64_t n, const float* __restrict__ a, const float* __restrict__ b, double* __restrict__ partials) {
-	double acc = 0.0;
-	for (int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) acc += (double)(a[i] * b[i]);
-	acc = block_sum(acc);
-	if (threadIdx.x == 0) partials[blockIdx.x] = acc;
-}
-
 namespace mf {
 int mic_sweep(int mode, const Dim& d, const int32_t* flags, float* dst, const float* var1, const float* Ap, const float* Ai,
               const float* Aj, const float* Ak, const CgScalars* sc, hipStream_t st, MicSweep* opt) {
@@ -1577,7 +1569,7 @@ int mic_apply_dot_fold(const Dim& d, const int32_t* flags, float* dst, const flo
 	int nsig = bwd.ndot;
 	if (nsig == 0) {
 		nsig = blocks_for(d.n, BLOCK * 4, 2048);
-		hipLaunchKernelGGL(k_mic_plain_dot, dim3(nsig), dim3(BLOCK), 0, st, d.n, dst, var1, part);
+		MF_TRY((reduce_partials<SumF64, 1>(d.n, dim3(nsig), DotTerm{dst, var1}, part, st)));   // without fusion: a plain dot over the grid
 	}
 	MF_TRY(launch_sum_finish(nsig, part, dot_dev, st));
 	if (nbr > 0) MF_TRY(launch_maxabs_finish(nbr, fpart, maxabs_dev, live ? &live->done : nullptr, st));

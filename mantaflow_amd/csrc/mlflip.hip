@@ -409,9 +409,7 @@ int mf_mlflip_regions(int sx, int sy, int sz, const int32_t* flags, int ctype, i
 	MF_LAUNCH_CHECK();
 	Workspace* w;
 	MF_TRY(get_workspace(&w));
-	MF_TRY(read_back(w->host, aux + n, sizeof(int32_t), st));
-	memcpy(count_host, w->host, sizeof(int32_t));
-	return 0;
+	return read_scalars(w, aux + n, sizeof(int32_t), count_host, st);
 }
 
 int mf_mlflip_extend_region(int sx, int sy, int sz, int32_t* flags, int32_t* tmp, int region, int exclude, int depth, void* stream) {

@@ -407,9 +407,8 @@ int mf_movingobs_project_count(int sx, int sy, int sz, int64_t np, int64_t pstri
 	hipLaunchKernelGGL(k_project_count, dim3(nblk(np + 1)), dim3(BLOCK), 0, st, d, np, pstride, pos, pflag, offsets);
 	MF_LAUNCH_CHECK();
 	MF_TRY(exclusive_sum(tmp, (size_t)tmp_bytes, offsets, offsets, np + 1, st));
-	MF_TRY(read_back(ws->host, offsets + np, sizeof(int32_t), st));
 	int32_t total;
-	memcpy(&total, ws->host, sizeof(total));
+	MF_TRY(read_scalars(ws, offsets + np, sizeof(total), &total, st));
 	*total_host = total;
 	return 0;
 }

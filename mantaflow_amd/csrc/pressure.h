@@ -121,8 +121,8 @@ struct BetaTail {
 	const double* dpart_res;  // their sums of squares (L2 norm)
 	int nsig;                 // dot partials to fold
 	// sc == nullptr and sum_out set: the z-slab solver's variant -- no beta step here (the scalars of all ranks are gathered first), the
-	// last workgroup only folds: *sum_out = sum of the nsig dot partials (k_sum_finish's order) and, with nbr > 0, *maxabs_out =
-	// max |fpart| unless live->done (k_maxabs_finish64)
+	// last workgroup only folds: *sum_out = sum of the nsig dot partials (launch_sum_finish's order) and, with nbr > 0, *maxabs_out =
+	// max |fpart| unless live->done (launch_maxabs_finish)
 	double* sum_out;
 	double* maxabs_out;
 	const CgScalars* live;

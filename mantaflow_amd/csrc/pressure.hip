@@ -1,7 +1,7 @@
 // pressure.hip -- pressure projection on gfx950: 7-point ApplyMatrix stencil, Laplace matrix / rhs assembly,
 // velocity correction (+ ghost fluid) and the device-resident PCG loop (the MIC(0) preconditioner lives in mic.hip).
 // Reference: source/conjugategrad.{h,cpp}, source/plugin/pressure.cpp (cited per kernel).
-#include "common.h"
+#include "reduce.h"
 #include "pressure.h"
 #include <float.h>
 #include <stdlib.h>

@@ -1,5 +1,5 @@
 // runtime.hip -- error reporting, workspace, element-wise grid ops and reductions (gfx950).
-#include "common.h"
+#include "reduce.h"
 #include <stdarg.h>
 #include <float.h>
 
@@ -177,77 +177,36 @@ static int run_binary(int64_t n, float* a, const float* b, float f, void* stream
 // ---------------------------------------------------------------------------------------------------------
 // reductions: per-block partials in fixed order -> one finishing block; deterministic run to run
 // ---------------------------------------------------------------------------------------------------------
-// mode 0: sum of fp32 products a*b accumulated in fp64 (GridDotProduct, conjugategrad.cpp:175-178)
-// mode 1: sum of squares of the value converted to fp64 (GridSumSqr, commonkernels.h:32-35)
-template <int MODE>
-__global__ void __launch_bounds__(BLOCK) k_dot_partials(int64_t n, const float* __restrict__ a, const float* __restrict__ b,
-                                                        double* __restrict__ partials) {
-	double acc = 0.0;
-	for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-		if (MODE == 0) {
-			const float pr = a[i] * b[i];
-			acc += (double)pr;
-		} else {
-			const double v = (double)a[i];
-			acc += v * v;
-		}
+// the terms; DotTerm (GridDotProduct) is in reduce.h
+// sum of squares of the value converted to fp64 (GridSumSqr, commonkernels.h:32-35)
+struct SumSqrTerm {
+	const float* a;
+	__device__ __forceinline__ void operator()(int64_t i, double (&acc)[1]) const {
+		const double v = (double)a[i];
+		acc[0] += v * v;
 	}
-	acc = block_sum(acc);
-	if (threadIdx.x == 0) partials[blockIdx.x] = acc;
-}
-__global__ void __launch_bounds__(BLOCK) k_sum_finish(int nb, const double* __restrict__ partials, double* __restrict__ out) {
-	double acc = strided_sum(partials, nb);
-	acc = block_sum(acc);
-	if (threadIdx.x == 0) *out = acc;
-}
+};
 // CompMinReal / CompMaxReal, grid.cpp:185-196
-__global__ void __launch_bounds__(BLOCK) k_minmax_partials(int64_t n, const float* __restrict__ a, float* __restrict__ partials) {
-	float lo = FLT_MAX, hi = -FLT_MAX;
-	for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-		const float v = a[i];
-		lo = fminf(lo, v);
-		hi = fmaxf(hi, v);
-	}
-	block_minmax(lo, hi);
-	if (threadIdx.x == 0) {
-		partials[2 * blockIdx.x] = lo;
-		partials[2 * blockIdx.x + 1] = hi;
-	}
-}
-__global__ void __launch_bounds__(BLOCK) k_minmax_finish(int nb, const float* __restrict__ partials, float* __restrict__ out) {
-	float lo = FLT_MAX, hi = -FLT_MAX;
-	for (int i = threadIdx.x; i < nb; i += blockDim.x) {
-		lo = fminf(lo, partials[2 * i]);
-		hi = fmaxf(hi, partials[2 * i + 1]);
-	}
-	block_minmax(lo, hi);
-	if (threadIdx.x == 0) {
-		out[0] = lo;
-		out[1] = hi;
-	}
-}
+struct MinMaxTerm {
+	const float* a;
+	__device__ __forceinline__ void operator()(int64_t i, Pair<float> (&acc)[1]) const { MinMaxF32::fold(acc[0], a[i]); }
+};
 // CompMaxVec, grid.cpp:218-224 : max of normSquare (x*x + y*y + z*z, vectorbase.h:392-395)
-__global__ void __launch_bounds__(BLOCK) k_maxnormsq_partials(int64_t n, const float* __restrict__ a, float* __restrict__ partials) {
-	float lo = FLT_MAX, hi = -FLT_MAX;
-	for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+struct NormSqTerm {
+	const float* a;
+	int64_t n;
+	__device__ __forceinline__ void operator()(int64_t i, Pair<float> (&acc)[1]) const {
 		const float x = a[i], y = a[n + i], z = a[2 * n + i];
-		const float q = x * x + y * y + z * z;
-		hi = fmaxf(hi, q);
-		lo = fminf(lo, q);
+		MinMaxF32::fold(acc[0], x * x + y * y + z * z);
 	}
-	block_minmax(lo, hi);
-	if (threadIdx.x == 0) {
-		partials[2 * blockIdx.x] = lo;
-		partials[2 * blockIdx.x + 1] = hi;
+};
+struct CountFlagTerm {
+	const int32_t* f;
+	int mask;
+	__device__ __forceinline__ void operator()(int64_t i, double (&acc)[1]) const {
+		if (f[i] & mask) acc[0] += 1.0;
 	}
-}
-__global__ void __launch_bounds__(BLOCK) k_count_flag_partials(int64_t n, const int32_t* __restrict__ f, int mask, double* __restrict__ partials) {
-	double acc = 0.0;
-	for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-		if (f[i] & mask) acc += 1.0;
-	acc = block_sum(acc);
-	if (threadIdx.x == 0) partials[blockIdx.x] = acc;
-}
+};
 
 // device-scalar variants (multi-GPU PCG: no host round trip between a reduction and the vector update that uses it)
 template <int OP>
@@ -255,15 +214,6 @@ __global__ void __launch_bounds__(BLOCK) k_binary_devf(int64_t n, float* a, cons
 	const float f = sign * fdev[0];   // sign is +-1: exact
 	for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
 		a[i] = op2<OP>(a[i], b[i], f);
-}
-__global__ void __launch_bounds__(BLOCK) k_maxabs_finish(int nb, const float* __restrict__ partials, float* __restrict__ out) {
-	float lo = FLT_MAX, hi = -FLT_MAX;
-	for (int i = threadIdx.x; i < nb; i += blockDim.x) {
-		lo = fminf(lo, partials[2 * i]);
-		hi = fmaxf(hi, partials[2 * i + 1]);
-	}
-	block_minmax(lo, hi);
-	if (threadIdx.x == 0) out[0] = maxabs(lo, hi);
 }
 
 // z-slab PCG scalar steps (common.h: slab_alpha, slab_beta_stop) on loose device scalars
@@ -290,27 +240,11 @@ __global__ void k_slab_beta(const double* __restrict__ g, int world, float* __re
 		state[1] = iter;
 	}
 }
-// stopped (nullable; the z-slab solver's iterations queued past the stop): *out keeps the value of the stopping iteration
-__global__ void __launch_bounds__(BLOCK) k_maxabs_finish64(int nb, const float* __restrict__ partials, double* __restrict__ out,
-                                                           const int* __restrict__ stopped) {
-	if (stopped && stopped[0]) return;
-	float lo = FLT_MAX, hi = -FLT_MAX;
-	for (int i = threadIdx.x; i < nb; i += blockDim.x) {
-		lo = fminf(lo, partials[2 * i]);
-		hi = fmaxf(hi, partials[2 * i + 1]);
-	}
-	block_minmax(lo, hi);
-	if (threadIdx.x == 0) out[0] = (double)maxabs(lo, hi);
-}
 int mf::launch_sum_finish(int nb, const double* partials, double* out, hipStream_t st) {
-	hipLaunchKernelGGL(k_sum_finish, dim3(1), dim3(BLOCK), 0, st, nb, partials, out);
-	MF_LAUNCH_CHECK();
-	return 0;
+	return reduce_finish<SumF64, 1>(nb, 1, partials, Store<double>{out}, st);
 }
 int mf::launch_maxabs_finish(int nb, const float* fpart, double* out, const int* stopped, hipStream_t st) {
-	hipLaunchKernelGGL(k_maxabs_finish64, dim3(1), dim3(BLOCK), 0, st, nb, fpart, out, stopped);
-	MF_LAUNCH_CHECK();
-	return 0;
+	return reduce_finish<MinMaxF32, 1>(nb, 1, (const Pair<float>*)fpart, StoreMaxAbs<double>{out, stopped}, st);
 }
 
 int mf::read_back(void* host, const void* dev, size_t bytes, hipStream_t st) {
@@ -318,11 +252,32 @@ int mf::read_back(void* host, const void* dev, size_t bytes, hipStream_t st) {
 	MF_HIP(hipStreamSynchronize(st));
 	return 0;
 }
-// the same through the pinned page
-static int read_back(Workspace* ws, const void* dev, size_t bytes, void* host_out, hipStream_t s) {
-	MF_TRY(mf::read_back(ws->host, dev, bytes, s));
+int mf::read_scalars(Workspace* ws, const void* dev, size_t bytes, void* host_out, hipStream_t s) {
+	MF_TRY(read_back(ws->host, dev, bytes, s));
 	memcpy(host_out, ws->host, bytes);
 	return 0;
+}
+
+// this file's reductions: blocks_for(n, BLOCK * 8, 1024) blocks, partials in the workspace.  The sum goes to out_dev, or (null) through
+// the workspace's scalar block to out_host
+template <class Term>
+static int sum_of(int64_t n, Term term, double* out_dev, double* out_host, void* s) {
+	Workspace* ws;
+	MF_TRY(get_workspace(&ws));
+	double* out = out_dev ? out_dev : (double*)ws->scalars;
+	MF_TRY((reduce<SumF64, 1>(n, dim3(blocks_for(n, BLOCK * 8, 1024)), term, ws->partials, Store<double>{out}, (hipStream_t)s)));
+	return out_dev ? 0 : read_scalars(ws, out, sizeof(double), out_host, (hipStream_t)s);
+}
+// max |.| of the minimum and the maximum to maxabs_dev, or (null) the two themselves to lohi_host
+template <class Term, class O>
+static int minmax_of(int64_t n, Term term, O* maxabs_dev, float* lohi_host, void* s) {
+	Workspace* ws;
+	MF_TRY(get_workspace(&ws));
+	const dim3 grid(blocks_for(n, BLOCK * 8, 1024));
+	Pair<float>*part = (Pair<float>*)ws->fpartials, *out = (Pair<float>*)ws->scalars;
+	if (maxabs_dev) return reduce<MinMaxF32, 1>(n, grid, term, part, StoreMaxAbs<O>{maxabs_dev, nullptr}, (hipStream_t)s);
+	MF_TRY((reduce<MinMaxF32, 1>(n, grid, term, part, Store<Pair<float>>{out}, (hipStream_t)s)));
+	return read_scalars(ws, out, sizeof(*out), lohi_host, (hipStream_t)s);
 }
 
 extern "C" {
@@ -365,39 +320,10 @@ int mf_grid_add_const(int64_t n, float* a, float v, void* s) { return run_unary<
 int mf_grid_mult_const(int64_t n, float* a, float v, void* s) { return run_unary<OP_MULC>(n, a, v, 0.f, s); }
 int mf_grid_clamp(int64_t n, float* a, float lo, float hi, void* s) { return run_unary<OP_CLAMP>(n, a, lo, hi, s); }
 
-int mf_grid_dot(int64_t n, const float* a, const float* b, double* r, void* s) {
-	Workspace* ws;
-	MF_TRY(get_workspace(&ws));
-	const int nb = blocks_for(n, BLOCK * 8, 1024);
-	hipLaunchKernelGGL(k_dot_partials<0>, dim3(nb), dim3(BLOCK), 0, (hipStream_t)s, n, a, b, ws->partials);
-	MF_TRY(launch_sum_finish(nb, ws->partials, (double*)ws->scalars, (hipStream_t)s));
-	return read_back(ws, ws->scalars, sizeof(double), r, (hipStream_t)s);
-}
-int mf_grid_dot_dev(int64_t n, const float* a, const float* b, double* out_dev, void* s) {
-	Workspace* ws;
-	MF_TRY(get_workspace(&ws));
-	const int nb = blocks_for(n, BLOCK * 8, 1024);
-	hipLaunchKernelGGL(k_dot_partials<0>, dim3(nb), dim3(BLOCK), 0, (hipStream_t)s, n, a, b, ws->partials);
-	MF_TRY(launch_sum_finish(nb, ws->partials, out_dev, (hipStream_t)s));
-	return 0;
-}
-int mf_grid_max_abs_dev(int64_t n, const float* a, float* out_dev, void* s) {
-	Workspace* ws;
-	MF_TRY(get_workspace(&ws));
-	const int nb = blocks_for(n, BLOCK * 8, 1024);
-	hipLaunchKernelGGL(k_minmax_partials, dim3(nb), dim3(BLOCK), 0, (hipStream_t)s, n, a, ws->fpartials);
-	hipLaunchKernelGGL(k_maxabs_finish, dim3(1), dim3(BLOCK), 0, (hipStream_t)s, nb, ws->fpartials, out_dev);
-	MF_LAUNCH_CHECK();
-	return 0;
-}
-int mf_grid_max_abs_dev_f64(int64_t n, const float* a, double* out_dev, void* s) {
-	Workspace* ws;
-	MF_TRY(get_workspace(&ws));
-	const int nb = blocks_for(n, BLOCK * 8, 1024);
-	hipLaunchKernelGGL(k_minmax_partials, dim3(nb), dim3(BLOCK), 0, (hipStream_t)s, n, a, ws->fpartials);
-	MF_TRY(launch_maxabs_finish(nb, ws->fpartials, out_dev, nullptr, (hipStream_t)s));
-	return 0;
-}
+int mf_grid_dot(int64_t n, const float* a, const float* b, double* r, void* s) { return sum_of(n, DotTerm{a, b}, nullptr, r, s); }
+int mf_grid_dot_dev(int64_t n, const float* a, const float* b, double* out_dev, void* s) { return sum_of(n, DotTerm{a, b}, out_dev, nullptr, s); }
+int mf_grid_max_abs_dev(int64_t n, const float* a, float* out_dev, void* s) { return minmax_of(n, MinMaxTerm{a}, out_dev, nullptr, s); }
+int mf_grid_max_abs_dev_f64(int64_t n, const float* a, double* out_dev, void* s) { return minmax_of(n, MinMaxTerm{a}, out_dev, nullptr, s); }
 int mf_cg_slab_alpha(const double* gathered, int world, const float* sigma_dev, float* alpha_dev, const int32_t* state_dev, void* s) {
 	hipLaunchKernelGGL(k_slab_alpha, dim3(1), dim3(1), 0, (hipStream_t)s, gathered, world, sigma_dev, alpha_dev, state_dev);
 	MF_LAUNCH_CHECK();
@@ -421,23 +347,10 @@ int mf_update_search_vec_dev(int64_t n, float* dst, const float* src, const floa
 	MF_LAUNCH_CHECK();
 	return 0;
 }
-int mf_grid_sum_sqr(int64_t n, const float* a, double* r, void* s) {
-	Workspace* ws;
-	MF_TRY(get_workspace(&ws));
-	const int nb = blocks_for(n, BLOCK * 8, 1024);
-	hipLaunchKernelGGL(k_dot_partials<1>, dim3(nb), dim3(BLOCK), 0, (hipStream_t)s, n, a, a, ws->partials);
-	MF_TRY(launch_sum_finish(nb, ws->partials, (double*)ws->scalars, (hipStream_t)s));
-	return read_back(ws, ws->scalars, sizeof(double), r, (hipStream_t)s);
-}
+int mf_grid_sum_sqr(int64_t n, const float* a, double* r, void* s) { return sum_of(n, SumSqrTerm{a}, nullptr, r, s); }
 int mf_grid_min_max(int64_t n, const float* a, float* mn, float* mx, void* s) {
-	Workspace* ws;
-	MF_TRY(get_workspace(&ws));
-	const int nb = blocks_for(n, BLOCK * 8, 1024);
-	hipLaunchKernelGGL(k_minmax_partials, dim3(nb), dim3(BLOCK), 0, (hipStream_t)s, n, a, ws->fpartials);
-	hipLaunchKernelGGL(k_minmax_finish, dim3(1), dim3(BLOCK), 0, (hipStream_t)s, nb, ws->fpartials, (float*)ws->scalars);
-	MF_LAUNCH_CHECK();
 	float r[2];
-	MF_TRY(read_back(ws, ws->scalars, sizeof(r), r, (hipStream_t)s));
+	MF_TRY(minmax_of(n, MinMaxTerm{a}, (float*)nullptr, r, s));
 	*mn = r[0];
 	*mx = r[1];
 	return 0;
@@ -449,25 +362,14 @@ int mf_grid_max_abs(int64_t n, const float* a, float* r, void* s) {
 	return 0;
 }
 int mf_grid_max_abs_vec3(int64_t n, const float* a, float* r, void* s) {
-	Workspace* ws;
-	MF_TRY(get_workspace(&ws));
-	const int nb = blocks_for(n, BLOCK * 8, 1024);
-	hipLaunchKernelGGL(k_maxnormsq_partials, dim3(nb), dim3(BLOCK), 0, (hipStream_t)s, n, a, ws->fpartials);
-	hipLaunchKernelGGL(k_minmax_finish, dim3(1), dim3(BLOCK), 0, (hipStream_t)s, nb, ws->fpartials, (float*)ws->scalars);
-	MF_LAUNCH_CHECK();
 	float v[2];
-	MF_TRY(read_back(ws, ws->scalars, sizeof(v), v, (hipStream_t)s));
+	MF_TRY(minmax_of(n, NormSqTerm{a, n}, (float*)nullptr, v, s));
 	*r = sqrtf(v[1]);
 	return 0;
 }
 int mf_count_empty_cells(int64_t n, const int32_t* flags, int32_t* r, void* s) {
-	Workspace* ws;
-	MF_TRY(get_workspace(&ws));
-	const int nb = blocks_for(n, BLOCK * 8, 1024);
-	hipLaunchKernelGGL(k_count_flag_partials, dim3(nb), dim3(BLOCK), 0, (hipStream_t)s, n, flags, (int)MF_EMPTY, ws->partials);
-	MF_TRY(launch_sum_finish(nb, ws->partials, (double*)ws->scalars, (hipStream_t)s));
 	double d;
-	MF_TRY(read_back(ws, ws->scalars, sizeof(double), &d, (hipStream_t)s));
+	MF_TRY(sum_of(n, CountFlagTerm{flags, (int)MF_EMPTY}, nullptr, &d, s));
 	*r = (int32_t)d;
 	return 0;
 }

@@ -10,10 +10,6 @@ using namespace mf::surfturb;
 
 namespace {
 
-#define ST_IDX(n)                                                      \
-	const int64_t idx = blockIdx.x * (int64_t)BLOCK + threadIdx.x;    \
-	if (idx >= (n)) return;
-
 __device__ __forceinline__ void store3(float* a, int64_t stride, int64_t i, V3 v) {
 	a[i] = v.x;
 	a[stride + i] = v.y;
@@ -21,14 +17,14 @@ __device__ __forceinline__ void store3(float* a, int64_t stride, int64_t i, V3 v
 }
 
 __global__ void __launch_bounds__(BLOCK) k_cell_keys(Par par, int R, Pts P, uint32_t* __restrict__ key, int32_t* __restrict__ val) {
-	ST_IDX(P.n)
+	ITEM_IDX(P.n)
 	key[idx] = (uint32_t)cell_of(pos_of(P, idx), par.res, R);
 	val[idx] = (int32_t)idx;
 }
 // the sorted keys -> start[ncells + 1]: one thread per cell finds the first sorted slot whose cell is not below its own (a thread per
 // slot filling the gap to the cell before it serialises on the long empty runs of a thin shell of points)
 __global__ void __launch_bounds__(BLOCK) k_cell_starts(int64_t n, int64_t ncells, const uint32_t* __restrict__ key, int32_t* __restrict__ start) {
-	ST_IDX(ncells + 1)
+	ITEM_IDX(ncells + 1)
 	int64_t lo = 0, hi = n;
 	while (lo < hi) {
 		const int64_t mid = (lo + hi) >> 1;
@@ -41,7 +37,7 @@ __global__ void __launch_bounds__(BLOCK) k_cell_starts(int64_t n, int64_t ncells
 __global__ void __launch_bounds__(BLOCK)
 k_init_mark(Par par, Cells CC, Pts coarse, int sx, int sy, int sz, const int32_t* __restrict__ gridflags, int64_t ndirs, const float* __restrict__ dirs,
             int32_t* __restrict__ mark) {
-	ST_IDX(coarse.n * ndirs)
+	ITEM_IDX(coarse.n * ndirs)
 	const int64_t p = idx / ndirs, d = idx % ndirs;
 	V3 out;
 	mark[idx] = init_fine(par, CC, coarse, sx, sy, sz, gridflags, p, V3{dirs[3 * d], dirs[3 * d + 1], dirs[3 * d + 2]}, out);
@@ -49,7 +45,7 @@ k_init_mark(Par par, Cells CC, Pts coarse, int sx, int sy, int sz, const int32_t
 __global__ void __launch_bounds__(BLOCK)
 k_init_fill(Par par, Pts coarse, int64_t ndirs, const float* __restrict__ dirs, const int32_t* __restrict__ mark, int64_t cap, float* __restrict__ pos,
             int32_t* __restrict__ flag) {
-	ST_IDX(coarse.n * ndirs)
+	ITEM_IDX(coarse.n * ndirs)
 	const int32_t below = idx ? mark[idx - 1] : 0;
 	if (mark[idx] == below) return;
 	const int64_t p = idx / ndirs, d = idx % ndirs;
@@ -58,20 +54,20 @@ k_init_fill(Par par, Pts coarse, int64_t ndirs, const float* __restrict__ dirs, 
 }
 
 __global__ void __launch_bounds__(BLOCK) k_advect(Par par, Cells CP, Pts prev, Pts coarse, Pts surf, float* pos) {
-	ST_IDX(surf.n)
+	ITEM_IDX(surf.n)
 	if (!active(surf, idx)) return;
 	store3(pos, surf.cap, idx, advect_point(par, CP, prev, coarse, pos_of(surf, idx)));
 }
 
 __global__ void __launch_bounds__(BLOCK) k_add_mark(Par par, Cells CC, Pts coarse, Cells CS, Pts surf, float* __restrict__ cand, int32_t* __restrict__ mark) {
-	ST_IDX(surf.n)
+	ITEM_IDX(surf.n)
 	V3 out;
 	mark[idx] = add_candidate(par, CC, coarse, CS, surf, idx, out);
 	store3(cand, surf.n, idx, out);
 }
 __global__ void __launch_bounds__(BLOCK)
 k_add_apply(int64_t n, int64_t cap, float* __restrict__ pos, int32_t* __restrict__ flag, const float* __restrict__ cand, const int32_t* __restrict__ mark) {
-	ST_IDX(n)
+	ITEM_IDX(n)
 	flag[idx] &= ~PNEW;
 	const int32_t below = idx ? mark[idx - 1] : 0;
 	if (mark[idx] == below || n + below >= cap) return;
@@ -81,7 +77,7 @@ k_add_apply(int64_t n, int64_t cap, float* __restrict__ pos, int32_t* __restrict
 
 __global__ void __launch_bounds__(BLOCK)
 k_greedy(Par par, Cells CS, Pts surf, const int32_t* __restrict__ in, int32_t* __restrict__ out, int32_t* __restrict__ head) {
-	ST_IDX(surf.n)
+	ITEM_IDX(surf.n)
 	int32_t s = in[idx];
 	if (s == 0) {
 		s = greedy_decide(par, CS, surf, in, idx);
@@ -91,7 +87,7 @@ k_greedy(Par par, Cells CS, Pts surf, const int32_t* __restrict__ in, int32_t* _
 }
 __global__ void __launch_bounds__(BLOCK)
 k_delete(Par par, Cells CC, Pts coarse, Pts surf, int32_t* flag, const int32_t* __restrict__ state, int32_t* __restrict__ head) {
-	ST_IDX(surf.n)
+	ITEM_IDX(surf.n)
 	const int r = delete_coarse(par, CC, coarse, pos_of(surf, idx));
 	const int k1 = state[idx] == 2;
 	if (k1) atomicAdd(&head[0], 1);
@@ -100,71 +96,71 @@ k_delete(Par par, Cells CC, Pts coarse, Pts surf, int32_t* flag, const int32_t* 
 	if (k1 || r) flag[idx] |= PDELETE;
 }
 __global__ void __launch_bounds__(BLOCK) k_clear_new(int64_t n, int32_t* __restrict__ flag) {
-	ST_IDX(n)
+	ITEM_IDX(n)
 	flag[idx] &= ~PNEW;
 }
 
 __global__ void __launch_bounds__(BLOCK) k_normals(Par par, Cells CC, Pts coarse, Cells CS, Pts surf, float* __restrict__ normals) {
-	ST_IDX(surf.n)
+	ITEM_IDX(surf.n)
 	store3(normals, surf.cap, idx, surface_normal(par, CC, coarse, CS, surf, idx));
 }
 __global__ void __launch_bounds__(BLOCK) k_avg_normals(Par par, Cells CS, Pts surf, const float* __restrict__ normals, float* __restrict__ tempv) {
-	ST_IDX(surf.n)
+	ITEM_IDX(surf.n)
 	store3(tempv, surf.n, idx, averaged_normal(par, CS, surf, normals, idx));
 }
 // dst[3][dcap] (+)= src[3][n]
 template <bool ADD>
 __global__ void __launch_bounds__(BLOCK) k_assign3(int64_t n, int64_t dcap, float* __restrict__ dst, const float* __restrict__ src) {
-	ST_IDX(n)
+	ITEM_IDX(n)
 	for (int c = 0; c < 3; c++) dst[c * dcap + idx] = ADD ? dst[c * dcap + idx] + src[c * n + idx] : src[c * n + idx];
 }
 __global__ void __launch_bounds__(BLOCK) k_density(Par par, Cells CS, Pts surf, float* __restrict__ tempf) {
-	ST_IDX(surf.n)
+	ITEM_IDX(surf.n)
 	tempf[idx] = surface_density(par, CS, surf, idx);
 }
 __global__ void __launch_bounds__(BLOCK)
 k_displacement(Par par, Cells CS, Pts surf, const float* __restrict__ normals, const float* __restrict__ tempf, float* __restrict__ tempv) {
-	ST_IDX(surf.n)
+	ITEM_IDX(surf.n)
 	store3(tempv, surf.n, idx, surface_displacement(par, CS, surf, normals, tempf, idx));
 }
 __global__ void __launch_bounds__(BLOCK) k_constrain(Par par, Cells CC, Pts coarse, Pts surf, float* pos) {
-	ST_IDX(surf.n)
+	ITEM_IDX(surf.n)
 	store3(pos, surf.cap, idx, constrained(par, CC, coarse, pos_of(surf, idx)));
 }
 
 __global__ void __launch_bounds__(BLOCK) k_add_seed(int64_t n, float* __restrict__ H, const float* __restrict__ seed) {
-	ST_IDX(n)
+	ITEM_IDX(n)
 	H[idx] += seed[idx];
 }
 __global__ void __launch_bounds__(BLOCK)
 k_wave_normal(Par par, Cells CS, Pts surf, const float* __restrict__ normals, const float* __restrict__ H, float* __restrict__ tempv) {
-	ST_IDX(surf.n)
+	ITEM_IDX(surf.n)
 	store3(tempv, surf.n, idx, wave_normal(par, CS, surf, normals, H, idx));
 }
 __global__ void __launch_bounds__(BLOCK)
 k_wave_laplacian(Par par, Cells CS, Pts surf, const float* __restrict__ normals, const float* __restrict__ H, const float* __restrict__ tempv,
                  float* __restrict__ tempf) {
-	ST_IDX(surf.n)
+	ITEM_IDX(surf.n)
 	tempf[idx] = wave_laplacian(par, CS, surf, normals, H, tempv, idx);
 }
 __global__ void __launch_bounds__(BLOCK)
 k_evolve(Par par, int64_t n, float* __restrict__ H, float* __restrict__ DtH, const float* __restrict__ seed, const float* __restrict__ tempf) {
-	ST_IDX(n)
+	ITEM_IDX(n)
 	float h = H[idx], d = DtH[idx];
 	evolve_wave(par, tempf[idx], seed[idx], h, d);
 	H[idx] = h;
 	DtH[idx] = d;
 }
 __global__ void __launch_bounds__(BLOCK) k_curvature(Par par, Cells CS, Pts surf, const float* __restrict__ normals, float* __restrict__ tempf) {
-	ST_IDX(surf.n)
+	ITEM_IDX(surf.n)
 	tempf[idx] = surface_curvature(par, CS, surf, normals, idx);
 }
 __global__ void __launch_bounds__(BLOCK) k_smooth_curvature(Par par, Cells CS, Pts surf, const float* __restrict__ tempf, float* __restrict__ source) {
-	ST_IDX(surf.n)
+	ITEM_IDX(surf.n)
 	source[idx] = smooth_curvature(par, CS, surf, tempf, idx);
 }
 __global__ void __launch_bounds__(BLOCK) k_seed(Par par, int64_t n, float* __restrict__ source, float* __restrict__ seed, float* __restrict__ amp) {
-	ST_IDX(n)
+	ITEM_IDX(n)
 	float so = source[idx], se = seed[idx], a = amp[idx];
 	seed_wave(par, so, se, a);
 	source[idx] = so;
@@ -173,24 +169,24 @@ __global__ void __launch_bounds__(BLOCK) k_seed(Par par, int64_t n, float* __res
 }
 
 __global__ void __launch_bounds__(BLOCK) k_save_prev(Pts coarse, int64_t pcap, float* __restrict__ prev) {
-	ST_IDX(coarse.n)
+	ITEM_IDX(coarse.n)
 	if ((coarse.flag[idx] & (PNEW | PDELETE)) == 0) store3(prev, pcap, idx, pos_of(coarse, idx));
 }
 __global__ void __launch_bounds__(BLOCK) k_live_mark(int64_t n, const int32_t* __restrict__ flag, int32_t* __restrict__ mark) {
-	ST_IDX(n)
+	ITEM_IDX(n)
 	mark[idx] = (flag[idx] & PDELETE) == 0 ? 1 : 0;
 }
 __global__ void __launch_bounds__(BLOCK)
 k_displaced(Pts surf, const float* __restrict__ normals, const float* __restrict__ H, const int32_t* __restrict__ mark, int64_t ocap, float* __restrict__ out,
             int32_t* __restrict__ oflag) {
-	ST_IDX(surf.n)
+	ITEM_IDX(surf.n)
 	if (!active(surf, idx)) return;
 	const int32_t r = mark[idx] - 1;
 	store3(out, ocap, r, pos_of(surf, idx) + vec_of(normals, surf.cap, idx) * H[idx]);
 	oflag[r] = 0;
 }
 __global__ void __launch_bounds__(BLOCK) k_check_parts(int sx, int sy, int sz, int64_t n, int64_t cap, const float* __restrict__ pos, int32_t* __restrict__ head) {
-	ST_IDX(n)
+	ITEM_IDX(n)
 	// toVec3i truncates; FlagGrid::isInBounds(p) with no boundary
 	const int x = cvt_x86(pos[idx]), y = cvt_x86(pos[cap + idx]), z = cvt_x86(pos[2 * cap + idx]);
 	if (x < 0 || y < 0 || z < 0 || x >= sx || y >= sy || z >= sz) atomicMin(&head[0], (int32_t)idx);

@@ -10,6 +10,8 @@ import os
 
 import numpy as np
 
+from reduce_model import fixed_order_sum          # the centre of mass: 1024 cells per block, at most 2048 blocks (its defaults)
+
 f32, f64 = np.float32, np.float64
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "datagen.npz")
 MAX_TAPS = 255
@@ -93,46 +95,6 @@ def com_terms(density):
     k, j, i = np.meshgrid(np.arange(sz, dtype=f32) + f32(0.5), np.arange(sy, dtype=f32) + f32(0.5), np.arange(sx, dtype=f32) + f32(0.5),
                           indexing="ij")
     return [(d * i).ravel(), (d * j).ravel(), (d * k).ravel(), d.ravel()]
-
-
-def _wave_sum(v):
-    """lane 0 of the 64-lane shuffle reduction (offsets 32, 16, .. 1) along the last axis"""
-    for o in (32, 16, 8, 4, 2, 1):
-        v = v[..., :o] + v[..., o:2 * o]
-    return v[..., 0]
-
-
-def _block_sum(v):
-    """thread 0 of a 256-thread block_sum along the last axis: four wavefront sums added in order"""
-    w = _wave_sum(v.reshape(v.shape[:-1] + (4, 64)))
-    return ((w[..., 0] + w[..., 1]) + w[..., 2]) + w[..., 3]
-
-
-def fixed_order_sum(t):
-    """the fp64 sum of the fp32 terms t in the library's order: nb = min(max(ceil(n / 1024), 1), 2048) blocks of 256 threads, thread g
-    adds cells g, g + 256 nb, ... in order; block_sum; then one block whose thread q adds partials q, q + 256, ... and block_sum"""
-    t = np.asarray(t, f64)
-    n = t.size
-    nb = min(max((n + 1023) // 1024, 1), 2048)
-    T = nb * 256
-    rows = (n + T - 1) // T
-    p = np.zeros(rows * T, f64)
-    p[:n] = t
-    p = p.reshape(rows, T)
-    live = (np.arange(rows * T) < n).reshape(rows, T)
-    acc = np.zeros(T, f64)
-    for r in range(rows):
-        acc = np.where(live[r], acc + p[r], acc)
-    part = _block_sum(acc.reshape(nb, 256))
-    rows2 = (nb + 255) // 256
-    q = np.zeros(rows2 * 256, f64)
-    q[:nb] = part
-    q = q.reshape(rows2, 256)
-    live2 = (np.arange(rows2 * 256) < nb).reshape(rows2, 256)
-    acc2 = np.zeros(256, f64)
-    for r in range(rows2):
-        acc2 = np.where(live2[r], acc2 + q[r], acc2)
-    return float(_block_sum(acc2))
 
 
 def center_of_mass(density):
