@@ -12,15 +12,14 @@
 // launch-bound).
 //
 // Set-up: the greedy coarse-vertex selection (genCoarseGrid) is serial and order-dependent; it runs on the host on the
-// downloaded type bytes, with the reference's bucket heap order.  Everything else of the set-up is a gather per vertex on the
+// downloaded type bytes, with the reference's bucket heap order (mg_host.h, shared with the 2-D hierarchy of mg2d.hip).  Everything else of the set-up is a gather per vertex on the
 // device.
 #include "common.h"
 #include "pressure.h"
+#include "mg_host.h"
 #include "../../include/manta_hip_multigrid.h"
 #include <algorithm>
 #include <chrono>
-#include <mutex>
-#include <set>
 #include <vector>
 #include <stdlib.h>
 #include <string.h>
@@ -33,8 +32,6 @@ constexpr int MAXL = 16;
 constexpr int TAIL_BLOCK = 1024;      // one workgroup; the coarsest level has at most 1000 vertices (one per thread in the CG)
 constexpr int TAIL_VERTS = 8192;      // levels of at most this many vertices run inside k_mg_tail
 constexpr unsigned MG_MAGIC = 0x4d474d47u;
-
-enum : unsigned char { vtInactive = 0, vtActive = 1, vtActiveTrivial = 2, vtRemoved = 3, vtZero = 4, vtFree = 5 };   // multigrid.h:87-94
 
 struct Lv {
 	int sx, sy, sz, n;
@@ -470,114 +467,14 @@ k_mg_tail(MgView M, int first, float accuracy, int* __restrict__ info) {
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-// the handles that mf_mg_create gave out and mf_mg_destroy has not taken back: a destroyed handle is refused without reading
-// the memory it pointed to
-std::mutex g_live_mutex;
-std::set<void*> g_live;
+// the handles that mf_mg_create gave out and mf_mg_destroy has not taken back (mg_host.h)
+LiveHandles g_live;
 Mg* as_mg(void* h) {
-	if (!h) return nullptr;
-	{
-		std::lock_guard<std::mutex> lock(g_live_mutex);
-		if (!g_live.count(h)) return nullptr;
-	}
+	if (!h || !g_live.has(h)) return nullptr;
 	Mg* m = (Mg*)h;
 	return m->magic == MG_MAGIC ? m : nullptr;
 }
-
-// The bucket min-heap of genCoarseGrid (NKMinHeap, multigrid.cpp:57-186): one doubly linked list per key; set_key puts an ID at
-// the HEAD of its new key's list and pop_min takes the head of the smallest non-empty key -- among equal keys the vertex whose
-// key was set last comes out first.  The selection depends on that order.
-struct BucketHeap {
-	int N, K, size, minKey;
-	std::vector<int> key, prev, next;      // entries 0..K-1: list heads; K + id: the IDs
-	BucketHeap(int n, int k) : N(n), K(k), size(0), minKey(-1), key(n + k, -1), prev(n + k, -1), next(n + k, -1) {}
-	int get_key(int id) const { return key[K + id]; }
-	void advance_min() {
-		for (; minKey < K; minKey++)
-			if (next[minKey] != -1) break;
-	}
-	void unlink(int e) {
-		const int pr = prev[e], su = next[e];
-		next[pr] = su;
-		if (su != -1) prev[su] = pr;
-	}
-	void set_key(int id, int k) {
-		const int e = K + id;
-		if (key[e] == k) return;
-		if (key[e] != -1) {
-			unlink(e);
-			if (key[e] == minKey) {
-				if (size == 1) minKey = -1;
-				else advance_min();
-			}
-			size--;
-		}
-		key[e] = k;
-		if (k == -1) {
-			next[e] = prev[e] = -1;
-			return;
-		}
-		size++;
-		minKey = (minKey == -1) ? k : std::min(minKey, k);
-		const int old = next[k];
-		next[k] = e;
-		prev[e] = k;
-		next[e] = old;
-		if (old != -1) prev[old] = e;
-	}
-	int pop_min() {
-		const int e = next[minKey];
-		unlink(e);
-		key[e] = prev[e] = next[e] = -1;
-		size--;
-		if (size == 0) minKey = -1;
-		else advance_min();
-		return e - K;
-	}
-};
-
-// genCoarseGrid + knActivateCoarseVertices, multigrid.cpp:507-578, on host copies of the type bytes; returns the active count
-int select_coarse(const Lv& F, const unsigned char* tf, const Lv& C, unsigned char* tc) {
-	std::fill(tc, tc + C.n, (unsigned char)vtFree);
-	BucketHeap heap(F.n, 9);
-	for (int v = 0; v < F.n; v++) {
-		if (tf[v] == vtInactive) continue;
-		const int X = v % F.sx, Y = (v / F.sx) % F.sy, Z = v / (F.sx * F.sy);
-		heap.set_key(v, 1 << ((X & 1) + (Y & 1) + (Z & 1)));
-	}
-	while (heap.size > 0) {
-		const int v = heap.pop_min();
-		const int X = v % F.sx, Y = (v / F.sx) % F.sy, Z = v / (F.sx * F.sy);
-		bool vdone = false;
-		for (int iz = Z / 2; iz <= (Z + 1) / 2; iz++)
-		for (int iy = Y / 2; iy <= (Y + 1) / 2; iy++)
-		for (int ix = X / 2; ix <= (X + 1) / 2; ix++) {
-			const int i = ix + C.sx * (iy + C.sy * iz);
-			if (tc[i] != vtFree) continue;
-			if (vdone) tc[i] = vtRemoved;
-			else {
-				tc[i] = vtZero;
-				vdone = true;
-			}
-			const int r0x = std::max(0, ix * 2 - 1), r0y = std::max(0, iy * 2 - 1), r0z = std::max(0, iz * 2 - 1);
-			const int r1x = std::min(F.sx - 1, ix * 2 + 1), r1y = std::min(F.sy - 1, iy * 2 + 1), r1z = std::min(F.sz - 1, iz * 2 + 1);
-			for (int rz = r0z; rz <= r1z; rz++)
-			for (int ry = r0y; ry <= r1y; ry++)
-			for (int rx = r0x; rx <= r1x; rx++) {
-				const int r = rx + F.sx * (ry + F.sy * rz);
-				const int k = heap.get_key(r);
-				if (k > 1) heap.set_key(r, k - 1);
-				else if (k > -1) heap.set_key(r, -1);
-			}
-		}
-	}
-	int active = 0;
-	for (int i = 0; i < C.n; i++) {
-		tc[i] = (tc[i] == vtZero) ? vtActive : vtInactive;      // free -> removed -> inactive
-		active += tc[i] == vtActive;
-	}
-	return active;
-}
+MgDim dim_of(const Lv& L) { return MgDim{L.sx, L.sy, L.sz, L.n}; }
 
 // the coarsening paths of level 1 in the reference's order, multigrid.cpp:286-318: generated U-major / stencil / N, then sorted by
 // (sc, position of U) with std::sort -- the comparator leaves ties, and the operator sums in the resulting order, so the same
@@ -645,7 +542,7 @@ int mg_set_a(Mg* m, const float* A0, const float* Ai, const float* Aj, const flo
 	for (int l = 1; l < V.nl; l++) {
 		const auto h0 = clk::now();
 		tc.resize(V.l[l].n);
-		m->nactive[l] = select_coarse(V.l[l - 1], tf.data(), V.l[l], tc.data());
+		m->nactive[l] = select_coarse(dim_of(V.l[l - 1]), tf.data(), dim_of(V.l[l]), tc.data());
 		us_host += std::chrono::duration_cast<std::chrono::microseconds>(clk::now() - h0).count();
 		MF_HIP(hipMemcpyAsync(V.l[l].t, tc.data(), tc.size(), hipMemcpyHostToDevice, st));
 		if (l == 1) hipLaunchKernelGGL(k_mg_operator1, dim3(nblk(V.l[l].n)), dim3(BLOCK), 0, st, V.l[0], V.l[1], m->paths, m->npaths);
@@ -767,10 +664,7 @@ int mf_mg_create(int sx, int sy, int sz, void** handle_out) {
 	if (const char* e = getenv("MF_MG_TAIL_VERTS")) tail_verts = atoi(e);
 	m->tail_first = V.nl - 1;
 	while (m->tail_first > 0 && V.l[m->tail_first - 1].n <= tail_verts) m->tail_first--;
-	{
-		std::lock_guard<std::mutex> lock(g_live_mutex);
-		g_live.insert(m);
-	}
+	g_live.insert(m);
 	*handle_out = m;
 	return 0;
 }
@@ -779,10 +673,7 @@ int mf_mg_destroy(void* handle) {
 	Mg* m = as_mg(handle);
 	if (!m) return fail("mf_mg_destroy: bad handle");
 	MF_HIP(hipDeviceSynchronize());
-	{
-		std::lock_guard<std::mutex> lock(g_live_mutex);
-		g_live.erase(handle);
-	}
+	g_live.erase(handle);
 	free_levels(m);
 	m->magic = 0;
 	delete m;

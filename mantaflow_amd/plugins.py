@@ -288,8 +288,7 @@ def solvePressureSystem(rhs, vel, pressure, flags, cgAccuracy=1e-3, phi=None, pe
             _mg_solvers.add(s)
         out = (ctypes.c_float * 3)()
         try:
-            lib.call("mf_mg_cg_solve", s._mg.handle, sx, sy, sz, flags.ptr, pressure.ptr, rhs.ptr, residual.ptr, search.ptr, tmp.ptr,
-                     A0.ptr, Ai.ptr, Aj.ptr, Ak.ptr, float(cgAccuracy), 100, int(bool(useL2Norm)), out, st)   # maxIter = 100, :419
+            s._mg.cg_solve((sx, sy, sz), flags, pressure, rhs, residual, search, tmp, (A0, Ai, Aj, Ak), cgAccuracy, 100, useL2Norm, out, st)   # maxIter = 100, :419
         except RuntimeError as e:
             if "diverged" in str(e):
                 # conjugategrad.cpp:287-291
@@ -345,23 +344,33 @@ def cgSolveDiffusion(flags, grid, alpha=0.25, cgMaxIterFac=1.0, cgAccuracy=1e-4)
 
 
 class _MgHandle(object):
-    """a multigrid hierarchy of the library (manta_hip_multigrid.h), destroyed with the object"""
+    """a multigrid hierarchy of the library, destroyed with the object: of manta_hip_multigrid.h on a 3-D grid, of
+    open/manta_hip_mg2d.h (the same entries, one for one, without sz and Ak) when sz == 1"""
 
     def __init__(self, lib, sx, sy, sz):
         self.lib = lib
+        self.two_d = sz == 1
+        self.prefix = "mf_mg2d_" if self.two_d else "mf_mg_"
         h = ctypes.c_void_p()
-        lib.call("mf_mg_create", sx, sy, sz, ctypes.byref(h))
+        lib.call(self.prefix + "create", *((sx, sy) if self.two_d else (sx, sy, sz)), ctypes.byref(h))
         self.handle = h
+
+    def cg_solve(self, dims, flags, pressure, rhs, residual, search, tmp, A, cgAccuracy, maxIter, useL2Norm, out, st):
+        """mf_mg_cg_solve / mf_mg2d_cg_solve on the grids' pointers; A: the four coefficient grids (a 2-D system has no Ak)"""
+        size, coef = (dims[:2], A[:3]) if self.two_d else (dims, A)
+        self.lib.call(self.prefix + "cg_solve", self.handle, *size, flags.ptr, pressure.ptr, rhs.ptr, residual.ptr, search.ptr, tmp.ptr,
+                      *[a.ptr for a in coef], float(cgAccuracy), int(maxIter), int(bool(useL2Norm)), out, st)
 
     def release(self):
         if self.handle is not None:
             h, self.handle = self.handle, None
-            self.lib.call("mf_mg_destroy", h)
+            self.lib.call(self.prefix + "destroy", h)
 
     def info(self):
-        """levels, set-ups so far, coarsest-CG iterations of the last V-cycle, per-level sizes and active vertices (mf_mg_info)"""
+        """levels, set-ups so far, coarsest-CG iterations of the last V-cycle, per-level sizes and active vertices (mf_mg_info /
+        mf_mg2d_info)"""
         out = (ctypes.c_int64 * (8 + 4 * 16))()
-        self.lib.call("mf_mg_info", self.handle, out, len(out))
+        self.lib.call(self.prefix + "info", self.handle, out, len(out))
         nl = int(out[0])
         return dict(levels=nl, setups=int(out[1]), coarse_cg_iterations=int(out[2]), nonzero_stencil_sum=bool(out[3]),
                     trivial_equations=bool(out[4]), tail_first_level=int(out[5]), setup_host_us=int(out[6]), setup_device_us=int(out[7]),
@@ -378,10 +387,20 @@ class _MgHandle(object):
 _mg_solvers = __import__("weakref").WeakSet()    # solvers that hold a hierarchy (gMapMG, pressure.cpp:248)
 
 
+_multigrid_2d = False    # the process-wide switch of mantaflow_amd.multigrid2d (setMultigrid2D): off unless a scene turns it on
+
+
 def _multigrid_lib(s, name):
-    """refuse, before any grid is touched, what the multigrid preconditioner does not run on"""
-    lib = _extension_lib(s, name, "multigrid")
-    if not s.is3D():
+    """refuse, before any grid is touched, what the multigrid preconditioner does not run on.  This is the one place that decides
+    whether a 2-D solver reaches the 2-D hierarchy (open/manta_hip_mg2d.h): only with the switch of mantaflow_amd.multigrid2d on.
+    The order: a z-slab solver and a backend without the extension first (core._extension_lib; the phrase is the mg2d row's when
+    a 2-D solver asks with the switch on, the multigrid row's otherwise), then a 2-D solver with the switch off, then a HIP
+    library that was built without the 2-D hierarchy"""
+    two_d = _multigrid_2d and not s.is3D()
+    if two_d and s.lib.backend == "hip" and tuple(s._slab_window) == (0, 0) and not s.lib.mg2d:
+        raise RuntimeError("%s: %s lacks the 2-D multigrid extension (manta_hip_mg2d.h) -- rebuild the library" % (name, s.lib.path))
+    lib = _extension_lib(s, name, "mg2d" if two_d else "multigrid")
+    if not s.is3D() and not two_d:
         raise RuntimeError("%s: the multigrid preconditioners PcMGStatic / PcMGDynamic run on 3-D solvers only" % name)
     return lib
 
