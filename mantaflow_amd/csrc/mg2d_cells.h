@@ -1,6 +1,6 @@
 // mg2d_cells.h -- the per-vertex bodies of mg2d.hip (the 2-D multigrid hierarchy, include/open/manta_hip_mg2d.h) as
-// __host__ __device__ functions: the kernels of mg2d.hip call them, and tools/mg2d_host_check.hip runs the same text on the
-// host, every launch replaced by a serial loop, for the host sanitizers.  Reference: source/multigrid.cpp, GridMg with
+// __host__ __device__ functions: the kernels of mg_driver.h call them, and tools/mg2d_host_check.hip runs the same text on the
+// host, every launch replaced by a serial loop, for the host sanitizers.  (set_rhs and ordered_sum are in mg_host.h.)  Reference: source/multigrid.cpp, GridMg with
 // mIs3D == false (cited per function).
 //
 // Layout.  Level 0 keeps a private SoA copy of the 5-point stencil in 3 planes (A0, Ai, Aj; x fastest) because trivial rows
@@ -15,10 +15,6 @@
 
 namespace mf {
 namespace mg2d {
-
-#define MG2D_HD __host__ __device__ __forceinline__
-
-constexpr int MAXL = 16;
 
 struct Lv {
 	int sx, sy, n;
@@ -37,11 +33,7 @@ struct Path {
 	float rw, iw;
 };
 
-MG2D_HD int imin(int a, int b) { return a < b ? a : b; }
-MG2D_HD int imax(int a, int b) { return a > b ? a : b; }
-MG2D_HD int odd2(int x, int y) { return (x & 1) + (y & 1); }
-// 1 / (1 << k), k = 0..2: exact
-MG2D_HD float pow2inv(int k) { return k == 0 ? 1.f : k == 1 ? 0.5f : 0.25f; }
+MG_HD int odd2(int x, int y) { return (x & 1) + (y & 1); }
 
 // ---------------------------------------------------------------------------------------------------------
 // set-up
@@ -49,7 +41,7 @@ MG2D_HD float pow2inv(int k) { return k == 0 ? 1.f : k == 1 ? 0.5f : 0.25f; }
 // knCopyA + knActivateVertices + analyzeStencil with is3D == false (A[3] = A[6] = 0), multigrid.cpp:321-384, at vertex v.
 // The reference scales the diagonal of trivial rows in place while other threads analyse their stencils; they only read the
 // off-diagonals of their neighbours, which nobody changes.
-MG2D_HD void copy_activate(const Lv& L, int v, const float* A0, const float* Ai, const float* Aj, int* info) {
+MG_HD void copy_activate(const Lv& L, int v, const float* A0, const float* Ai, const float* Aj, int* info) {
 	const int X = v % L.sx, Y = v / L.sx;
 	float a[7];
 	a[0] = A0[v];
@@ -82,7 +74,7 @@ MG2D_HD void copy_activate(const Lv& L, int v, const float* A0, const float* Ai,
 }
 
 // knGenCoarseGridOperator for l == 1, multigrid.cpp:594-614: the sorted paths, one after the other, into the 5 entries of V
-MG2D_HD void operator1(const Lv& F, const Lv& C, int idx, const Path* paths, int npaths) {
+MG_HD void operator1(const Lv& F, const Lv& C, int idx, const Path* paths, int npaths) {
 	if (C.t[idx] == vtInactive) return;
 	const int VX = idx % C.sx, VY = idx / C.sx;
 	float acc = 0.f;
@@ -115,7 +107,7 @@ MG2D_HD void operator1(const Lv& F, const Lv& C, int idx, const Path* paths, int
 
 // knGenCoarseGridOperator for l > 1, multigrid.cpp:615-656 (the reference's loop nest and its truncating divisions) over the
 // 9-point neighbourhood: mStencilSize = 5, so the entries sc < 4 are left to the neighbours and entry sc is stored at sc - 4
-MG2D_HD void operatorN(const Lv& F, const Lv& C, int idx) {
+MG_HD void operatorN(const Lv& F, const Lv& C, int idx) {
 	if (C.t[idx] == vtInactive) return;
 	const int VX = idx % C.sx, VY = idx / C.sx;
 	for (int s = 0; s < 5; s++) C.A[s * C.n + idx] = 0.f;
@@ -155,7 +147,7 @@ MG2D_HD void operatorN(const Lv& F, const Lv& C, int idx) {
 // ---------------------------------------------------------------------------------------------------------
 // b - (off-diagonal part of A x) at vertex v of level 0 in knSmoothColor's / knCalcResidual's order (d = 0, 1; the lower
 // neighbour before the upper one), multigrid.cpp:684-689, 748-753
-MG2D_HD float offdiag0(const Lv& L, int v, int X, int Y, float sum) {
+MG_HD float offdiag0(const Lv& L, int v, int X, int Y, float sum) {
 	const float *Ai = L.A + L.n, *Aj = L.A + 2 * L.n;
 	if (X > 0) sum -= Ai[v - 1] * L.x[v - 1];
 	if (X < L.sx - 1) sum -= Ai[v] * L.x[v + 1];
@@ -167,7 +159,7 @@ MG2D_HD float offdiag0(const Lv& L, int v, int X, int Y, float sum) {
 // lower entries (s < 5) are read from the neighbour's row, the upper ones from the vertex's own.  SKIP_CENTRE: the smoother
 // leaves s == 4 out.
 template <bool SKIP_CENTRE>
-MG2D_HD float row9_sub(const Lv& L, int v, int X, int Y, float sum) {
+MG_HD float row9_sub(const Lv& L, int v, int X, int Y, float sum) {
 	int s = 0;
 	for (int dy = -1; dy <= 1; dy++)
 	for (int dx = -1; dx <= 1; dx++, s++) {
@@ -182,14 +174,14 @@ MG2D_HD float row9_sub(const Lv& L, int v, int X, int Y, float sum) {
 	return sum;
 }
 
-MG2D_HD int smooth_items(const Lv& L, bool l0) { return l0 ? ((L.sx + 1) >> 1) * L.sy : ((L.sx + 1) >> 1) * ((L.sy + 1) >> 1); }
-MG2D_HD int smooth_colours(bool l0) { return l0 ? 2 : 4; }
+MG_HD int smooth_items(const Lv& L, bool l0) { return l0 ? ((L.sx + 1) >> 1) * L.sy : ((L.sx + 1) >> 1) * ((L.sy + 1) >> 1); }
+MG_HD int smooth_colours(bool l0) { return l0 ? 2 : 4; }
 
 // knSmoothColor, multigrid.cpp:668-711, one colour (smoothGS, :723-726).  Level 0: colour 0 is {(0,0), (1,1)} and colour 1
 // {(1,0), (0,1)} of each 2 x 2 block, that is the parity (x + y) & 1 == colour; an item is a pair of x-neighbours, of which one
 // has the colour.  Levels > 0: colour c is the single offset (c & 1, c >> 1) in the 2 x 2 blocks; an item is a block.
 // Vertices of one colour do not read each other.
-MG2D_HD void pass_smooth(const Lv& L, bool l0, int colour, int start, int stride) {
+MG_HD void pass_smooth(const Lv& L, bool l0, int colour, int start, int stride) {
 	const int items = smooth_items(L, l0);
 	const int hx = (L.sx + 1) >> 1;
 	for (int it = start; it < items; it += stride) {
@@ -209,7 +201,7 @@ MG2D_HD void pass_smooth(const Lv& L, bool l0, int colour, int start, int stride
 	}
 }
 // knCalcResidual, multigrid.cpp:739-771
-MG2D_HD void pass_residual(const Lv& L, bool l0, int start, int stride) {
+MG_HD void pass_residual(const Lv& L, bool l0, int start, int stride) {
 	for (int v = start; v < L.n; v += stride) {
 		if (L.t[v] == vtInactive) continue;
 		const int X = v % L.sx, Y = v / L.sx;
@@ -224,7 +216,7 @@ MG2D_HD void pass_residual(const Lv& L, bool l0, int start, int stride) {
 	}
 }
 // knRestrict (b of the coarse level from r of the fine one), multigrid.cpp:904-927, and knSet(x_coarse, 0), :472
-MG2D_HD void pass_restrict(const Lv& F, const Lv& C, int start, int stride) {
+MG_HD void pass_restrict(const Lv& F, const Lv& C, int start, int stride) {
 	for (int idx = start; idx < C.n; idx += stride) {
 		C.x[idx] = 0.f;
 		if (C.t[idx] == vtInactive) continue;
@@ -243,7 +235,7 @@ MG2D_HD void pass_restrict(const Lv& F, const Lv& C, int start, int stride) {
 }
 // knInterpolate into r of the fine level + knAddAssign(x, r), multigrid.cpp:484-486, 934-954.  The interpolated value is not
 // stored: nothing reads r before the next residual pass overwrites it, and the inactive vertices (whose r stays 0) add 0.
-MG2D_HD void pass_interp_add(const Lv& F, const Lv& C, int start, int stride) {
+MG_HD void pass_interp_add(const Lv& F, const Lv& C, int start, int stride) {
 	for (int v = start; v < F.n; v += stride) {
 		if (F.t[v] == vtInactive) continue;
 		const int X = v % F.sx, Y = v / F.sx;
@@ -257,16 +249,9 @@ MG2D_HD void pass_interp_add(const Lv& F, const Lv& C, int start, int stride) {
 		F.x[v] = F.x[v] + c;
 	}
 }
-// knSetRhs (trivial rows scaled), multigrid.cpp:417-424, and knSet(x_0, 0), :458
-MG2D_HD void set_rhs(const Lv& L, int v, const float* rhs) {
-	float b = rhs[v];
-	if (L.t[v] == vtActiveTrivial) b *= 1E-6f;
-	L.b[v] = b;
-	L.x[v] = 0.f;
-}
 
 // applyAStencil of solveCG (multigrid.cpp:798-826) on a double vector
-MG2D_HD double cg_apply(const Lv& L, bool l0, int v, int X, int Y, const double* vec) {
+MG_HD double cg_apply(const Lv& L, bool l0, int v, int X, int Y, const double* vec) {
 	double sum = 0.0;
 	if (l0) {
 		const float *Ai = L.A + L.n, *Aj = L.A + 2 * L.n;
@@ -288,18 +273,6 @@ MG2D_HD double cg_apply(const Lv& L, bool l0, int v, int X, int Y, const double*
 		}
 	}
 	return sum;
-}
-// the sum of a[0..n) in index order, as the reference's serial loop forms it (the entries of inactive vertices are +0, which
-// leaves a sum that started at +0 unchanged)
-MG2D_HD double ordered_sum(const double* a, int n) {
-	double s = 0.0;
-	int i = 0;
-	for (; i + 8 <= n; i += 8) {
-		const double a0 = a[i], a1 = a[i + 1], a2 = a[i + 2], a3 = a[i + 3], a4 = a[i + 4], a5 = a[i + 5], a6 = a[i + 6], a7 = a[i + 7];
-		s += a0; s += a1; s += a2; s += a3; s += a4; s += a5; s += a6; s += a7;
-	}
-	for (; i < n; i++) s += a[i];
-	return s;
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -1,7 +1,10 @@
-// mg_host.h -- what the two multigrid hierarchies (multigrid.hip: 3-D, mg2d.hip: 2-D) share: the vertex types, the host side of
-// the set-up (the bucket heap and the greedy coarse-vertex selection of genCoarseGrid) and the registry of live handles.
-// Host code and constants only: the kernels of the two files are their own.
+// mg_host.h -- what the two multigrid hierarchies (multigrid.hip: 3-D over mg3d_cells.h, mg2d.hip: 2-D over mg2d_cells.h) and their
+// one driver (mg_driver.h) share below the level types: the vertex types, the small exact helpers of the per-vertex bodies
+// (imin, imax, pow2inv, ordered_sum, set_rhs), the host side of the set-up (the bucket heap and the greedy coarse-vertex
+// selection of genCoarseGrid) and the registry of live handles.  Nothing here launches anything: tools/mg2d_host_check.hip runs
+// the same text on the host.
 #pragma once
+#include "common.h"
 #include <algorithm>
 #include <mutex>
 #include <set>
@@ -15,6 +18,36 @@ enum : unsigned char { vtInactive = 0, vtActive = 1, vtActiveTrivial = 2, vtRemo
 struct MgDim {
 	int sx, sy, sz, n;
 };
+
+#define MG_HD __host__ __device__ __forceinline__
+
+constexpr int MAXL = 16;      // levels of a hierarchy at most
+
+MG_HD int imin(int a, int b) { return a < b ? a : b; }
+MG_HD int imax(int a, int b) { return a > b ? a : b; }
+// 1 / (1 << k), k = 0..3: exact
+MG_HD float pow2inv(int k) { return k == 0 ? 1.f : k == 1 ? 0.5f : k == 2 ? 0.25f : 0.125f; }
+
+// knSetRhs (trivial rows scaled), multigrid.cpp:417-424, and knSet(x_0, 0), :458, at vertex v of level 0
+template <class Lv>
+MG_HD void set_rhs(const Lv& L, int v, const float* rhs) {
+	float b = rhs[v];
+	if (L.t[v] == vtActiveTrivial) b *= 1E-6f;
+	L.b[v] = b;
+	L.x[v] = 0.f;
+}
+// the sum of a[0..n) in index order, as the reference's serial loop forms it (the entries of inactive vertices are +0, which
+// leaves a sum that started at +0 unchanged)
+MG_HD double ordered_sum(const double* a, int n) {
+	double s = 0.0;
+	int i = 0;
+	for (; i + 8 <= n; i += 8) {
+		const double a0 = a[i], a1 = a[i + 1], a2 = a[i + 2], a3 = a[i + 3], a4 = a[i + 4], a5 = a[i + 5], a6 = a[i + 6], a7 = a[i + 7];
+		s += a0; s += a1; s += a2; s += a3; s += a4; s += a5; s += a6; s += a7;
+	}
+	for (; i < n; i++) s += a[i];
+	return s;
+}
 
 // The handles that a create entry gave out and its destroy entry has not taken back: a destroyed or foreign handle is refused
 // without reading the memory it points to.

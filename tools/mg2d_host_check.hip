@@ -1,4 +1,5 @@
-// tools/mg2d_host_check.hip -- the per-vertex bodies of mantaflow_amd/csrc/mg2d_cells.h run on the HOST: every launch of mg2d.hip
+// tools/mg2d_host_check.hip -- the per-vertex bodies of mantaflow_amd/csrc/mg2d_cells.h (and set_rhs, ordered_sum of mg_host.h) run on the
+// HOST: every launch that mg_driver.h makes for the 2-D hierarchy of mg2d.hip
 // replaced by a serial loop over its work items (in the stride-1 form the grid-wide kernels use and, for the levels of the tail, in
 // the stride-1024 form of the single-workgroup kernel), the tail's coarsest-level CG by a serial loop over the same per-vertex
 // steps, as a stand-alone program for the host sanitizers.  tools/mg2d_host_check.py drives it with the cases of
@@ -32,7 +33,7 @@ static float* nans(int n) {
 	return p;
 }
 
-// the tail's solveCG (k_mg2d_tail), one vertex after the other: the same per-vertex steps between the same barriers
+// the tail's solveCG (k_mg_tail of mg_driver.h), stated a second time and serially, one vertex after the other: the same per-vertex steps between the same barriers
 static int solve_cg(const Lv& L, bool l0, float accuracy) {
 	const int n = L.n;
 	double *x = exact<double>(n), *r = exact<double>(n), *z = exact<double>(n), *p = exact<double>(n), *s1 = exact<double>(n), *s2 = exact<double>(n);
@@ -113,7 +114,7 @@ int main(int argc, char** argv) {
 	int tail_first = V.nl - 1;
 	while (tail_first > 0 && V.l[tail_first - 1].n <= tail_verts) tail_first--;
 
-	// set-up (mg_set_a)
+	// set-up (set_a of mg_driver.h)
 	int info[3] = {0, 0, 0};
 	int active[MAXL];
 	const std::vector<Path> ps = make_paths();
@@ -130,7 +131,7 @@ int main(int argc, char** argv) {
 		}
 	}
 
-	// one V-cycle (mg_vcycle): grid-wide kernels above tail_first (stride = the whole grid: every item by its own thread), the tail's
+	// one V-cycle (vcycle of mg_driver.h): grid-wide kernels above tail_first (stride = the whole grid: every item by its own thread), the tail's
 	// 1024 workers below
 	const int last = V.nl - 1;
 	for (int v = 0; v < n0; v++) set_rhs(V.l[0], v, rhs);

@@ -6,7 +6,7 @@ the GPU, alternating in one process so clocks and cache state are shared.  Two i
 Timed per input: solvePressureSystem(PcMIC) through the parent's library, through this tree's library, PcMGStatic in steady state
 (hierarchy kept), PcMGDynamic (set-up in every solve), the set-up split into host selection / everything else (mf_mg_info), one
 V-cycle (device events), and one V-cycle with the single-workgroup tail reduced to the coarsest-level CG (MF_MG_TAIL_VERTS=0), whose
-k_mg_tail time in the kernel statistics is the ordered coarsest solve alone.
+k_mg_tail<Mg3d> time in the kernel statistics (k_mg_tail in the records of before mg_driver.h) is the ordered coarsest solve alone.
 
 The parent's library is not built here (the tree that runs may not be a git checkout).  Build it once from the parent commit:
   git archive <parent> mantaflow_amd/csrc include | tar -x -C <dir> && make -f <dir>/mantaflow_amd/csrc/Makefile
