@@ -68,6 +68,7 @@ OPEN_EXTENSIONS = (
     Extension("surfturb", "surface turbulence", "does", "open"),
     Extension("vsheet", "vortex sheets", "do", "open"),
     Extension("mg2d", "the multigrid preconditioners PcMGStatic / PcMGDynamic on 2-D solvers", "do", "open"),
+    Extension("mgslab", "the multigrid preconditioners PcMGStatic / PcMGDynamic on z-slabs", "do", "open"),
 )
 """The third table, and the last one.  MORE_EXTENSIONS is frozen as well: tests/test_turbulence_api.py pins its one name and the set of
 headers include/ext/manta_hip_*.h.  This table is open: the next extension appends a row here, puts its header under include/open/
@@ -80,7 +81,7 @@ def all_extensions():
     return EXTENSIONS + MORE_EXTENSIONS + OPEN_EXTENSIONS
 
 
-for _ext in all_extensions():    # OBSTACLES_HEADER ... SECPARTS_HEADER, TURBULENCE_HEADER, FIELDS_HEADER, MESH_HEADER, MESHSDF_HEADER, REINIT_HEADER, GRID4D_HEADER, VORTEX_HEADER, MLFLIP_HEADER, DATAGEN_HEADER, MOVINGOBS_HEADER, GRIDOPS_HEADER, MESHOPS_HEADER, SURFTURB_HEADER, VSHEET_HEADER, MG2D_HEADER
+for _ext in all_extensions():    # OBSTACLES_HEADER ... SECPARTS_HEADER, TURBULENCE_HEADER, FIELDS_HEADER, MESH_HEADER, MESHSDF_HEADER, REINIT_HEADER, GRID4D_HEADER, VORTEX_HEADER, MLFLIP_HEADER, DATAGEN_HEADER, MOVINGOBS_HEADER, GRIDOPS_HEADER, MESHOPS_HEADER, SURFTURB_HEADER, VSHEET_HEADER, MG2D_HEADER, MGSLAB_HEADER
     globals()[_ext.name.upper() + "_HEADER"] = _ext.header
 
 

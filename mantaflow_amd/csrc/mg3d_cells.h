@@ -6,8 +6,10 @@
 // are rescaled; levels > 0 keep the 14 stored entries of the symmetric 27-point stencil as 14 planes, so the 64 vertices of a
 // wavefront read 14 coalesced streams.  Vertex types are one byte per vertex.
 //
-// Every pass of a V-cycle is a function over "work items start, start + stride, ...": a grid-wide kernel gives every thread
-// one item, the single-workgroup tail kernel strides by its block size.
+// Every pass of a V-cycle is a function over the work items begin + start, begin + start + stride, ... below end: a grid-wide
+// kernel gives every thread one item of [0, items), the single-workgroup tail kernel strides over them by its block size, and
+// the ranged kernels of mgslab.hip give every thread one item of a sub-range.  The items of every pass are Z-major, so the
+// planes [z0, z1) of a level are the items [z0 * (items per plane), z1 * (items per plane)).
 #pragma once
 #include "common.h"
 #include "mg_host.h"
@@ -190,11 +192,10 @@ MG_HD int smooth_colours(bool l0) { return l0 ? 2 : 8; }
 // {000, 110, 101, 011} and {100, 010, 001, 111}); an item is a pair of x-neighbours, of which one has the colour.  Levels > 0:
 // colour c is the offset (c & 1, c >> 1 & 1, c >> 2) in the 2 x 2 x 2 blocks; an item is a block.  Vertices of one colour do
 // not read each other.
-MG_HD void pass_smooth(const Lv& L, bool l0, int colour, int start, int stride) {
+MG_HD void pass_smooth(const Lv& L, bool l0, int colour, int begin, int end, int start, int stride) {
 	if (l0) {
 		const int hx = (L.sx + 1) >> 1;
-		const int items = hx * L.sy * L.sz;
-		for (int it = start; it < items; it += stride) {
+		for (int it = begin + start; it < end; it += stride) {
 			const int q = it % hx, Y = (it / hx) % L.sy, Z = it / (hx * L.sy);
 			const int X = 2 * q + ((Y + Z + colour) & 1);
 			if (X >= L.sx) continue;
@@ -204,9 +205,8 @@ MG_HD void pass_smooth(const Lv& L, bool l0, int colour, int start, int stride) 
 			L.x[v] = sum / L.A[v];
 		}
 	} else {
-		const int bx = (L.sx + 1) >> 1, by = (L.sy + 1) >> 1, bz = (L.sz + 1) >> 1;
-		const int items = bx * by * bz;
-		for (int it = start; it < items; it += stride) {
+		const int bx = (L.sx + 1) >> 1, by = (L.sy + 1) >> 1;
+		for (int it = begin + start; it < end; it += stride) {
 			const int X = 2 * (it % bx) + (colour & 1), Y = 2 * ((it / bx) % by) + ((colour >> 1) & 1), Z = 2 * (it / (bx * by)) + (colour >> 2);
 			if (X >= L.sx || Y >= L.sy || Z >= L.sz) continue;
 			const int v = X + L.sx * (Y + L.sy * Z);
@@ -216,9 +216,10 @@ MG_HD void pass_smooth(const Lv& L, bool l0, int colour, int start, int stride) 
 		}
 	}
 }
+MG_HD void pass_smooth(const Lv& L, bool l0, int colour, int start, int stride) { pass_smooth(L, l0, colour, 0, smooth_items(L, l0), start, stride); }
 // knCalcResidual, multigrid.cpp:739-771
-MG_HD void pass_residual(const Lv& L, bool l0, int start, int stride) {
-	for (int v = start; v < L.n; v += stride) {
+MG_HD void pass_residual(const Lv& L, bool l0, int begin, int end, int start, int stride) {
+	for (int v = begin + start; v < end; v += stride) {
 		if (L.t[v] == vtInactive) continue;
 		const int X = v % L.sx, Y = (v / L.sx) % L.sy, Z = v / (L.sx * L.sy);
 		float sum;
@@ -231,9 +232,10 @@ MG_HD void pass_residual(const Lv& L, bool l0, int start, int stride) {
 		L.r[v] = sum;
 	}
 }
+MG_HD void pass_residual(const Lv& L, bool l0, int start, int stride) { pass_residual(L, l0, 0, L.n, start, stride); }
 // knRestrict (b of the coarse level from r of the fine one), multigrid.cpp:904-927, and knSet(x_coarse, 0), :472
-MG_HD void pass_restrict(const Lv& F, const Lv& C, int start, int stride) {
-	for (int idx = start; idx < C.n; idx += stride) {
+MG_HD void pass_restrict(const Lv& F, const Lv& C, int begin, int end, int start, int stride) {
+	for (int idx = begin + start; idx < end; idx += stride) {
 		C.x[idx] = 0.f;
 		if (C.t[idx] == vtInactive) continue;
 		const int VX = idx % C.sx, VY = (idx / C.sx) % C.sy, VZ = idx / (C.sx * C.sy);
@@ -250,10 +252,11 @@ MG_HD void pass_restrict(const Lv& F, const Lv& C, int start, int stride) {
 		C.b[idx] = sum;
 	}
 }
+MG_HD void pass_restrict(const Lv& F, const Lv& C, int start, int stride) { pass_restrict(F, C, 0, C.n, start, stride); }
 // knInterpolate into r of the fine level + knAddAssign(x, r), multigrid.cpp:484-486, 934-954.  The interpolated value is not
 // stored: nothing reads r before the next residual pass overwrites it, and the inactive vertices (whose r stays 0) add 0.
-MG_HD void pass_interp_add(const Lv& F, const Lv& C, int start, int stride) {
-	for (int v = start; v < F.n; v += stride) {
+MG_HD void pass_interp_add(const Lv& F, const Lv& C, int begin, int end, int start, int stride) {
+	for (int v = begin + start; v < end; v += stride) {
 		if (F.t[v] == vtInactive) continue;
 		const int X = v % F.sx, Y = (v / F.sx) % F.sy, Z = v / (F.sx * F.sy);
 		float sum = 0.f;
@@ -267,6 +270,7 @@ MG_HD void pass_interp_add(const Lv& F, const Lv& C, int start, int stride) {
 		F.x[v] = F.x[v] + c;
 	}
 }
+MG_HD void pass_interp_add(const Lv& F, const Lv& C, int start, int stride) { pass_interp_add(F, C, 0, F.n, start, stride); }
 
 // applyAStencil of solveCG (multigrid.cpp:798-826) on a double vector
 MG_HD double cg_apply(const Lv& L, bool l0, int v, int X, int Y, int Z, const double* vec) {
@@ -357,6 +361,22 @@ inline std::vector<Path> make_paths() {
 }
 
 inline MgDim dim_of(const Lv& L) { return MgDim{L.sx, L.sy, L.sz, L.n}; }
+
+// ---------------------------------------------------------------------------------------------------------
+// what mgslab.hip (include/open/manta_hip_mgslab.h) borrows of a handle of mf_mg_create.  The registry of live handles and the
+// kernels of the driver are multigrid.hip's own, so these three are defined there.  `who` is the entry name of the refusals.
+// ---------------------------------------------------------------------------------------------------------
+struct Borrowed {
+	View v;              // the levels (device pointers of the handle; valid until mf_mg_destroy)
+	int tail_first;      // first level of the single-workgroup tail
+};
+// refuses a destroyed or foreign handle (a 2-D one of mf_mg2d_create included) and a handle without a matrix, before reading it
+int borrow(void* handle, const char* who, Borrowed* out);
+// the levels 1 .. L-1 of a V-cycle, down and up again, exactly as mf_mg_vcycle queues them (grid-wide passes above the tail, the
+// tail, grid-wide passes up to level 1); refuses a hierarchy whose tail holds level 0
+int coarse_cycle(void* handle, const char* who, hipStream_t st);
+// mCoarsestLevelAccuracy = accuracy * 1e-4, as InitPreconditionMultigrid sets it (conjugategrad.cpp:100-106)
+int set_solve_accuracy(void* handle, const char* who, float accuracy);
 
 }  // namespace mg3d
 }  // namespace mf

@@ -268,14 +268,15 @@ int set_a(Mg<H>* m, const float* A0, const float* Ai, const float* Aj, const flo
 	return 0;
 }
 
+// the levels from .. L-1 of doVCycle, down and up again (multigrid.cpp:460-494): grid-wide passes on the levels above the tail,
+// the tail, grid-wide passes back up to level `from`.  from <= tail_first; a whole V-cycle is from = 0, and a caller that has
+// done level 0 itself (mgslab.hip, on a range of planes per rank) runs from = 1 between its restriction and its interpolation.
 template <class H>
-int vcycle(Mg<H>* m, float* dst, const float* rhs, hipStream_t st) {
+void levels_down_up(Mg<H>* m, int from, hipStream_t st) {
 	using Lv = typename H::Lv;
-	if (!m->aset) return fail("%s_vcycle: GridMg::setRhs Error: A has not been set.", H::NAME);
 	const typename H::View& V = m->v;
 	const int first = m->tail_first;
-	hipLaunchKernelGGL(k_mg_set_rhs<H>, dim3(nblk(V.l[0].n)), dim3(BLOCK), 0, st, V.l[0], rhs);
-	for (int l = 0; l < first; l++) {
+	for (int l = from; l < first; l++) {
 		const Lv& L = V.l[l];
 		const int l0 = l == 0;
 		const int items = smooth_items(L, l0);
@@ -284,13 +285,21 @@ int vcycle(Mg<H>* m, float* dst, const float* rhs, hipStream_t st) {
 		hipLaunchKernelGGL(k_mg_restrict<H>, dim3(nblk(V.l[l + 1].n)), dim3(BLOCK), 0, st, L, V.l[l + 1]);
 	}
 	hipLaunchKernelGGL(k_mg_tail<H>, dim3(1), dim3(TAIL_BLOCK), 0, st, V, first, m->coarsestAcc, m->d_info);
-	for (int l = first - 1; l >= 0; l--) {
+	for (int l = first - 1; l >= from; l--) {
 		const Lv& L = V.l[l];
 		const int l0 = l == 0;
 		const int items = smooth_items(L, l0);
 		hipLaunchKernelGGL(k_mg_interp_add<H>, dim3(nblk(L.n)), dim3(BLOCK), 0, st, L, V.l[l + 1]);
 		for (int c = H::smooth_colours(l0) - 1; c >= 0; c--) hipLaunchKernelGGL(k_mg_smooth<H>, dim3(nblk(items)), dim3(BLOCK), 0, st, L, l0, c);
 	}
+}
+
+template <class H>
+int vcycle(Mg<H>* m, float* dst, const float* rhs, hipStream_t st) {
+	if (!m->aset) return fail("%s_vcycle: GridMg::setRhs Error: A has not been set.", H::NAME);
+	const typename H::View& V = m->v;
+	hipLaunchKernelGGL(k_mg_set_rhs<H>, dim3(nblk(V.l[0].n)), dim3(BLOCK), 0, st, V.l[0], rhs);
+	levels_down_up(m, 0, st);
 	MF_LAUNCH_CHECK();
 	MF_HIP(hipMemcpyAsync(dst, V.l[0].x, sizeof(float) * V.l[0].n, hipMemcpyDeviceToDevice, st));      // knCopyToGrid, multigrid.cpp:499
 	return 0;

@@ -52,6 +52,43 @@ struct Mg3d {
 
 }  // namespace
 
+// what mgslab.hip borrows of a live handle (mg3d_cells.h)
+namespace mf {
+namespace mg3d {
+static int live3d(void* handle, const char* who, Mg<Mg3d>** out) {
+	Mg<Mg3d>* m = as_mg<Mg3d>(handle);
+	if (!m) return fail("%s: bad handle (not a live 3-D hierarchy of mf_mg_create)", who);
+	if (!m->aset) return fail("%s: GridMg::setRhs Error: A has not been set.", who);
+	*out = m;
+	return 0;
+}
+int borrow(void* handle, const char* who, Borrowed* out) {
+	Mg<Mg3d>* m;
+	MF_TRY(live3d(handle, who, &m));
+	out->v = m->v;
+	out->tail_first = m->tail_first;
+	return 0;
+}
+int coarse_cycle(void* handle, const char* who, hipStream_t st) {
+	Mg<Mg3d>* m;
+	MF_TRY(live3d(handle, who, &m));
+	if (m->tail_first < 1)
+		return fail("%s: level 0 of this hierarchy runs inside the single-workgroup tail (mf_mg_info slot [5] == 0): it is not cut, use mf_mg_vcycle", who);
+	// knSet(x_1, 0), multigrid.cpp:472: whole, whatever coarse planes the caller restricted into
+	MF_HIP(hipMemsetAsync(m->v.l[1].x, 0, sizeof(float) * m->v.l[1].n, st));
+	levels_down_up(m, 1, st);
+	MF_LAUNCH_CHECK();
+	return 0;
+}
+int set_solve_accuracy(void* handle, const char* who, float accuracy) {
+	Mg<Mg3d>* m;
+	MF_TRY(live3d(handle, who, &m));
+	m->coarsestAcc = (float)(accuracy * 1E-4);
+	return 0;
+}
+}  // namespace mg3d
+}  // namespace mf
+
 extern "C" {
 
 int mf_multigrid_abi_version(void) { return MF_MULTIGRID_ABI_VERSION; }

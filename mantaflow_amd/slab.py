@@ -15,7 +15,9 @@ The reference has no multi-device code at all, so this layer is new
   MIC(0) sweep has a k-1 dependency that spans slabs; here each slab applies MIC(0) of its own diagonal block
   (block-Jacobi: the coupling Ak across slab faces is dropped in the preconditioner only).  With one rank this is
   exactly the reference algorithm; with P > 1 the iterates differ and the result is validated at converged-solution
-  level (same stopping rule max|residual| < cgAccuracy on the true residual).
+  level (same stopping rule max|residual| < cgAccuracy on the true residual).  With preconditioner=PcMGDynamic | PcMGStatic the
+  same PCG applies one multigrid V-cycle per iteration instead (SlabMG: level 0 cut along z, levels >= 1 replicated; four one-plane
+  exchanges and one all-gather per V-cycle), bit-identical to the undivided grid's, so the iterates do not depend on P.
 No data-path collective other than these; FLIP particles across slabs (reverse halo + migration) are "next".
 """
 import ctypes
@@ -26,11 +28,13 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import _lib
 from . import core
 from .core import _ptr
 
 
-STOP_POLL = 4          # slab PCG: iterations between two host reads of the device-side stop state
+PcMIC, PcMGDynamic, PcMGStatic = 1, 2, 3          # the values of solvePressure(preconditioner=) (plugins.py)
+STOP_POLL = 4         # slab PCG: iterations between two host reads of the device-side stop state
 MIC_BLOCK_CELLS_X = int(os.environ.get("MF_SLAB_XBLOCK", "128"))   # x-extent of a preconditioner block for P > 1 (0 = whole rows)
 MIC_BLOCK_ROWS = int(os.environ.get("MF_SLAB_YBLOCK", "64"))   # y-extent of a preconditioner block when the domain is split over several ranks (0 = do not cut)
 
@@ -229,9 +233,12 @@ def advectSemiLagrange(dom, flags, vel, grid, order=1, strength=1.0, clampMode=2
     plugins._apply_outflow_bc(flags, grid, prev, s.getDt())
 
 
-def solvePressure(dom, vel, pressure, flags, cgAccuracy=1e-3, cgMaxIterFac=1.5, stats=None, phi=None, gfClamp=1e-04):
-    """computePressureRhs + PCG (slab-local MIC) + correctVelocity on a slab.  vel ghosts (1 plane) must be current; with `phi`
-    (ghost-fluid free surface, pressure.cpp:136-214) its one-plane ghosts as well."""
+def solvePressure(dom, vel, pressure, flags, cgAccuracy=1e-3, cgMaxIterFac=1.5, stats=None, phi=None, gfClamp=1e-04,
+                  preconditioner=PcMIC):
+    """computePressureRhs + PCG + correctVelocity on a slab.  vel ghosts (1 plane) must be current; with `phi` (ghost-fluid free
+    surface, pressure.cpp:136-214) its one-plane ghosts as well.  preconditioner: PcMIC (the default: slab-local MIC(0)), or
+    PcMGDynamic / PcMGStatic -- one V-cycle of GridMg per iteration, bit-identical to the undivided grid's (SlabMG below)."""
+    use_mg = _mg_wanted(dom, preconditioner)          # refuses before any grid is touched and before any collective
     s = dom.solver
     lib, st = s.lib, s.stream
     sx, sy, sz = dom.NX, dom.NY, dom.LZ
@@ -267,6 +274,11 @@ def solvePressure(dom, vel, pressure, flags, cgAccuracy=1e-3, cgMaxIterFac=1.5, 
     # multiply those values with the zero residual of the ghost planes), the owned planes are unaffected (the stencil never
     # looks at a neighbour's flags)
     lib.call("mf_pack_matrix", sx, sy, wz, W(fmic), W(A0), W(Ai), W(Aj), W(Ak), st)       # 9 (13 with a ghost-fluid diagonal) instead of 28 B per cell
+    if use_mg:
+        window = dict(wz=wz, wgl=wgl, woff=woff, fmic=fmic)
+        iters = _pcg_multigrid(dom, preconditioner, window, pressure, rhs, residual, search, tmp, (A0, Ai, Aj, Ak), cgAccuracy, stats)
+        _correct_velocity(dom, flags, vel, pressure, phi, gfClamp)
+        return iters
     Akm.copyFrom(Ak)
     av = Akm.data.view(sz, XY)
     if dom.gl:
@@ -389,6 +401,15 @@ def solvePressure(dom, vel, pressure, flags, cgAccuracy=1e-3, cgMaxIterFac=1.5, 
     if stats is not None:
         stats["iterations"], stats["residual"] = iters, float(resNorm)
         stats["mic_blocking"] = (jblock, xblock)     # rows along y / cells along x of a preconditioner block (0: not cut)
+    _correct_velocity(dom, flags, vel, pressure, phi, gfClamp)
+    return iters
+
+
+def _correct_velocity(dom, flags, vel, pressure, phi, gfClamp):
+    """the last step of solvePressure on a slab, after either PCG"""
+    s = dom.solver
+    lib, st = s.lib, s.stream
+    sx, sy, sz = dom.NX, dom.NY, dom.LZ
     # knReplaceClampedGhostFluidVels reads the CORRECTED z-velocity of the planes below and above: the first ghost plane must come
     # out right as well, and its correction reads the pressure of the second one
     dom.exchange(pressure, 1 if phi is None else 2)
@@ -397,6 +418,252 @@ def solvePressure(dom, vel, pressure, flags, cgAccuracy=1e-3, cgMaxIterFac=1.5, 
         # knCorrectVelocityGhostFluid + knReplaceClampedGhostFluidVels, pressure.cpp:154-214 (read pressure / phi / flags at +-1)
         lib.call("mf_correct_velocity_ghost_fluid", sx, sy, sz, vel.ptr, flags.ptr, pressure.ptr, phi.ptr, float(gfClamp), None, 0.0, st)
         lib.call("mf_replace_clamped_ghost_fluid_vels", sx, sy, sz, vel.ptr, flags.ptr, pressure.ptr, phi.ptr, float(gfClamp), st)
+
+
+# =========================================================================================================
+# the multigrid preconditioner on slabs (include/open/manta_hip_mgslab.h): level 0 of the V-cycle cut along z,
+# the levels >= 1 replicated.  Every rank holds an ordinary whole-domain hierarchy (mf_mg_create(NX, NY, NZ)) whose matrix is
+# the all-gathered system, so the set-up (the serial host selection included) and every level >= 1 run replicated, on code
+# that is pinned against the reference; only the level-0 passes run on the owned planes.  Per V-cycle: four one-plane
+# exchanges (x after each smoothing colour that a neighbour's next pass reads, r before the restriction) and one all-gather
+# (b of level 1, rows copied by owner).  The owned planes of the result have the bits of mf_mg_vcycle on the undivided grid.
+# =========================================================================================================
+MG_X, MG_B, MG_R = 2, 3, 4           # the vectors of a level, as mf_mgslab_get_planes / _put_planes number them
+MG_MAX_ITER = 100                    # pressure.cpp:419: the PCG's iteration limit with a multigrid preconditioner
+
+
+def _mg_wanted(dom, preconditioner, who="slab.solvePressure"):
+    """False for PcMIC, True for the two multigrid preconditioners; refuses everything else, the CPU checker backend (it has no
+    multigrid) and a library without the extension -- by name, before any grid is touched and before any collective.  All ranks
+    hold the same library and pass the same value, so all take the same branch."""
+    if isinstance(preconditioner, bool) or preconditioner not in (PcMIC, PcMGDynamic, PcMGStatic):
+        raise RuntimeError("%s: preconditioner must be PcMIC (1), PcMGDynamic (2) or PcMGStatic (3), got %r" % (who, preconditioner))
+    if preconditioner == PcMIC:
+        return False
+    lib = dom.solver.lib
+    ext = _lib.extension("mgslab")
+    if lib.backend != "hip":
+        raise RuntimeError(ext.not_implemented(who, lib.backend))
+    if not (lib.multigrid and lib.mgslab):
+        raise RuntimeError("%s: %s lacks the z-slab multigrid extension (manta_hip_mgslab.h) -- rebuild the library" % (who, lib.path))
+    return True
+
+
+def coarse_planes(z0, z1, NZ):
+    """the planes [K0, K1) of level 1 that the owner of the fine planes [z0, z1) restricts into.  Coarse plane K reads the fine
+    planes 2K - 1 .. 2K + 1 and belongs to the owner of fine plane min(2K, NZ - 1): with one ghost plane of r that rank has all
+    three.  When NZ is even, the top coarse plane has 2K == NZ, reads plane NZ - 1 only and goes to the last rank.  A one-plane
+    slab at an odd plane owns no coarse plane."""
+    return (z0 + 1) // 2, ((NZ + 2) // 2 if z1 >= NZ else (z1 + 1) // 2)
+
+
+class SlabMG(object):
+    """the hierarchy of one slab domain.  Creating it is a collective (the ranks' z-ranges are gathered once)."""
+
+    def __init__(self, dom):
+        from . import plugins
+        s = dom.solver
+        self.dom = dom
+        self.ranges = slab_ranges_of(dom)
+        self.h = plugins._MgHandle(s.lib, dom.NX, dom.NY, dom.NZ)
+        info = self.h.info()
+        self.levels, self.sizes = info["levels"], info["sizes"]
+        # a hierarchy whose level 0 runs inside the single-workgroup tail (one-level hierarchies among them) is not cut
+        self.cut = info["tail_first_level"] > 0
+        self.form = "cut" if self.cut else "replicated"
+        self.is_set = False
+        f32 = dict(dtype=torch.float32, device=s.device)
+        self.mx_own = max(b - a for a, b in self.ranges)
+        if self.cut:
+            self.cranges = [coarse_planes(a, b, dom.NZ) for a, b in self.ranges]
+            self.cXY = self.sizes[1][0] * self.sizes[1][1]
+            self.b1 = torch.zeros(max(max(b - a for a, b in self.cranges), 1) * self.cXY, **f32)
+            self.stage = [torch.empty(dom.XY, **f32) for _ in range(4)]      # send / receive plane, below and above
+
+    def release(self):
+        self.h.release()
+
+    def _call(self, name, *args):
+        self.dom.solver.lib.call(name, self.h.handle, *args)
+
+    def _allgather_owned(self, tensors):
+        """the owned planes of slab-local vectors -> whole-domain tensors [len(tensors)][NZ * XY], rows in rank order"""
+        dom = self.dom
+        XY, off, nown, k = dom.XY, dom.own_off(), dom.n_own, len(tensors)
+        mine = torch.zeros((k, self.mx_own * XY), dtype=torch.float32, device=dom.solver.device)
+        for c, t in enumerate(tensors):
+            mine[c, :nown] = t[off:off + nown]
+        rows = dom.comm.allgather_dev(mine.view(-1)).view(len(self.ranges), k, self.mx_own * XY)
+        whole = torch.empty((k, dom.NZ * XY), dtype=torch.float32, device=dom.solver.device)
+        for q, (a, b) in enumerate(self.ranges):
+            whole[:, a * XY:b * XY] = rows[q][:, :(b - a) * XY]
+        return whole
+
+    def set_a(self, A):
+        """GridMg::setA on every rank from the all-gathered system: identical on all ranks, and identical to one device, by
+        construction.  The host selection inside mf_mg_set_a stays serial and replicated."""
+        s = self.dom.solver
+        whole = self._allgather_owned([g.data for g in A])
+        self._call("mf_mg_set_a", *[_ptr(whole[c]) for c in range(4)], s.stream)       # synchronises the stream
+        self.is_set = True
+
+    def set_accuracy(self, cgAccuracy):
+        self._call("mf_mgslab_set_accuracy", float(cgAccuracy))
+
+    def _exchange(self, what):
+        """my ghost planes z0 - 1 and z1 of level 0's `what` from the neighbours' boundary planes"""
+        dom, st = self.dom, self.dom.solver.stream
+        if dom.comm.world == 1:
+            return
+        pairs, puts = [], []
+        for peer, mine, ghost, snd, rcv in ((dom.below, dom.z0, dom.z0 - 1, self.stage[0], self.stage[1]),
+                                            (dom.above, dom.z1 - 1, dom.z1, self.stage[2], self.stage[3])):
+            if peer is None:
+                continue
+            self._call("mf_mgslab_get_planes", 0, what, mine, mine + 1, _ptr(snd), st)
+            pairs.append((snd, rcv, peer))
+            puts.append((ghost, rcv))
+        dom.comm.sendrecv(pairs)
+        for ghost, rcv in puts:
+            self._call("mf_mgslab_put_planes", 0, what, ghost, ghost + 1, _ptr(rcv), st)
+
+    def _gather_b1(self):
+        """b of level 1, whole on every rank: every coarse plane copied from its owner (never summed: the sign of a zero survives)"""
+        dom, st = self.dom, self.dom.solver.stream
+        if dom.comm.world == 1:
+            return
+        k0, k1 = self.cranges[dom.comm.rank]
+        self._call("mf_mgslab_get_planes", 1, MG_B, k0, k1, _ptr(self.b1), st)
+        rows = dom.comm.allgather_dev(self.b1)
+        for q, (a, b) in enumerate(self.cranges):
+            if q != dom.comm.rank and b > a:
+                self._call("mf_mgslab_put_planes", 1, MG_B, a, b, _ptr(rows[q]), st)
+        self._rows = rows        # stays referenced until the next gather: the copies out of it are queued, not done
+
+    def vcycle(self, dst, rhs):
+        """dst = one V-cycle on rhs (setRhs + doVCycle, zero initial guess, (1, 1) smoothing) on the owned planes of two slab-local
+        grids.  Reads and writes nothing of them outside the owned planes."""
+        dom = self.dom
+        s = dom.solver
+        st, off, XY = s.stream, dom.own_off(), dom.XY
+        z0, z1, NZ = dom.z0, dom.z1, dom.NZ
+        if not self.cut:
+            # replicated fallback: the undivided V-cycle on the gathered rhs, on every rank
+            whole = self._allgather_owned([rhs.data])
+            out = torch.empty(NZ * XY, dtype=torch.float32, device=s.device)
+            self._call("mf_mg_vcycle", _ptr(out), _ptr(whole[0]), st)
+            dst.data[off:off + dom.n_own] = out[z0 * XY:z1 * XY]
+            return
+        k0, k1 = self.cranges[dom.comm.rank]
+        self._call("mf_mgslab_set_rhs", z0, z1, _off(rhs.data, off), st)       # x_0 = 0 on the owned and the ghost planes
+        self._call("mf_mgslab_smooth", 0, z0, z1, st)
+        self._exchange(MG_X)                                                    # colour 1 reads colour 0 across the faces
+        self._call("mf_mgslab_smooth", 1, z0, z1, st)
+        self._exchange(MG_X)                                                    # the residual reads both colours across the faces
+        self._call("mf_mgslab_residual", z0, z1, st)
+        self._exchange(MG_R)                                                    # coarse plane K reads r of 2K - 1 .. 2K + 1
+        self._call("mf_mgslab_restrict", k0, k1, st)
+        self._gather_b1()
+        self._call("mf_mgslab_coarse", st)                                      # levels 1 .. L-1, replicated
+        # level 1 and the vertex types are replicated and the ghost x is current since the second exchange: no exchange here
+        self._call("mf_mgslab_interp_add", max(z0 - 1, 0), min(z1 + 1, NZ), st)
+        self._call("mf_mgslab_smooth", 1, z0, z1, st)
+        self._exchange(MG_X)                                                    # colour 0 reads the new colour 1 across the faces
+        self._call("mf_mgslab_smooth", 0, z0, z1, st)
+        self._call("mf_mgslab_get_planes", 0, MG_X, z0, z1, _off(dst.data, off), st)
+
+
+def releaseMG(dom):
+    """release the hierarchy PcMGStatic keeps on a slab domain (pressure.cpp:252-267)"""
+    mg, dom._mg = getattr(dom, "_mg", None), None
+    if mg is not None:
+        mg.release()
+
+
+def applyMG(dom, dst, src):
+    """dst = one V-cycle on src with the hierarchy a PcMGStatic solve left on the domain (owned planes of two slab-local grids)"""
+    mg = getattr(dom, "_mg", None)
+    if mg is None or not mg.is_set:
+        raise RuntimeError("slab.applyMG: the domain holds no multigrid hierarchy (run solvePressure with PcMGStatic first)")
+    mg.vcycle(dst, src)
+
+
+def _pcg_multigrid(dom, preconditioner, window, pressure, rhs, residual, search, tmp, A, cgAccuracy, stats):
+    """GridCg::doInit / iterate with PC_MGP (conjugategrad.cpp:210-300) on a slab: the loop of the MIC route with the V-cycle in
+    the place of the sweeps.  The stretch behind the first gather is composed of the loose-scalar entries (alpha from the
+    gathered rows; x += alpha search and r -= alpha tmp with max|r|; the V-cycle; dot(tmp, r) over the owned planes): the
+    fused entries of the MIC route defer the x update through `xpending` / `sigmaPrev`, which only their own kernels keep.  The
+    V-cycle does not read the stop state, so the host reads it every iteration and queues nothing past the stop."""
+    s = dom.solver
+    lib, st = s.lib, s.stream
+    sx, sy = dom.NX, dom.NY
+    off, nown, world = dom.own_off(), dom.n_own, dom.comm.world
+    wz, wgl, woff, fmic = window["wz"], window["wgl"], window["woff"], window["fmic"]
+
+    def W(g):
+        return _off(g.data, woff)
+
+    # pressure.cpp:419-431, 452-454: Dynamic builds the hierarchy for this solve and drops it afterwards; Static keeps the one
+    # it finds -- with its matrix, whatever the flags are now -- until releaseMG
+    if preconditioner == PcMGDynamic:
+        releaseMG(dom)
+    mg = getattr(dom, "_mg", None)
+    if mg is None:
+        mg = dom._mg = SlabMG(dom)
+    try:
+        if not mg.is_set:
+            mg.set_a(A)                                              # InitPreconditionMultigrid, conjugategrad.cpp:100-106
+        mg.set_accuracy(cgAccuracy)
+        dev = s.device
+        red = torch.zeros(2, dtype=torch.float64, device=dev)        # {max|residual|, dot} of this rank
+        sc = torch.zeros(16, dtype=torch.float32, device=dev)        # the scalar block: sigma, alpha, nalpha, beta, resNorm
+        p_sc = ctypes.c_void_p(sc.data_ptr())
+        p_sigma, p_alpha, p_beta, p_res = (ctypes.c_void_p(sc.data_ptr() + 4 * i) for i in (0, 1, 3, 4))
+        p_red0, p_red1 = ctypes.c_void_p(red.data_ptr()), ctypes.c_void_p(red.data_ptr() + 8)
+        state = torch.zeros(2, dtype=torch.int32, device=dev)
+        p_state = ctypes.c_void_p(state.data_ptr())
+        acc32 = float(np.float32(cgAccuracy))
+
+        def dot_own(a, b):
+            lib.call("mf_grid_dot_dev", nown, _off(a.data, off), _off(b.data, off), p_red1, st)
+
+        # doInit, conjugategrad.cpp:210-235
+        pressure.clear()
+        residual.copyFrom(rhs)
+        mg.vcycle(tmp, residual)
+        search.copyFrom(tmp)
+        dot_own(tmp, residual)
+        sc[0] = 1.0
+        g = dom.comm.allgather_dev(red)
+        lib.call("mf_cg_slab_beta", _ptr(g), world, p_sigma, p_beta, p_res, 0.0, 0, None, st)
+        iters, stop = 0, 0
+        for it in range(1, MG_MAX_ITER + 1):
+            dom.exchange(search, 1)
+            lib.call("mf_apply_matrix_dot_dev", sx, sy, wz, W(fmic), W(tmp), W(search), W(A[0]), W(A[1]), W(A[2]), W(A[3]),
+                     wgl, wgl + dom.nown, p_sc, p_red1, st)
+            g1 = dom.comm.allgather_dev(red)
+            lib.call("mf_cg_slab_alpha", _ptr(g1), world, p_sigma, p_alpha, p_state, st)
+            lib.call("mf_cg_slab_axpy2", nown, p_sc, _off(pressure.data, off), _off(search.data, off), _off(residual.data, off),
+                     _off(tmp.data, off), p_red0, st)
+            mg.vcycle(tmp, residual)
+            dot_own(tmp, residual)
+            g2 = dom.comm.allgather_dev(red)
+            lib.call("mf_cg_slab_beta", _ptr(g2), world, p_sigma, p_beta, p_res, acc32, it, p_state, st)
+            stop, at = (int(v) for v in state.tolist())               # synchronises: g1 and g2 have been consumed
+            iters = it
+            if stop:
+                iters = at
+                break
+            lib.call("mf_update_search_vec_dev", nown, _off(search.data, off), _off(tmp.data, off), p_beta, st)
+        resNorm = float(sc[4])
+        if stats is not None:
+            stats["iterations"], stats["residual"] = iters, resNorm
+            stats["mg_levels"], stats["mg_form"] = mg.levels, mg.form
+    finally:
+        if preconditioner == PcMGDynamic:
+            releaseMG(dom)
+    if stop == 2:
+        raise RuntimeError("GridCg::iterate: The CG solver diverged, residual norm > 1e30, stopping.")
     return iters
 
 
