@@ -16,8 +16,19 @@
  *   - all functions return 0 on success, non-zero on error; mf_last_error() gives the message
  *     (reference: Manta::Error thrown by errMsg/assertMsg, general.h:42-77, surfaced as RuntimeError).
  *   - pointers are BORROWED; nothing is allocated that the caller must free, except through mf_ws_*.
- *   - `stream` is a hipStream_t (NULL = default stream); CPU libraries ignore it.  Calls are asynchronous
- *     on the stream unless they return a scalar through a host pointer (those synchronise the stream).
+ *   - `stream` is a hipStream_t (NULL = default stream; a non-blocking stream is fine); CPU libraries ignore it.  All device work
+ *     of a call is queued on that stream.  A call returns without waiting for it, except where it needs a device result on the host;
+ *     these synchronise the stream (and only it) before they return:
+ *       - every entry that returns through a host pointer (mf_grid_dot, mf_grid_sum_sqr, mf_grid_max_abs*, mf_grid_min_max, the
+ *         out_host of mf_cg_solve / mf_solve_pressure_fused, the totals, counts and statistics of the extension headers);
+ *       - mf_cg_solve, mf_solve_pressure_fused and the mf_cg_slab_* loop (convergence test), mf_make_rhs with a host result;
+ *       - mf_mic_init / mf_mic_init_blocked and mf_pack_matrix (the verdict whether the matrix can be packed), mf_mic_apply the first
+ *         time it sees a grid size (its hand-off buffers are set up on the stream), mf_mic_check;
+ *       - mf_grid_particle_index (the length of the index), mf_noise_generate_tile (the tile is built on the host),
+ *         the mf_reinit_* march (round counters; its serial fall-back runs on the host), mf_mg_set_a / mf_mg2d_set_a (coarse
+ *         vertices are selected on the host).
+ *     mf_mg_create, mf_mg_destroy, mf_mg_info, mf_mg_read_level (and their mf_mg2d_ twins), which take no stream, and the first call on
+ *     a device or one that needs a larger internal scratch block, wait for the whole device.  INTEGRATION.md, "Stream contract".
  *   - grids are dense, x fastest: idx = i + sx*(j + sy*k)  (reference grid.h:77).  2-D grids have sz == 1.
  *   - Real grids: float[N]; FlagGrid/IntGrid: int32[N]  (N = sx*sy*sz).
  *   - Vec3 / MAC grids are STRUCTURE-OF-ARRAYS: float[3][N] (x plane, y plane, z plane).  The reference

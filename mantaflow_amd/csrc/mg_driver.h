@@ -364,6 +364,8 @@ int mg_create(int sx, int sy, int sz, void** handle_out) {
 		if (e == hipSuccess) e = hipMemcpy(m->paths, ps.data(), ps.size() * sizeof(Path), hipMemcpyHostToDevice);
 		if (e == hipSuccess) e = hipMalloc((void**)&m->d_info, 4 * sizeof(int));
 		if (e == hipSuccess) e = hipMemset(m->d_info, 0, 4 * sizeof(int));
+		// create has no stream: its fills are done before it returns, so a caller's stream of any kind finds the levels cleared
+		if (e == hipSuccess) e = hipDeviceSynchronize();
 		if (e != hipSuccess) rc = fail("%s_create: %s", H::NAME, hipGetErrorString(e));
 	}
 	if (rc != 0) {

@@ -1369,7 +1369,7 @@ static int rows_prepare(const Dim& d, FlowState** out, hipStream_t st, int jbloc
 	if (jb < 1 || jb > nbj) jb = nbj;
 	if (!f->ctl) {
 		MF_HIP(hipMalloc((void**)&f->ctl, sizeof(FlowCtl)));
-		MF_HIP(hipMemset(f->ctl, 0, sizeof(FlowCtl)));
+		MF_HIP(hipMemsetAsync(f->ctl, 0, sizeof(FlowCtl), st));
 	}
 	if (f->nbj != nbj || f->nbk != nbk || f->nchunks != nchunks || f->jb != jb || f->nxb != nxb) {
 		MF_HIP(hipStreamSynchronize(st));
@@ -1390,9 +1390,10 @@ static int rows_prepare(const Dim& d, FlowState** out, hipStream_t st, int jbloc
 					}
 		}
 		if (!f->rows_xt) MF_HIP(hipMalloc((void**)&f->rows_xt, 2 * sizeof(int)));
-		MF_HIP(hipMemset(f->rows_xt, 0, 2 * sizeof(int)));
+		// every fill and copy below is queued on the caller's stream, where the sweeps that poll these buffers follow it
+		MF_HIP(hipMemsetAsync(f->rows_xt, 0, 2 * sizeof(int), st));
 		MF_TRY(grow_buffer(&f->border, &f->border_cap, sizeof(int) * h.size(), st));
-		MF_HIP(hipMemcpy(f->border, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice));
+		MF_HIP(hipMemcpyAsync(f->border, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice, st));
 		// one granule per (bundle, x', face lane) and face
 		// (fine-grained memory, hipExtMallocWithFlags, was tried for these: 0.45 instead of 0.71 us per idle hand-off in
 		// tools/micro/pingpong_scalar.hip, but no change of the sweep time -- 575.0 vs 576.4 us per apply at 256^3; so were four
@@ -1404,8 +1405,9 @@ static int rows_prepare(const Dim& d, FlowState** out, hipStream_t st, int jbloc
 			MF_TRY(grow_buffer(q, &cap, need, st));
 		}
 		f->sx_cap = cap;
-		for (unsigned long long* q : {f->sxj, f->sxk, f->sxj1, f->sxk1}) MF_HIP(hipMemset(q, 0, f->sx_cap));
-		MF_HIP(hipMemset(f->ctl, 0, sizeof(FlowCtl)));
+		for (unsigned long long* q : {f->sxj, f->sxk, f->sxj1, f->sxk1}) MF_HIP(hipMemsetAsync(q, 0, f->sx_cap, st));
+		MF_HIP(hipMemsetAsync(f->ctl, 0, sizeof(FlowCtl), st));
+		MF_HIP(hipStreamSynchronize(st));      // h leaves scope: the ticket order has to be on the device by then
 		f->sgen = 0;
 		f->nbj = nbj;
 		f->nbk = nbk;
@@ -1619,14 +1621,15 @@ const unsigned char* mic_pack_user(const int32_t* flags, const float* A0, const 
 	*a0_packed = f->up_A0 != nullptr && f->up_A0 == A0;
 	return f->upack;
 }
-int mic_flow_error() {
+int mic_flow_error(hipStream_t st) {
 	FlowState* f;
 	MF_TRY(flow_state(&f));
 	if (!f->ctl) return 0;
 	FlowCtl fc;
-	MF_HIP(hipMemcpy(&fc, f->ctl, sizeof fc, hipMemcpyDeviceToHost));
+	MF_HIP(hipMemcpyAsync(&fc, f->ctl, sizeof fc, hipMemcpyDeviceToHost, st));
+	MF_HIP(hipStreamSynchronize(st));
 	if (fc.err) {
-		MF_HIP(hipMemset(f->ctl, 0, sizeof(FlowCtl)));
+		MF_HIP(hipMemsetAsync(f->ctl, 0, sizeof(FlowCtl), st));
 		return fail("MIC dataflow sweep: a workgroup timed out waiting for its predecessor faces");
 	}
 	return 0;
@@ -1730,7 +1733,7 @@ int mf_mic_apply_dot_dev(int sx, int sy, int sz, const int32_t* flags, float* ds
 // looks at it itself, callers that drive mf_mic_apply directly (the z-slab solver) ask here once per solve
 int mf_mic_check(void* stream) {
 	MF_HIP(hipStreamSynchronize((hipStream_t)stream));
-	return mic_flow_error();
+	return mic_flow_error((hipStream_t)stream);
 }
 
 }  // extern "C"

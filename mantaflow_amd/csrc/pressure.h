@@ -182,5 +182,5 @@ int mic_mode();          // the requested sweep mode (mf_set_mic_mode): 0 levels
 // factor from the packed bytes and the registration of (flags, Aprecond) as a system without coefficient arrays
 int mic_fused_begin(const Dim& d, hipStream_t st, unsigned char** pack, int** bempty, int* nbj);
 int mic_fused_finish(const Dim& d, const int32_t* flags, float* Aprecond, hipStream_t st);
-int mic_flow_error();    // reads (and clears) the deadlock-guard flag of the single-launch sweeps; needs a synchronised stream
+int mic_flow_error(hipStream_t st);    // reads (and clears) the deadlock-guard flag of the single-launch sweeps after the work queued on st; synchronises st
 }  // namespace mf

@@ -1378,7 +1378,7 @@ static int cg_solve_core(const Dim& d, const int32_t* flags, float* dst, const f
 	out_host[0] = (float)h.iterations;
 	out_host[1] = h.resNorm;
 	out_host[2] = h.sigma;
-	if (pc == MF_PC_MICP) MF_TRY(mic_flow_error());
+	if (pc == MF_PC_MICP) MF_TRY(mic_flow_error(st));
 	if (h.diverged) return fail("GridCg::iterate: The CG solver diverged, residual norm > 1e30, stopping.");
 	return 0;
 }

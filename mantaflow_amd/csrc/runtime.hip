@@ -37,6 +37,7 @@ static int make_workspace(Workspace* w) {
 	MF_HIP(hipHostMalloc(&w->host, 4096, hipHostMallocDefault));
 	MF_HIP(hipMalloc((void**)&w->tilework, 4096));
 	MF_HIP(hipMemset(w->tilework, 0, 4096));
+	MF_HIP(hipDeviceSynchronize());      // once per device: the two fills are done before any stream's kernel accumulates into them
 	return 0;
 }
 int get_workspace(Workspace** out) {

@@ -109,6 +109,38 @@ def run_mic_ref(dims, flags, A, var1):
     return ap, dst
 
 
+# ---- reductions through a host pointer and the element-wise operations (runtime.hip) -----------------------------------------------
+REDUCTION_N = (1 << 20) + 3
+
+
+def reduction_inputs():
+    return util.rand_real((REDUCTION_N,), 30, 3.0), util.rand_real((REDUCTION_N,), 31, 2.0)
+
+
+def run_reductions_impl(impl, a, b):
+    """-> (dot, max |a|, min a, max a, a after axpy / clamp, b after xpay / safeDivide)"""
+    n = a.size
+    da, db = impl.dev(a), impl.dev(b)
+    d = ctypes.c_double(); f = ctypes.c_float(); lo = ctypes.c_float(); hi = ctypes.c_float()
+    impl.call("mf_grid_dot", n, da, db, ctypes.byref(d), None)
+    impl.call("mf_grid_max_abs", n, da, ctypes.byref(f), None)
+    impl.call("mf_grid_min_max", n, da, ctypes.byref(lo), ctypes.byref(hi), None)
+    impl.call("mf_grid_scaled_add", n, da, db, 0.37, None)
+    impl.call("mf_update_search_vec", n, db, da, -1.7, None)
+    impl.call("mf_grid_clamp", n, da, -1.0, 1.5, None)
+    impl.call("mf_grid_safe_divide", n, db, da, None)
+    impl.sync()
+    return d.value, f.value, lo.value, hi.value, impl.host(da), impl.host(db)
+
+
+def check_reductions(h, o):
+    """h: the implementation under test, o: the oracle -- the bar of test_gpu_parity.test_reductions_and_elementwise"""
+    assert abs(h[0] - o[0]) <= 1e-12 * abs(o[0]) and np.float32(h[0]) == np.float32(o[0])
+    assert h[1:4] == o[1:4]
+    util.assert_bitexact(h[4], o[4], "axpy/clamp")
+    util.assert_bitexact(h[5], o[5], "xpay/safeDivide")
+
+
 def cg_rhs(dims, flags, seed):
     sx, sy, sz = dims
     rhs = util.rand_real((sz, sy, sx), seed + 23)

@@ -726,27 +726,8 @@ def test_interpolate_between_grid_sizes(hip_backend, case, orderSpace):
 
 
 def test_reductions_and_elementwise(hip, oracle):
-    n = 1 << 20
-    a, b = util.rand_real((n + 3,), 30, 3.0), util.rand_real((n + 3,), 31, 2.0)
-    for impl_pair in [(hip, oracle)]:
-        res = []
-        for impl in impl_pair:
-            da, db = impl.dev(a), impl.dev(b)
-            d = ctypes.c_double(); f = ctypes.c_float(); lo = ctypes.c_float(); hi = ctypes.c_float()
-            impl.call("mf_grid_dot", n + 3, da, db, ctypes.byref(d), None)
-            impl.call("mf_grid_max_abs", n + 3, da, ctypes.byref(f), None)
-            impl.call("mf_grid_min_max", n + 3, da, ctypes.byref(lo), ctypes.byref(hi), None)
-            impl.call("mf_grid_scaled_add", n + 3, da, db, 0.37, None)
-            impl.call("mf_update_search_vec", n + 3, db, da, -1.7, None)
-            impl.call("mf_grid_clamp", n + 3, da, -1.0, 1.5, None)
-            impl.call("mf_grid_safe_divide", n + 3, db, da, None)
-            impl.sync()
-            res.append((d.value, f.value, lo.value, hi.value, impl.host(da), impl.host(db)))
-        h, o = res
-        assert abs(h[0] - o[0]) <= 1e-12 * abs(o[0]) and np.float32(h[0]) == np.float32(o[0])
-        assert h[1:4] == o[1:4]
-        assert_bitexact(h[4], o[4], "axpy/clamp")
-        assert_bitexact(h[5], o[5], "xpay/safeDivide")
+    a, b = cases.reduction_inputs()
+    cases.check_reductions(cases.run_reductions_impl(hip, a, b), cases.run_reductions_impl(oracle, a, b))
 
 
 # ---- BASELINE.json size (256^3): direct comparison of the stencil + preconditioner and whole-solve properties ----
